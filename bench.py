@@ -9,13 +9,16 @@ library (include/vmpc.h vmpc_comm_*: ncclAllGather on the MSM's own stream) and 
 them in rank order ("weak" scaling).  The commitments of a launch are over DISTINCT
 scalar vectors.  For N > 1 the result is checked across ranks (exponent identity), `"checked": true`.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (k_msm_bucket), timed with HIP
-events on the kernel's own stream (alone on the GPU after the timed region, and inside it);
-`cpu_baseline` is the C restatement of the REFERENCE algorithm (per-term double-and-add + product
-tree) on one host core over a bounded sample.  At N = 1 the line also carries the AC20 Protocol-5
-prove time at N = 2^20 in both transcript modes (extra keys, not the headline value); at N > 1 the
-sharded prover's.  A run that makes no progress for --watchdog-s seconds prints the line with an
-`error` entry and exits with status 3.
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: it sets up, warms up,
+times the K steps once, writes the last step's commitments if --dump-outputs DIR is given, and prints
+the line.  Everything else is measured with --full: the median of --repeats (default 5) timed regions,
+the result check, the other generator forms, `roofline` for the dominant kernel (k_msm_bucket, timed
+with HIP events on the kernel's own stream, alone on the GPU after the timed region and inside it),
+`cpu_baseline` (the C restatement of the REFERENCE algorithm - per-term double-and-add + product
+tree - on one host core over a bounded sample), and at N = 1 the AC20 Protocol-5 prove time at
+N = 2^20 in both transcript modes, other sizes and BN256 (extra keys, not the headline value); at
+N > 1 the sharded prover's and config 4.  A run that makes no progress for --watchdog-s seconds
+prints the line with an `error` entry and exits with status 3.
 """
 import argparse
 import json
@@ -959,6 +962,16 @@ def self_launch(args, argv):
     return worst
 
 
+def dump_outputs(out_dir, results, result_idx):
+    """--dump-outputs DIR: what the timed path hands its caller in the last step - the commitments of the last launch,
+    each as its canonical affine bytes (x then y, 32 bytes each, little-endian; every byte exact in float32) - and
+    which of the seeded scalar vectors each one commits to."""
+    os.makedirs(out_dir, exist_ok=True)
+    aff = np.array([np.frombuffer(pt.to_affine_bytes(), np.uint8) for pt in results], dtype=np.float32)
+    np.save(os.path.join(out_dir, "commitments_affine_bytes.npy"), aff)
+    np.save(os.path.join(out_dir, "commitments_scalar_vector_index.npy"), np.asarray(result_idx, dtype=np.float32))
+
+
 def oracle_commitment_check(points_affine, scalar_arrs, need, got):
     """Every commitment in `got` ({scalar-vector index: point}) recomputed by the oracle's C restatement of the
     reference algorithm over the same host arrays; asserts equality of the canonical affine bytes."""
@@ -983,8 +996,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)       # 60 ms timed region per generator form
     ap.add_argument("--warmup", type=int, default=6)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="back-to-back repetitions of the K-step timed region; the line reports their median")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the commitments of the last timed step to DIR/*.npy (float32)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="back-to-back repetitions of the K-step timed region; the line reports their median "
+                         "(default: 1, with --full 5)")
     ap.add_argument("--log2n", type=int, default=20, help="MSM terms per GPU = 2^log2n")
     ap.add_argument("--cpu-log2n", type=int, default=17, help="cpu_baseline sample size")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1027,6 +1045,8 @@ def main():
     ap.add_argument("--watchdog-s", type=float, default=float(os.environ.get("VMPC_BENCH_WATCHDOG_S", "1500")),
                     help="give up (JSON line with an error entry, exit status 3) after this long")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plain (as the N = 1 line is): start the N ranks ourselves, as children, before any GPU call
@@ -1034,8 +1054,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    gpu_clocks = clocks_sample() if rank == 0 else None          # before anything below initialises the GPU
-    sampler = ClockSampler() if rank == 0 else None              # (likewise: its child starts before GPU init)
+    gpu_clocks = clocks_sample() if rank == 0 and args.full else None    # before anything below initialises the GPU
+    sampler = ClockSampler() if rank == 0 and args.full else None        # (likewise: its child starts before GPU init)
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
     import torch
     ndev = torch.cuda.device_count()
@@ -1205,174 +1225,161 @@ def main():
         return runs, res
 
     enter("timed region")
-    # the headline: median of `--repeats` back-to-back repetitions of the K-step region (one 20-60 ms window used to
-    # decide it; boxes and windows differ by several per cent), min / max reported beside it
+    # the headline: median of `--repeats` back-to-back repetitions of the K-step region (--full: five; one 20-60 ms
+    # window used to decide it; boxes and windows differ by several per cent), min / max reported beside it
     t_region0 = time.time()
     elapsed_runs, (results, result_idx) = timed(points, args.repeats)
     t_region1 = time.time()
     elapsed = sorted(elapsed_runs)[len(elapsed_runs) // 2]
-    # once more with the per-stage HIP events on every stream the kernels are launched on: the in-region kernel
-    # durations of the roofline entry (not part of the headline: the events themselves cost time)
-    timed_profile = os.environ.get("VMPC_BENCH_TIMED_PROFILE", "1") != "0"
-    prof = {}
-    if timed_profile:
-        for c_ in prof_ctxs:
-            c_.profile(True)
-            c_.profile_read(reset=True)
-        torch.cuda.synchronize()
-        barrier()
-        steps(args.steps, points)
-        torch.cuda.synchronize()
-        barrier()
-        for c_ in prof_ctxs:       # HIP events on each stream the kernels were launched on
-            for name, (ms, cnt) in c_.profile_read(reset=True).items():
-                a, b = prof.get(name, (0.0, 0))
-                prof[name] = (a + ms, b + cnt)
-            c_.profile(False)
-    ctx.sync()
-
-    # outside the timed region: the same commitment alone on the GPU (one in flight), so that
-    # the per-stage durations are not stretched by the other in-flight commitments' kernels,
-    # and the integer-ALU ceiling the bucket stage is priced against
-    enter("one commitment alone")
-    iso, alu_peak, iso_ms, iso_steps = {}, None, None, 5
-    c0 = prof_ctxs[0]
-    # (every rank: with a collective the launches are collective too)
-    for _ in range(2):
-        shard.finish(shard.launch(scalar_vectors[0], points, 0))
-    t1 = time.perf_counter()
-    for _ in range(iso_steps):             # latency: no stage events on the stream (they cost ~0.1 ms per commitment)
-        shard.finish(shard.launch(scalar_vectors[0], points, 0))
-    iso_ms = (time.perf_counter() - t1) / iso_steps * 1e3
-    if rank == 0:
-        c0.profile(True)
-        c0.profile_read(reset=True)
-    for _ in range(iso_steps):             # the same again with the per-stage HIP events: the roofline's kernel time
-        shard.finish(shard.launch(scalar_vectors[0], points, 0))
-    busy_clocks = None
-    if rank == 0:
-        iso = {k: ms / max(c, 1) for k, (ms, c) in c0.profile_read(reset=True).items()}
-        c0.profile(False)
-        alu_peak = max(c0.madd_rate(400) for _ in range(3))
-    if rank == 0 and sampler is not None and not shard.collective:
-        # the clocks the alone-kernel figures were taken at: the same commitment back to back for ~0.25 s while the
-        # child samples sclk / power (the 5-launch loops above are over before two samples are in)
-        t_a0 = time.time()
-        while time.time() - t_a0 < 0.25:
-            shard.finish(shard.launch(scalar_vectors[0], points, 0))
-        t_a1 = time.time()
-        time.sleep(0.02)
-        try:        # the card this process computes on, by PCI address (the box's sysfs shows every GPU of the node)
-            pr = torch.cuda.get_device_properties(device_index)
-            pci = f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
-        except Exception:
-            pci = None
-        busy_clocks = {"one_commitment_alone_loop": sampler.window(t_a0, t_a1, pci),
-                       "timed_region": sampler.window(t_region0, t_region1, pci),
-                       "source": "sysfs pp_dpm_sclk / pp_dpm_mclk / hwmon power1_average, read every ~5 ms by a child "
-                                 "process started before GPU initialisation"}
-    if sampler is not None:
-        sampler.stop()
-    # (for comparison) one commitment alone over a 4-row fixed-base table of the same generators (what a CRS
-    # that serves many commitments holds; 3 extra multiples per generator): the recombination chain is 48 doublings
-    # instead of 240 and the reduction covers 4 bucket sets instead of 16
-    alone_table = None
-    if rank == 0 and not args.variable_base and os.environ.get("VMPC_BENCH_ALONE_TABLE", "1") != "0":
-        try:
-            tab = vm.PointVector(points_plain.a, None, ctx).precompute([], rows=4)
-            t_, res_ = tab._table, ctx.alloc(128)
-            for _ in range(2):
-                ctx.msm_table(t_.ptr, t_.n, 0, scalar_vectors[0].ptr, n, None, res_.ptr, None, rows=4)
-            ctx.sync()
-            t3 = time.perf_counter()
-            for _ in range(iso_steps):
-                ctx.msm_table(t_.ptr, t_.n, 0, scalar_vectors[0].ptr, n, None, res_.ptr, None, rows=4)
-                ctx.sync()
-            alone_table = {"rows": 4, "table_MiB": (4 * n * 128) >> 20,
-                           "ms_per_commitment": round((time.perf_counter() - t3) / iso_steps * 1e3, 4)}
-            got = vm.Ed25519Point.from_proj_bytes(ctx.download(res_.ptr, 128).tobytes()[:96]).normalize()
-            alone_table["same_point_as_prepared_form"] = bool(got == shard.finish(shard.launch(scalar_vectors[0], points, 0))) \
-                if not shard.collective else None
-            del tab, t_, res_
-        except Exception as e:
-            alone_table = {"error": f"{type(e).__name__}: {e}"}
-    # the other generator form, same K steps, same brackets
-    enter("other generator form")
-    other_pts = points_plain if points is points_prepared else points_prepared
-    grow_workspaces(other_pts)
-    if args.warmup:
-        steps(args.warmup, other_pts)
-    other_runs, (other_results, other_idx) = timed(other_pts, args.repeats)
-    other_elapsed = sorted(other_runs)[len(other_runs) // 2]
-    # ... and, when the headline runs over a table of multiples, the prepared form WITHOUT multiples (one 128-byte line
-    # per generator: the headline of rounds 2-5)
-    prepared1 = None
-    if not args.variable_base and args.table_rows != 1:
-        enter("prepared form without multiples")
-        p1 = vm.PointVector(points_plain.a, None, ctx).precompute([], rows=1)
-        grow_workspaces(p1)
-        if args.warmup:
-            steps(args.warmup, p1)
-        p1_runs, (p1_results, p1_idx) = timed(p1, max(1, args.repeats - 2))
-        p1_elapsed = sorted(p1_runs)[len(p1_runs) // 2]
-        prepared1 = {"value": world * n * args.steps / p1_elapsed, "ms_per_step": p1_elapsed / args.steps * 1e3,
-                     "table_MiB": (n * 128) >> 20,
-                     "note": "same K steps and brackets; generators as one prepared 128-byte line each, 16 mixed "
-                             "additions per term (16-bit windows) + recombination"}
-        if not shard.collective:
-            same = {i: pt for pt, i in zip(results, result_idx)}
-            prepared1["same_points_as_headline"] = all(pt == same[i] for pt, i in zip(p1_results, p1_idx) if i in same)
-        del p1
-    no_check = bool(os.environ.get("BENCH_NO_CHECK"))          # (developer A/B builds that break the result)
-
-    # size-independent correctness property at full size, for every commitment of the last launch:
-    #     sum_i s_i * (e_i * B) == (sum_i s_i e_i mod l) * B,     the sum running over ALL ranks' shards
-    enter("result check")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results, result_idx)
     checked, oracle_check = False, None
-    if not no_check:
-        need = sorted(set(result_idx) | set(other_idx))
-        mine = {i: exponent_sum(scalar_arrs[i], exps_arr, vm.groups.ORDER) for i in need}
-        if dist:
-            every = [None] * world
-            dist.all_gather_object(every, mine)
-            assert all(sorted(e) == need for e in every), "ranks disagree on which commitments ran last"
-            tot = {i: sum(e[i] for e in every) % vm.groups.ORDER for i in need}
-        else:
-            tot = mine
-        want = vm.PointVector.fixed_base(group.generator, [tot[i] for i in need], keep_proj=False)
-        want = {i: want[j] for j, i in enumerate(need)}
-        for res, idx in ((results, result_idx), (other_results, other_idx)):
-            for pt, i in zip(res, idx):
-                assert pt == want[i], f"MSM property check failed (rank {rank}, scalar vector {i})"
-        checked = True
-        if world == 1 and os.environ.get("VMPC_BENCH_ORACLE_CHECK", "1") != "0":
-            # and bit for bit against the C restatement of the REFERENCE algorithm (pivot.py:139-145: a ladder per
-            # term + the product tree; oracle/ed25519_oracle.c, ladders spread over the host's cores) - the same
-            # library the cpu_baseline leg times, here as the checker only, outside every timed region
-            oracle_check = oracle_commitment_check(points_plain.affine_array(), scalar_arrs, need,
-                                                   {i: pt for res, idx in ((results, result_idx),
-                                                                           (other_results, other_idx))
-                                                    for pt, i in zip(res, idx)})
+    if args.full:
+        # once more with the per-stage HIP events on every stream the kernels are launched on: the in-region kernel
+        # durations of the roofline entry (not part of the headline: the events themselves cost time)
+        timed_profile = os.environ.get("VMPC_BENCH_TIMED_PROFILE", "1") != "0"
+        prof = {}
+        if timed_profile:
+            for c_ in prof_ctxs:
+                c_.profile(True)
+                c_.profile_read(reset=True)
+            torch.cuda.synchronize()
+            barrier()
+            steps(args.steps, points)
+            torch.cuda.synchronize()
+            barrier()
+            for c_ in prof_ctxs:       # HIP events on each stream the kernels were launched on
+                for name, (ms, cnt) in c_.profile_read(reset=True).items():
+                    a, b = prof.get(name, (0.0, 0))
+                    prof[name] = (a + ms, b + cnt)
+                c_.profile(False)
+        ctx.sync()
+
+        # outside the timed region: the same commitment alone on the GPU (one in flight), so that
+        # the per-stage durations are not stretched by the other in-flight commitments' kernels,
+        # and the integer-ALU ceiling the bucket stage is priced against
+        enter("one commitment alone")
+        iso, alu_peak, iso_ms, iso_steps = {}, None, None, 5
+        c0 = prof_ctxs[0]
+        # (every rank: with a collective the launches are collective too)
+        for _ in range(2):
+            shard.finish(shard.launch(scalar_vectors[0], points, 0))
+        t1 = time.perf_counter()
+        for _ in range(iso_steps):             # latency: no stage events on the stream (they cost ~0.1 ms per commitment)
+            shard.finish(shard.launch(scalar_vectors[0], points, 0))
+        iso_ms = (time.perf_counter() - t1) / iso_steps * 1e3
+        if rank == 0:
+            c0.profile(True)
+            c0.profile_read(reset=True)
+        for _ in range(iso_steps):             # the same again with the per-stage HIP events: the roofline's kernel time
+            shard.finish(shard.launch(scalar_vectors[0], points, 0))
+        busy_clocks = None
+        if rank == 0:
+            iso = {k: ms / max(c, 1) for k, (ms, c) in c0.profile_read(reset=True).items()}
+            c0.profile(False)
+            alu_peak = max(c0.madd_rate(400) for _ in range(3))
+        if rank == 0 and sampler is not None and not shard.collective:
+            # the clocks the alone-kernel figures were taken at: the same commitment back to back for ~0.25 s while the
+            # child samples sclk / power (the 5-launch loops above are over before two samples are in)
+            t_a0 = time.time()
+            while time.time() - t_a0 < 0.25:
+                shard.finish(shard.launch(scalar_vectors[0], points, 0))
+            t_a1 = time.time()
+            time.sleep(0.02)
+            try:        # the card this process computes on, by PCI address (the box's sysfs shows every GPU of the node)
+                pr = torch.cuda.get_device_properties(device_index)
+                pci = f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
+            except Exception:
+                pci = None
+            busy_clocks = {"one_commitment_alone_loop": sampler.window(t_a0, t_a1, pci),
+                           "timed_region": sampler.window(t_region0, t_region1, pci),
+                           "source": "sysfs pp_dpm_sclk / pp_dpm_mclk / hwmon power1_average, read every ~5 ms by a child "
+                                     "process started before GPU initialisation"}
+        if sampler is not None:
+            sampler.stop()
+        # (for comparison) one commitment alone over a 4-row fixed-base table of the same generators (what a CRS
+        # that serves many commitments holds; 3 extra multiples per generator): the recombination chain is 48 doublings
+        # instead of 240 and the reduction covers 4 bucket sets instead of 16
+        alone_table = None
+        if rank == 0 and not args.variable_base and os.environ.get("VMPC_BENCH_ALONE_TABLE", "1") != "0":
+            try:
+                tab = vm.PointVector(points_plain.a, None, ctx).precompute([], rows=4)
+                t_, res_ = tab._table, ctx.alloc(128)
+                for _ in range(2):
+                    ctx.msm_table(t_.ptr, t_.n, 0, scalar_vectors[0].ptr, n, None, res_.ptr, None, rows=4)
+                ctx.sync()
+                t3 = time.perf_counter()
+                for _ in range(iso_steps):
+                    ctx.msm_table(t_.ptr, t_.n, 0, scalar_vectors[0].ptr, n, None, res_.ptr, None, rows=4)
+                    ctx.sync()
+                alone_table = {"rows": 4, "table_MiB": (4 * n * 128) >> 20,
+                               "ms_per_commitment": round((time.perf_counter() - t3) / iso_steps * 1e3, 4)}
+                got = vm.Ed25519Point.from_proj_bytes(ctx.download(res_.ptr, 128).tobytes()[:96]).normalize()
+                alone_table["same_point_as_prepared_form"] = bool(got == shard.finish(shard.launch(scalar_vectors[0], points, 0))) \
+                    if not shard.collective else None
+                del tab, t_, res_
+            except Exception as e:
+                alone_table = {"error": f"{type(e).__name__}: {e}"}
+        # the other generator form, same K steps, same brackets
+        enter("other generator form")
+        other_pts = points_plain if points is points_prepared else points_prepared
+        grow_workspaces(other_pts)
+        if args.warmup:
+            steps(args.warmup, other_pts)
+        other_runs, (other_results, other_idx) = timed(other_pts, args.repeats)
+        other_elapsed = sorted(other_runs)[len(other_runs) // 2]
+        # ... and, when the headline runs over a table of multiples, the prepared form WITHOUT multiples (one 128-byte line
+        # per generator: the headline of rounds 2-5)
+        prepared1 = None
+        if not args.variable_base and args.table_rows != 1:
+            enter("prepared form without multiples")
+            p1 = vm.PointVector(points_plain.a, None, ctx).precompute([], rows=1)
+            grow_workspaces(p1)
+            if args.warmup:
+                steps(args.warmup, p1)
+            p1_runs, (p1_results, p1_idx) = timed(p1, max(1, args.repeats - 2))
+            p1_elapsed = sorted(p1_runs)[len(p1_runs) // 2]
+            prepared1 = {"value": world * n * args.steps / p1_elapsed, "ms_per_step": p1_elapsed / args.steps * 1e3,
+                         "table_MiB": (n * 128) >> 20,
+                         "note": "same K steps and brackets; generators as one prepared 128-byte line each, 16 mixed "
+                                 "additions per term (16-bit windows) + recombination"}
+            if not shard.collective:
+                same = {i: pt for pt, i in zip(results, result_idx)}
+                prepared1["same_points_as_headline"] = all(pt == same[i] for pt, i in zip(p1_results, p1_idx) if i in same)
+            del p1
+        no_check = bool(os.environ.get("BENCH_NO_CHECK"))          # (developer A/B builds that break the result)
+
+        # size-independent correctness property at full size, for every commitment of the last launch:
+        #     sum_i s_i * (e_i * B) == (sum_i s_i e_i mod l) * B,     the sum running over ALL ranks' shards
+        enter("result check")
+        if not no_check:
+            need = sorted(set(result_idx) | set(other_idx))
+            mine = {i: exponent_sum(scalar_arrs[i], exps_arr, vm.groups.ORDER) for i in need}
+            if dist:
+                every = [None] * world
+                dist.all_gather_object(every, mine)
+                assert all(sorted(e) == need for e in every), "ranks disagree on which commitments ran last"
+                tot = {i: sum(e[i] for e in every) % vm.groups.ORDER for i in need}
+            else:
+                tot = mine
+            want = vm.PointVector.fixed_base(group.generator, [tot[i] for i in need], keep_proj=False)
+            want = {i: want[j] for j, i in enumerate(need)}
+            for res, idx in ((results, result_idx), (other_results, other_idx)):
+                for pt, i in zip(res, idx):
+                    assert pt == want[i], f"MSM property check failed (rank {rank}, scalar vector {i})"
+            checked = True
+            if world == 1 and os.environ.get("VMPC_BENCH_ORACLE_CHECK", "1") != "0":
+                # and bit for bit against the C restatement of the REFERENCE algorithm (pivot.py:139-145: a ladder per
+                # term + the product tree; oracle/ed25519_oracle.c, ladders spread over the host's cores) - the same
+                # library the cpu_baseline leg times, here as the checker only, outside every timed region
+                oracle_check = oracle_commitment_check(points_plain.affine_array(), scalar_arrs, need,
+                                                       {i: pt for res, idx in ((results, result_idx),
+                                                                               (other_results, other_idx))
+                                                        for pt, i in zip(res, idx)})
 
     line = None
     if rank == 0:
-        traffic = pmc_traffic_calibrated("k_msm_bucket")
-        bucket_ms, bucket_n = prof.get("msm_bucket", (0.0, 0))
-        t_bucket_timed = bucket_ms / max(bucket_n, 1) / 1e3          # in the timed region: three launches in flight
-        c_bits, windows = ctx.msm_plan(n)
-        if args.table_rows == 13 and not args.variable_base:
-            c_bits, windows = 20, 13            # the wide-window table: thirteen 20-bit digits per scalar
-        madds = n * windows                     # one mixed addition per non-zero digit (upper bound)
-        iso_bucket_s = iso.get("msm_bucket", 0.0) / 1e3
-        # The roofline figure uses the kernel ALONE on the GPU (one commitment in flight, same inputs, same
-        # process): that is the duration rocprofv3 reports for it (profiles/*_alone_kernel_stats.csv agrees
-        # within a few %).  With three launches in flight a HIP-event bracket also counts the time the
-        # kernel's workgroups wait behind other streams' kernels; that figure is reported beside it.
-        t_bucket = iso_bucket_s if iso_bucket_s > 0 else t_bucket_timed
-        achieved = BYTES_PER_TERM * n / t_bucket / 1e9 if t_bucket > 0 else 0.0
         value = world * n * args.steps / elapsed
-        other_value = world * n * args.steps / other_elapsed
-        var_value = value if args.variable_base else other_value
         line = {
             "metric": "Ed25519 MSM scalar-mults/sec", "value": value,
             "unit": "scalar-mults/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1387,7 +1394,10 @@ def main():
                             if oracle_check else
                             "exponent identity sum_i s_i (e_i B) == (sum_i s_i e_i mod l) B across ranks against the "
                             "product's fixed-base kernel (N > 1: each rank holds a shard; the single-GPU line and "
-                            "tests/test_gpu_full_size.py check against the C oracle bit for bit)"),
+                            "tests/test_gpu_full_size.py check against the C oracle bit for bit)"
+                            if checked else
+                            "not checked in a plain run: bench.py --full checks the commitments of the last timed "
+                            "launches (exponent identity; on one GPU also bit for bit against the C oracle)"),
             "config": {"workload": f"Pedersen vector-commitment MSM, n=2^{args.log2n} Ed25519 "
                                    f"generators per GPU, uniform 252-bit scalars",
                        "terms_per_gpu": n, "total_terms": world * n, "launches_in_flight": depth,
@@ -1399,22 +1409,7 @@ def main():
                                   "ms_per_step_min": round(min(elapsed_runs) / args.steps * 1e3, 4),
                                   "ms_per_step_max": round(max(elapsed_runs) / args.steps * 1e3, 4),
                                   "headline": "median of the repeats (each: EXACTLY K steps between barrier + device "
-                                              "synchronisation, max over ranks)",
-                                  # the DEFAULT path of a generator vector that is committed to more than once
-                                  # (pivot._auto_tabulate: the 13-row wide-window table at 2^20); other forms beside it
-                                  "latency_ms_one_commitment_alone":
-                                      round(iso_ms, 4) if args.table_rows == 13 else
-                                      (alone_table or {}).get("ms_per_commitment") or round(iso_ms, 4),
-                                  "latency_ms_one_commitment_alone_form":
-                                      ("13-row wide-window table (what a PointVector of >= 2^19 generators becomes at its "
-                                       "second commitment)" if args.table_rows == 13 else
-                                       f"{alone_table['rows']}-row fixed-base table" if (alone_table or {}).get("ms_per_commitment")
-                                       else "prepared generators"),
-                                  "latency_ms_one_commitment_alone_4_row_table": (alone_table or {}).get("ms_per_commitment"),
-                                  "latency_ms_one_commitment_alone_headline_form": round(iso_ms, 4),
-                                  "what": "value = pipelined throughput (launches_in_flight x commitments_per_launch "
-                                          "commitments in flight); a prover's commitments are sequential and cost "
-                                          "the latency figure"},
+                                              "synchronisation, max over ranks)"},
                        "generators": ("plain affine points, prepared inside every call" if args.variable_base else
                                       "resident in prepared form (128-byte niels image of each point, made once "
                                       "at CRS load, untimed)" if args.table_rows == 1 else
@@ -1424,14 +1419,53 @@ def main():
                                       if args.table_rows == 13 else
                                       f"resident as a {args.table_rows}-row fixed-base table ({args.table_rows - 1} extra "
                                       f"multiples per generator, made once at CRS load, untimed)"),
-                       "variable_base_scalar_mults_per_s": round(var_value, 1),
                        "collective": (f"all_gather(128 B/rank and commitment) + rank-ordered add, transport: {comm_kind}"
                                       if shard.collective else "none"),
                        "dist_backend": args.dist_backend if dist else None,
                        "comm": comm_info,
-                       "gpu_clocks": {"idle_before_gpu_init": gpu_clocks, "busy": busy_clocks},
                        "launched_by": ("bench.py itself (child processes)" if os.environ.get("VMPC_BENCH_SELF_LAUNCHED")
-                                       else "external launcher" if "WORLD_SIZE" in os.environ else "plain process")},
+                                       else "external launcher" if "WORLD_SIZE" in os.environ else "plain process"),
+                       "run": "full (--full)" if args.full else "plain: headline only (--full measures the rest)"},
+        }
+        if comm_note:
+            line["config"]["native_comm_error"] = comm_note
+        state["line"] = line
+    if rank == 0 and args.full:
+        traffic = pmc_traffic_calibrated("k_msm_bucket")
+        bucket_ms, bucket_n = prof.get("msm_bucket", (0.0, 0))
+        t_bucket_timed = bucket_ms / max(bucket_n, 1) / 1e3          # in the timed region: three launches in flight
+        c_bits, windows = ctx.msm_plan(n)
+        if args.table_rows == 13 and not args.variable_base:
+            c_bits, windows = 20, 13            # the wide-window table: thirteen 20-bit digits per scalar
+        madds = n * windows                     # one mixed addition per non-zero digit (upper bound)
+        iso_bucket_s = iso.get("msm_bucket", 0.0) / 1e3
+        # The roofline figure uses the kernel ALONE on the GPU (one commitment in flight, same inputs, same
+        # process): that is the duration rocprofv3 reports for it (profiles/*_alone_kernel_stats.csv agrees
+        # within a few %).  With three launches in flight a HIP-event bracket also counts the time the
+        # kernel's workgroups wait behind other streams' kernels; that figure is reported beside it.
+        t_bucket = iso_bucket_s if iso_bucket_s > 0 else t_bucket_timed
+        achieved = BYTES_PER_TERM * n / t_bucket / 1e9 if t_bucket > 0 else 0.0
+        other_value = world * n * args.steps / other_elapsed
+        var_value = value if args.variable_base else other_value
+        line["config"]["timing"].update({
+            # the DEFAULT path of a generator vector that is committed to more than once
+            # (pivot._auto_tabulate: the 13-row wide-window table at 2^20); other forms beside it
+            "latency_ms_one_commitment_alone":
+                round(iso_ms, 4) if args.table_rows == 13 else
+                (alone_table or {}).get("ms_per_commitment") or round(iso_ms, 4),
+            "latency_ms_one_commitment_alone_form":
+                ("13-row wide-window table (what a PointVector of >= 2^19 generators becomes at its "
+                 "second commitment)" if args.table_rows == 13 else
+                 f"{alone_table['rows']}-row fixed-base table" if (alone_table or {}).get("ms_per_commitment")
+                 else "prepared generators"),
+            "latency_ms_one_commitment_alone_4_row_table": (alone_table or {}).get("ms_per_commitment"),
+            "latency_ms_one_commitment_alone_headline_form": round(iso_ms, 4),
+            "what": "value = pipelined throughput (launches_in_flight x commitments_per_launch "
+                    "commitments in flight); a prover's commitments are sequential and cost "
+                    "the latency figure"})
+        line["config"]["variable_base_scalar_mults_per_s"] = round(var_value, 1)
+        line["config"]["gpu_clocks"] = {"idle_before_gpu_init": gpu_clocks, "busy": busy_clocks}
+        line.update({
             "roofline": {"bound": "hbm", "kernel": "k_msm_bucket", "achieved": achieved,
                          "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
                          "traffic": traffic["bytes"], "traffic_source": traffic["source"],
@@ -1463,11 +1497,8 @@ def main():
             "stages_us": {k: round(ms / max(c, 1) * 1e3, 1) for k, (ms, c) in prof.items()},
             "alone": {"over_fixed_base_table": alone_table,
                       "over_headline_form": {"ms_per_commitment": round(iso_ms, 4),
-                                                   "stages_us": {k: round(v * 1e3, 1) for k, v in iso.items()}}},
-        }
-        if comm_note:
-            line["config"]["native_comm_error"] = comm_note
-        state["line"] = line
+                                             "stages_us": {k: round(v * 1e3, 1) for k, v in iso.items()}}},
+        })
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_log2n, 5)
             try:
@@ -1502,13 +1533,13 @@ def main():
             except Exception as e:
                 line["bn256_n2^18"]["whole_proof_error"] = f"{type(e).__name__}: {e}"
     sharded_info, sharded_weak, cfg4 = None, None, None
-    if dist and world > 1 and args.config4_log2n > 0:
+    if args.full and dist and world > 1 and args.config4_log2n > 0:
         enter("config 4")
         try:
             cfg4 = config4_timing(vm, parallel, shard, args.config4_log2n, world, rank, dist, barrier, torch)
         except Exception as e:
             cfg4 = {"error": f"{type(e).__name__}: {e}"}
-    if dist and (args.sharded_prove or (world > 1 and not args.no_sharded_prove)):
+    if dist and (args.sharded_prove or (args.full and world > 1 and not args.no_sharded_prove)):
         # every rank takes part; a failure here must not cost the headline line (a stuck collective ends in the
         # watchdog: line + error entry, exit status 3)
         enter("sharded prove")
@@ -1533,37 +1564,38 @@ def main():
             line[f"ac20_n2^{args.sharded_log2n + world.bit_length() - 1}_sharded_weak_scaling"] = sharded_weak
         if cfg4 is not None:
             line[f"msm_config4_n2^{args.config4_log2n}_over_{world}_gpus"] = cfg4
-        # the numbers a reader of the last 2000 characters of this line should see (a harness that keeps a tail of stdout
-        # keeps THIS; everything here is also further up, with its context) - last key of the line on purpose
-        try:
-            a20, hf = line.get("ac20_n2^20") or {}, (line.get("ac20_n2^20") or {}).get("hash_floor") or {}
-            busy = ((line["config"].get("gpu_clocks") or {}).get("busy") or {}).get("timed_region") or {}
-            sizes = line.get("msm_other_sizes") or {}
-            line["summary"] = {
-                "G_scalar_mults_per_s": round(line["value"] / 1e9, 4), "ms_per_step": round(line["ms_per_step"], 4),
-                "generators": f"{args.table_rows}-row table" if not args.variable_base else "plain points",
-                "same_run_prepared_form_ms_per_step": round((line.get("prepared_generators_no_multiples") or {}).get("ms_per_step") or 0, 4) or None,
-                "same_run_variable_base_ms_per_step": round((line.get("variable_base") or {}).get("ms_per_step") or 0, 4) or None,
-                "one_commitment_alone_ms": line["config"]["timing"].get("latency_ms_one_commitment_alone"),
-                "k_msm_bucket_alone_ms": round(line["roofline"]["avg_kernel_ms"], 4),
-                "roofline_frac_hbm": round(line["roofline"]["frac"], 5),
-                "alu_frac": round(line["roofline"]["alu"]["frac"] or 0, 4),
-                "traffic_GB_per_launch": round((line["roofline"]["traffic"] or 0) / 1e9, 3) or None,
-                "checked_against": "C oracle (reference algorithm), bit-exact" if oracle_check else "exponent identity",
-                "prove_ms_compact": a20.get("prove_ms_compact"), "verify_ms_compact": a20.get("verify_ms_compact"),
-                "prove_ms_reference": a20.get("prove_ms_reference"), "verify_ms_reference": a20.get("verify_ms_reference"),
-                "sha256_floor_ms": hf.get("hash_floor_ms"), "prove_over_floor": hf.get("prove_over_floor"),
-                "verify_over_floor": hf.get("verify_over_floor"),
-                "prove_outside_hash_ms": hf.get("prove_ms_outside_sha256_update"),
-                "verify_outside_hash_ms": hf.get("verify_ms_outside_sha256_update"),
-                "n2^16_ms_over_crs_table": (sizes.get("n2^16") or {}).get("ms_over_crs_table"),
-                "n2^21_ms_over_crs_table": (sizes.get("n2^21") or {}).get("ms_over_crs_table"),
-                "pinocchio_2^18_whole_proof_ms": (line.get("bn256_n2^18") or {}).get("whole_proof_ms"),
-                "busy_sclk_mhz_median": (busy.get("sclk_mhz") or {}).get("median"),
-                "busy_socket_power_w_median": (busy.get("socket_power_w") or {}).get("median"),
-                "cpu_reference_algorithm_1_core_per_s": round((line.get("cpu_baseline") or {}).get("value") or 0, 1) or None}
-        except Exception as e:
-            line["summary"] = {"error": f"{type(e).__name__}: {e}"}
+        if args.full:
+            # the numbers a reader of the last 2000 characters of this line should see (a harness that keeps a tail of stdout
+            # keeps THIS; everything here is also further up, with its context) - last key of the line on purpose
+            try:
+                a20, hf = line.get("ac20_n2^20") or {}, (line.get("ac20_n2^20") or {}).get("hash_floor") or {}
+                busy = ((line["config"].get("gpu_clocks") or {}).get("busy") or {}).get("timed_region") or {}
+                sizes = line.get("msm_other_sizes") or {}
+                line["summary"] = {
+                    "G_scalar_mults_per_s": round(line["value"] / 1e9, 4), "ms_per_step": round(line["ms_per_step"], 4),
+                    "generators": f"{args.table_rows}-row table" if not args.variable_base else "plain points",
+                    "same_run_prepared_form_ms_per_step": round((line.get("prepared_generators_no_multiples") or {}).get("ms_per_step") or 0, 4) or None,
+                    "same_run_variable_base_ms_per_step": round((line.get("variable_base") or {}).get("ms_per_step") or 0, 4) or None,
+                    "one_commitment_alone_ms": line["config"]["timing"].get("latency_ms_one_commitment_alone"),
+                    "k_msm_bucket_alone_ms": round(line["roofline"]["avg_kernel_ms"], 4),
+                    "roofline_frac_hbm": round(line["roofline"]["frac"], 5),
+                    "alu_frac": round(line["roofline"]["alu"]["frac"] or 0, 4),
+                    "traffic_GB_per_launch": round((line["roofline"]["traffic"] or 0) / 1e9, 3) or None,
+                    "checked_against": "C oracle (reference algorithm), bit-exact" if oracle_check else "exponent identity",
+                    "prove_ms_compact": a20.get("prove_ms_compact"), "verify_ms_compact": a20.get("verify_ms_compact"),
+                    "prove_ms_reference": a20.get("prove_ms_reference"), "verify_ms_reference": a20.get("verify_ms_reference"),
+                    "sha256_floor_ms": hf.get("hash_floor_ms"), "prove_over_floor": hf.get("prove_over_floor"),
+                    "verify_over_floor": hf.get("verify_over_floor"),
+                    "prove_outside_hash_ms": hf.get("prove_ms_outside_sha256_update"),
+                    "verify_outside_hash_ms": hf.get("verify_ms_outside_sha256_update"),
+                    "n2^16_ms_over_crs_table": (sizes.get("n2^16") or {}).get("ms_over_crs_table"),
+                    "n2^21_ms_over_crs_table": (sizes.get("n2^21") or {}).get("ms_over_crs_table"),
+                    "pinocchio_2^18_whole_proof_ms": (line.get("bn256_n2^18") or {}).get("whole_proof_ms"),
+                    "busy_sclk_mhz_median": (busy.get("sclk_mhz") or {}).get("median"),
+                    "busy_socket_power_w_median": (busy.get("socket_power_w") or {}).get("median"),
+                    "cpu_reference_algorithm_1_core_per_s": round((line.get("cpu_baseline") or {}).get("value") or 0, 1) or None}
+            except Exception as e:
+                line["summary"] = {"error": f"{type(e).__name__}: {e}"}
         try:        # RCCL's version banner sits in the C stdio buffer: push it out first, the JSON line is the last line
             import ctypes
             ctypes.CDLL(None).fflush(None)

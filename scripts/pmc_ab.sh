@@ -1,10 +1,11 @@
 #!/bin/bash
 # FETCH_SIZE of k_msm_bucket under two library builds (GPU box): bash scripts/pmc_ab.sh libA.so libB.so
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for L in "$@"; do
   OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_ab_$(basename $L .so)
   rm -rf $OUT; mkdir -p $OUT
-  VMPC_LIB_PATH=$GRAFT_REPO_ROOT/$L rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT -- python3 $GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 2 --batch 1 --no-cpu-baseline --no-prove > /dev/null 2> $OUT.err
+  VMPC_LIB_PATH=$REPO/$L rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT -- python3 $REPO/bench.py --full --steps 4 --warmup 2 --batch 1 --no-cpu-baseline --no-prove > /dev/null 2> $OUT.err
   python3 - <<PY
 import csv, glob
 f = sorted(glob.glob("$OUT/**/*counter_collection.csv", recursive=True))[-1]

@@ -4,8 +4,9 @@
 TAG=$1; CTRS=$2
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CTRS --output-format csv -d $OUT -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-prove --no-pipeline > /dev/null 2> $OUT.err
+rocprofv3 --pmc $CTRS --output-format csv -d $OUT -- python3 $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-prove --no-pipeline > /dev/null 2> $OUT.err
 cd $GRAFT_REPO_ROOT
 python3 - <<PY
 import csv, glob, collections

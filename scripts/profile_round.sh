@@ -11,22 +11,22 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python3 bench.py > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
+python3 bench.py --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
 tail -c 300 "$OUT/bench_$TAG.json"
 cd /tmp
 rm -rf "$OUT"/prof_${TAG}* "$OUT"/pmc_fetch_$TAG "$OUT"/pmc_write_$TAG "$OUT"/pmc_calib_$TAG
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -- \
-    python3 "$REPO/bench.py" --no-cpu-baseline --no-prove > "$OUT/prof_$TAG.bench.json" 2> "$OUT/prof_$TAG.err"
+    python3 "$REPO/bench.py" --full --no-cpu-baseline --no-prove > "$OUT/prof_$TAG.bench.json" 2> "$OUT/prof_$TAG.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${TAG}_alone" -- \
-    python3 "$REPO/bench.py" --no-cpu-baseline --no-prove --no-pipeline > "$OUT/prof_${TAG}_alone.bench.json" 2> "$OUT/prof_${TAG}_alone.err"
+    python3 "$REPO/bench.py" --full --no-cpu-baseline --no-prove --no-pipeline > "$OUT/prof_${TAG}_alone.bench.json" 2> "$OUT/prof_${TAG}_alone.err"
 for MODE in compact reference; do
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${TAG}_prove_$MODE" -- \
       python3 "$REPO/scripts/prove_run.py" $MODE 20 3 > "$OUT/prof_${TAG}_prove_$MODE.json" 2> "$OUT/prof_${TAG}_prove_$MODE.err"
 done
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_$TAG" -- \
-    python3 "$REPO/bench.py" --steps 4 --warmup 2 --batch 1 --no-cpu-baseline --no-prove > /dev/null 2> "$OUT/pmc_fetch_$TAG.err"
+    python3 "$REPO/bench.py" --full --steps 4 --warmup 2 --batch 1 --no-cpu-baseline --no-prove > /dev/null 2> "$OUT/pmc_fetch_$TAG.err"
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_$TAG" -- \
-    python3 "$REPO/bench.py" --steps 4 --warmup 2 --batch 1 --no-cpu-baseline --no-prove > /dev/null 2> "$OUT/pmc_write_$TAG.err"
+    python3 "$REPO/bench.py" --full --steps 4 --warmup 2 --batch 1 --no-cpu-baseline --no-prove > /dev/null 2> "$OUT/pmc_write_$TAG.err"
 # the same counter on reads of KNOWN size in the bucket stage's access pattern (csrc/probe.hip): the factor that turns
 # FETCH_SIZE into bytes for a one-lane-per-128-byte-line gather (MI355X_MICROARCH.md: calibrate other patterns yourself)
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_calib_$TAG" -- \

@@ -126,7 +126,7 @@ def main():
             for ln in f:
                 h, name = ln.split()
                 sources[name] = h
-    summary = {"revision": rev, "kernel_sources_sha256": sources, "calibration": calib, "calibrated": calibrated, "command": "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --steps 4 --warmup 2 "
+    summary = {"revision": rev, "kernel_sources_sha256": sources, "calibration": calib, "calibrated": calibrated, "command": "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --full --steps 4 --warmup 2 "
                           "--batch 1 --no-cpu-baseline --no-prove (one pass per counter, one commitment per launch; "
                           "scripts/profile_round.sh)",
                "correction": "bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024  (gfx950: FETCH_SIZE tallies 128-B "

@@ -40,7 +40,7 @@ def test_two_ranks_of_bench_py_over_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "2", "--log2n", "12",
-           "--dist-backend", "gloo", "--sharded-log2n", "12", "--watchdog-s", "600"]
+           "--dist-backend", "gloo", "--sharded-log2n", "12", "--watchdog-s", "600", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     d = last_json_line(out.stdout)
@@ -62,7 +62,7 @@ def test_two_ranks_started_plain_no_launcher():
     env.update(VMPC_P4_JUMP_MIN_LOG2="9", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
            "--log2n", "12", "--dist-backend", "gloo", "--sharded-log2n", "11", "--config4-log2n", "13",
-           "--watchdog-s", "600"]
+           "--watchdog-s", "600", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -103,7 +103,7 @@ def test_eight_ranks_of_bench_py_over_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "5", "--warmup", "1", "--log2n", "11",
-           "--dist-backend", "gloo", "--sharded-log2n", "12", "--config4-log2n", "15", "--watchdog-s", "900"]
+           "--dist-backend", "gloo", "--sharded-log2n", "12", "--config4-log2n", "15", "--watchdog-s", "900", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     d = last_json_line(out.stdout)
@@ -127,7 +127,7 @@ def test_one_rank_over_rccl_force_collective():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(free_port()))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "1", "--log2n", "14",
            "--force-collective", "--sharded-prove", "--sharded-log2n", "14", "--no-cpu-baseline", "--no-prove",
-           "--watchdog-s", "600"]
+           "--watchdog-s", "600", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     d = last_json_line(out.stdout)
@@ -150,7 +150,7 @@ def test_torch_distributed_fallback_path_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(free_port()))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--log2n", "13",
            "--force-collective", "--comm", "torch", "--sharded-prove", "--sharded-log2n", "12",
-           "--no-cpu-baseline", "--no-prove", "--watchdog-s", "600"]
+           "--no-cpu-baseline", "--no-prove", "--watchdog-s", "600", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     d = last_json_line(out.stdout)
