@@ -368,6 +368,38 @@ int vmpc_bn256_table_msm_dev(vmpc_ctx *ctx, int group, const void *table, size_t
 int vmpc_bn256_table_msm_multi_dev(vmpc_ctx *ctx, int group, const void *const *tables, int n_tables, size_t table_n,
                                    const void *scalars, size_t m, void *out_jacobian);
 
+/* ---- BN-256 optimal-ate pairing (verifiable_mpc/ac20/pairing.py:614-643; the Pinocchio verifier, trinocchio/
+ * pynocchio.py:276-325) -------------------------------------------------------------------------------------------
+ * g1: G1 affine points, 64 B each; g2: twist affine points, 128 B each (x.re, x.im, y.re, y.im); canonical LE, the
+ * all-zero encoding is the point at infinity - the formats of vmpc_bn256_*_msm.  Points are NOT validated here
+ * (vmpc_bn256_validate_dev does that); a point at infinity on either side gives 1.
+ * GT element: 12 canonical 32-byte LE residues, 384 B, in the order of the reference's tower
+ *     f = x w + y in Fp6[w]/(w^2 - tau), x = x.x tau^2 + x.y tau + x.z in Fp2[tau]/(tau^3 - xi), xi = i + 3:
+ *     x.x.re, x.x.im, x.y.re, x.y.im, x.z.re, x.z.im, y.x.re, y.x.im, y.y.re, y.y.im, y.z.re, y.z.im
+ * (1 is y.z.re = 1, every other residue 0).  The value is the reference's pynocchio.pairing(a, b) = optimal_ate(b, a)
+ * coefficient for coefficient. */
+/* gt_out[j] = e(g1[j], g2[j]), j < n */
+int vmpc_bn256_pairing_dev(vmpc_ctx *ctx, const void *g1, const void *g2, size_t n, void *gt_out);
+/* for k < n_products: prod_{offsets[k] <= j < offsets[k+1]} e(g1[j], g2[j]) over n_pairs pairs, ONE final
+ * exponentiation per product; is_one[k] = (product == 1) (1 / 0), gt_out[k] the product (either may be NULL, not
+ * both).  offsets: n_products + 1 device words; an empty range is the product 1; a range outside [0, n_pairs] is
+ * not computed and reports is_one 0 and an all-zero gt_out entry.  Device buffers; nothing is synchronised. */
+int vmpc_bn256_pairing_product_dev(vmpc_ctx *ctx, const void *g1, const void *g2, size_t n_pairs,
+                                   const uint32_t *offsets, size_t n_products, uint8_t *is_one, void *gt_out);
+/* out[b] = s (sum_{i < n_bases} scalars[b][i] bases[i] + sum_{j < n_row_points} row_points[b][j]) for b < batch,
+ * s = -1 if negate else 1: the verifier's IO sums (few bases, many rows), with the proof's own points added as
+ * terms of coefficient 1.  group 1 (64-byte points) or 2 (128-byte); scalars: batch x n_bases 32-byte LE integers
+ * (< 2^256, not reduced); row_points: batch x n_row_points points; out: batch affine points.  Points are not
+ * validated (vmpc_bn256_validate_dev). */
+int vmpc_bn256_lincomb_batch_dev(vmpc_ctx *ctx, int group, const void *bases, size_t n_bases, const void *scalars,
+                                 const void *row_points, size_t n_row_points, size_t batch, int negate, void *out);
+/* host-buffer one-shots of the three above (own context; lincomb validates its points: VMPC_E_NOTONCURVE) */
+int vmpc_bn256_pairing(const uint8_t *g1, const uint8_t *g2, size_t n, uint8_t *gt_out);
+int vmpc_bn256_pairing_product(const uint8_t *g1, const uint8_t *g2, size_t n_pairs, const uint32_t *offsets,
+                               size_t n_products, uint8_t *is_one, uint8_t *gt_out);
+int vmpc_bn256_lincomb_batch(int group, const uint8_t *bases, size_t n_bases, const uint8_t *scalars,
+                             const uint8_t *row_points, size_t n_row_points, size_t batch, int negate, uint8_t *out);
+
 /* SHA-256 of every `chunk_bytes`-sized piece of a device buffer (last piece may be short):
  * out_digests[i] = SHA256(data[i*chunk : (i+1)*chunk]), 32 bytes each.  Leaves of the compact
  * transcript's two-level digests; not used by the reference transcript. */

@@ -43,6 +43,8 @@ SYMBOLS = [
     "vmpc_comm_allgather_dev", "vmpc_comm_points_allsum_dev", "vmpc_p4_create_sharded", "vmpc_gather_probe_dev", "vmpc_bn256_madd_rate",
     "vmpc_stream_create", "vmpc_stream_destroy", "vmpc_ctx_set_bucket_stream",
     "vmpc_set_reference_format", "vmpc_get_reference_format",
+    "vmpc_bn256_pairing_dev", "vmpc_bn256_pairing_product_dev", "vmpc_bn256_lincomb_batch_dev",
+    "vmpc_bn256_pairing", "vmpc_bn256_pairing_product", "vmpc_bn256_lincomb_batch",
 ]
 
 
@@ -141,6 +143,12 @@ def load_library():
         "vmpc_bn256_g2_msm_dev": (i32, [vp, vp, vp, sz, vp]),
         "vmpc_bn256_validate_dev": (i32, [vp, i32, vp, sz, u64p]),
         "vmpc_bn256_fixed_base_dev": (i32, [vp, i32, vp, vp, sz, vp]),
+        "vmpc_bn256_pairing_dev": (i32, [vp, vp, vp, sz, vp]),
+        "vmpc_bn256_pairing_product_dev": (i32, [vp, vp, vp, sz, vp, sz, vp, vp]),
+        "vmpc_bn256_lincomb_batch_dev": (i32, [vp, i32, vp, sz, vp, vp, sz, sz, i32, vp]),
+        "vmpc_bn256_pairing": (i32, [vp, vp, sz, vp]),
+        "vmpc_bn256_pairing_product": (i32, [vp, vp, sz, vp, sz, vp, vp]),
+        "vmpc_bn256_lincomb_batch": (i32, [i32, vp, sz, vp, vp, sz, sz, i32, vp]),
         "vmpc_msm_table_fold_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp]),
         "vmpc_msm_table_fold_table_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp, sz, i32, vp]),
         "vmpc_p4_create": (i32, [vp, vp, sz, sz, i32, i32, i32, vp, vp, vp, ctypes.POINTER(vp)]),
@@ -804,6 +812,22 @@ class Context:
         _check(self.lib.vmpc_bn256_fixed_base_dev(self.handle, group, ctypes.c_void_p(base_ptr),
                                                   ctypes.c_void_p(scalars_ptr), n, ctypes.c_void_p(out_ptr)),
                "vmpc_bn256_fixed_base_dev")
+
+    def bn256_pairing(self, g1_ptr, g2_ptr, n, gt_ptr):
+        _check(self.lib.vmpc_bn256_pairing_dev(self.handle, ctypes.c_void_p(g1_ptr), ctypes.c_void_p(g2_ptr), n,
+                                               ctypes.c_void_p(gt_ptr)), "vmpc_bn256_pairing_dev")
+
+    def bn256_pairing_product(self, g1_ptr, g2_ptr, n_pairs, offsets_ptr, n_products, is_one_ptr, gt_ptr=None):
+        _check(self.lib.vmpc_bn256_pairing_product_dev(self.handle, ctypes.c_void_p(g1_ptr), ctypes.c_void_p(g2_ptr),
+                                                       n_pairs, ctypes.c_void_p(offsets_ptr), n_products,
+                                                       ctypes.c_void_p(is_one_ptr), ctypes.c_void_p(gt_ptr)),
+               "vmpc_bn256_pairing_product_dev")
+
+    def bn256_lincomb_batch(self, group, bases_ptr, n_bases, scalars_ptr, rows_ptr, n_rows, batch, negate, out_ptr):
+        _check(self.lib.vmpc_bn256_lincomb_batch_dev(self.handle, group, ctypes.c_void_p(bases_ptr), n_bases,
+                                                     ctypes.c_void_p(scalars_ptr), ctypes.c_void_p(rows_ptr), n_rows,
+                                                     batch, 1 if negate else 0, ctypes.c_void_p(out_ptr)),
+               "vmpc_bn256_lincomb_batch_dev")
 
     def bn256_validate(self, group, points_ptr, n):
         bad = ctypes.c_uint64()

@@ -9,8 +9,16 @@ zero-knowledge case, adds `delta * evalkey[<t term>]`.  Here every element is ON
 (csrc/bn256.hip) with the zero-knowledge terms appended as extra (scalar, point) pairs.
 Keys and proofs hold `BN256Point` / `BN256TwistPoint` objects (affine coordinates); foreign
 points (e.g. MPyC's Jacobian elements) are accepted if they expose `.normalize()` and three
-indexable coordinates.  Key generation, QAP construction and the pairing-based verifier stay
-with the reference (out of scope).
+indexable coordinates.  Key generation and QAP construction stay with the reference (out of scope,
+SURVEY.md 2 rows 10, 13).
+
+    pairing          verifiable_mpc/trinocchio/pynocchio.py:67-72 (ac20/pairing.py optimal_ate)
+    verify           verifiable_mpc/trinocchio/pynocchio.py:276-325
+    verify_batch     the same for many proofs over one verification key
+
+The verifier evaluates each of the five checks as "product of pairings == 1" (csrc/bn256_pairing.hip: one lane
+per Miller loop, one lane per product for the final exponentiation); pairing values equal the reference's
+coefficient for coefficient.  Off-curve points raise ValueError; G2 subgroup membership is not checked.
 """
 import numpy as np
 
@@ -425,3 +433,262 @@ def compute_proof(qap, c, h, evalkey, deltas=None):
             zk((dv, "r_v*beta*t*g1"), (dw, "r_w*beta*t*g1"), (dy, "r_y*beta*t*g1"))),
         "h*g1": msm(h_scalars, h_points),
     }
+
+
+# ---- the pairing and the verifier (trinocchio/pynocchio.py:67-72, 276-325; csrc/bn256_pairing.hip) ----------------
+
+class GT:
+    """An element of the pairing's target group: the 12 coefficients of the reference's tower element, in the order
+    of include/vmpc.h (x.x.re, x.x.im, x.y.re, ..., y.z.im of f = x w + y).  Immutable; 1 is (0, ..., 0, 1, 0)."""
+    __slots__ = ("coeffs",)
+
+    def __init__(self, coeffs):
+        coeffs = tuple(int(v) % P for v in coeffs)
+        if len(coeffs) != 12:
+            raise ValueError("a GT element has 12 coefficients")
+        object.__setattr__(self, "coeffs", coeffs)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("GT is immutable")
+
+    @classmethod
+    def from_bytes(cls, raw):
+        return cls(int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(12))
+
+    def is_one(self):
+        return self.coeffs == _GT_ONE
+
+    def __eq__(self, other):
+        return isinstance(other, GT) and self.coeffs == other.coeffs
+
+    def __hash__(self):
+        return hash(("GT", self.coeffs))
+
+    def __repr__(self):
+        return "GT(" + ", ".join(hex(v) for v in self.coeffs) + ")"
+
+
+_GT_ONE = (0,) * 10 + (1, 0)
+
+
+def _validate(ctx, group, buf, n, what):
+    if n and ctx.bn256_validate(group, buf.ptr, n):
+        raise ValueError(f"{what}: point not on the {'BN-256 curve' if group == 1 else 'BN-256 twist'}")
+
+
+def pairing(a, b, ctx=None):
+    """e(a, b) for a in G1 and b on the twist, the reference's pynocchio.pairing(a, b) = optimal_ate(b, a), as a GT.
+    Accepts BN256Point / BN256TwistPoint and foreign MPyC-style points; the point at infinity gives 1."""
+    ctx = ctx or get_context()
+    (ga, ra), (gb, rb) = _as_bytes(a), _as_bytes(b)
+    if ga != 1 or gb != 2:
+        raise ValueError("pairing(a, b): a must be a G1 point and b a twist point")
+    da, db, out = ctx.upload(np.frombuffer(ra, np.uint8)), ctx.upload(np.frombuffer(rb, np.uint8)), ctx.alloc(384)
+    _validate(ctx, 1, da, 1, "pairing: first argument")
+    _validate(ctx, 2, db, 1, "pairing: second argument")
+    ctx.bn256_pairing(da.ptr, db.ptr, 1, out.ptr)
+    ctx.sync()
+    return GT.from_bytes(ctx.download(out.ptr, 384).tobytes())
+
+
+def pairing_product(g1_points, g2_points, offsets, ctx=None):
+    """products prod_{offsets[k] <= j < offsets[k+1]} e(g1_points[j], g2_points[j]) -> (list of GT, list of bool
+    is_one); one final exponentiation per product"""
+    ctx = ctx or get_context()
+    assert len(g1_points) == len(g2_points)
+    g1 = _points_array(g1_points, 1, "pairing_product: G1 points")
+    g2 = _points_array(g2_points, 2, "pairing_product: twist points")
+    gt, ones = _pairing_product_arrays(ctx, g1, g2, offsets, want_gt=True)
+    return [GT.from_bytes(gt[384 * k:384 * k + 384]) for k in range(len(offsets) - 1)], ones
+
+
+def _points_array(points, group, what):
+    enc = [_as_bytes(p) for p in points]
+    if any(g != group for g, _ in enc):
+        raise ValueError(f"{what}: wrong group")
+    width = 64 if group == 1 else 128
+    return np.frombuffer(b"".join(r for _, r in enc), np.uint8).reshape(-1, width)
+
+
+def _pairing_product_arrays(ctx, g1, g2, offsets, want_gt=False, validate=True):
+    n, n_products = len(g1), len(offsets) - 1
+    off = np.asarray(offsets, dtype=np.uint32)
+    if n_products < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off.astype(np.int64)) < 0):
+        raise ValueError("offsets must rise from 0 to the number of pairs")
+    d1, d2 = ctx.upload(g1) if n else ctx.alloc(64), ctx.upload(g2) if n else ctx.alloc(128)
+    if validate:
+        _validate(ctx, 1, d1, n, "pairing_product: G1 points")
+        _validate(ctx, 2, d2, n, "pairing_product: twist points")
+    doff, dones = ctx.upload(off), ctx.alloc(max(n_products, 1))
+    dgt = ctx.alloc(384 * n_products) if want_gt else None
+    ctx.bn256_pairing_product(d1.ptr, d2.ptr, n, doff.ptr, n_products, dones.ptr, dgt.ptr if dgt else None)
+    ctx.sync()
+    ones = [bool(v) for v in ctx.download(dones.ptr, n_products)]
+    gt = ctx.download(dgt.ptr, 384 * n_products).tobytes() if want_gt else None
+    return gt, ones
+
+
+_P_WORDS = np.array([(P >> (32 * k)) & 0xFFFFFFFF for k in range(8)], dtype=np.int64)
+
+
+def _neg_g1_rows(rows):
+    """(n, 64) uint8 affine G1 points -> their negatives (y -> p - y; infinity stays all zero)"""
+    out = np.array(rows, dtype=np.uint8, copy=True)
+    if not len(out):
+        return out
+    y = out[:, 32:].copy().view("<u4").astype(np.int64)
+    res = np.zeros_like(y)
+    borrow = np.zeros(len(y), np.int64)
+    for k in range(8):
+        d = _P_WORDS[k] - y[:, k] - borrow
+        borrow = (d < 0).astype(np.int64)
+        res[:, k] = d + (borrow << 32)
+    inf = ~out.any(axis=1)
+    res[inf] = 0
+    out[:, 32:] = res.astype("<u4").view(np.uint8).reshape(-1, 32)
+    return out
+
+
+# proof elements in the order the verifier reads them (group 1 except the one twist element)
+_PROOF_G1 = ("r_v*v_mid*g1", "r_y*y_mid*g1", "r_v*alpha_v*v_mid*g1", "r_w*alpha_w*w_mid*g1", "r_y*alpha_y*y_mid*g1",
+             "r_v*beta*v_mid+r_w*beta*w_mid+r_y*beta*y_mid*g1", "h*g1")
+_PROOF_G2 = "r_w*w_mid*g2"
+_CHECKS = ("H", "V", "W", "Y", "Z")
+# pairs per check, in order: H 3, V 2, W 2, Y 2, Z 3 (12 per proof)
+_CHECK_OFFSETS = (0, 3, 5, 7, 9, 12)
+
+
+class _VerifyingKey:
+    """The verification key on the device: the bases of the three IO sums and the fixed pairing arguments,
+    converted and validated once."""
+
+    def __init__(self, ctx, qap, verikey):
+        self.io = list(qap.indices_io)
+
+        def pts(names, group):
+            for name in names:
+                if name not in verikey:
+                    raise KeyError(name)
+            arr = _points_array([verikey[n] for n in names], group, "verikey")
+            buf = ctx.upload(arr)
+            if ctx.bn256_validate(group, buf.ptr, len(names)):
+                for j, name in enumerate(names):
+                    one = ctx.upload(arr[j:j + 1])
+                    _validate(ctx, group, one, 1, f"verikey[{name!r}]")
+            return arr, buf
+
+        self.v_bases = pts(["r_v*v0*g1"] + [f"r_v*v{i}*g1" for i in self.io], 1)[1]
+        self.w_bases = pts(["r_w*w0*g2"] + [f"r_w*w{i}*g2" for i in self.io], 2)[1]
+        self.y_bases = pts([f"r_y*y{i}*g1" for i in self.io], 1)[1]
+        g1_fixed, _ = pts(["alpha_w*g1", "beta*gamma*g1"], 1)
+        g2_fixed, _ = pts(["g2", "r_y*t*g2", "alpha_v*g2", "alpha_y*g2", "gamma*g2", "beta*gamma*g2"], 2)
+        self.alpha_w_g1 = g1_fixed[0]
+        self.neg_beta_gamma_g1 = _neg_g1_rows(g1_fixed[1:2])[0]
+        (self.g2, self.r_y_t_g2, self.alpha_v_g2, self.alpha_y_g2, self.gamma_g2,
+         self.beta_gamma_g2) = g2_fixed
+
+
+def _proof_arrays(proofs):
+    """(7, B, 64) G1 elements in _PROOF_G1 order and (B, 128) twist elements"""
+    g1 = np.empty((len(_PROOF_G1), len(proofs), 64), np.uint8)
+    g2 = np.empty((len(proofs), 128), np.uint8)
+    for b, proof in enumerate(proofs):
+        for k, name in enumerate(_PROOF_G1):
+            grp, raw = _as_bytes(proof[name])
+            if grp != 1:
+                raise ValueError(f"proof {b}: {name!r} is not a G1 point")
+            g1[k, b] = np.frombuffer(raw, np.uint8)
+        grp, raw = _as_bytes(proof[_PROOF_G2])
+        if grp != 2:
+            raise ValueError(f"proof {b}: {_PROOF_G2!r} is not a twist point")
+        g2[b] = np.frombuffer(raw, np.uint8)
+    return g1, g2
+
+
+def _first_bad(ctx, group, arr):
+    """index of the first point of arr (n, width) that is not on its curve (arr holds at least one)"""
+    lo, hi = 0, len(arr)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        buf = ctx.upload(arr[lo:mid])
+        if ctx.bn256_validate(group, buf.ptr, mid - lo):
+            hi = mid
+        else:
+            lo = mid
+    return lo
+
+
+def _verify_many(ctx, vk, proofs, cs):
+    B = len(proofs)
+    if B == 0:
+        return []
+    if len(cs) != B:
+        raise ValueError("one witness per proof")
+    pg1, pg2 = _proof_arrays(proofs)
+    dg1, dg2 = ctx.upload(pg1), ctx.upload(pg2)
+    for k, name in enumerate(_PROOF_G1):
+        if ctx.bn256_validate(1, dg1.ptr + 64 * B * k, B):
+            b = _first_bad(ctx, 1, pg1[k])
+            raise ValueError(f"proof {b}: {name!r} is not on the BN-256 curve")
+    if ctx.bn256_validate(2, dg2.ptr, B):
+        b = _first_bad(ctx, 2, pg2)
+        raise ValueError(f"proof {b}: {_PROOF_G2!r} is not on the BN-256 twist")
+    # IO sums: A = v0 + sum c_i v_i + pi_v, Bt = w0 + sum c_i w_i + pi_w, C = -(sum c_i y_i + pi_y), Z = -(pi_v + pi_y)
+    n_io = len(vk.io)
+    one = (1).to_bytes(32, "little")
+    c_io = scalars_to_array([int(c[i]) % ORDER for c in cs for i in vk.io]).reshape(B, n_io, 32)
+    sc_vw = np.concatenate([np.tile(np.frombuffer(one, np.uint8), (B, 1, 1)), c_io], axis=1)
+    d_vw, d_y = ctx.upload(np.ascontiguousarray(sc_vw)), ctx.upload(np.ascontiguousarray(c_io)) if n_io else None
+    d_vy = ctx.upload(np.ascontiguousarray(np.stack([pg1[0], pg1[1]], axis=1)))
+    outA, outB, outC, outZ = ctx.alloc(64 * B), ctx.alloc(128 * B), ctx.alloc(64 * B), ctx.alloc(64 * B)
+    ctx.bn256_lincomb_batch(1, vk.v_bases.ptr, n_io + 1, d_vw.ptr, dg1.ptr, 1, B, False, outA.ptr)
+    ctx.bn256_lincomb_batch(2, vk.w_bases.ptr, n_io + 1, d_vw.ptr, dg2.ptr, 1, B, False, outB.ptr)
+    ctx.bn256_lincomb_batch(1, vk.y_bases.ptr if n_io else None, n_io, d_y.ptr if n_io else None,
+                            dg1.ptr + 64 * B, 1, B, True, outC.ptr)
+    ctx.bn256_lincomb_batch(1, None, 0, None, d_vy.ptr, 2, B, True, outZ.ptr)
+    ctx.sync()
+    A = ctx.download(outA.ptr, 64 * B).reshape(B, 64)
+    Bt = ctx.download(outB.ptr, 128 * B).reshape(B, 128)
+    C = ctx.download(outC.ptr, 64 * B).reshape(B, 64)
+    Z = ctx.download(outZ.ptr, 64 * B).reshape(B, 64)
+    v, y, av, aw, ay, beta, h = pg1
+    g1 = np.empty((B, 12, 64), np.uint8)
+    g2 = np.empty((B, 12, 128), np.uint8)
+    # H: e(A, Bt) e(-(yio + pi_y), g2) e(-pi_h, r_y t g2) == 1
+    g1[:, 0], g2[:, 0] = A, Bt
+    g1[:, 1], g2[:, 1] = C, vk.g2
+    g1[:, 2], g2[:, 2] = _neg_g1_rows(h), vk.r_y_t_g2
+    # V: e(pi_v, alpha_v g2) e(-pi_av, g2) == 1
+    g1[:, 3], g2[:, 3] = v, vk.alpha_v_g2
+    g1[:, 4], g2[:, 4] = _neg_g1_rows(av), vk.g2
+    # W: e(alpha_w g1, pi_w) e(-pi_aw, g2) == 1
+    g1[:, 5], g2[:, 5] = vk.alpha_w_g1, pg2
+    g1[:, 6], g2[:, 6] = _neg_g1_rows(aw), vk.g2
+    # Y: e(pi_ay, g2) e(-pi_y, alpha_y g2) == 1
+    g1[:, 7], g2[:, 7] = ay, vk.g2
+    g1[:, 8], g2[:, 8] = _neg_g1_rows(y), vk.alpha_y_g2
+    # Z: e(pi_beta, gamma g2) e(-(pi_v + pi_y), beta gamma g2) e(-beta gamma g1, pi_w) == 1
+    g1[:, 9], g2[:, 9] = beta, vk.gamma_g2
+    g1[:, 10], g2[:, 10] = Z, vk.beta_gamma_g2
+    g1[:, 11], g2[:, 11] = vk.neg_beta_gamma_g1, pg2
+    offsets = (np.arange(B, dtype=np.int64)[:, None] * 12 + np.array(_CHECK_OFFSETS[:-1])).reshape(-1)
+    offsets = np.append(offsets, 12 * B)
+    _, ones = _pairing_product_arrays(ctx, g1.reshape(-1, 64), g2.reshape(-1, 128), offsets, validate=False)
+    return [dict(zip(_CHECKS, ones[5 * b:5 * b + 5])) for b in range(B)]
+
+
+def verify(qap, verikey, proof, c, ctx=None):
+    """The reference's verify (trinocchio/pynocchio.py:276-325): {"H", "V", "W", "Y", "Z"} -> bool.  Each check
+    lhs == rhs is evaluated as the equivalent product of pairings == 1 (the right-hand side's G1 argument negated,
+    the point sums folded into the IO linear combinations as terms of coefficient 1); the five products run in ONE
+    launch.  Reads only qap.indices_io.  Points not on their curve raise ValueError (the reference would compute on
+    them); G2 subgroup membership is not checked."""
+    ctx = ctx or get_context()
+    return _verify_many(ctx, _VerifyingKey(ctx, qap, verikey), [proof], [c])[0]
+
+
+def verify_batch(qap, verikey, proofs, cs, ctx=None):
+    """[verify(qap, verikey, p, c) for p, c in zip(proofs, cs)] with the key uploaded once, each IO sum of all proofs
+    in one launch and all 12 B pairings in one product launch"""
+    ctx = ctx or get_context()
+    return _verify_many(ctx, _VerifyingKey(ctx, qap, verikey), list(proofs), list(cs))
