@@ -475,12 +475,37 @@ def _protocol_4_prover_loop(g_hat, k, Q, L_tilde, z_hat, gf, proof, round_i, tra
             table_rounds.close()
 
 
+_AGAIN = object()
+
+
+def _table_call(call, *args):
+    """call(*args) on the round context, or _AGAIN if it answered VMPC_E_AGAIN: a pair took the fused short path and
+    met scalars beyond its capacities (csrc/msm_short.hip; a z_hat that is constant or small-valued, or folds to such a
+    vector).  The context is then of no further use (csrc/prover.hip poisons it) and its status words have been read
+    (vmpc_ctx_sync): the caller closes it and computes the round's pair the ordinary way."""
+    try:
+        return call(*args)
+    except _native.VmpcError as e:
+        if e.code != _native.E_AGAIN:
+            raise
+        return _AGAIN
+
+
+def _table_pair(call, *args):
+    """_table_call for a call that returns A_i, B_i: the two points, or None (VMPC_E_AGAIN)"""
+    ab = _table_call(call, *args)
+    return None if ab is _AGAIN else (Ed25519Point.from_affine_bytes(ab[0]), Ed25519Point.from_affine_bytes(ab[1]))
+
+
 def _protocol_4_prover_rounds(g_hat, k, Q, L_tilde, z_hat, gf, proof, round_i, transcript, tail_cs, early, table_rounds):
     fed = 0                  # challenges the context has been given since its last fold
     if table_rounds is not None:
-        a0, b0 = table_rounds.round(None)
-        first = (Ed25519Point.from_affine_bytes(a0), Ed25519Point.from_affine_bytes(b0))
-        early = lambda: first                                                    # noqa: E731
+        first = _table_pair(table_rounds.round, None)
+        if first is None:
+            table_rounds.close()
+            table_rounds = None
+        else:
+            early = lambda: first                                                # noqa: E731
     while True:
         if _on_device(L_tilde.coeffs, z_hat):
             z_hat = pivot._as_device(z_hat)
@@ -490,15 +515,22 @@ def _protocol_4_prover_rounds(g_hat, k, Q, L_tilde, z_hat, gf, proof, round_i, t
                 and isinstance(L_tilde.coeffs, ScalarVector) and len(g_hat) == m and m >= 4 and m & (m - 1) == 0 \
                 and _tabulated(g_hat, k, whole=True):
             return _protocol_4_native_rounds(g_hat, k, L_tilde, z_hat, gf, proof, round_i, transcript)
-        z_l, z_r, gamma_a, gamma_b = _round_prover_scalars(L_tilde, z_hat, half, gf, exponents=early is None)
+        pair = None
+        if early is not None:
+            # (collected before the scalars: a pair the round context could not make - None - needs the exponents)
+            pair = early()
+            early = None
+            if pair is None:
+                table_rounds.close()
+                table_rounds = None
+        z_l, z_r, gamma_a, gamma_b = _round_prover_scalars(L_tilde, z_hat, half, gf, exponents=pair is None)
         logger_cp.debug("Calculate A_i, B_i.")
         if tail_cs is None and transcript.mode == "compact" and isinstance(z_l, ScalarVector) \
                 and len(g_hat) == m and m >= 4 and (len(g_hat) <= TAIL_BASE or _tabulated(g_hat, k)):
             tail_cs = []
             tail_products = ScalarVector.empty(len(g_hat), g_hat.ctx)     # challenge products per generator
-        if early is not None:
-            A, B = early()
-            early = None
+        if pair is not None:
+            A, B = pair
         elif tail_cs is not None:
             ctx = g_hat.ctx
             v_a, v_b = ScalarVector.empty(len(g_hat), ctx), ScalarVector.empty(len(g_hat), ctx)
@@ -534,9 +566,12 @@ def _protocol_4_prover_rounds(g_hat, k, Q, L_tilde, z_hat, gf, proof, round_i, t
                         pair_after_fold = True          # (own stream: asked for right after the fold is enqueued)
                     else:
                         # the NEXT round's pair from the round context, before this round's exact fold is enqueued
-                        an, bn = table_rounds.round(c)
-                        nxt = (Ed25519Point.from_affine_bytes(an), Ed25519Point.from_affine_bytes(bn))
-                        early = lambda nxt=nxt: nxt                              # noqa: E731
+                        nxt = _table_pair(table_rounds.round, c)
+                        if nxt is None:
+                            table_rounds.close()
+                            table_rounds = None
+                        else:
+                            early = lambda nxt=nxt: nxt                          # noqa: E731
                 else:
                     table_rounds.close()
                     table_rounds = None
@@ -555,21 +590,26 @@ def _protocol_4_prover_rounds(g_hat, k, Q, L_tilde, z_hat, gf, proof, round_i, t
                 # own stream: the pair is ENQUEUED right after the exact fold's first slice (it runs beside it; the
                 # other slices are ordered behind it) and collected when the next round asks for it - the host work
                 # in between (the rest of the fold's launches, Q, L~'s text) no longer waits for the pair
-                def hook(more, rounds=table_rounds, main=g_hat.ctx):
-                    rounds.round_begin(c)
+                begun = []
+
+                def hook(more, rounds=table_rounds, main=g_hat.ctx, begun=begun):
+                    begun.append(_table_call(rounds.round_begin, c) is not _AGAIN)
                     if more:
                         main.wait_for(rounds.ctx)
 
-                def early(rounds=table_rounds, fold_due=fold_due):
-                    an, bn = rounds.round_end()
-                    if fold_due:
-                        # the context's one fold of its generators, behind the pair, under the next hash
-                        rounds.prefold()
-                    return Ed25519Point.from_affine_bytes(an), Ed25519Point.from_affine_bytes(bn)
+                def early(rounds=table_rounds, fold_due=fold_due, begun=begun):
+                    # (None: the context could not make the pair, see _table_call)
+                    pair = _table_pair(rounds.round_end) if begun and begun[0] else None
+                    if pair is not None and fold_due and _table_call(rounds.prefold) is _AGAIN:
+                        # (the context's one fold of its generators, behind the pair, under the next hash)
+                        pair = None
+                    return pair
             g_hat = g_l.fold(g_r, c, stream_text=transcript.mode == "reference", after_first=hook)
-            if fold_due and not pair_after_fold:
-                # the context's one fold of its generators, behind the exact fold just enqueued, under the next hash
-                table_rounds.prefold()
+            if fold_due and not pair_after_fold and _table_call(table_rounds.prefold) is _AGAIN:
+                # (the context's one fold of its generators, behind the exact fold just enqueued, under the next hash;
+                # the next round's pair has been collected already)
+                table_rounds.close()
+                table_rounds = None
             if ahead and not EARLY_PAIR_FIRST:
                 early = _early_pair_launch(unfolded, k, half, prep)
         if transcript.mode == "reference":

@@ -741,14 +741,38 @@ static int p4_round_enqueue(vmpc_p4 *p, const uint32_t *c_mem) {
     return VMPC_OK;
 }
 
+// Z_a Z_b = 0: one of the pair is the void result of a fused short-path commitment that met scalars beyond its
+// capacities (msm_short.hip: no point has Z = 0)
+static bool p4_pair_void(const uint8_t ext[256]) {
+    uint8_t zz[32];
+    fe51::to_bytes(zz, fe51::mul(fe51::from_bytes(ext + 64), fe51::from_bytes(ext + 128 + 64)));
+    for (int i = 0; i < 32; i++)
+        if (zz[i]) return false;
+    return true;
+}
+
 static int p4_round_collect(vmpc_p4 *p, uint8_t out_A[64], uint8_t out_B[64]) {
     vmpc_ctx *ctx = p->ctx;
     const uint8_t *ext = (const uint8_t *)ctx->pin_out;
     // The first round's synchronisation also fetches the device status words (a non-canonical scalar in the caller's
     // z_hat / L~ shows up in this round's recoding); later rounds only consume scalars this context produced, so
-    // they just wait for the stream - vmpc_p4_finish checks the status once more at the end.
+    // they just wait for the stream.  Their pairs can still overflow the fused short path, though (a vector that folds
+    // to a constant or to small values puts one bucket's worth of entries into a bin): the void pair says so itself,
+    // and then the status words are read and cleared after all and the round answers VMPC_E_AGAIN - never (0, 0)
+    // points.  (The rounds vmpc_p4_run_compact queues ahead are not collected here: vmpc_p4_finish's status check
+    // answers for them.)
     if (p->committed == 0 || vmpc_getenv_experimental("VMPC_P4_FULL_SYNC")) VMPC_CHECK(vmpc_ctx_sync(ctx));
     else VMPC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (p4_pair_void(ext)) {
+        int rc = vmpc_ctx_sync(ctx);          // (clears the status words, starts the short path's back-off)
+        if (rc == VMPC_OK) {
+            snprintf(vmpc_err_buf, sizeof vmpc_err_buf,
+                     "vmpc_p4: round %d's pair is void (the short-commitment path overflowed): repeat on the general path",
+                     p->round);
+            rc = VMPC_E_AGAIN;
+        }
+        return rc;
+    }
     p->committed++;
     p4_affine_pair(ext, out_A, out_B);
     return VMPC_OK;
