@@ -38,6 +38,7 @@ extern "C" {
 #define VMPC_E_NOMEM (-12)
 #define VMPC_E_HIP (-5)         /* HIP runtime error, see vmpc_last_error() */
 #define VMPC_E_NODEV (-19)      /* no GPU visible */
+#define VMPC_E_RANGE (-75)      /* a length above what the entry supports (it states its cap); nothing was written */
 #define VMPC_E_AGAIN (-11)      /* vmpc_ctx_sync: a commitment took the fused short path (16-row table of <= 2^17 columns)
                                  * and its scalars were skewed beyond that path's fixed capacities (e.g. a witness of
                                  * mostly small values: > ~24 K non-zero digits in one bin); nothing of the call's
@@ -399,6 +400,24 @@ int vmpc_bn256_pairing_product(const uint8_t *g1, const uint8_t *g2, size_t n_pa
                                size_t n_products, uint8_t *is_one, uint8_t *gt_out);
 int vmpc_bn256_lincomb_batch(int group, const uint8_t *bases, size_t n_bases, const uint8_t *scalars,
                              const uint8_t *row_points, size_t n_row_points, size_t batch, int negate, uint8_t *out);
+
+/* ---- GF(n) for the BN-256 group order n: the scalar side of the knowledge-of-exponent pivot (AC20 section 9,
+ * verifiable_mpc/ac20/knowledge_of_exponent.py) ------------------------------------------------------------------
+ * Scalars: 32 bytes little-endian.  INPUTS may be any 32-byte value (they are reduced mod n when they are loaded);
+ * outputs are canonical residues < n. */
+/* out[k] = sum_{i + j = k} a[i] * b[j] mod n for k < na + nb - 1: the product of two coefficient vectors, the
+ * prover's c_poly = c_poly_lhs * c_poly_rhs of knowledge_of_exponent.py:121-123 (verifiable_mpc/tools/qap_creator.py
+ * Poly.__mul__, O(n^2) Python).  na, nb >= 1.  Cap: na and nb at most VMPC_BN256_FR_POLY_MAX each; above it the
+ * entry answers VMPC_E_RANGE before it looks at any pointer and writes nothing.  `out` must not overlap a or b.
+ * Uses the context arena (partial sums of a large product). */
+#define VMPC_BN256_FR_POLY_MAX ((size_t)1 << 20)
+int vmpc_bn256_fr_poly_mul_dev(vmpc_ctx *ctx, const void *a, size_t na, const void *b, size_t nb, void *out);
+/* host-buffer form of the above (own context, synchronous) */
+int vmpc_bn256_fr_poly_mul(const uint8_t *a, size_t na, const uint8_t *b, size_t nb, uint8_t *out);
+/* out[i] = scale * z^(i+1) mod n for i < count (z, scale: one 32-byte device scalar each): the exponents of the
+ * trusted setup, which knowledge_of_exponent.py:52-66 reaches by 2n sequential `g1_base ** z` / `g2_base ** z` on the
+ * points themselves; here the 2n points are vmpc_bn256_fixed_base_dev of these exponents. */
+int vmpc_bn256_fr_powers_dev(vmpc_ctx *ctx, const void *z, const void *scale, size_t count, void *out);
 
 /* SHA-256 of every `chunk_bytes`-sized piece of a device buffer (last piece may be short):
  * out_digests[i] = SHA256(data[i*chunk : (i+1)*chunk]), 32 bytes each.  Leaves of the compact

@@ -15,10 +15,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VMPC_LIB_PATH") or os.path.join(_HERE, "libvmpc_hip.so")   # override: developer A/B builds
 
 OK = 0
-E_INVAL, E_NONCANON, E_NOTONCURVE, E_NOMEM, E_HIP, E_NODEV, E_AGAIN = -22, -34, -33, -12, -5, -19, -11
+E_INVAL, E_NONCANON, E_NOTONCURVE, E_NOMEM, E_HIP, E_NODEV, E_AGAIN, E_RANGE = -22, -34, -33, -12, -5, -19, -11, -75
 _ERR_NAMES = {E_AGAIN: "VMPC_E_AGAIN", E_INVAL: "VMPC_E_INVAL", E_NONCANON: "VMPC_E_NONCANON",
               E_NOTONCURVE: "VMPC_E_NOTONCURVE", E_NOMEM: "VMPC_E_NOMEM", E_HIP: "VMPC_E_HIP",
-              E_NODEV: "VMPC_E_NODEV"}
+              E_NODEV: "VMPC_E_NODEV", E_RANGE: "VMPC_E_RANGE"}
 
 SCALAR_BYTES, AFFINE_BYTES, PROJ_BYTES, EXT_BYTES = 32, 64, 96, 128
 
@@ -45,6 +45,7 @@ SYMBOLS = [
     "vmpc_set_reference_format", "vmpc_get_reference_format",
     "vmpc_bn256_pairing_dev", "vmpc_bn256_pairing_product_dev", "vmpc_bn256_lincomb_batch_dev",
     "vmpc_bn256_pairing", "vmpc_bn256_pairing_product", "vmpc_bn256_lincomb_batch",
+    "vmpc_bn256_fr_poly_mul_dev", "vmpc_bn256_fr_poly_mul", "vmpc_bn256_fr_powers_dev",
 ]
 
 
@@ -149,6 +150,9 @@ def load_library():
         "vmpc_bn256_pairing": (i32, [vp, vp, sz, vp]),
         "vmpc_bn256_pairing_product": (i32, [vp, vp, sz, vp, sz, vp, vp]),
         "vmpc_bn256_lincomb_batch": (i32, [i32, vp, sz, vp, vp, sz, sz, i32, vp]),
+        "vmpc_bn256_fr_poly_mul_dev": (i32, [vp, vp, sz, vp, sz, vp]),
+        "vmpc_bn256_fr_poly_mul": (i32, [vp, sz, vp, sz, vp]),
+        "vmpc_bn256_fr_powers_dev": (i32, [vp, vp, vp, sz, vp]),
         "vmpc_msm_table_fold_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp]),
         "vmpc_msm_table_fold_table_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp, sz, i32, vp]),
         "vmpc_p4_create": (i32, [vp, vp, sz, sz, i32, i32, i32, vp, vp, vp, ctypes.POINTER(vp)]),
@@ -829,6 +833,17 @@ class Context:
                                                      batch, 1 if negate else 0, ctypes.c_void_p(out_ptr)),
                "vmpc_bn256_lincomb_batch_dev")
 
+    def bn256_fr_poly_mul(self, a_ptr, na, b_ptr, nb, out_ptr):
+        """out[k] = sum_{i+j=k} a[i] b[j] mod the BN-256 group order (na + nb - 1 scalars); VmpcError E_RANGE above
+        the library's cap, before anything is read or written"""
+        _check(self.lib.vmpc_bn256_fr_poly_mul_dev(self.handle, ctypes.c_void_p(a_ptr), na, ctypes.c_void_p(b_ptr), nb,
+                                                   ctypes.c_void_p(out_ptr)), "vmpc_bn256_fr_poly_mul_dev")
+
+    def bn256_fr_powers(self, z_ptr, scale_ptr, count, out_ptr):
+        """out[i] = scale * z^(i+1) mod the BN-256 group order"""
+        _check(self.lib.vmpc_bn256_fr_powers_dev(self.handle, ctypes.c_void_p(z_ptr), ctypes.c_void_p(scale_ptr),
+                                                 count, ctypes.c_void_p(out_ptr)), "vmpc_bn256_fr_powers_dev")
+
     def bn256_validate(self, group, points_ptr, n):
         bad = ctypes.c_uint64()
         _check(self.lib.vmpc_bn256_validate_dev(self.handle, group, ctypes.c_void_p(points_ptr), n,
@@ -1164,4 +1179,17 @@ def bn256_msm(group, scalars, points):
     out = np.zeros(width, dtype=np.uint8)
     fn = lib.vmpc_bn256_g1_msm if group == 1 else lib.vmpc_bn256_g2_msm
     _check(fn(_np_ptr(s), _np_ptr(p), len(s), _np_ptr(out)), f"vmpc_bn256_g{group}_msm")
+    return out
+
+
+BN256_FR_POLY_MAX = 1 << 20      # VMPC_BN256_FR_POLY_MAX of include/vmpc.h
+
+
+def bn256_fr_poly_mul(a, b):
+    """host arrays (na, 32), (nb, 32) uint8 -> (na + nb - 1, 32) canonical residues of the product mod the BN-256
+    group order (own context, synchronous)"""
+    lib = load_library()
+    a, b = as_bytes_array(a, 32), as_bytes_array(b, 32)
+    out = np.zeros((max(len(a) + len(b) - 1, 0), 32), np.uint8)
+    _check(lib.vmpc_bn256_fr_poly_mul(_np_ptr(a), len(a), _np_ptr(b), len(b), _np_ptr(out)), "vmpc_bn256_fr_poly_mul")
     return out

@@ -1,0 +1,194 @@
+// The scalar side of the knowledge-of-exponent pivot over BN-256 (AC20 section 9,
+// verifiable_mpc/ac20/knowledge_of_exponent.py): arithmetic in GF(n), n the group order (csrc/fr_bn.h).
+//
+//   k_frbn_polymul   c = a * b for two coefficient vectors: the prover's c_poly_lhs * c_poly_rhs
+//                    (knowledge_of_exponent.py:121-123; qap_creator.Poly.__mul__ is O(n^2) Python).  n - 1 = 2^5 * odd, so
+//                    there is no NTT of useful length in this field; the product is the schoolbook one.
+//   k_frbn_powers    scale * z^(i+1): the exponents of the trusted setup (knowledge_of_exponent.py:52-66 reaches them by
+//                    2n sequential scalar multiplications of a point).
+//
+// Product kernel shape: output-stationary.  A workgroup owns a tile of KOE_TILE consecutive output coefficients, one
+// per lane, and one SEGMENT of the index i of a: out[k] += a[i] b[k - i] for i in the segment.  Chunks of KOE_CHUNK
+// coefficients of a and the KOE_CHUNK + KOE_TILE - 1 coefficients of b that the tile meets them with are staged in
+// LDS, reduced mod n on the way in and zero where the index leaves the vector, so the inner loop has no bounds.  b is
+// stored limb-major (lane t reads word t + const of a limb row: consecutive banks), a element-major (every lane reads
+// the same element: a broadcast).  A lane adds unreduced 8 x 8-limb products into frbn_acc and reduces once.
+// The triangle (tiles near k = n meet the whole of a, tiles at the ends almost nothing) is balanced by the segments:
+// a tile is cut into as many workgroups as its i-range has segments, so every workgroup does about the same work;
+// their partial sums (reduced mod n) go to the context arena and k_frbn_polysum adds them.  A product whose tiles all
+// fit one segment is written straight to `out`.
+#include "common.h"
+#include "fr_bn.h"
+
+#define KOE_TILE 256
+#define KOE_CHUNK 64
+#define KOE_BROW (KOE_CHUNK + KOE_TILE)   // words per limb row of the staged b (KOE_CHUNK + KOE_TILE - 1 used)
+#define KOE_MIN_SEG 256                   // shortest segment; a multiple of KOE_CHUNK
+#define KOE_TARGET_WGS (1 << 12)          // full-size workgroups a large product is cut into
+
+// [first, last] of the i that tile k0 meets, and how many segments of length seg that range touches
+struct koe_span {
+    long long lo, hi;
+    unsigned first_seg, n_seg;
+};
+__host__ __device__ static inline koe_span koe_tile_span(long long k0, long long na, long long nb, long long seg) {
+    koe_span s;
+    s.lo = k0 - (nb - 1) > 0 ? k0 - (nb - 1) : 0;
+    s.hi = k0 + KOE_TILE - 1 < na - 1 ? k0 + KOE_TILE - 1 : na - 1;
+    s.first_seg = (unsigned)(s.lo / seg);
+    s.n_seg = (unsigned)(s.hi / seg) - s.first_seg + 1;
+    return s;
+}
+
+__device__ __forceinline__ frbn koe_load_or_zero(const uint32_t *__restrict__ v, long long idx, long long n) {
+    if (idx < 0 || idx >= n) return frbn_zero();
+    const uint4 *p = (const uint4 *)(v + 8 * idx);
+    const uint4 x = p[0], y = p[1];
+    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+    return frbn_load(w);
+}
+
+// grid (tiles, most segments of a tile); dst row y holds the partial sums of every tile's y-th segment
+__global__ void __launch_bounds__(KOE_TILE)
+k_frbn_polymul(const uint32_t *__restrict__ a, long long na, const uint32_t *__restrict__ b, long long nb,
+               long long seg, uint32_t *__restrict__ dst) {
+    __shared__ uint32_t sA[KOE_CHUNK * 8];
+    __shared__ uint32_t sB[8 * KOE_BROW];
+    const int t = threadIdx.x;
+    const long long n_out = na + nb - 1;
+    const long long k0 = (long long)blockIdx.x * KOE_TILE;
+    const koe_span span = koe_tile_span(k0, na, nb, seg);
+    if (blockIdx.y >= span.n_seg) return;      // (uniform) this tile has fewer segments
+    const long long seg_lo = (long long)(span.first_seg + blockIdx.y) * seg;
+    frbn_acc acc = frbn_acc_zero();
+    for (long long i0 = seg_lo; i0 < seg_lo + seg; i0 += KOE_CHUNK) {
+        if (i0 + KOE_CHUNK <= span.lo || i0 > span.hi) continue;   // (uniform)
+        __syncthreads();
+        if (t < KOE_CHUNK) {
+            const frbn x = koe_load_or_zero(a, i0 + t, na);
+#pragma unroll
+            for (int l = 0; l < 8; l++) sA[8 * t + l] = x.v[l];
+        }
+        // sB word j of a limb row is b[k0 - i0 - (KOE_CHUNK - 1) + j]: lane t at step ii reads j = t + KOE_CHUNK - 1 - ii
+        for (int j = t; j < KOE_CHUNK + KOE_TILE - 1; j += KOE_TILE) {
+            const frbn x = koe_load_or_zero(b, k0 - i0 - (KOE_CHUNK - 1) + j, nb);
+#pragma unroll
+            for (int l = 0; l < 8; l++) sB[l * KOE_BROW + j] = x.v[l];
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int ii = 0; ii < KOE_CHUNK; ii++) {
+            uint32_t x[8], y[8];
+#pragma unroll
+            for (int l = 0; l < 8; l++) {
+                x[l] = sA[8 * ii + l];
+                y[l] = sB[l * KOE_BROW + t + KOE_CHUNK - 1 - ii];
+            }
+            frbn_acc_mac(acc, x, y);
+        }
+    }
+    const long long k = k0 + t;
+    if (k < n_out) frbn_store(dst + 8 * ((long long)blockIdx.y * n_out + k), frbn_acc_reduce(acc));
+}
+
+__global__ void __launch_bounds__(256)
+k_frbn_polysum(const uint32_t *__restrict__ part, long long na, long long nb, long long seg,
+               uint32_t *__restrict__ out) {
+    const long long n_out = na + nb - 1;
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_out) return;
+    const koe_span span = koe_tile_span(k / KOE_TILE * KOE_TILE, na, nb, seg);
+    frbn s = frbn_load(part + 8 * k);
+    for (unsigned y = 1; y < span.n_seg; y++) s = frbn_add(s, frbn_load(part + 8 * ((long long)y * n_out + k)));
+    frbn_store(out + 8 * k, s);
+}
+
+// lane g writes out[8g .. 8g+7]: z^(8g+1) by square-and-multiply on the index, then seven products by z
+#define KOE_POW_RUN 8
+__global__ void __launch_bounds__(256)
+k_frbn_powers(const uint32_t *__restrict__ z_in, const uint32_t *__restrict__ scale_in, size_t count,
+              uint32_t *__restrict__ out) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t first = g * KOE_POW_RUN;
+    if (first >= count) return;
+    const frbn z = frbn_load(z_in);
+    frbn v = frbn_load(scale_in), sq = z;
+    for (size_t e = first + 1; e; e >>= 1) {
+        if (e & 1) v = frbn_mul(v, sq);
+        sq = frbn_mul(sq, sq);
+    }
+    const size_t last = first + KOE_POW_RUN < count ? first + KOE_POW_RUN : count;
+    for (size_t i = first; i < last; i++) {
+        frbn_store(out + 8 * i, v);
+        v = frbn_mul(v, z);
+    }
+}
+
+extern "C" int vmpc_bn256_fr_poly_mul_dev(vmpc_ctx *ctx, const void *a, size_t na, const void *b, size_t nb,
+                                          void *out) {
+    if (na > VMPC_BN256_FR_POLY_MAX || nb > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !out || na == 0 || nb == 0) return VMPC_E_INVAL;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const long long n_out = (long long)(na + nb - 1);
+    const unsigned tiles = (unsigned)((n_out + KOE_TILE - 1) / KOE_TILE);
+    // segment length: a power of two that cuts the na * nb products into about KOE_TARGET_WGS workgroups' worth
+    long long seg = KOE_MIN_SEG;
+    while (seg * 2 * KOE_TILE * KOE_TARGET_WGS <= (long long)na * (long long)nb) seg *= 2;
+    unsigned max_segs = 1;
+    for (unsigned t = 0; t < tiles; t++) {
+        const unsigned s = koe_tile_span((long long)t * KOE_TILE, (long long)na, (long long)nb, seg).n_seg;
+        if (s > max_segs) max_segs = s;
+    }
+    uint32_t *dst = (uint32_t *)out;
+    if (max_segs > 1) {
+        const size_t bytes = (size_t)max_segs * (size_t)n_out * 32;
+        VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(bytes) + 256));
+        dst = (uint32_t *)vmpc_ws_take(ctx, bytes);
+    }
+    {
+        vmpc_stage_scope s(ctx, "bn_fr_poly_mul");
+        k_frbn_polymul<<<dim3(tiles, max_segs), KOE_TILE, 0, ctx->stream>>>(
+            (const uint32_t *)a, (long long)na, (const uint32_t *)b, (long long)nb, seg, dst);
+        VMPC_KERNEL_CHECK();
+    }
+    if (max_segs > 1) {
+        vmpc_stage_scope s(ctx, "bn_fr_poly_sum");
+        k_frbn_polysum<<<(unsigned)((n_out + 255) / 256), 256, 0, ctx->stream>>>(dst, (long long)na, (long long)nb, seg,
+                                                                                (uint32_t *)out);
+        VMPC_KERNEL_CHECK();
+    }
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_bn256_fr_powers_dev(vmpc_ctx *ctx, const void *z, const void *scale, size_t count, void *out) {
+    if (!ctx || !z || !scale || (count && !out) || count > ((size_t)1 << 32)) return VMPC_E_INVAL;
+    if (count == 0) return VMPC_OK;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope s(ctx, "bn_fr_powers");
+    const size_t lanes = (count + KOE_POW_RUN - 1) / KOE_POW_RUN;
+    k_frbn_powers<<<(unsigned)((lanes + 255) / 256), 256, 0, ctx->stream>>>((const uint32_t *)z, (const uint32_t *)scale,
+                                                                           count, (uint32_t *)out);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_bn256_fr_poly_mul(const uint8_t *a, size_t na, const uint8_t *b, size_t nb, uint8_t *out) {
+    if (na > VMPC_BN256_FR_POLY_MAX || nb > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!a || !b || !out || na == 0 || nb == 0) return VMPC_E_INVAL;
+    vmpc_ctx *ctx = nullptr;
+    VMPC_CHECK(vmpc_ctx_create(0, &ctx));
+    void *da = nullptr, *db = nullptr, *dout = nullptr;
+    int rc = vmpc_malloc(ctx, na * 32, &da);
+    if (!rc) rc = vmpc_malloc(ctx, nb * 32, &db);
+    if (!rc) rc = vmpc_malloc(ctx, (na + nb - 1) * 32, &dout);
+    if (!rc) rc = vmpc_memcpy_h2d(ctx, da, a, na * 32);
+    if (!rc) rc = vmpc_memcpy_h2d(ctx, db, b, nb * 32);
+    if (!rc) rc = vmpc_bn256_fr_poly_mul_dev(ctx, da, na, db, nb, dout);
+    if (!rc) rc = vmpc_ctx_sync(ctx);
+    if (!rc) rc = vmpc_memcpy_d2h(ctx, out, dout, (na + nb - 1) * 32);
+    if (da) vmpc_free(ctx, da);
+    if (db) vmpc_free(ctx, db);
+    if (dout) vmpc_free(ctx, dout);
+    vmpc_ctx_destroy(ctx);
+    return rc;
+}

@@ -1,0 +1,274 @@
+"""The knowledge-of-exponent pivot of AC20 (section 9) over BN-256 on MI355X: constant-size openings of a linear form.
+
+    trusted_setup                  verifiable_mpc/ac20/knowledge_of_exponent.py:50-72
+    restriction_argument_prover    knowledge_of_exponent.py:75-95
+    restriction_argument_verifier  knowledge_of_exponent.py:98-102
+    opening_linear_form_prover     knowledge_of_exponent.py:105-133
+    opening_linear_form_verifier   knowledge_of_exponent.py:136-153
+
+Same names, arguments and return values as the reference.  The group work is the BN-256 layer of pynocchio.py
+(csrc/bn256.hip MSMs over fixed-base tables, csrc/bn256_pairing.hip pairing products); the scalar work is
+csrc/bn256_koe.hip over csrc/fr_bn.h: the powers g_exp z^(i+1) of the setup and the prover's one super-linear step,
+the product of two degree-n polynomials over GF(order) (no NTT exists in that field: order - 1 = 2^5 * odd).
+
+A `pp` is {"pp_lhs": ..., "pp_rhs": ...}.  trusted_setup returns the two sides as `PPVector`s: sequences of
+BN256Point / BN256TwistPoint (len, indexing, iteration) whose points stay in HBM and whose MSM tables are built once,
+at first use.  A plain dict of point lists - foreign (MPyC-style) points included - is accepted wherever a pp is taken.
+Points are written additively here (the reference switches its groups to multiplicative notation): `g ** k` there is
+`k * g` here.  The verifier evaluates both checks as "product of pairings == 1" in ONE pairing_product launch; points
+not on their curve raise ValueError; G2 subgroup membership is not checked (as in pynocchio.verify).
+
+Not here: prove_nullity_koe (its challenge hashes repr() of an MPyC point), the circuit front end's koe branch
+(circuit_sat.create_generators keeps raising NotImplementedError for PivotChoice.koe) and the MPC setup.
+"""
+from random import SystemRandom
+
+import numpy as np
+
+from . import _native
+from .device import get_context
+from .pynocchio import (ORDER, BN256Point, BN256TwistPoint, _as_bytes, _neg_g1_rows, _pairing_product_arrays,
+                        scalars_to_array)
+
+prng = SystemRandom()
+
+_CLS = {1: BN256Point, 2: BN256TwistPoint}
+_CURVE = {1: "BN-256 curve", 2: "BN-256 twist"}
+
+
+class PPVector:
+    """One side of a pp on the device: n affine points (64 B in G1, 128 B on the twist).  Read like a list of points;
+    the fixed-base table behind its MSMs is built at the first MSM and kept."""
+
+    def __init__(self, ctx, group, buf, n, tabulate=True):
+        self.ctx, self.group, self.buf, self.n = ctx, group, buf, n
+        self.width = 64 * group
+        self._tabulate, self._table, self._rows = tabulate, None, None
+
+    @classmethod
+    def from_points(cls, ctx, points, what, group):
+        """upload a list of (possibly foreign) points, all of `group`, and check that they are on their curve; such a
+        vector lives for one call, so its sums run without a table"""
+        enc = [_as_bytes(p) for p in points]
+        if any(g != group for g, _ in enc):
+            raise ValueError(f"{what}: not a point of the {_CURVE[group]}")
+        rows = np.frombuffer(b"".join(r for _, r in enc), np.uint8).reshape(-1, 64 * group)
+        buf = ctx.upload(rows)
+        if ctx.bn256_validate(group, buf.ptr, len(rows)):
+            raise ValueError(f"{what}: point not on the {_CURVE[group]}")
+        self = cls(ctx, group, buf, len(rows), tabulate=False)
+        self._rows = rows
+        return self
+
+    def rows(self):
+        """(n, width) uint8 host copy of the points (downloaded once)"""
+        if self._rows is None:
+            self.ctx.sync()
+            self._rows = self.ctx.download(self.buf.ptr, self.width * self.n).reshape(self.n, self.width)
+        return self._rows
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, key):
+        if isinstance(key, slice):
+            return [self[i] for i in range(*key.indices(self.n))]
+        i = key + self.n if key < 0 else key
+        if not 0 <= i < self.n:
+            raise IndexError(key)
+        return _CLS[self.group].from_bytes(self.rows()[i].tobytes())
+
+    def __iter__(self):
+        return (self[i] for i in range(self.n))
+
+    def msm(self, scalars):
+        """sum_{i < m} scalars[i] * self[i] for an (m, 32) uint8 array or a device buffer of m scalars -> point"""
+        ctx = self.ctx
+        ds, m = scalars if isinstance(scalars, tuple) else (ctx.upload(scalars), len(scalars))
+        assert 0 < m <= self.n
+        out = ctx.alloc(self.width)
+        if self._tabulate:
+            if self._table is None:
+                self._table = ctx.bn256_table_build(self.group, self.buf.ptr, self.n)
+            ctx.bn256_table_msm(self.group, self._table.ptr, self.n, ds.ptr, m, out.ptr, None)
+        else:
+            ctx.bn256_msm(self.group, ds.ptr, self.buf.ptr, m, out.ptr)
+        ctx.sync()
+        return _CLS[self.group].from_bytes(ctx.download(out.ptr, self.width).tobytes())
+
+
+def _side(ctx, pp, name, count=None):
+    """pp[name] as a PPVector (its first `count` points when it arrives as a list)"""
+    side = pp[name]
+    if isinstance(side, PPVector):
+        return side
+    return PPVector.from_points(ctx, list(side[:count] if count is not None else side), name, 1 if name == "pp_lhs" else 2)
+
+
+def _scalar_bytes(v):
+    return np.frombuffer((int(v) % ORDER).to_bytes(32, "little"), np.uint8)
+
+
+def fr_powers(z, scale, count, ctx=None):
+    """device buffer of `count` scalars scale * z^(i+1) mod ORDER (csrc/bn256_koe.hip)"""
+    ctx = ctx or get_context()
+    dz, dscale, out = ctx.upload(_scalar_bytes(z)), ctx.upload(_scalar_bytes(scale)), ctx.alloc(max(32, 32 * count))
+    ctx.bn256_fr_powers(dz.ptr, dscale.ptr, count, out.ptr)
+    return out
+
+
+def fr_poly_mul(a, b, ctx=None):
+    """coefficients (lists of ints / field elements, or (len, 32) uint8 arrays of any 32-byte values) of two polynomials
+    over GF(ORDER) -> (len(a) + len(b) - 1, 32) uint8 canonical coefficients of their product (csrc/bn256_koe.hip)"""
+    ctx = ctx or get_context()
+    a, b = scalars_to_array(a), scalars_to_array(b)
+    da, db = ctx.upload(a), ctx.upload(b)
+    out = ctx.alloc(32 * (len(a) + len(b) - 1))
+    ctx.bn256_fr_poly_mul(da.ptr, len(a), db.ptr, len(b), out.ptr)
+    ctx.sync()
+    return ctx.download(out.ptr, 32 * (len(a) + len(b) - 1)).reshape(-1, 32)
+
+
+def trusted_setup(_g1, _g2, n, order, progress_bar=False):
+    """pp_lhs[i] = (g_exp z^(i+1)) * _g1 and pp_rhs[i] = (g_exp alpha z^(i+1)) * _g2 for i < 2n, with g_exp, alpha, z
+    drawn from this module's `prng` in the reference's order (knowledge_of_exponent.py:50-72).  The 2n exponents are
+    one launch (fr_powers), the points one fixed-base launch per group.  `progress_bar` is accepted and ignored."""
+    if int(order) != ORDER:
+        raise ValueError("trusted_setup: order is not the BN-256 group order")
+    g_exp = prng.randrange(1, order)
+    alpha = prng.randrange(order)
+    z = prng.randrange(order)
+    ctx = get_context()
+    pp = {}
+    for name, group, base, scale in (("pp_lhs", 1, _g1, g_exp), ("pp_rhs", 2, _g2, g_exp * alpha % ORDER)):
+        grp, raw = _as_bytes(base)
+        if grp != group:
+            raise ValueError(f"trusted_setup: generator {group} is not a point of the {_CURVE[group]}")
+        dbase = ctx.upload(np.frombuffer(raw, np.uint8))
+        if ctx.bn256_validate(group, dbase.ptr, 1):
+            raise ValueError(f"trusted_setup: generator {group} is not on the {_CURVE[group]}")
+        exps = fr_powers(z, scale, 2 * n, ctx)
+        pts = ctx.alloc(max(1, 64 * group * 2 * n))
+        ctx.bn256_fixed_base(group, dbase.ptr, exps.ptr, 2 * n, pts.ptr)
+        ctx.sync()
+        pp[name] = PPVector(ctx, group, pts, 2 * n)
+    return pp
+
+
+def _restriction_scalars(S, x, gamma):
+    """(max(S) + 2, 32) scalars: gamma, then x[i] at position i + 1 for i in S and 0 elsewhere"""
+    if isinstance(S, range) and S.step == 1 and S.start == 0:
+        return scalars_to_array([gamma] + [x[i] for i in S])
+    S = list(S)
+    sc = [0] * (max(S) + 2 if S else 1)
+    sc[0] = gamma
+    for i in S:
+        sc[i + 1] = x[i]
+    return scalars_to_array(sc)
+
+
+def restriction_argument_prover(S, x, gamma, pp):
+    """(P, pi): the commitment gamma pp_lhs[0] + sum_{i in S} x[i] pp_lhs[i+1] to the S-indices of x and the same sum
+    over pp_rhs (knowledge_of_exponent.py:75-95).  One G1 MSM and one G2 MSM."""
+    ctx = get_context()
+    sc = _restriction_scalars(S, x, gamma)
+    ds = (ctx.upload(sc), len(sc))
+    return _side(ctx, pp, "pp_lhs", len(sc)).msm(ds), _side(ctx, pp, "pp_rhs", len(sc)).msm(ds)
+
+
+def _proof_point(ctx, pt, group, name):
+    grp, raw = _as_bytes(pt)
+    row = np.frombuffer(raw, np.uint8)
+    if grp != group or ctx.bn256_validate(group, ctx.upload(row).ptr, 1):
+        raise ValueError(f"{name} is not on the {_CURVE[group]}")
+    return row
+
+
+def restriction_argument_verifier(P, pi, pp):
+    """e(P, pp_rhs[0]) == e(pp_lhs[0], pi) (knowledge_of_exponent.py:98-102), as e(P, g2) e(-g1, pi) == 1"""
+    ctx = get_context()
+    g1, g2 = _side(ctx, pp, "pp_lhs", 1).rows()[0], _side(ctx, pp, "pp_rhs", 1).rows()[0]
+    rP, rpi = _proof_point(ctx, P, 1, "P"), _proof_point(ctx, pi, 2, "pi")
+    _, ones = _pairing_product_arrays(ctx, np.stack([rP, _neg_g1_rows(g1[None])[0]]), np.stack([g2, rpi]), [0, 2],
+                                      validate=False)
+    return ones[0]
+
+
+def _form_parts(L):
+    """(coefficients as a list, constant) of a LinearForm / AffineForm, this package's or the reference's"""
+    coeffs = L.coeffs.to_ints() if hasattr(L.coeffs, "to_ints") else L.coeffs
+    return coeffs, getattr(L, "constant", 0)
+
+
+def _reversed_coeffs(coeffs, n):
+    """[coeffs[n - (j + 1)] for j < n] as (n, 32) scalars: the linear form as the polynomial it is multiplied in as"""
+    return np.ascontiguousarray(scalars_to_array(coeffs[:n])[::-1])
+
+
+def _like(sample, value):
+    """`value` (an int mod ORDER) in the field type of `sample` when that is a field element of this order"""
+    cls = type(sample)
+    if hasattr(sample, "value") and getattr(cls, "modulus", None) == ORDER:
+        return cls(value)
+    return value
+
+
+def opening_linear_form_prover(L, x, gamma, pp, P=None, pi=None):
+    """(proof, u): proof = {"P", "pi", "Q"} opens L on the committed x to u = L(x) (knowledge_of_exponent.py:105-133).
+    c = (gamma, x_0, ..., x_{n-1}) * (L_{n-1}, ..., L_0) is one launch of the polynomial-product kernel; its
+    coefficient n is u minus L's constant, and Q = -sum_{i != n} c[i] pp_lhs[i] is one G1 MSM.  u comes back as a field
+    element when L's coefficients (or its constant) are field elements of this order, else as an int below ORDER."""
+    ctx = get_context()
+    proof = {}
+    n = len(x)
+    S = range(n)
+    n_lhs = len(pp["pp_lhs"])
+    assert 2 * n - 1 <= n_lhs, "Requirement does not hold: 2*len(x)-1 <= number of generators in first group."
+    if P is None:
+        P, pi = restriction_argument_prover(S, x, gamma, pp)
+    proof["P"] = P
+    proof["pi"] = pi
+
+    coeffs, constant = _form_parts(L)
+    assert len(coeffs) == n, "Length of inputs to be equal to coefficients of linear form."
+    lhs = scalars_to_array([gamma] + list(x))
+    rhs = _reversed_coeffs(coeffs, n)
+    d_lhs, d_rhs, c_bar = ctx.upload(lhs), ctx.upload(rhs), ctx.alloc(32 * 2 * n)
+    ctx.bn256_fr_poly_mul(d_lhs.ptr, n + 1, d_rhs.ptr, n, c_bar.ptr)
+    ctx.sync()
+    u_linear = int.from_bytes(ctx.download(c_bar.ptr + 32 * n, 32).tobytes(), "little")
+    ctx.upload_into(c_bar.ptr + 32 * n, np.zeros(32, np.uint8))
+    assert n_lhs == 2 * n
+    Q = _side(ctx, pp, "pp_lhs").msm((c_bar, 2 * n))
+    if Q.coords is not None:
+        Q = BN256Point((Q.coords[0], -Q.coords[1]))
+    proof["Q"] = Q
+    sample = constant if hasattr(constant, "value") else (coeffs[0] if n else 0)
+    u = _like(sample, (u_linear + int(constant)) % ORDER)
+    return proof, u
+
+
+def opening_linear_form_verifier(L, pp, proof, u):
+    """{"restriction_arg_check", "PRQ_check"} -> bool (knowledge_of_exponent.py:136-153).  R = sum_j L[n-1-j] pp_rhs[j]
+    is one G2 MSM; then both checks in one pairing_product launch, five Miller loops and two final exponentiations:
+        e(P, g2) e(-g1, pi) == 1      and      e(P, R) e(Q, g2) e(-g1, u pp_rhs[n]) == 1"""
+    ctx = get_context()
+    coeffs, constant = _form_parts(L)
+    n = len(coeffs)
+    lhs, rhs = _side(ctx, pp, "pp_lhs", 1), _side(ctx, pp, "pp_rhs", n + 1)
+    if len(rhs) <= n:
+        raise ValueError("pp_rhs holds fewer than len(L) + 1 points")
+    u_linear = (int(u) - int(constant)) % ORDER
+    rP, rpi, rQ = (_proof_point(ctx, proof[k], g, k) for k, g in (("P", 1), ("pi", 2), ("Q", 1)))
+    R = np.frombuffer(rhs.msm(_reversed_coeffs(coeffs, n)).to_bytes(), np.uint8)
+    # u * pp_rhs[n]: the one-base case of the verifier's small linear combinations (csrc/bn256_pairing.hip)
+    uT = ctx.alloc(128)
+    ctx.bn256_lincomb_batch(2, rhs.buf.ptr + 128 * n, 1, ctx.upload(_scalar_bytes(u_linear)).ptr, None, 0, 1, False,
+                            uT.ptr)
+    ctx.sync()
+    uT = ctx.download(uT.ptr, 128)
+    g2 = rhs.rows()[0]
+    neg_g1 = _neg_g1_rows(lhs.rows()[:1])[0]
+    _, ones = _pairing_product_arrays(ctx, np.stack([rP, neg_g1, rP, rQ, neg_g1]), np.stack([g2, rpi, R, g2, uT]),
+                                      [0, 2, 5], validate=False)
+    return {"restriction_arg_check": ones[0], "PRQ_check": ones[1]}
