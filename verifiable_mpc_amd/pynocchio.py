@@ -249,10 +249,12 @@ class PreparedKey:
         self.vectors["h*g1"] = _KeyVector(self.ctx, powers)
 
     @classmethod
-    def synthetic(cls, ctx, n, seed=3):
+    def synthetic(cls, ctx, n, seed=3, mid=None, exponents=False):
         """A key of n `mid` wires whose every entry is a distinct multiple of its group's generator, built on the
-        device: the shape of a real prepared key without a circuit (bench.py, scripts/pinocchio_probe.py - timing
-        only; parity of compute_proof is pinned on the reference-made fixture)."""
+        device: the shape of a real prepared key without a circuit (bench.py, scripts/pinocchio_probe.py).
+        mid: the key's wire indices (default 0 .. n-1).  exponents=True: return (key, {element: (n + tail, 32) uint8
+        discrete logs of its key vector}), zero where a column holds the point at infinity - what a test needs to
+        know every sum's value (tests/test_gpu_bn256_edges.py)."""
         g1 = (1).to_bytes(32, "little") + (P - 2).to_bytes(32, "little")
         g2 = b"".join(v.to_bytes(32, "little") for v in (
             64746500191241794695844075326670126197795977525365406531717464316923369116492,
@@ -261,8 +263,10 @@ class PreparedKey:
             20666913350058776956210519119118544732556678129809273996262322366050359951122))
         rng = np.random.default_rng(seed)
         key = cls.__new__(cls)
-        key.ctx, key.mid, key.vectors = ctx, list(range(n)), {}
-        key.mid_index, key.zk_missing = np.arange(n), {}
+        key.ctx, key.mid, key.vectors = ctx, list(range(n)) if mid is None else [int(i) for i in mid], {}
+        key.mid_index, key.zk_missing = np.asarray(key.mid, dtype=np.int64), {}
+        assert len(key.mid) == n
+        logs = {}
         for name in list(_ELEMENTS) + ["h*g1"]:
             grp, gen, width = (2, g2, 128) if name.endswith("g2") else (1, g1, 64)
             zk = _ELEMENTS[name][1] if name in _ELEMENTS else ()
@@ -277,7 +281,12 @@ class PreparedKey:
                     ctx.upload_into(pts.ptr + width * (n + j), np.zeros(width, np.uint8))
             ctx.sync()
             key.vectors[name] = _KeyVector.from_device(ctx, grp, pts, n + len(tail))
-        return key
+            if exponents:
+                logs[name] = ex.copy()
+                for j, used in enumerate(tail):
+                    if not used:
+                        logs[name][n + j] = 0
+        return (key, logs) if exponents else key
 
 
 # The six G1 sums over c_mid (pynocchio.py:229-246) go through ONE multi-key pass (vmpc_bn256_table_msm_multi_dev):
