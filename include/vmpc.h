@@ -419,6 +419,32 @@ int vmpc_bn256_fr_poly_mul(const uint8_t *a, size_t na, const uint8_t *b, size_t
  * points themselves; here the 2n points are vmpc_bn256_fixed_base_dev of these exponents. */
 int vmpc_bn256_fr_powers_dev(vmpc_ctx *ctx, const void *z, const void *scale, size_t count, void *out);
 
+/* ---- Pinocchio key generation (verifiable_mpc/trinocchio/pynocchio.py:101-200): the exponents of the key points,
+ * same scalar conventions.  Every key entry is (exponent) * g1 or g2, made by vmpc_bn256_fixed_base_dev. */
+/* ell_out[j-1] = l_j(s) for j = 1..d, the Lagrange basis of the points 1..d at s (the reference's QAP interpolates
+ * constraint j at x = j, qap_creator.r1cs_to_qap_ff), and t_out = t(s) = prod_{j=1..d} (s - j).  Exact for every s,
+ * s in {1..d} (l_j = [j = s], t = 0) and s = 0 included.  d >= 1; cap VMPC_BN256_QAP_MAX_D: above it the entry answers
+ * VMPC_E_RANGE before it looks at any pointer.  Uses the context arena (3 (d + 1) scalars). */
+#define VMPC_BN256_QAP_MAX_D ((size_t)1 << 22)
+int vmpc_bn256_qap_lagrange_dev(vmpc_ctx *ctx, const void *s, size_t d, void *ell_out, void *t_out);
+/* out[c] = sum over the entries e of column c of vals[e] * basis[rows[e]]: the values v_i(s), w_i(s), y_i(s) of a
+ * sparse R1CS (basis = l(s)) or of dense QAP polynomials (basis = 1, s, .., s^d).  The entries are in column order;
+ * `items` holds n_items triples (start, end, dst) of uint32 that cover them: entries [start, end) sum to out[dst], or,
+ * when bit 31 of dst is set, to partial sum (dst & 0x7fffffff) < n_partial.  `long_cols` holds n_long triples
+ * (col, first, count): out[col] = the sum of partial sums first .. first + count - 1.  Rows >= n_basis add nothing;
+ * destinations out of range are not written.  Deterministic (no atomics).  Uses the context arena (the partials). */
+int vmpc_bn256_qap_colsum_dev(vmpc_ctx *ctx, const void *basis, size_t n_basis, const uint32_t *rows, const void *vals,
+                              size_t nnz, const uint32_t *items, size_t n_items, const uint32_t *long_cols,
+                              size_t n_long, size_t n_partial, void *out, size_t n_out);
+/* The exponents of the evaluation key's per-wire entries (pynocchio.py:106-154) for the wires idx[0 .. n_idx): seven
+ * vectors of n_idx + 3 scalars each, consecutive in `out`, with coef = 9 scalars (r_v, r_w, r_y, alpha_v r_v,
+ * alpha_w r_w, alpha_y r_y, beta r_v, beta r_w, beta r_y), vwy = v(s) || w(s) || y(s) (n_wires each) and t = t(s):
+ *   r_v v_i, r_w w_i, r_y y_i, alpha_v r_v v_i, alpha_w r_w w_i, alpha_y r_y y_i, beta (r_v v_i + r_w w_i + r_y y_i).
+ * The three trailing rows of each vector belong to the deltas (v, w, y): the vector's coefficient of that delta times
+ * t(s) where the proof element uses it, 0 where it does not. */
+int vmpc_bn256_keygen_exps_dev(vmpc_ctx *ctx, const void *coef, const void *vwy, size_t n_wires, const void *t,
+                               const uint32_t *idx, size_t n_idx, void *out);
+
 /* SHA-256 of every `chunk_bytes`-sized piece of a device buffer (last piece may be short):
  * out_digests[i] = SHA256(data[i*chunk : (i+1)*chunk]), 32 bytes each.  Leaves of the compact
  * transcript's two-level digests; not used by the reference transcript. */

@@ -46,6 +46,7 @@ SYMBOLS = [
     "vmpc_bn256_pairing_dev", "vmpc_bn256_pairing_product_dev", "vmpc_bn256_lincomb_batch_dev",
     "vmpc_bn256_pairing", "vmpc_bn256_pairing_product", "vmpc_bn256_lincomb_batch",
     "vmpc_bn256_fr_poly_mul_dev", "vmpc_bn256_fr_poly_mul", "vmpc_bn256_fr_powers_dev",
+    "vmpc_bn256_qap_lagrange_dev", "vmpc_bn256_qap_colsum_dev", "vmpc_bn256_keygen_exps_dev",
 ]
 
 
@@ -153,6 +154,9 @@ def load_library():
         "vmpc_bn256_fr_poly_mul_dev": (i32, [vp, vp, sz, vp, sz, vp]),
         "vmpc_bn256_fr_poly_mul": (i32, [vp, sz, vp, sz, vp]),
         "vmpc_bn256_fr_powers_dev": (i32, [vp, vp, vp, sz, vp]),
+        "vmpc_bn256_qap_lagrange_dev": (i32, [vp, vp, sz, vp, vp]),
+        "vmpc_bn256_qap_colsum_dev": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, vp, sz]),
+        "vmpc_bn256_keygen_exps_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp]),
         "vmpc_msm_table_fold_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp]),
         "vmpc_msm_table_fold_table_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp, sz, i32, vp]),
         "vmpc_p4_create": (i32, [vp, vp, sz, sz, i32, i32, i32, vp, vp, vp, ctypes.POINTER(vp)]),
@@ -843,6 +847,27 @@ class Context:
         """out[i] = scale * z^(i+1) mod the BN-256 group order"""
         _check(self.lib.vmpc_bn256_fr_powers_dev(self.handle, ctypes.c_void_p(z_ptr), ctypes.c_void_p(scale_ptr),
                                                  count, ctypes.c_void_p(out_ptr)), "vmpc_bn256_fr_powers_dev")
+
+    def bn256_qap_lagrange(self, s_ptr, d, ell_ptr, t_ptr):
+        """ell[j-1] = l_j(s) (j = 1..d, the Lagrange basis of the points 1..d) and t = prod (s - j); VmpcError E_RANGE
+        above the library's cap, before anything is read or written"""
+        _check(self.lib.vmpc_bn256_qap_lagrange_dev(self.handle, ctypes.c_void_p(s_ptr), d, ctypes.c_void_p(ell_ptr),
+                                                    ctypes.c_void_p(t_ptr)), "vmpc_bn256_qap_lagrange_dev")
+
+    def bn256_qap_colsum(self, basis_ptr, n_basis, rows_ptr, vals_ptr, nnz, items_ptr, n_items, long_ptr, n_long,
+                         n_partial, out_ptr, n_out):
+        """out[col] = sum of vals[e] * basis[rows[e]] over a column's entries (include/vmpc.h)"""
+        _check(self.lib.vmpc_bn256_qap_colsum_dev(self.handle, ctypes.c_void_p(basis_ptr), n_basis,
+                                                  ctypes.c_void_p(rows_ptr), ctypes.c_void_p(vals_ptr), nnz,
+                                                  ctypes.c_void_p(items_ptr), n_items, ctypes.c_void_p(long_ptr),
+                                                  n_long, n_partial, ctypes.c_void_p(out_ptr), n_out),
+               "vmpc_bn256_qap_colsum_dev")
+
+    def bn256_keygen_exps(self, coef_ptr, vwy_ptr, n_wires, t_ptr, idx_ptr, n_idx, out_ptr):
+        """the seven exponent vectors (n_idx + 3 scalars each) of the evaluation key's per-wire entries"""
+        _check(self.lib.vmpc_bn256_keygen_exps_dev(self.handle, ctypes.c_void_p(coef_ptr), ctypes.c_void_p(vwy_ptr),
+                                                   n_wires, ctypes.c_void_p(t_ptr), ctypes.c_void_p(idx_ptr), n_idx,
+                                                   ctypes.c_void_p(out_ptr)), "vmpc_bn256_keygen_exps_dev")
 
     def bn256_validate(self, group, points_ptr, n):
         bad = ctypes.c_uint64()

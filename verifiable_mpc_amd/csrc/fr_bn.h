@@ -195,6 +195,18 @@ VMPC_HD frbn frbn_mul(const frbn &a, const frbn &b) {
     return frbn_reduce512(t);
 }
 
+// a^(n-2) = 1/a for a != 0 (Fermat; 0 -> 0): 255 squarings and one product per set bit of n - 2, left to right
+VMPC_HD frbn frbn_inv(const frbn &a) {
+    uint32_t e[8] = VMPC_FRBN_N;
+    e[0] -= 2;  // n is odd and its low limb exceeds 2: no borrow
+    frbn r = frbn_one();
+    for (int i = 255; i >= 0; i--) {
+        r = frbn_mul(r, r);
+        if ((e[i >> 5] >> (i & 31)) & 1u) r = frbn_mul(r, a);
+    }
+    return r;
+}
+
 // ---- the wide accumulator of the polynomial product ----------------------------------------------------------------
 // value = sum_k lo[k] 2^(32 k) + sum_i hi[i] 2^(32 (i + 8)).  frbn_acc_mac adds one unreduced 8 x 8-limb product: row i
 // of the schoolbook product runs its carry chain through lo[i .. i+7] and drops the carry that leaves the row into

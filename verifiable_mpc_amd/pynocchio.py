@@ -9,8 +9,17 @@ zero-knowledge case, adds `delta * evalkey[<t term>]`.  Here every element is ON
 (csrc/bn256.hip) with the zero-knowledge terms appended as extra (scalar, point) pairs.
 Keys and proofs hold `BN256Point` / `BN256TwistPoint` objects (affine coordinates); foreign
 points (e.g. MPyC's Jacobian elements) are accepted if they expose `.normalize()` and three
-indexable coordinates.  Key generation and QAP construction stay with the reference (out of scope,
-SURVEY.md 2 rows 10, 13).
+indexable coordinates.  QAP construction from code stays with the reference (out of scope, SURVEY.md 2 rows 10, 13);
+so does the prover's h (compute_p_poly, p / qap.t, compute_h_zk_terms: this field has no NTT of useful length).
+
+    Trapdoor, SampleDeltas, Generators        verifiable_mpc/trinocchio/pynocchio.py:36-69 (draws from `prng`)
+    generate_evalkey, generate_verikey        verifiable_mpc/trinocchio/pynocchio.py:101-200
+    PreparedKey.generate                      PreparedKey(qap, generate_evalkey(...)) without a host round trip
+
+Key generation evaluates every QAP polynomial at the secret s on the device (csrc/bn256_keygen.hip): a reference QAP
+as a mat-vec of its coefficients against 1, s, .., s^d; an R1CSQAP (the sparse R1CS, constraint j at x = j) as
+v_i(s) = sum_j V[j][i] l_j(s) over the Lagrange basis at s, O(nnz + d).  Each key entry is then one fixed-base product
+of g1 or g2 (the scaled generators' factors folded into the exponent).
 
     pairing          verifiable_mpc/trinocchio/pynocchio.py:67-72 (ac20/pairing.py optimal_ate)
     verify           verifiable_mpc/trinocchio/pynocchio.py:276-325
@@ -20,6 +29,8 @@ The verifier evaluates each of the five checks as "product of pairings == 1" (cs
 per Miller loop, one lane per product for the final exponentiation); pairing values equal the reference's
 coefficient for coefficient.  Off-curve points raise ValueError; G2 subgroup membership is not checked.
 """
+import random
+
 import numpy as np
 
 from . import _native
@@ -701,3 +712,390 @@ def verify_batch(qap, verikey, proofs, cs, ctx=None):
     in one launch and all 12 B pairings in one product launch"""
     ctx = ctx or get_context()
     return _verify_many(ctx, _VerifyingKey(ctx, qap, verikey), list(proofs), list(cs))
+
+
+# ---- key generation (trinocchio/pynocchio.py:36-200; csrc/bn256_keygen.hip) -----------------------------------------
+
+prng = random.SystemRandom()
+
+
+class Trapdoor:
+    """The reference's trapdoor: r_v, r_w, s, alpha_v, alpha_w, alpha_y, beta, gamma drawn from this module's `prng` in
+    that order, r_y = r_v r_w mod modulus (pynocchio.py:36-49)."""
+
+    def __init__(self, modulus):
+        _td = list(prng.randrange(modulus) for i in range(8))
+        r_v, r_w, s, alpha_v, alpha_w, alpha_y, beta, gamma = _td
+        self.r_v = r_v
+        self.r_w = r_w
+        self.r_y = r_v * r_w % modulus
+        self.s = s
+        self.alpha_v = alpha_v
+        self.alpha_w = alpha_w
+        self.alpha_y = alpha_y
+        self.beta = beta
+        self.gamma = gamma
+
+
+class SampleDeltas:
+    """delta_v, delta_w, delta_y from `prng` (pynocchio.py:52-58)"""
+
+    def __init__(self, modulus):
+        self.v, self.w, self.y = (prng.randrange(modulus) for i in range(3))
+
+
+def _generator(ctx, pt, group, what):
+    """(device buffer, host bytes) of a generator, checked to be on its curve"""
+    grp, raw = _as_bytes(pt)
+    name = "BN-256 curve" if group == 1 else "BN-256 twist"
+    if grp != group:
+        raise ValueError(f"{what}: not a point of the {name}")
+    buf = ctx.upload(np.frombuffer(raw, np.uint8))
+    if ctx.bn256_validate(group, buf.ptr, 1):
+        raise ValueError(f"{what}: generator not on the {name}")
+    return buf, raw
+
+
+def _fixed_base_points(ctx, group, base_buf, exps_ptr, n):
+    """n device scalars -> list of points exps[i] * base"""
+    if not n:
+        return []
+    width = 64 * group
+    out = ctx.alloc(width * n)
+    ctx.bn256_fixed_base(group, base_buf.ptr, exps_ptr, n, out.ptr)
+    ctx.sync()
+    raw = ctx.download(out.ptr, width * n).tobytes()
+    cls = BN256Point if group == 1 else BN256TwistPoint
+    return [cls.from_bytes(raw[width * i:width * i + width]) for i in range(n)]
+
+
+class Generators:
+    """g1, g2 and the scaled generators r_v g1, r_w g1, r_w g2, r_y g1, r_y g2 (pynocchio.py:61-69), made by one
+    fixed-base launch per group.  g1 / g2 may be foreign (MPyC-style) points; off-curve generators raise ValueError."""
+
+    def __init__(self, td, g1, g2, ctx=None):
+        ctx = ctx or get_context()
+        b1, raw1 = _generator(ctx, g1, 1, "Generators: g1")
+        b2, raw2 = _generator(ctx, g2, 2, "Generators: g2")
+        self.g1, self.g2 = BN256Point.from_bytes(raw1), BN256TwistPoint.from_bytes(raw2)
+        e1 = ctx.upload(_native.ints_to_array([int(td.r_v) % ORDER, int(td.r_w) % ORDER, int(td.r_y) % ORDER], 32))
+        e2 = ctx.upload(_native.ints_to_array([int(td.r_w) % ORDER, int(td.r_y) % ORDER], 32))
+        self.g1_v, self.g1_w, self.g1_y = _fixed_base_points(ctx, 1, b1, e1.ptr, 3)
+        self.g2_w, self.g2_y = _fixed_base_points(ctx, 2, b2, e2.ptr, 2)
+
+
+_PIECE = 64      # column entries one lane of k_kg_colsum sums (csrc/bn256_keygen.hip)
+
+
+def _colsum_plan(col_ptr, piece=_PIECE):
+    """items (start, end, dst) and long columns (col, first partial, count) of vmpc_bn256_qap_colsum_dev for entries in
+    column order (col_ptr: n_cols + 1 offsets); an empty column is one empty item (it writes 0)"""
+    col_ptr = np.asarray(col_ptr, np.int64)
+    lens = np.diff(col_ptr)
+    pieces = np.maximum(1, (lens + piece - 1) // piece)
+    n_items = int(pieces.sum())
+    col_of = np.repeat(np.arange(len(lens), dtype=np.int64), pieces)
+    first_item = np.cumsum(pieces) - pieces
+    start = col_ptr[col_of] + (np.arange(n_items, dtype=np.int64) - first_item[col_of]) * piece
+    end = np.minimum(start + piece, col_ptr[col_of + 1])
+    is_long = pieces > 1
+    is_part = is_long[col_of]
+    part_idx = np.cumsum(is_part) - 1
+    dst = np.where(is_part, 0x80000000 | part_idx, col_of)
+    items = np.stack([start, end, dst], axis=1).astype(np.uint32)
+    long_cols = np.nonzero(is_long)[0]
+    longs = np.stack([long_cols, part_idx[first_item[long_cols]], pieces[long_cols]], axis=1).astype(np.uint32)
+    return items, longs, int(is_part.sum())
+
+
+class _ColumnPlan:
+    """entries of a QAP's 3 (m + 1) (+ 1) columns in column order, on the device, with their colsum plan"""
+
+    def __init__(self, ctx, cols, rows, vals, n_cols):
+        order = np.argsort(cols, kind="stable")
+        counts = np.bincount(cols, minlength=n_cols) if len(cols) else np.zeros(n_cols, np.int64)
+        col_ptr = np.concatenate([[0], np.cumsum(counts)])
+        items, longs, self.n_partial = _colsum_plan(col_ptr)
+        self.ctx, self.nnz, self.n_cols = ctx, len(cols), n_cols
+        self.rows = ctx.upload(np.ascontiguousarray(np.asarray(rows, np.uint32)[order]))
+        self.vals = ctx.upload(np.ascontiguousarray(vals[order])) if len(cols) else ctx.alloc(32)
+        self.items, self.n_items = ctx.upload(items), len(items)
+        self.longs, self.n_long = ctx.upload(longs), len(longs)
+
+    def run(self, basis_ptr, n_basis, out_ptr):
+        self.ctx.bn256_qap_colsum(basis_ptr, n_basis, self.rows.ptr, self.vals.ptr, self.nnz, self.items.ptr,
+                                  self.n_items, self.longs.ptr, self.n_long, self.n_partial, out_ptr, self.n_cols)
+
+
+_ORDER_WORDS = np.array([(ORDER >> (32 * k)) & 0xFFFFFFFF for k in range(8)], dtype=np.int64)
+
+
+def _values_array(vals):
+    """R1CS values -> (nnz, 32) uint8 residues mod ORDER: a (nnz, 32) uint8 array passes through (the device reduces
+    it), an integer array is reduced here (negative entries become ORDER - |v|), anything else goes through ints"""
+    if isinstance(vals, np.ndarray) and vals.dtype == np.uint8 and vals.ndim == 2:
+        return np.ascontiguousarray(vals)
+    if isinstance(vals, np.ndarray) and vals.dtype.kind in "iu" and vals.ndim == 1 and vals.dtype.itemsize <= 8:
+        a = vals.astype(np.int64) if vals.dtype.kind == "i" else vals.astype(np.uint64)
+        neg = a < 0
+        mag = np.where(neg, -a.astype(np.int64), a).astype(np.uint64) if a.dtype.kind == "i" else a
+        words = np.zeros((len(a), 8), np.int64)
+        words[:, 0] = (mag & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        words[:, 1] = (mag >> np.uint64(32)).astype(np.int64)
+        if neg.any():
+            borrow = np.zeros(int(neg.sum()), np.int64)
+            sub = words[neg]
+            for k in range(8):
+                dk = _ORDER_WORDS[k] - sub[:, k] - borrow
+                borrow = (dk < 0).astype(np.int64)
+                sub[:, k] = dk + (borrow << 32)
+            words[neg] = sub
+        return words.astype("<u4").view(np.uint8).reshape(-1, 32)
+    return scalars_to_array([int(v) % ORDER for v in vals])
+
+
+def _matrix_entries(M, n_cols=None):
+    """(rows, cols, values (nnz, 32), n_rows, n_cols) of one constraint matrix: a tuple (row_ptr, col, vals) is CSR,
+    a list of rows (code_to_r1cs.flatcode_to_r1cs) or a 2-D array is dense"""
+    if isinstance(M, tuple):
+        row_ptr, col, vals = M
+        row_ptr = np.asarray(row_ptr, np.int64)
+        col = np.asarray(col, np.int64)
+        n_rows = len(row_ptr) - 1
+        if n_rows < 0 or row_ptr[0] != 0 or np.any(np.diff(row_ptr) < 0) or row_ptr[-1] != len(col):
+            raise ValueError("R1CSQAP: row_ptr must rise from 0 to the number of entries")
+        rows = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(row_ptr))
+        v = _values_array(vals)
+        if len(v) != len(col):
+            raise ValueError("R1CSQAP: one value per entry")
+        return rows, col, v, n_rows, n_cols
+    dense = [[int(x) for x in row] for row in M]
+    n_rows = len(dense)
+    width = len(dense[0]) if dense else 0
+    if any(len(r) != width for r in dense):
+        raise ValueError("R1CSQAP: dense rows of different lengths")
+    rows, cols, ints = [], [], []
+    for r, row in enumerate(dense):
+        for c, x in enumerate(row):
+            if x % ORDER:
+                rows.append(r)
+                cols.append(c)
+                ints.append(x % ORDER)
+    return (np.asarray(rows, np.int64), np.asarray(cols, np.int64), scalars_to_array(ints).reshape(-1, 32), n_rows,
+            width)
+
+
+class R1CSQAP:
+    """A QAP given by its sparse R1CS: constraint j (row j - 1) is interpolated at x = j, t(x) = prod_{j=1..d} (x - j),
+    the convention of the reference's code_to_qap.QAP (qap_creator.r1cs_to_qap_ff) - but the v/w/y/t coefficients are
+    never formed: key generation evaluates v_i(s) = sum_j V[j][i] l_j(s) on the device in O(nnz + d).
+
+    V, W, Y: each a tuple (row_ptr, col, vals) in CSR form (vals: (nnz, 32) uint8, or ints - negative ones and ones
+    >= the group order included - reduced mod the order; duplicate (row, col) entries add), or the reference's dense
+    row lists (code_to_r1cs.flatcode_to_r1cs).  Column 0 is the constant wire "one", 1..out_ix the io wires, the rest
+    mid wires.  m: the number of wires without "one" (default: from the matrices)."""
+
+    def __init__(self, V, W, Y, out_ix, m=None):
+        mats = [_matrix_entries(M) for M in (V, W, Y)]
+        ds = {e[3] for e in mats}
+        if len(ds) != 1:
+            raise ValueError("R1CSQAP: V, W and Y must have the same number of rows")
+        self.d = ds.pop()
+        if self.d < 1:
+            raise ValueError("R1CSQAP: at least one constraint")
+        widths = [e[4] for e in mats if e[4] is not None]
+        top = max([int(e[1].max()) + 1 for e in mats if len(e[1])] + widths + [out_ix + 1])
+        self.m = top - 1 if m is None else int(m)
+        n_wires = self.m + 1
+        for e in mats:
+            if len(e[1]) and (e[1].min() < 0 or e[1].max() >= n_wires):
+                raise ValueError("R1CSQAP: a column index outside 0..m")
+        if not 0 <= out_ix <= self.m:
+            raise ValueError("R1CSQAP: out_ix outside 0..m")
+        self.out_ix = int(out_ix)
+        self.indices = range(self.m + 1)
+        self.indices_io_and_0 = range(0, self.out_ix + 1)
+        self.indices_io = range(1, self.out_ix + 1)
+        self.indices_mid = range(self.out_ix + 1, self.m + 1)
+        self._rows = np.concatenate([e[0] for e in mats])
+        self._cols = np.concatenate([e[1] + k * n_wires for k, e in enumerate(mats)])
+        self._vals = np.concatenate([e[2] for e in mats]) if len(self._cols) else np.zeros((0, 32), np.uint8)
+        self._plans = {}
+
+    def _plan(self, ctx):
+        key = id(ctx)
+        if key not in self._plans:
+            self._plans[key] = (ctx, _ColumnPlan(ctx, self._cols, self._rows, self._vals, 3 * (self.m + 1)))
+        return self._plans[key][1]
+
+
+def _dense_plan(ctx, qap):
+    """a reference QAP's coefficient polynomials as columns (v_0..v_m, w_0..w_m, y_0..y_m, t), rows = degrees"""
+    polys = list(qap.v) + list(qap.w) + list(qap.y) + [qap.t]
+    rows, cols, ints = [], [], []
+    top = 0
+    for c, poly in enumerate(polys):
+        coeffs = poly.coeffs if hasattr(poly, "coeffs") else poly
+        top = max(top, len(coeffs))
+        for k, x in enumerate(coeffs):
+            x = int(x) % ORDER
+            if x:
+                rows.append(k)
+                cols.append(c)
+                ints.append(x)
+    vals = scalars_to_array(ints).reshape(-1, 32)
+    return _ColumnPlan(ctx, np.asarray(cols, np.int64), np.asarray(rows, np.int64), vals, len(polys)), top
+
+
+def _scalar_buf(ctx, values):
+    return ctx.upload(_native.ints_to_array([int(v) % ORDER for v in values], 32))
+
+
+class _QAPAtS:
+    """v_i(s), w_i(s), y_i(s), t(s) (vwyt: 3 (m + 1) + 1 device scalars) and 1, s, .., s^d (powers) of one QAP"""
+
+    def __init__(self, ctx, qap, s):
+        self.n_wires = len(qap.indices)
+        d = int(qap.d)
+        self.d = d
+        nw = self.n_wires
+        self.vwyt = ctx.alloc(32 * (3 * nw + 1))
+        self.t_ptr = self.vwyt.ptr + 32 * 3 * nw
+        sb = _scalar_buf(ctx, [s, 1])
+        self._keep = [sb]
+        if isinstance(qap, R1CSQAP):
+            plan, n_pow = qap._plan(ctx), d + 1
+        else:
+            plan, top = _dense_plan(ctx, qap)
+            n_pow = max(d + 1, top)
+            self._keep.append(plan)
+        self.powers = ctx.alloc(32 * n_pow)
+        ctx.upload_into(self.powers.ptr, _native.ints_to_array([1], 32))
+        ctx.bn256_fr_powers(sb.ptr, sb.ptr + 32, n_pow - 1, self.powers.ptr + 32)
+        if isinstance(qap, R1CSQAP):
+            self.ell = ctx.alloc(32 * d)
+            ctx.bn256_qap_lagrange(sb.ptr, d, self.ell.ptr, self.t_ptr)
+            plan.run(self.ell.ptr, d, self.vwyt.ptr)
+        else:
+            plan.run(self.powers.ptr, n_pow, self.vwyt.ptr)
+
+    def exps(self, ctx, td, wires):
+        """device buffer of the seven exponent vectors (len(wires) + 3 rows each, csrc/bn256_keygen.hip) for `wires`"""
+        n = len(wires)
+        coef = _scalar_buf(ctx, [td.r_v, td.r_w, td.r_y, td.alpha_v * td.r_v, td.alpha_w * td.r_w,
+                                 td.alpha_y * td.r_y, td.beta * td.r_v, td.beta * td.r_w, td.beta * td.r_y])
+        idx = ctx.upload(np.asarray(list(wires), np.uint32)) if n else ctx.alloc(4)
+        out = ctx.alloc(32 * 7 * (n + 3))
+        ctx.bn256_keygen_exps(coef.ptr, self.vwyt.ptr, self.n_wires, self.t_ptr, idx.ptr, n, out.ptr)
+        self._keep += [coef, idx]
+        return out
+
+
+# evalkey names per exponent vector of csrc/bn256_keygen.hip, in the reference's order (pynocchio.py:106-140)
+_EVAL_NAMES = (lambda i: f"r_v*v{i}*g1", lambda i: f"r_w*w{i}*g2", lambda i: f"r_y*y{i}*g1",
+               lambda i: f"r_v*alpha_v*v{i}*g1", lambda i: f"r_w*alpha_w*w{i}*g1", lambda i: f"r_y*alpha_y*y{i}*g1",
+               lambda i: f"r_v*beta*v+r_w*beta*w+r_y*beta*y{i}_g1")
+# zero-knowledge entries (pynocchio.py:143-154): (name, exponent vector, tail row); "t*g1" is t(s) itself
+_ZK_ENTRIES = (("r_v*t*g1", 0, 0), ("r_w*t*g2", 1, 0), ("r_y*t*g1", 2, 2), ("r_v*alpha_v*t*g1", 3, 0),
+               ("r_w*alpha_w*t*g1", 4, 1), ("r_y*alpha_y*t*g1", 5, 2), ("r_v*beta*t*g1", 6, 0),
+               ("r_w*beta*t*g1", 6, 1), ("r_y*beta*t*g1", 6, 2))
+
+
+def evalkey_vectors(td, qap, gen, ctx=None):
+    """The evaluation key's point vectors on the device, as PreparedKey.generate tabulates them: {element of
+    compute_proof (or "h*g1"): (group, device buffer of affine points, count)}; each element's vector holds its
+    per-wire points over qap.indices_mid, then its zero-knowledge tail (_tail_slots: infinity where unused)."""
+    return _evalkey_device(td, qap, gen, ctx or get_context())[0]
+
+
+def _evalkey_device(td, qap, gen, ctx):
+    b1, _ = _generator(ctx, gen.g1, 1, "generate: gen.g1")
+    b2, _ = _generator(ctx, gen.g2, 2, "generate: gen.g2")
+    at = _QAPAtS(ctx, qap, td.s)
+    mid = list(qap.indices_mid)
+    n = len(mid)
+    exps = at.exps(ctx, td, mid)
+    out = {}
+    for k, (name, (_, zk)) in enumerate(_ELEMENTS.items()):
+        group, base = (2, b2) if name.endswith("g2") else (1, b1)
+        count = n + len(_tail_slots(name, zk))
+        pts = ctx.alloc(64 * group * count)
+        ctx.bn256_fixed_base(group, base.ptr, exps.ptr + 32 * k * (n + 3), count, pts.ptr)
+        out[name] = (group, pts, count)
+    pts = ctx.alloc(64 * (at.d + 1))
+    ctx.bn256_fixed_base(1, b1.ptr, at.powers.ptr, at.d + 1, pts.ptr)
+    out["h*g1"] = (1, pts, at.d + 1)
+    ctx.sync()
+    return out, at, b1
+
+
+def _points_of(ctx, group, buf, count):
+    width = 64 * group
+    raw = ctx.download(buf.ptr, width * count).tobytes()
+    cls = BN256Point if group == 1 else BN256TwistPoint
+    return [cls.from_bytes(raw[width * i:width * i + width]) for i in range(count)]
+
+
+def generate_evalkey(td, qap, gen, ctx=None):
+    """The reference's generate_evalkey (pynocchio.py:101-167): the same names in the same order, every point equal to
+    the reference's for the same td.  Each entry is one fixed-base product of g1 or g2 by an exponent made on the device
+    (v_i(s), w_i(s), y_i(s), t(s) by csrc/bn256_keygen.hip).  qap: a reference QAP or an R1CSQAP."""
+    ctx = ctx or get_context()
+    vecs, at, b1 = _evalkey_device(td, qap, gen, ctx)
+    mid = list(qap.indices_mid)
+    n = len(mid)
+    pts = {name: _points_of(ctx, *vecs[name]) for name in vecs}
+    names = list(_ELEMENTS)
+    key = {}
+    for k in range(6):
+        key.update((_EVAL_NAMES[k](i), pts[names[k]][j]) for j, i in enumerate(mid))
+    key.update(("s^" + str(i) + "*g1", p) for i, p in enumerate(pts["h*g1"]))
+    key.update((_EVAL_NAMES[6](i), pts[names[6]][j]) for j, i in enumerate(mid))
+    for zname, k, row in _ZK_ENTRIES:
+        key[zname] = pts[names[k]][n + row]
+    key["t*g1"] = _fixed_base_points(ctx, 1, b1, at.t_ptr, 1)[0]
+    return key
+
+
+def generate_verikey(td, qap, gen, ctx=None):
+    """The reference's generate_verikey (pynocchio.py:170-200): same names, order and points."""
+    ctx = ctx or get_context()
+    b1, raw1 = _generator(ctx, gen.g1, 1, "generate_verikey: gen.g1")
+    b2, raw2 = _generator(ctx, gen.g2, 2, "generate_verikey: gen.g2")
+    at = _QAPAtS(ctx, qap, td.s)
+    io0 = list(qap.indices_io_and_0)
+    n = len(io0)
+    exps = at.exps(ctx, td, io0)
+    s1 = _scalar_buf(ctx, [td.alpha_w, td.beta * td.gamma])
+    s2 = _scalar_buf(ctx, [td.alpha_v, td.alpha_y, td.gamma, td.beta * td.gamma])
+    aw_g1, bg_g1 = _fixed_base_points(ctx, 1, b1, s1.ptr, 2)
+    av_g2, ay_g2, g_g2, bg_g2 = _fixed_base_points(ctx, 2, b2, s2.ptr, 4)
+    ryt_g2 = _fixed_base_points(ctx, 2, b2, exps.ptr + 32 * (2 * (n + 3) + n + 2), 1)[0]
+    v = _fixed_base_points(ctx, 1, b1, exps.ptr, n)
+    w = _fixed_base_points(ctx, 2, b2, exps.ptr + 32 * (n + 3), n)
+    y = _fixed_base_points(ctx, 1, b1, exps.ptr + 32 * 2 * (n + 3), n)
+    key = {"g1": BN256Point.from_bytes(raw1), "g2": BN256TwistPoint.from_bytes(raw2), "alpha_v*g2": av_g2,
+           "alpha_w*g1": aw_g1, "alpha_y*g2": ay_g2, "gamma*g2": g_g2, "beta*gamma*g1": bg_g1,
+           "beta*gamma*g2": bg_g2, "r_y*t*g2": ryt_g2}
+    key.update((f"r_v*v{i}*g1", v[j]) for j, i in enumerate(io0))
+    key.update((f"r_w*w{i}*g2", w[j]) for j, i in enumerate(io0))
+    key.update((f"r_y*y{i}*g1", y[j]) for j, i in enumerate(io0))
+    return key
+
+
+def _prepared_generate(cls, td, qap, gen, ctx=None):
+    """PreparedKey(qap, generate_evalkey(td, qap, gen)) without the host round trip: the exponent vectors stay on the
+    device, go to bn256_fixed_base, and the points to _KeyVector.from_device (validated and tabulated there)"""
+    ctx = ctx or get_context()
+    vecs = evalkey_vectors(td, qap, gen, ctx)
+    key = cls.__new__(cls)
+    key.ctx = ctx
+    key.mid = list(qap.indices_mid)
+    key.mid_index = np.asarray(key.mid, dtype=np.int64)
+    key.vectors, key.zk_missing = {}, {}
+    for name, (group, pts, count) in vecs.items():
+        key.vectors[name] = _KeyVector.from_device(ctx, group, pts, count)
+    return key
+
+
+PreparedKey.generate = classmethod(_prepared_generate)
