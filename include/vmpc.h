@@ -445,6 +445,40 @@ int vmpc_bn256_qap_colsum_dev(vmpc_ctx *ctx, const void *basis, size_t n_basis, 
 int vmpc_bn256_keygen_exps_dev(vmpc_ctx *ctx, const void *coef, const void *vwy, size_t n_wires, const void *t,
                                const uint32_t *idx, size_t n_idx, void *out);
 
+/* ---- The Pinocchio prover's h = (V W - Y) / t (verifiable_mpc/trinocchio/pynocchio.py:203-225: compute_p_poly,
+ * p / qap.t, compute_h_zk_terms - quadratic Python over the dense QAP) from the row values a = V c, b = W c, y = Y c of
+ * the R1CS (a_j = V(j): constraint j sits at x = j), same scalar conventions (csrc/bn256_qap_h.hip, DESIGN.md section
+ * 14).  With w_j = t'(j) = (-1)^(d-j) (j-1)! (d-j)!, u_j = a_j / w_j and the moments A_k = sum_j u_j j^(k-1) (B_k from b),
+ *     C_k = sum_{i=1..k-1} A_i B_(k-i) + delta_v B_k + delta_w A_k,   h_e = sum_{i=e+1..d} t_i C_(i-e) + delta_v delta_w t_e
+ *                                                                            - [e = 0] delta_y      (e = 0..d).
+ * Cap for all six entries: d + 1 <= VMPC_BN256_FR_POLY_MAX; above it they answer VMPC_E_RANGE before they look at any
+ * pointer.  d >= 1. */
+/* out0[k] = sum_{j=1..d} u0[j-1] j^k mod n for k < n_out (n_out <= VMPC_BN256_FR_POLY_MAX), and the same for u1 -> out1
+ * when u1 is not NULL (the two share the powers of j).  Replaces nothing the reference has: it stands in for the
+ * interpolation of V and W (qap_creator.r1cs_to_qap_ff) and the product of pynocchio.py:203-211.  Deterministic (no
+ * atomics).  Uses the context arena: at most 2 x 32 x n_out scalars (the partial sums of the ranges of j). */
+int vmpc_bn256_qap_moments_dev(vmpc_ctx *ctx, const void *u0, const void *u1, size_t d, size_t n_out, void *out0,
+                               void *out1);
+/* ua[j-1] = a[j-1] / w_j and, when b is not NULL, ub[j-1] = b[j-1] / w_j for j = 1..d: factorial prefix products and
+ * one inversion.  Uses the context arena (d + d / 64 + 4 scalars). */
+int vmpc_bn256_qap_h_weights_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t d, void *ua, void *ub);
+/* *first_bad (a device uint32) = the smallest i < d with a[i] * b[i] != y[i] mod n, 0xffffffff if there is none: the
+ * check that the reference's demo makes on the remainder of p / qap.t.  No arena. */
+int vmpc_bn256_qap_check_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t d, uint32_t *first_bad);
+/* out[0..d] = the coefficients of t(x) = prod_{j=1..d} (x - j), lowest first (qap_creator.r1cs_to_qap_ff builds qap.t by
+ * d Poly.__mul__): leaves of 128 factors and a product tree over vmpc_bn256_fr_poly_mul_dev.  scratch: device memory
+ * of 2 (d + (d + 127) / 128) scalars (not read when d <= 128).  Uses the context arena as the products do. */
+int vmpc_bn256_qap_t_coeffs_dev(vmpc_ctx *ctx, size_t d, void *scratch, void *out);
+/* out[p d + i] = sum_k coeffs[p n_coeffs + k] (i + 1)^k for i < d, p < n_polys (<= 65535): the values V(j), W(j), Y(j)
+ * of a dense QAP's V = sum_i c_i v_i (pynocchio.py:203-209), Horner with small multipliers.  No arena. */
+int vmpc_bn256_qap_horner_dev(vmpc_ctx *ctx, const void *coeffs, size_t n_coeffs, size_t n_polys, size_t d, void *out);
+/* out[0..d] = h_0 .. h_d as above (pynocchio.py:212-225: p / qap.t plus compute_h_zk_terms) from the moments
+ * A[i] = A_(i+1), B[i] = B_(i+1) (i < d), t's d + 1 coefficients and deltas = (delta_v, delta_w, delta_y) (NULL: all
+ * zero).  scratch: device memory of 5 d scalars.  Two d x d products through vmpc_bn256_fr_poly_mul_dev, whose arena
+ * use it has. */
+int vmpc_bn256_qap_h_combine_dev(vmpc_ctx *ctx, const void *A, const void *B, const void *t, size_t d,
+                                 const void *deltas, void *scratch, void *out);
+
 /* SHA-256 of every `chunk_bytes`-sized piece of a device buffer (last piece may be short):
  * out_digests[i] = SHA256(data[i*chunk : (i+1)*chunk]), 32 bytes each.  Leaves of the compact
  * transcript's two-level digests; not used by the reference transcript. */

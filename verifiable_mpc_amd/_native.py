@@ -47,6 +47,8 @@ SYMBOLS = [
     "vmpc_bn256_pairing", "vmpc_bn256_pairing_product", "vmpc_bn256_lincomb_batch",
     "vmpc_bn256_fr_poly_mul_dev", "vmpc_bn256_fr_poly_mul", "vmpc_bn256_fr_powers_dev",
     "vmpc_bn256_qap_lagrange_dev", "vmpc_bn256_qap_colsum_dev", "vmpc_bn256_keygen_exps_dev",
+    "vmpc_bn256_qap_moments_dev", "vmpc_bn256_qap_h_weights_dev", "vmpc_bn256_qap_check_dev",
+    "vmpc_bn256_qap_t_coeffs_dev", "vmpc_bn256_qap_horner_dev", "vmpc_bn256_qap_h_combine_dev",
 ]
 
 
@@ -157,6 +159,12 @@ def load_library():
         "vmpc_bn256_qap_lagrange_dev": (i32, [vp, vp, sz, vp, vp]),
         "vmpc_bn256_qap_colsum_dev": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_bn256_keygen_exps_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp]),
+        "vmpc_bn256_qap_moments_dev": (i32, [vp, vp, vp, sz, sz, vp, vp]),
+        "vmpc_bn256_qap_h_weights_dev": (i32, [vp, vp, vp, sz, vp, vp]),
+        "vmpc_bn256_qap_check_dev": (i32, [vp, vp, vp, vp, sz, vp]),
+        "vmpc_bn256_qap_t_coeffs_dev": (i32, [vp, sz, vp, vp]),
+        "vmpc_bn256_qap_horner_dev": (i32, [vp, vp, sz, sz, sz, vp]),
+        "vmpc_bn256_qap_h_combine_dev": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
         "vmpc_msm_table_fold_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp]),
         "vmpc_msm_table_fold_table_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp, sz, i32, vp]),
         "vmpc_p4_create": (i32, [vp, vp, sz, sz, i32, i32, i32, vp, vp, vp, ctypes.POINTER(vp)]),
@@ -868,6 +876,42 @@ class Context:
         _check(self.lib.vmpc_bn256_keygen_exps_dev(self.handle, ctypes.c_void_p(coef_ptr), ctypes.c_void_p(vwy_ptr),
                                                    n_wires, ctypes.c_void_p(t_ptr), ctypes.c_void_p(idx_ptr), n_idx,
                                                    ctypes.c_void_p(out_ptr)), "vmpc_bn256_keygen_exps_dev")
+
+    def bn256_qap_moments(self, u0_ptr, u1_ptr, d, n_out, out0_ptr, out1_ptr):
+        """out0[k] = sum_j u0[j-1] j^k (k < n_out) and the same for u1 -> out1 unless u1_ptr is 0 / None; VmpcError
+        E_RANGE above the library's cap, before anything is read or written (as for the five entries below)"""
+        _check(self.lib.vmpc_bn256_qap_moments_dev(self.handle, ctypes.c_void_p(u0_ptr), ctypes.c_void_p(u1_ptr), d,
+                                                   n_out, ctypes.c_void_p(out0_ptr), ctypes.c_void_p(out1_ptr)),
+               "vmpc_bn256_qap_moments_dev")
+
+    def bn256_qap_h_weights(self, a_ptr, b_ptr, d, ua_ptr, ub_ptr):
+        """ua[j-1] = a[j-1] / w_j (and ub from b unless b_ptr is 0 / None), w_j = (-1)^(d-j) (j-1)! (d-j)!"""
+        _check(self.lib.vmpc_bn256_qap_h_weights_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), d,
+                                                     ctypes.c_void_p(ua_ptr), ctypes.c_void_p(ub_ptr)),
+               "vmpc_bn256_qap_h_weights_dev")
+
+    def bn256_qap_check(self, a_ptr, b_ptr, y_ptr, d, first_bad_ptr):
+        """device uint32 at first_bad_ptr = smallest i with a[i] b[i] != y[i], 0xffffffff if none"""
+        _check(self.lib.vmpc_bn256_qap_check_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr),
+                                                 ctypes.c_void_p(y_ptr), d, ctypes.c_void_p(first_bad_ptr)),
+               "vmpc_bn256_qap_check_dev")
+
+    def bn256_qap_t_coeffs(self, d, scratch_ptr, out_ptr):
+        """out[0..d] = coefficients of prod_{j=1..d} (x - j); scratch: 2 (d + ceil(d / 128)) scalars"""
+        _check(self.lib.vmpc_bn256_qap_t_coeffs_dev(self.handle, d, ctypes.c_void_p(scratch_ptr),
+                                                    ctypes.c_void_p(out_ptr)), "vmpc_bn256_qap_t_coeffs_dev")
+
+    def bn256_qap_horner(self, coeffs_ptr, n_coeffs, n_polys, d, out_ptr):
+        """out[p d + i] = P_p(i + 1) for the n_polys coefficient vectors of n_coeffs scalars each"""
+        _check(self.lib.vmpc_bn256_qap_horner_dev(self.handle, ctypes.c_void_p(coeffs_ptr), n_coeffs, n_polys, d,
+                                                  ctypes.c_void_p(out_ptr)), "vmpc_bn256_qap_horner_dev")
+
+    def bn256_qap_h_combine(self, a_ptr, b_ptr, t_ptr, d, deltas_ptr, scratch_ptr, out_ptr):
+        """out[0..d] = h from the moments, t's coefficients and the three deltas (0 / None: none); scratch: 5 d scalars"""
+        _check(self.lib.vmpc_bn256_qap_h_combine_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr),
+                                                     ctypes.c_void_p(t_ptr), d, ctypes.c_void_p(deltas_ptr),
+                                                     ctypes.c_void_p(scratch_ptr), ctypes.c_void_p(out_ptr)),
+               "vmpc_bn256_qap_h_combine_dev")
 
     def bn256_validate(self, group, points_ptr, n):
         bad = ctypes.c_uint64()

@@ -1,0 +1,496 @@
+// The Pinocchio prover's quotient polynomial h = (V W - Y) / t over BN-256's GF(n), from the row values of the R1CS
+// (verifiable_mpc/trinocchio/pynocchio.py:203-225: compute_p_poly, p / qap.t, compute_h_zk_terms - quadratic Python over
+// the dense QAP).  n - 1 = 2^5 * odd: no NTT; the polynomials V, W are never interpolated.  With a_j = V(j), b_j = W(j)
+// (j = 1..d), w_j = t'(j) = (-1)^(d-j) (j-1)! (d-j)! and u_j = a_j / w_j,
+//     V(x) / t(x) = sum_j u_j / (x - j) = sum_{k>=1} A_k x^-k,   A_k = sum_j u_j j^(k-1)   (the moments of u)
+// so the polynomial part of V W / t (= h for a satisfying witness, deg Y < d) is a correlation of t's coefficients
+// with the low half of the product of the two moment series.
+//
+//   vmpc_bn256_qap_moments_dev     out[k] = sum_{j=1..d} u[j-1] j^k for k < n_out, one or two vectors.  THE hot kernel:
+//                                  d * n_out steps, but a step multiplies the running value u_j j^k by the small integer
+//                                  j (frbn_mul_small), not by a field element.  A workgroup owns QH_KS consecutive k and
+//                                  a range of j; lane t holds QH_J running values per vector (j = chunk base + t + 256 i),
+//                                  started at the segment's first k by square-and-multiply (the power of j shared by
+//                                  both vectors).  Per k a lane adds its values in nine limbs, cuts the sum into 26-bit
+//                                  pieces and the wave adds each piece in 32-bit registers (DPP within rows of 16, four
+//                                  readlanes across them); lane (k mod 64) keeps the wave's total.  Every 64 k the four
+//                                  waves' totals go through LDS into the workgroup's nine-limb accumulators (one per k
+//                                  and vector), which persist over the workgroup's chunks of j.  One partial per
+//                                  (j range, k), reduced mod n, goes to the arena; k_qh_partsum adds them in a fixed
+//                                  order.  Integer additions only: deterministic, no atomics.
+//   vmpc_bn256_qap_h_weights_dev   ua[j-1] = a_j / w_j, ub[j-1] = b_j / w_j: with E_m = d (d-1) .. (d-m+1),
+//                                  1 / ((j-1)! (d-j)!) = E_(d-j+1) E_j / d!^2 - prefix products of small integers and ONE
+//                                  inversion, as vmpc_bn256_qap_lagrange_dev does for its Q_j.
+//   vmpc_bn256_qap_check_dev       the smallest j with a_j b_j != y_j
+//   vmpc_bn256_qap_t_coeffs_dev    the d + 1 coefficients of t = prod (x - j): leaves of QH_LEAF factors multiplied out
+//                                  in LDS, then a product tree over vmpc_bn256_fr_poly_mul_dev
+//   vmpc_bn256_qap_horner_dev      P(1), .., P(d) of coefficient vectors (the dense QAP form), one lane per point
+//   vmpc_bn256_qap_h_combine_dev   moments, t, deltas -> h (two products through vmpc_bn256_fr_poly_mul_dev)
+#include <vector>
+
+#include "common.h"
+#include "fr_bn.h"
+
+#define QH_WG 256
+#define QH_J 4                      // running values per lane and vector
+#define QH_CHUNK (QH_WG * QH_J)     // j per workgroup pass
+#define QH_KS 512                   // k per workgroup (LDS: 2 x 512 x 36 B accumulators + 18 KB staging)
+#define QH_KB 64                    // k between two accumulator updates (one per lane of a wave)
+#define QH_MAX_GROUPS 32            // j ranges (partials per k) at most
+#define QH_TARGET_WGS 2048
+#define QH_RUN 64                   // sequence elements per lane in the weights' scan
+#define QH_SCAN 256
+#define QH_LEAF 128                 // factors (x - j) per leaf of t's product tree
+
+__device__ __forceinline__ frbn qh_ld(const void *p, long long i) {
+    const uint4 *q = (const uint4 *)((const uint32_t *)p + 8 * i);
+    const uint4 x = q[0], y = q[1];
+    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+    return frbn_load(w);
+}
+
+__device__ __forceinline__ void qh_st(void *p, long long i, const frbn &a) {
+    uint4 *q = (uint4 *)((uint32_t *)p + 8 * i);
+    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
+    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
+}
+
+// the sum of x over the 64 lanes (uniform), for lane values below 2^26: rows of 16 by DPP (xor 1, xor 2, half
+// mirror, mirror leave the row's sum in every lane), the four rows by readlane
+__device__ __forceinline__ uint32_t qh_wave_sum(uint32_t x) {
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xF, 0xF, true);   // row_half_mirror
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xF, 0xF, true);   // row_mirror
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 0) + (uint32_t)__builtin_amdgcn_readlane((int)x, 16) +
+           (uint32_t)__builtin_amdgcn_readlane((int)x, 32) + (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
+}
+
+// grid (k segments, j groups).  part[v][(g n_out + k)] = sum over group g's j of u_v[j-1] j^k mod n.
+// Bounds: j <= d < 2^21 (frbn_mul_small); a lane's QH_J values sum below 2^258 (ten 26-bit pieces), 64 lanes' pieces
+// below 2^32, a wave total below 2^264, four waves and at most 2^10 chunks below 2^276 < 2^288 (frbn_wide).
+template <int NV>
+__global__ void __launch_bounds__(QH_WG)
+k_qh_moments(const uint32_t *__restrict__ u0, const uint32_t *__restrict__ u1, uint32_t d, uint32_t n_out, uint32_t ks,
+             uint32_t chunks_per_group, uint32_t *__restrict__ part0, uint32_t *__restrict__ part1) {
+    __shared__ uint32_t sAcc[NV][QH_KS][9];
+    __shared__ uint32_t sSt[QH_WG / 64][NV][9][64];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t k0 = blockIdx.x * ks, g = blockIdx.y;
+    for (uint32_t i = t; i < NV * QH_KS * 9; i += QH_WG) (&sAcc[0][0][0])[i] = 0;
+    __syncthreads();
+    const uint32_t n_chunks = (d + QH_CHUNK - 1) / QH_CHUNK;
+    const uint32_t c_end = (g + 1) * chunks_per_group < n_chunks ? (g + 1) * chunks_per_group : n_chunks;
+    for (uint32_t c = g * chunks_per_group; c < c_end; c++) {
+        uint32_t jv[QH_J];
+        frbn v[NV][QH_J];
+#pragma unroll
+        for (int i = 0; i < QH_J; i++) {
+            const uint32_t idx = c * QH_CHUNK + i * QH_WG + t;   // j - 1
+            const bool in = idx < d;
+            jv[i] = in ? idx + 1 : 0;
+            frbn pw = frbn_one();
+            if (k0) {   // (uniform) j^k0, left to right: full squarings, small multiplications
+                for (int b = 31 - __clz(k0); b >= 0; b--) {
+                    pw = frbn_mul(pw, pw);
+                    if ((k0 >> b) & 1u) pw = frbn_mul_small(pw, jv[i]);
+                }
+            }
+#pragma unroll
+            for (int nv = 0; nv < NV; nv++) {
+                const uint32_t *u = nv ? u1 : u0;
+                v[nv][i] = in ? qh_ld(u, idx) : frbn_zero();
+                if (k0) v[nv][i] = frbn_mul(v[nv][i], pw);
+            }
+        }
+        for (uint32_t kb = 0; kb < ks; kb += QH_KB) {
+            uint32_t mine[NV][10];
+#pragma unroll
+            for (int nv = 0; nv < NV; nv++)
+#pragma unroll
+                for (int q = 0; q < 10; q++) mine[nv][q] = 0;
+#pragma unroll 1
+            for (uint32_t kk = 0; kk < QH_KB; kk++) {
+#pragma unroll
+                for (int nv = 0; nv < NV; nv++) {
+                    frbn_wide s = frbn_wide_zero();
+#pragma unroll
+                    for (int i = 0; i < QH_J; i++) frbn_wide_add_fr(s, v[nv][i]);
+                    uint32_t p[10];
+                    frbn_wide_split26(s, p);
+#pragma unroll
+                    for (int q = 0; q < 10; q++) {
+                        const uint32_t tot = qh_wave_sum(p[q]);
+                        mine[nv][q] = lane == kk ? tot : mine[nv][q];
+                    }
+#pragma unroll
+                    for (int i = 0; i < QH_J; i++) v[nv][i] = frbn_mul_small(v[nv][i], jv[i]);
+                }
+            }
+            // lane l of each wave holds the wave's total for k = k0 + kb + l: add the four into the accumulators
+#pragma unroll
+            for (int nv = 0; nv < NV; nv++) {
+                const frbn_wide w = frbn_wide_join26(mine[nv]);
+#pragma unroll
+                for (int l = 0; l < 9; l++) sSt[wave][nv][l][lane] = w.v[l];
+            }
+            __syncthreads();
+            if (t < 64 * NV) {
+                const uint32_t nv = t >> 6;
+                uint32_t *acc = sAcc[nv][kb + lane];
+                frbn_wide a;
+#pragma unroll
+                for (int l = 0; l < 9; l++) a.v[l] = acc[l];
+#pragma unroll
+                for (int w = 0; w < QH_WG / 64; w++) {
+                    frbn_wide o;
+#pragma unroll
+                    for (int l = 0; l < 9; l++) o.v[l] = sSt[w][nv][l][lane];
+                    frbn_wide_add(a, o);
+                }
+#pragma unroll
+                for (int l = 0; l < 9; l++) acc[l] = a.v[l];
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = t; i < NV * ks; i += QH_WG) {
+        const uint32_t nv = i / ks, k = i % ks;
+        if (k0 + k >= n_out) continue;
+        frbn_wide a;
+#pragma unroll
+        for (int l = 0; l < 9; l++) a.v[l] = sAcc[nv][k][l];
+        qh_st(nv ? part1 : part0, (long long)g * n_out + k0 + k, frbn_wide_reduce(a));
+    }
+}
+
+// out[k] = part[0][k] + part[1][k] + .. in that order
+__global__ void __launch_bounds__(256)
+k_qh_partsum(const uint32_t *__restrict__ part, uint32_t n_out, uint32_t groups, uint32_t *__restrict__ out) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_out) return;
+    frbn s = qh_ld(part, k);
+    for (uint32_t g = 1; g < groups; g++) s = frbn_add(s, qh_ld(part, (long long)g * n_out + k));
+    qh_st(out, k, s);
+}
+
+extern "C" int vmpc_bn256_qap_moments_dev(vmpc_ctx *ctx, const void *u0, const void *u1, size_t d, size_t n_out,
+                                          void *out0, void *out1) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_out > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !u0 || !out0 || (u1 && !out1) || d == 0) return VMPC_E_INVAL;
+    if (n_out == 0) return VMPC_OK;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const int nv = u1 ? 2 : 1;
+    const uint32_t ks = (uint32_t)(n_out >= QH_KS ? QH_KS : (n_out + QH_KB - 1) / QH_KB * QH_KB);
+    const uint32_t n_kseg = (uint32_t)((n_out + ks - 1) / ks);
+    const uint32_t n_chunks = (uint32_t)((d + QH_CHUNK - 1) / QH_CHUNK);
+    uint32_t groups = QH_TARGET_WGS / n_kseg;
+    if (groups < 1) groups = 1;
+    if (groups > QH_MAX_GROUPS) groups = QH_MAX_GROUPS;
+    if (groups > n_chunks) groups = n_chunks;
+    const uint32_t cpg = (n_chunks + groups - 1) / groups;
+    groups = (n_chunks + cpg - 1) / cpg;
+    const size_t part_b = (size_t)groups * n_out * 32;
+    VMPC_CHECK(vmpc_ws_reserve(ctx, 2 * vmpc_align(part_b) + 512));
+    uint32_t *part0 = (uint32_t *)vmpc_ws_take(ctx, part_b);
+    uint32_t *part1 = (uint32_t *)vmpc_ws_take(ctx, part_b);
+    {
+        vmpc_stage_scope sc(ctx, "bn_qap_moments");
+        const dim3 grid(n_kseg, groups);
+        if (nv == 2)
+            k_qh_moments<2><<<grid, QH_WG, 0, ctx->stream>>>((const uint32_t *)u0, (const uint32_t *)u1, (uint32_t)d,
+                                                             (uint32_t)n_out, ks, cpg, part0, part1);
+        else
+            k_qh_moments<1><<<grid, QH_WG, 0, ctx->stream>>>((const uint32_t *)u0, nullptr, (uint32_t)d,
+                                                             (uint32_t)n_out, ks, cpg, part0, part1);
+        VMPC_KERNEL_CHECK();
+    }
+    {
+        vmpc_stage_scope sc(ctx, "bn_qap_moments_sum");
+        const unsigned blocks = (unsigned)((n_out + 255) / 256);
+        k_qh_partsum<<<blocks, 256, 0, ctx->stream>>>(part0, (uint32_t)n_out, groups, (uint32_t *)out0);
+        VMPC_KERNEL_CHECK();
+        if (nv == 2) {
+            k_qh_partsum<<<blocks, 256, 0, ctx->stream>>>(part1, (uint32_t)n_out, groups, (uint32_t *)out1);
+            VMPC_KERNEL_CHECK();
+        }
+    }
+    return VMPC_OK;
+}
+
+// ---- the weights 1 / w_j ---------------------------------------------------------------------------------------------
+// E[m] = d (d-1) .. (d-m+1) for m = 0..d (E[d] = d!): exclusive prefix products of e_k = d - k
+
+// run[l] = product of e_k over [l QH_RUN, (l+1) QH_RUN) n [0, d)
+__global__ void __launch_bounds__(256) k_qh_runprod(uint32_t d, uint32_t lanes, uint32_t *__restrict__ run) {
+    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= lanes) return;
+    const uint32_t k0 = l * QH_RUN, k1 = k0 + QH_RUN < d ? k0 + QH_RUN : d;
+    frbn p = frbn_one();
+    for (uint32_t k = k0; k < k1; k++) p = frbn_mul_small(p, d - k);
+    qh_st(run, l, p);
+}
+
+// one workgroup: run[*] -> exclusive prefix products, total = d!, inv_sq = 1 / d!^2 (one Fermat inversion)
+__global__ void __launch_bounds__(QH_SCAN)
+k_qh_runscan(uint32_t lanes, uint32_t *__restrict__ run, uint32_t *__restrict__ total, uint32_t *__restrict__ inv_sq) {
+    __shared__ frbn buf[2][QH_SCAN];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (lanes + QH_SCAN - 1) / QH_SCAN;
+    const uint32_t b0 = t * per < lanes ? t * per : lanes, b1 = b0 + per < lanes ? b0 + per : lanes;
+    frbn p = frbn_one();
+    for (uint32_t i = b0; i < b1; i++) p = frbn_mul(p, qh_ld(run, i));
+    int cur = 0;
+    buf[cur][t] = p;
+    __syncthreads();
+    for (uint32_t off = 1; off < QH_SCAN; off <<= 1) {
+        frbn v = buf[cur][t];
+        if (t >= off) v = frbn_mul(buf[cur][t - off], v);
+        buf[cur ^ 1][t] = v;
+        cur ^= 1;
+        __syncthreads();
+    }
+    frbn acc = t ? buf[cur][t - 1] : frbn_one();
+    for (uint32_t i = b0; i < b1; i++) {
+        const frbn x = qh_ld(run, i);
+        qh_st(run, i, acc);
+        acc = frbn_mul(acc, x);
+    }
+    if (t == QH_SCAN - 1) {
+        qh_st(total, 0, acc);
+        const frbn iv = frbn_inv(acc);
+        qh_st(inv_sq, 0, frbn_mul(iv, iv));
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_qh_runfill(uint32_t d, uint32_t lanes, const uint32_t *__restrict__ run, const uint32_t *__restrict__ total,
+             uint32_t *__restrict__ E) {
+    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= lanes) return;
+    frbn v = qh_ld(run, l);
+    const uint32_t k0 = l * QH_RUN, k1 = k0 + QH_RUN < d ? k0 + QH_RUN : d;
+    for (uint32_t k = k0; k < k1; k++) {
+        qh_st(E, k, v);
+        v = frbn_mul_small(v, d - k);
+    }
+    if (l == lanes - 1) qh_st(E, d, qh_ld(total, 0));
+}
+
+// ua[j-1] = a_j f_j, ub[j-1] = b_j f_j, f_j = (-1)^(d-j) E[d-j+1] E[j] / d!^2 = 1 / w_j
+__global__ void __launch_bounds__(256)
+k_qh_weights(uint32_t d, const uint32_t *__restrict__ E, const uint32_t *__restrict__ inv_sq,
+             const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ ua,
+             uint32_t *__restrict__ ub) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d) return;
+    const uint32_t j = i + 1;
+    frbn f = frbn_mul(frbn_mul(qh_ld(E, d - j + 1), qh_ld(E, j)), qh_ld(inv_sq, 0));
+    if ((d - j) & 1u) f = frbn_sub(frbn_zero(), f);
+    qh_st(ua, i, frbn_mul(qh_ld(a, i), f));
+    if (b) qh_st(ub, i, frbn_mul(qh_ld(b, i), f));
+}
+
+extern "C" int vmpc_bn256_qap_h_weights_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t d, void *ua, void *ub) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !a || !ua || (b && !ub) || d == 0) return VMPC_E_INVAL;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const uint32_t dd = (uint32_t)d, lanes = (uint32_t)((d + QH_RUN - 1) / QH_RUN);
+    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align((size_t)lanes * 32) + vmpc_align((d + 1) * 32) + 1024));
+    uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, (size_t)lanes * 32);
+    uint32_t *E = (uint32_t *)vmpc_ws_take(ctx, (d + 1) * 32);
+    uint32_t *small = (uint32_t *)vmpc_ws_take(ctx, 64);   // d!, 1 / d!^2
+    vmpc_stage_scope sc(ctx, "bn_qap_h_weights");
+    const unsigned lb = (lanes + 255) / 256;
+    k_qh_runprod<<<lb, 256, 0, ctx->stream>>>(dd, lanes, run);
+    VMPC_KERNEL_CHECK();
+    k_qh_runscan<<<1, QH_SCAN, 0, ctx->stream>>>(lanes, run, small, small + 8);
+    VMPC_KERNEL_CHECK();
+    k_qh_runfill<<<lb, 256, 0, ctx->stream>>>(dd, lanes, run, small, E);
+    VMPC_KERNEL_CHECK();
+    k_qh_weights<<<(unsigned)((d + 255) / 256), 256, 0, ctx->stream>>>(dd, E, small + 8, (const uint32_t *)a,
+                                                                      (const uint32_t *)b, (uint32_t *)ua,
+                                                                      (uint32_t *)ub);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+// ---- the witness check -------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_qh_check(uint32_t d, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ y,
+           uint32_t *__restrict__ first_bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d) return;
+    const frbn p = frbn_mul(qh_ld(a, i), qh_ld(b, i)), q = qh_ld(y, i);
+    bool same = true;
+#pragma unroll
+    for (int l = 0; l < 8; l++) same = same && p.v[l] == q.v[l];
+    if (!same) atomicMin(first_bad, i);   // an index, not a field value: the minimum does not depend on the order
+}
+
+extern "C" int vmpc_bn256_qap_check_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t d,
+                                        uint32_t *first_bad) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !y || !first_bad || d == 0) return VMPC_E_INVAL;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope sc(ctx, "bn_qap_check");
+    VMPC_HIP_CHECK(hipMemsetAsync(first_bad, 0xFF, 4, ctx->stream));
+    k_qh_check<<<(unsigned)((d + 255) / 256), 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)a,
+                                                                    (const uint32_t *)b, (const uint32_t *)y, first_bad);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+// ---- t's coefficients --------------------------------------------------------------------------------------------------
+// leaf l: prod (x - j) over j = l QH_LEAF + 1 .. min((l+1) QH_LEAF, d), its deg + 1 coefficients at dst + 32 (l QH_LEAF + l)
+// (leaves packed one after the other).  Thread i owns coefficient i: new_i = old_(i-1) - j old_i.
+__global__ void __launch_bounds__(QH_WG) k_qh_tleaf(uint32_t d, uint32_t *__restrict__ dst) {
+    __shared__ frbn sP[2][QH_LEAF + 1];
+    const uint32_t t = threadIdx.x, l = blockIdx.x;
+    const uint32_t j0 = l * QH_LEAF + 1, j1 = j0 + QH_LEAF - 1 < d ? j0 + QH_LEAF - 1 : d;
+    int cur = 0;
+    if (t <= QH_LEAF) sP[0][t] = t == 0 ? frbn_one() : frbn_zero();
+    __syncthreads();
+    for (uint32_t j = j0; j <= j1; j++) {
+        if (t <= QH_LEAF) {
+            const frbn left = t ? sP[cur][t - 1] : frbn_zero();
+            sP[cur ^ 1][t] = frbn_sub(left, frbn_mul_small(sP[cur][t], j));
+        }
+        cur ^= 1;
+        __syncthreads();
+    }
+    const uint32_t deg = j1 - j0 + 1;
+    if (t <= deg) qh_st(dst, (long long)l * (QH_LEAF + 1) + t, sP[cur][t]);
+}
+
+extern "C" int vmpc_bn256_qap_t_coeffs_dev(vmpc_ctx *ctx, size_t d, void *scratch, void *out) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !out || d == 0 || (d > QH_LEAF && !scratch)) return VMPC_E_INVAL;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t leaves = (d + QH_LEAF - 1) / QH_LEAF;
+    if (leaves == 1) {
+        vmpc_stage_scope sc(ctx, "bn_qap_t_leaf");
+        k_qh_tleaf<<<1, QH_WG, 0, ctx->stream>>>((uint32_t)d, (uint32_t *)out);
+        VMPC_KERNEL_CHECK();
+        return VMPC_OK;
+    }
+    // two level buffers of d + leaves scalars each: a level's polynomials lie one after the other
+    const size_t level_b = (d + leaves) * 32;
+    char *buf[2] = {(char *)scratch, (char *)scratch + level_b};
+    {
+        vmpc_stage_scope sc(ctx, "bn_qap_t_leaf");
+        k_qh_tleaf<<<(unsigned)leaves, QH_WG, 0, ctx->stream>>>((uint32_t)d, (uint32_t *)buf[0]);
+        VMPC_KERNEL_CHECK();
+    }
+    std::vector<size_t> off(leaves), len(leaves);
+    for (size_t l = 0; l < leaves; l++) {
+        off[l] = l * (QH_LEAF + 1);
+        len[l] = (l + 1 < leaves ? QH_LEAF : d - l * QH_LEAF) + 1;
+    }
+    int cur = 0;
+    while (off.size() > 1) {
+        std::vector<size_t> noff, nlen;
+        size_t pos = 0;
+        const bool last = off.size() == 2;
+        char *dst = last ? (char *)out : buf[cur ^ 1];
+        for (size_t i = 0; i + 1 < off.size(); i += 2) {
+            VMPC_CHECK(vmpc_bn256_fr_poly_mul_dev(ctx, buf[cur] + 32 * off[i], len[i], buf[cur] + 32 * off[i + 1],
+                                                  len[i + 1], dst + 32 * pos));
+            noff.push_back(pos);
+            nlen.push_back(len[i] + len[i + 1] - 1);
+            pos += nlen.back();
+        }
+        if (off.size() & 1) {
+            const size_t i = off.size() - 1;
+            VMPC_HIP_CHECK(hipMemcpyAsync(dst + 32 * pos, buf[cur] + 32 * off[i], 32 * len[i], hipMemcpyDeviceToDevice,
+                                          ctx->stream));
+            noff.push_back(pos);
+            nlen.push_back(len[i]);
+        }
+        off.swap(noff);
+        len.swap(nlen);
+        cur ^= 1;
+    }
+    return VMPC_OK;
+}
+
+// ---- values at the integer points (dense QAP form) --------------------------------------------------------------------
+// out[p d + i] = sum_k coeffs[p n_coeffs + k] (i + 1)^k: Horner with small multipliers, one lane per point
+__global__ void __launch_bounds__(256)
+k_qh_horner(const uint32_t *__restrict__ coeffs, uint32_t n_coeffs, uint32_t d, uint32_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y;
+    if (i >= d) return;
+    const uint32_t *c = coeffs + 8 * (size_t)p * n_coeffs;
+    frbn acc = frbn_zero();
+    for (uint32_t k = n_coeffs; k-- > 0;) acc = frbn_add(frbn_mul_small(acc, i + 1), qh_ld(c, k));
+    qh_st(out, (long long)p * d + i, acc);
+}
+
+extern "C" int vmpc_bn256_qap_horner_dev(vmpc_ctx *ctx, const void *coeffs, size_t n_coeffs, size_t n_polys, size_t d,
+                                         void *out) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_coeffs > VMPC_BN256_FR_POLY_MAX || n_polys > 65535) return VMPC_E_RANGE;
+    if (!ctx || !out || d == 0 || (n_coeffs && !coeffs)) return VMPC_E_INVAL;
+    if (n_polys == 0) return VMPC_OK;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope sc(ctx, "bn_qap_horner");
+    k_qh_horner<<<dim3((unsigned)((d + 255) / 256), (unsigned)n_polys), 256, 0, ctx->stream>>>(
+        (const uint32_t *)coeffs, (uint32_t)n_coeffs, (uint32_t)d, (uint32_t *)out);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+// ---- the combination --------------------------------------------------------------------------------------------------
+// A[i] = A_(i+1), B[i] = B_(i+1) (the moments), P = A * B.  crev[r] = C_(d-r) with
+//     C_k = P[k-2] (k >= 2) + delta_v B_k + delta_w A_k
+__global__ void __launch_bounds__(256)
+k_qh_cmid(uint32_t d, const uint32_t *__restrict__ A, const uint32_t *__restrict__ B, const uint32_t *__restrict__ P,
+          const uint32_t *__restrict__ deltas, uint32_t *__restrict__ crev) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= d) return;
+    const uint32_t i = d - 1 - r;   // C_(i+1)
+    frbn c = i ? qh_ld(P, i - 1) : frbn_zero();
+    if (deltas) {
+        c = frbn_add(c, frbn_mul(qh_ld(deltas, 0), qh_ld(B, i)));
+        c = frbn_add(c, frbn_mul(qh_ld(deltas, 1), qh_ld(A, i)));
+    }
+    qh_st(crev, r, c);
+}
+
+// Q = (t_1 .. t_d) * crev: h_e = Q[d-1+e] + delta_v delta_w t_e - [e = 0] delta_y for e < d, h_d = delta_v delta_w t_d
+__global__ void __launch_bounds__(256)
+k_qh_final(uint32_t d, const uint32_t *__restrict__ Q, const uint32_t *__restrict__ tc,
+           const uint32_t *__restrict__ deltas, uint32_t *__restrict__ out) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e > d) return;
+    frbn h = e < d ? qh_ld(Q, (long long)d - 1 + e) : frbn_zero();
+    if (deltas) {
+        h = frbn_add(h, frbn_mul(frbn_mul(qh_ld(deltas, 0), qh_ld(deltas, 1)), qh_ld(tc, e)));
+        if (e == 0) h = frbn_sub(h, qh_ld(deltas, 2));
+    }
+    qh_st(out, e, h);
+}
+
+extern "C" int vmpc_bn256_qap_h_combine_dev(vmpc_ctx *ctx, const void *A, const void *B, const void *t, size_t d,
+                                            const void *deltas, void *scratch, void *out) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !A || !B || !t || !scratch || !out || d == 0) return VMPC_E_INVAL;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    // scratch: P (2d - 1), crev (d), Q (2d - 1)
+    char *P = (char *)scratch, *crev = P + 32 * (2 * d - 1), *Q = crev + 32 * d;
+    const unsigned blocks = (unsigned)((d + 1 + 255) / 256);
+    VMPC_CHECK(vmpc_bn256_fr_poly_mul_dev(ctx, A, d, B, d, P));
+    {
+        vmpc_stage_scope sc(ctx, "bn_qap_h_cmid");
+        k_qh_cmid<<<blocks, 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)A, (const uint32_t *)B,
+                                                   (const uint32_t *)P, (const uint32_t *)deltas, (uint32_t *)crev);
+        VMPC_KERNEL_CHECK();
+    }
+    VMPC_CHECK(vmpc_bn256_fr_poly_mul_dev(ctx, (const char *)t + 32, d, crev, d, Q));
+    {
+        vmpc_stage_scope sc(ctx, "bn_qap_h_final");
+        k_qh_final<<<blocks, 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)Q, (const uint32_t *)t,
+                                                    (const uint32_t *)deltas, (uint32_t *)out);
+        VMPC_KERNEL_CHECK();
+    }
+    return VMPC_OK;
+}

@@ -9,8 +9,14 @@ zero-knowledge case, adds `delta * evalkey[<t term>]`.  Here every element is ON
 (csrc/bn256.hip) with the zero-knowledge terms appended as extra (scalar, point) pairs.
 Keys and proofs hold `BN256Point` / `BN256TwistPoint` objects (affine coordinates); foreign
 points (e.g. MPyC's Jacobian elements) are accepted if they expose `.normalize()` and three
-indexable coordinates.  QAP construction from code stays with the reference (out of scope, SURVEY.md 2 rows 10, 13);
-so does the prover's h (compute_p_poly, p / qap.t, compute_h_zk_terms: this field has no NTT of useful length).
+indexable coordinates.  QAP construction from code stays with the reference (out of scope).
+
+    compute_h        verifiable_mpc/trinocchio/pynocchio.py:203-225 (compute_p_poly, p / qap.t, compute_h_zk_terms)
+
+The prover's h = (V W - Y) / t comes from the R1CS row values at the witness (csrc/bn256_qap_h.hip, DESIGN.md section
+14): this field has no NTT of useful length, and V, W are never interpolated - their quotients by t are power series
+whose coefficients are the moments sum_j (a_j / t'(j)) j^k of the weighted row values, and h is a correlation of t's
+coefficients with the low half of the two series' product.  The result stays on the device for compute_proof.
 
     Trapdoor, SampleDeltas, Generators        verifiable_mpc/trinocchio/pynocchio.py:36-69 (draws from `prng`)
     generate_evalkey, generate_verikey        verifiable_mpc/trinocchio/pynocchio.py:101-200
@@ -361,7 +367,7 @@ def _compute_proof_prepared(key, c, h, deltas):
     inversion for all seven G1 results).
     c: indexable by qap.indices_mid (the reference's list of ints / field elements), or an (n_wires, 32) uint8
     array of canonical residues (rows taken by index); h: the reference's polynomial (.coeffs), a list, or an
-    (len, 32) uint8 array."""
+    (len, 32) uint8 array, or compute_h's HPoly (read where it lies on the device)."""
     from .device import get_aux_context
     ctx = key.ctx
     n_mid = len(key.mid)
@@ -385,7 +391,8 @@ def _compute_proof_prepared(key, c, h, deltas):
         ctx.upload_into(head.ptr + 32 * n_mid, _native.ints_to_array(dvals, 32))
     hv = key.vectors["h*g1"]
     h_ctx = get_aux_context(21)
-    h_coeffs = h if isinstance(h, (np.ndarray, list)) else h.coeffs
+    h_dev = h if isinstance(h, HPoly) else None
+    h_coeffs = None if h_dev is not None else h if isinstance(h, (np.ndarray, list)) else h.coeffs
     g1 = [key.vectors[name] for name in _SHARED_G1]
     out_g1 = ctx.alloc(96 * len(g1))
     # three streams: the twist sum (the longest single one) first, the six-sum pass beside it, h's sum on a third -
@@ -400,12 +407,17 @@ def _compute_proof_prepared(key, c, h, deltas):
     ctx.bn256_table_msm_multi(1, [v.table.ptr for v in g1], g1[0].n, head.ptr, n_shared, out_g1.ptr)
     # h's coefficients: converted (the reference's ints) and uploaded on the third stream while the GPU works through
     # the seven sums over c (an upload only synchronises the stream it is issued on)
-    if isinstance(h_coeffs, np.ndarray):
-        h_arr = scalars_to_array(h_coeffs)
+    if h_dev is not None:
+        # compute_h's coefficients are on the device already: the h stream waits for the stream that made them
+        h_ctx.wait_for(h_dev.ctx)
+        pending_h = hv.launch(h_ctx, h_dev.buf if len(h_dev) else None, len(h_dev))
     else:
-        h_arr = scalars_to_array([h_coeffs[i] for i in range(len(h))])
-    h_head = h_ctx.upload(h_arr) if len(h_arr) else None
-    pending_h = hv.launch(h_ctx, h_head, len(h_arr))
+        if isinstance(h_coeffs, np.ndarray):
+            h_arr = scalars_to_array(h_coeffs)
+        else:
+            h_arr = scalars_to_array([h_coeffs[i] for i in range(len(h))])
+        h_head = h_ctx.upload(h_arr) if len(h_arr) else None
+        pending_h = hv.launch(h_ctx, h_head, len(h_arr))
     ctx.sync()
     h_ctx.sync()
     raw = ctx.download(out_g1.ptr, 96 * len(g1)).tobytes() + h_ctx.download(pending_h[1].ptr, 96).tobytes()
@@ -1099,3 +1111,136 @@ def _prepared_generate(cls, td, qap, gen, ctx=None):
 
 
 PreparedKey.generate = classmethod(_prepared_generate)
+
+
+# ---- the prover's h (trinocchio/pynocchio.py:203-225; csrc/bn256_qap_h.hip) ------------------------------------------
+
+class HPoly:
+    """compute_h's result: h's coefficients in device memory (`buf`, 32 bytes each, lowest first, `len()` of them, made
+    on `ctx`'s stream).  `.coeffs` downloads them once, as Python ints - what the reference's Poly offers."""
+
+    def __init__(self, ctx, buf, n):
+        self.ctx, self.buf, self._n, self._coeffs = ctx, buf, n, None
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def coeffs(self):
+        if self._coeffs is None:
+            self.ctx.sync()
+            raw = self.ctx.download(self.buf.ptr, 32 * self._n).tobytes() if self._n else b""
+            self._coeffs = [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(self._n)]
+        return self._coeffs
+
+
+def _witness_array(qap, c):
+    """the witness over qap.indices as (n_wires, 32) uint8 (any 32-byte values: the device reduces them)"""
+    n_wires = len(qap.indices)
+    if isinstance(c, np.ndarray):
+        arr = _native.as_bytes_array(c, 32)
+        if len(arr) != n_wires:
+            raise ValueError(f"compute_h: the witness has {len(arr)} rows, the QAP {n_wires} wires")
+        return arr
+    return scalars_to_array([c[i] for i in qap.indices])
+
+
+def _per_ctx(qap, name, ctx, make):
+    """a device object of `qap` made once per context (kept on the QAP object)"""
+    cache = qap.__dict__.setdefault("_h_cache", {})
+    key = (name, id(ctx))
+    if key not in cache:
+        cache[key] = (ctx, make())
+    return cache[key][1]
+
+
+def _row_plan(ctx, qap):
+    """an R1CSQAP's entries in ROW order (a, b, y stacked: 3 d sums), for vmpc_bn256_qap_colsum_dev with basis = c"""
+    n_wires = qap.m + 1
+    kind, wire = qap._cols // n_wires, qap._cols % n_wires
+    return _ColumnPlan(ctx, qap._rows + kind * qap.d, wire, qap._vals, 3 * qap.d)
+
+
+def _coeff_plan(ctx, qap):
+    """a reference QAP's coefficients with the roles exchanged: "column" = (polynomial kind, degree), "row" = wire, so
+    that the column sums against c are the coefficients of V, W and Y -> (plan, coefficients per polynomial)"""
+    top = max([len(p.coeffs if hasattr(p, "coeffs") else p) for polys in (qap.v, qap.w, qap.y) for p in polys] + [1])
+    rows, cols, ints = [], [], []
+    for kind, polys in enumerate((qap.v, qap.w, qap.y)):
+        for i, poly in zip(qap.indices, polys):
+            for k, x in enumerate(poly.coeffs if hasattr(poly, "coeffs") else poly):
+                x = int(x) % ORDER
+                if x:
+                    rows.append(i)
+                    cols.append(kind * top + k)
+                    ints.append(x)
+    vals = scalars_to_array(ints).reshape(-1, 32)
+    return _ColumnPlan(ctx, np.asarray(cols, np.int64), np.asarray(rows, np.int64), vals, 3 * top), top
+
+
+def _t_coeffs(ctx, qap):
+    """device buffer of t's d + 1 coefficients, made once per (context, QAP)"""
+    d = int(qap.d)
+
+    def make():
+        out = ctx.alloc(32 * (d + 1))
+        if isinstance(qap, R1CSQAP):
+            scratch = ctx.alloc(64 * (d + (d + 127) // 128))
+            ctx.bn256_qap_t_coeffs(d, scratch.ptr, out.ptr)
+            ctx.sync()
+        else:
+            t = [int(x) % ORDER for x in qap.t.coeffs]
+            if len(t) != d + 1:
+                raise ValueError("compute_h: qap.t must have d + 1 coefficients")
+            ctx.upload_into(out.ptr, _native.ints_to_array(t, 32))
+        return out
+    return _per_ctx(qap, "t", ctx, make)
+
+
+def _row_values(ctx, qap, dc, n_wires):
+    """device buffer a || b || y (d scalars each): the R1CS row values V(j), W(j), Y(j) at the witness"""
+    d = int(qap.d)
+    aby = ctx.alloc(32 * 3 * d)
+    if isinstance(qap, R1CSQAP):
+        _per_ctx(qap, "rows", ctx, lambda: _row_plan(ctx, qap)).run(dc.ptr, n_wires, aby.ptr)
+        return aby, ()
+    plan, top = _per_ctx(qap, "coeffs", ctx, lambda: _coeff_plan(ctx, qap))
+    coef = ctx.alloc(32 * 3 * top)
+    plan.run(dc.ptr, n_wires, coef.ptr)
+    ctx.bn256_qap_horner(coef.ptr, top, 3, d, aby.ptr)
+    return aby, (coef,)
+
+
+def compute_h(qap, c, deltas=None, ctx=None):
+    """The reference's h, coefficient for coefficient and length included (pynocchio.py:203-225): with `deltas`
+    h + compute_h_zk_terms(qap, c, deltas), d + 1 coefficients; without, p / qap.t, max(d - 1, 0) coefficients (top
+    zeros kept).  qap: an R1CSQAP or a reference QAP; c: as compute_proof takes it (ints / field elements indexable by
+    qap.indices, negative or >= the order reduced, or an (n_wires, 32) uint8 array).  All O(d^2) work runs on the
+    device; the result (an HPoly) stays there and compute_proof over a PreparedKey reads it in place.  A witness that
+    violates a constraint raises ValueError naming the first violated constraint (1-based, the point x = j)."""
+    ctx = ctx or get_context()
+    d = int(qap.d)
+    if d + 1 > _native.BN256_FR_POLY_MAX:
+        raise ValueError(f"compute_h: d + 1 = {d + 1} exceeds the polynomial product's cap {_native.BN256_FR_POLY_MAX}")
+    c_arr = _witness_array(qap, c)
+    n_wires = len(c_arr)
+    dc = ctx.upload(c_arr) if n_wires else ctx.alloc(32)
+    aby, keep = _row_values(ctx, qap, dc, n_wires)
+    a_ptr, b_ptr, y_ptr = aby.ptr, aby.ptr + 32 * d, aby.ptr + 64 * d
+    bad = ctx.alloc(4)
+    ctx.bn256_qap_check(a_ptr, b_ptr, y_ptr, d, bad.ptr)
+    ctx.sync()
+    first = int(ctx.download(bad.ptr, 4).view("<u4")[0])
+    if first != 0xFFFFFFFF:
+        raise ValueError(f"compute_h: the witness violates constraint {first + 1} (V(j) W(j) != Y(j) at j = {first + 1})")
+    t = _t_coeffs(ctx, qap)
+    u = ctx.alloc(32 * 2 * d)
+    ctx.bn256_qap_h_weights(a_ptr, b_ptr, d, u.ptr, u.ptr + 32 * d)
+    mom = ctx.alloc(32 * 2 * d)
+    ctx.bn256_qap_moments(u.ptr, u.ptr + 32 * d, d, d, mom.ptr, mom.ptr + 32 * d)
+    dd = _scalar_buf(ctx, [deltas.v, deltas.w, deltas.y]) if deltas is not None else None
+    scratch, out = ctx.alloc(32 * 5 * d), ctx.alloc(32 * (d + 1))
+    ctx.bn256_qap_h_combine(mom.ptr, mom.ptr + 32 * d, t.ptr, d, dd.ptr if dd else None, scratch.ptr, out.ptr)
+    ctx.sync()      # the temporaries above may be released once the stream has drained
+    del keep
+    return HPoly(ctx, out, d + 1 if deltas is not None else max(d - 1, 0))
