@@ -479,6 +479,46 @@ int vmpc_bn256_qap_horner_dev(vmpc_ctx *ctx, const void *coeffs, size_t n_coeffs
 int vmpc_bn256_qap_h_combine_dev(vmpc_ctx *ctx, const void *A, const void *B, const void *t, size_t d,
                                  const void *deltas, void *scratch, void *out);
 
+/* ---- Protocol 8 from a sparse circuit (verifiable_mpc/ac20/circuit_sat_cb.py:59-252), scalars mod l as above ------
+ * m multiplication gates, M = m + 1, z = (x, f(0), g(0), h(0), h(1), .., h(2m)); f runs through (j, a_j) for j = 1..m
+ * and (m + 1, r_a), g alike (circuit_sat_r1cs.py:380-388).  m <= VMPC_FR_CS_MAX_M: above it the entries answer
+ * VMPC_E_RANGE before they look at any pointer.  All deterministic (integer sums in a fixed order, no atomics on
+ * field values). */
+#define VMPC_FR_CS_MAX_M ((size_t)1 << 20)
+/* For the n_gates gates `gates[t]` (NULL: gates 0 .. n_gates-1) of one depth level: a_out[i], b_out[i] = the affine
+ * forms of the left / right wire (CSR rows i of A / B: row_ptr, col, 32-byte vals, one 32-byte constant per row) at
+ * (x, gamma), where column c < n_x reads z[c] and column c >= n_x reads z[gamma_offset + c - n_x]; then
+ * z[gamma_offset + i] = a_i b_i (circuit_builder.py:133-151).  The caller launches the levels in order and has
+ * checked that every column index is in range.  check = 1: z's gammas are the caller's, nothing is written to z, and
+ * *first_bad (a device uint32) = the smallest i with a_i b_i != z[gamma_offset + i], 0xffffffff if none.  check = 2:
+ * a_out, b_out only (the values of output rows: pass them as A and as B).  No arena. */
+int vmpc_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_vals,
+                           const void *a_const, const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_vals,
+                           const void *b_const, const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset,
+                           void *z, void *a_out, void *b_out, int check, uint32_t *first_bad);
+/* fact[k] = k!, ifact[k] = 1 / k! for k = 0..K (K >= 1): two product scans and one inversion.  Arena: 2 K scalars. */
+int vmpc_fr_cs_tables_dev(vmpc_ctx *ctx, size_t K, void *fact, void *ifact);
+/* a, b: M scalars (a_1..a_m, r_a).  Writes z_tail[0] = f(0), [1] = g(0), [2] = h(0), [2 + m + 1] = r_a r_b and
+ * [2 + x] = f(x) g(x) for x = m+2 .. 2m; z_tail[3 .. 2 + m] (the gammas) are left alone.  fact / ifact: the tables with
+ * K >= 2m + 1.  Two m x m correlations with 1 / k, schoolbook with lazy reduction (circuit_sat_r1cs.py:384-386 and
+ * circuit_sat_cb.py:89-90 interpolate, multiply and evaluate coefficient lists).  Arena: about (4 + 2 s) m scalars
+ * for s segments of j. */
+int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact, const void *ifact,
+                          void *z_tail);
+/* out[j] = the Lagrange basis polynomial of node j among 0..K at c, j = 0..K (ac20/recombine.py:5-32 as called by
+ * circuit_builder.py:548-549); ifact: the table with at least K + 1 entries.  No inversion: exact for every c, a
+ * node included (the unit vector).  Arena: 3 K scalars. */
+int vmpc_fr_cs_lagrange_dev(vmpc_ctx *ctx, const uint8_t c[32], size_t K, const void *ifact, void *out);
+/* Transposed sparse mat-vec: out is zeroed (n_out scalars), then out[col_pos[c]] = sum over the entries e of listed
+ * column c of vals[e] * weights[rows[e]] (circuit_builder.py:517-545).  Entries are in column order; segment s is
+ * entries [seg_ptr[s], seg_ptr[s+1]) (one lane each, so keep them short) and column c owns segments
+ * [col_seg[c], col_seg[c+1]).  Rows >= n_rows add nothing, positions >= n_out are not written.  Arena: n_segs scalars. */
+int vmpc_fr_cs_colsum_dev(vmpc_ctx *ctx, const void *weights, size_t n_rows, const uint32_t *rows, const void *vals,
+                          const uint32_t *seg_ptr, size_t n_segs, const uint32_t *col_seg, const uint32_t *col_pos,
+                          size_t n_cols, void *out, size_t n_out);
+/* *first_diff (a device uint32) = the smallest i < n with a[i] != b[i], 0xffffffff if none.  No arena. */
+int vmpc_fr_cs_first_diff_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, uint32_t *first_diff);
+
 /* SHA-256 of every `chunk_bytes`-sized piece of a device buffer (last piece may be short):
  * out_digests[i] = SHA256(data[i*chunk : (i+1)*chunk]), 32 bytes each.  Leaves of the compact
  * transcript's two-level digests; not used by the reference transcript. */

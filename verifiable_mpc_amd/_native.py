@@ -49,6 +49,8 @@ SYMBOLS = [
     "vmpc_bn256_qap_lagrange_dev", "vmpc_bn256_qap_colsum_dev", "vmpc_bn256_keygen_exps_dev",
     "vmpc_bn256_qap_moments_dev", "vmpc_bn256_qap_h_weights_dev", "vmpc_bn256_qap_check_dev",
     "vmpc_bn256_qap_t_coeffs_dev", "vmpc_bn256_qap_horner_dev", "vmpc_bn256_qap_h_combine_dev",
+    "vmpc_fr_cs_triples_dev", "vmpc_fr_cs_tables_dev", "vmpc_fr_cs_extend_dev", "vmpc_fr_cs_lagrange_dev",
+    "vmpc_fr_cs_colsum_dev", "vmpc_fr_cs_first_diff_dev",
 ]
 
 
@@ -165,6 +167,12 @@ def load_library():
         "vmpc_bn256_qap_t_coeffs_dev": (i32, [vp, sz, vp, vp]),
         "vmpc_bn256_qap_horner_dev": (i32, [vp, vp, sz, sz, sz, vp]),
         "vmpc_bn256_qap_h_combine_dev": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
+        "vmpc_fr_cs_triples_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, i32, vp]),
+        "vmpc_fr_cs_tables_dev": (i32, [vp, sz, vp, vp]),
+        "vmpc_fr_cs_extend_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
+        "vmpc_fr_cs_lagrange_dev": (i32, [vp, vp, sz, vp, vp]),
+        "vmpc_fr_cs_colsum_dev": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, sz]),
+        "vmpc_fr_cs_first_diff_dev": (i32, [vp, vp, vp, sz, vp]),
         "vmpc_msm_table_fold_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp]),
         "vmpc_msm_table_fold_table_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp, sz, i32, vp]),
         "vmpc_p4_create": (i32, [vp, vp, sz, sz, i32, i32, i32, vp, vp, vp, ctypes.POINTER(vp)]),
@@ -786,6 +794,43 @@ class Context:
         _check(self.lib.vmpc_fr_dot_to_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), n,
                                            ctypes.c_void_p(out.ptr)), "vmpc_fr_dot_to_dev")
         return out
+
+    # ---- Protocol 8 from a sparse circuit (csrc/circuit_sat.hip) ------------------------------------------------------
+    def cs_triples(self, A, B, gates_ptr, n_gates, n_x, gamma_offset, z_ptr, a_ptr, b_ptr, check=0, first_bad_ptr=None):
+        """A, B: (row_ptr, col, vals, consts) device pointers"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_fr_cs_triples_dev(self.handle, p(A[0]), p(A[1]), p(A[2]), p(A[3]), p(B[0]), p(B[1]), p(B[2]),
+                                               p(B[3]), p(gates_ptr), n_gates, n_x, gamma_offset, p(z_ptr), p(a_ptr),
+                                               p(b_ptr), check, p(first_bad_ptr)), "vmpc_fr_cs_triples_dev")
+
+    def cs_tables(self, K, fact_ptr, ifact_ptr):
+        _check(self.lib.vmpc_fr_cs_tables_dev(self.handle, K, ctypes.c_void_p(fact_ptr), ctypes.c_void_p(ifact_ptr)),
+               "vmpc_fr_cs_tables_dev")
+
+    def cs_extend(self, a_ptr, b_ptr, m, fact_ptr, ifact_ptr, z_tail_ptr):
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_fr_cs_extend_dev(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr),
+                                              p(z_tail_ptr)), "vmpc_fr_cs_extend_dev")
+
+    def cs_lagrange(self, c, K, ifact_ptr, out_ptr):
+        cb = ctypes.create_string_buffer(scalar_to_bytes(c), 32)
+        _check(self.lib.vmpc_fr_cs_lagrange_dev(self.handle, cb, K, ctypes.c_void_p(ifact_ptr), ctypes.c_void_p(out_ptr)),
+               "vmpc_fr_cs_lagrange_dev")
+
+    def cs_colsum(self, weights_ptr, n_rows, rows_ptr, vals_ptr, seg_ptr, n_segs, col_seg_ptr, col_pos_ptr, n_cols,
+                  out_ptr, n_out):
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_fr_cs_colsum_dev(self.handle, p(weights_ptr), n_rows, p(rows_ptr), p(vals_ptr), p(seg_ptr),
+                                              n_segs, p(col_seg_ptr), p(col_pos_ptr), n_cols, p(out_ptr), n_out),
+               "vmpc_fr_cs_colsum_dev")
+
+    def cs_first_diff(self, a_ptr, b_ptr, n):
+        """the smallest i with a[i] != b[i], or None"""
+        out = self.alloc(4)
+        _check(self.lib.vmpc_fr_cs_first_diff_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), n,
+                                                  ctypes.c_void_p(out.ptr)), "vmpc_fr_cs_first_diff_dev")
+        v = int(self.download(out.ptr, 4).view(np.uint32)[0])
+        return None if v == 0xFFFFFFFF else v
 
     def _format(self, fn, name, src_ptr, n, per_item_cap, *extra):
         cap = n * per_item_cap + 16

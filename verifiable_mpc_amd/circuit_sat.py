@@ -6,9 +6,11 @@ AC20 hot path: generator setup and the pivot dispatch enum.
     next_power_of_2                 circuit_sat_r1cs.py:391-392
     check_input_length_power_of_2   circuit_sat_cb.py:46-56
 
-The circuit front end (circuit_builder, Protocol 8's form construction) is out of scope
+The circuit front end (circuit_builder's operator overloading and gadgets) is out of scope
 and keeps running in the reference's Python; `verifiable_mpc_amd.install()` points the
-reference's modules at the functions of this package.
+reference's modules at the functions of this package.  Protocol 8 itself runs on the device
+for a circuit given as data (circuit_sat_gpu.SparseCircuit); circuit_sat_prover / _verifier
+below dispatch on the circuit's type.
 """
 from enum import Enum
 from random import SystemRandom
@@ -89,10 +91,11 @@ def check_input_length_power_of_2(x, circuit, padding_value=0):
 
 
 # ---- the harness names (circuit_sat_cb.py:255-318) ----------------------------------------------------------------
-# The circuit front end - circuit_builder, the Protocol-8 form construction, the dispatch on PivotChoice - is
-# quadratic-time Python that stays with the reference (out of scope).  These two names exist so
-# that a caller who switches to this package finds them: they install() the hot path into the reference's modules
-# and hand the call to the reference's own function, unchanged.
+# For a circuit_builder.Circuit the front end - circuit_builder, the Protocol-8 form construction, the dispatch on
+# PivotChoice - is quadratic-time Python that stays with the reference (out of scope).  These two
+# names exist so that a caller who switches to this package finds them: they install() the hot path into the
+# reference's modules and hand the call to the reference's own function, unchanged.  (A SparseCircuit goes to
+# circuit_sat_gpu instead.)
 REFERENCE_PACKAGE = "verifiable_mpc.ac20"
 
 
@@ -111,15 +114,27 @@ def _reference_circuit_sat():
 
 def circuit_sat_prover(generators, circuit, x, gf, pivot_choice=PivotChoice.compressed):
     """circuit_sat_cb.py:255-282, same arguments and return value: the reference's function over this package's
-    vector_commitment / protocol_5_prover / create_generators (install())."""
+    vector_commitment / protocol_5_prover / create_generators (install()).  A circuit_sat_gpu.SparseCircuit is proved
+    wholly in this package (Protocol 8 on the device)."""
+    if _is_sparse(circuit):
+        from . import circuit_sat_gpu
+        return circuit_sat_gpu.circuit_sat_prover(generators, circuit, x, gf, pivot_choice)
     ref = _reference_circuit_sat()
     return ref.circuit_sat_prover(generators, circuit, x, gf, _ref_choice(ref, pivot_choice))
 
 
 def circuit_sat_verifier(proof, generators, circuit, gf, pivot_choice=PivotChoice.compressed):
     """circuit_sat_cb.py:285-318, same arguments and return value (the verification dict)."""
+    if _is_sparse(circuit):
+        from . import circuit_sat_gpu
+        return circuit_sat_gpu.circuit_sat_verifier(proof, generators, circuit, gf, pivot_choice)
     ref = _reference_circuit_sat()
     return ref.circuit_sat_verifier(proof, generators, circuit, gf, _ref_choice(ref, pivot_choice))
+
+
+def _is_sparse(circuit):
+    from .circuit_sat_gpu import SparseCircuit
+    return isinstance(circuit, SparseCircuit)
 
 
 def _ref_choice(ref, choice):

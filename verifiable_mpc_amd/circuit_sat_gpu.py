@@ -1,0 +1,677 @@
+"""Protocol 8 of AC20 (circuit satisfiability, verifiable_mpc/ac20/circuit_sat_cb.py:59-318) from a SPARSE circuit, on
+the device: the step that turns "a circuit and its inputs" into the triple (z, [z], L) the pivots take.
+
+    SparseCircuit                    what Protocol 8 needs of a circuit_builder.Circuit, as CSR data
+    protocol_8_excl_pivot_prover     circuit_sat_cb.py:59-166
+    protocol_8_excl_pivot_verifier   circuit_sat_cb.py:169-252
+    circuit_sat_prover / _verifier   circuit_sat_cb.py:255-318 (PivotChoice.compressed and .pivot)
+
+The reference evaluates the gates one by one, interpolates f and g as coefficient lists, multiplies them and evaluates h
+at 2m + 1 points (quadratic Python with a large constant), and builds a dense form per gate.  Here (csrc/circuit_sat.hip)
+the triples are computed level by level, f and g are extended to 0 and m+2..2m in barycentric form (a correlation with
+the table 1/k: the one quadratic step, this field has no NTT), the Lagrange vectors at the challenge are prefix / suffix
+products, and the forms are transposed sparse mat-vecs.  z and L never leave the device between the triples and the
+pivot.
+
+Transcripts, selected by `transcript=` (default: TRANSCRIPT below): "compact" (DESIGN.md section 15 states the bytes;
+tests/p8_ref.py restates them) - the path that scales, z and L device-resident - and "reference": the reference's two
+str(input_list) hashes with its element types, list mode, O((n_out + 3) N) text, for parity on small circuits.
+"""
+import hashlib
+from random import SystemRandom
+
+import numpy as np
+
+from . import compressed_pivot, pivot, wire
+from .device import ScalarVector, get_context
+from .groups import ORDER
+
+prng = SystemRandom()
+
+TRANSCRIPT = "compact"
+SEG = 64                     # entries per lane of the column sums (long columns are cut)
+
+_ORDER_WORDS = np.array([(ORDER >> (32 * k)) & 0xFFFFFFFF for k in range(8)], dtype=np.int64)
+
+
+def _ints_to_array(vals):
+    return np.frombuffer(b"".join((int(v) % ORDER).to_bytes(32, "little") for v in vals), np.uint8).reshape(-1, 32).copy() \
+        if len(vals) else np.zeros((0, 32), np.uint8)
+
+
+def _values_array(vals):
+    """coefficients -> (nnz, 32) uint8 canonical residues mod l: ints of any sign or size, an integer numpy array, or a
+    (nnz, 32) uint8 array of 256-bit little-endian values (the conventions of pynocchio._values_array, this field)"""
+    if isinstance(vals, np.ndarray) and vals.dtype == np.uint8 and vals.ndim == 2:
+        a = np.ascontiguousarray(vals).copy()
+        big = np.nonzero(a[:, 31] >= 0x10)[0]          # only these can be >= l
+        for i in big.tolist():
+            a[i] = np.frombuffer((int.from_bytes(a[i].tobytes(), "little") % ORDER).to_bytes(32, "little"), np.uint8)
+        return a
+    if isinstance(vals, np.ndarray) and vals.dtype.kind in "iu" and vals.ndim == 1 and vals.dtype.itemsize <= 8:
+        a = vals.astype(np.int64) if vals.dtype.kind == "i" else vals.astype(np.uint64)
+        neg = a < 0 if a.dtype.kind == "i" else np.zeros(len(a), bool)
+        mag = np.where(neg, -a, a).astype(np.uint64)
+        words = np.zeros((len(a), 8), np.int64)
+        words[:, 0] = (mag & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        words[:, 1] = (mag >> np.uint64(32)).astype(np.int64)
+        if neg.any():
+            borrow = np.zeros(int(neg.sum()), np.int64)
+            sub = words[neg]
+            for k in range(8):
+                dk = _ORDER_WORDS[k] - sub[:, k] - borrow
+                borrow = (dk < 0).astype(np.int64)
+                sub[:, k] = dk + (borrow << 32)
+            words[neg] = sub
+        return np.ascontiguousarray(words.astype("<u4")).view(np.uint8).reshape(-1, 32)
+    return _ints_to_array(list(vals))
+
+
+class _Matrix:
+    """affine forms as canonical CSR: entries sorted by (row, col), duplicates added, zeros dropped"""
+
+    def __init__(self, M, n_cols, what):
+        if len(M) == 4:
+            row_ptr, col, vals, consts = M
+        else:
+            (row_ptr, col, vals), consts = M, None
+        row_ptr = np.asarray(row_ptr, np.int64)
+        col = np.asarray(col, np.int64)
+        n_rows = len(row_ptr) - 1
+        if n_rows < 0 or row_ptr[0] != 0 or np.any(np.diff(row_ptr) < 0) or row_ptr[-1] != len(col):
+            raise ValueError(f"SparseCircuit: {what}: row_ptr must rise from 0 to the number of entries")
+        v = _values_array(vals)
+        if len(v) != len(col):
+            raise ValueError(f"SparseCircuit: {what}: one value per entry")
+        if len(col) and (col.min() < 0 or col.max() >= n_cols):
+            raise ValueError(f"SparseCircuit: {what}: column index out of range")
+        rows = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(row_ptr))
+        key = rows * max(n_cols, 1) + col
+        order = np.argsort(key, kind="stable")
+        key, rows, col, v = key[order], rows[order], col[order], v[order]
+        dup = np.nonzero(key[1:] == key[:-1])[0]
+        if len(dup):
+            keep = np.ones(len(key), bool)
+            for i in dup.tolist():          # entry i + 1 repeats entry i: add it into the first of its run
+                first = i
+                while not keep[first]:
+                    first -= 1
+                s = int.from_bytes(v[first].tobytes(), "little") + int.from_bytes(v[i + 1].tobytes(), "little")
+                v[first] = np.frombuffer((s % ORDER).to_bytes(32, "little"), np.uint8)
+                keep[i + 1] = False
+            rows, col, v = rows[keep], col[keep], v[keep]
+        nz = v.any(axis=1) if len(v) else np.zeros(0, bool)
+        rows, col, v = rows[nz], col[nz], v[nz]
+        self.n_rows, self.n_cols = n_rows, n_cols
+        self.rows, self.col, self.vals = rows, col, np.ascontiguousarray(v)
+        self.row_ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n_rows))]).astype(np.int64) \
+            if n_rows else np.zeros(1, np.int64)
+        self.consts = _values_array(consts) if consts is not None else np.zeros((n_rows, 32), np.uint8)
+        if len(self.consts) != n_rows:
+            raise ValueError(f"SparseCircuit: {what}: one constant per row")
+
+    def canonical_bytes(self):
+        return b"".join([self.n_rows.to_bytes(8, "little"), len(self.col).to_bytes(8, "little"),
+                         self.row_ptr.astype("<u8").tobytes(), self.col.astype("<u8").tobytes(), self.vals.tobytes(),
+                         self.consts.tobytes()])
+
+    def const_ints(self):
+        raw = self.consts.tobytes()
+        return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+
+
+class _DeviceMatrix:
+    """a _Matrix in HBM: CSR for the row evaluation, column order with its segment plan for the transposed product"""
+
+    def __init__(self, ctx, M):
+        self.ctx, self.n_rows, self.nnz = ctx, M.n_rows, len(M.col)
+        self.row_ptr = ctx.upload(M.row_ptr.astype(np.uint32))
+        self.col = ctx.upload(M.col.astype(np.uint32)) if self.nnz else ctx.alloc(4)
+        self.vals = ctx.upload(M.vals) if self.nnz else ctx.alloc(32)
+        self.consts = ScalarVector.from_array(M.consts, ctx) if M.n_rows else ScalarVector.empty(0, ctx)
+        order = np.argsort(M.col, kind="stable")                 # by column, rows ascending inside a column
+        counts = np.bincount(M.col, minlength=M.n_cols) if self.nnz else np.zeros(M.n_cols, np.int64)
+        self.listed = np.nonzero(counts)[0]
+        col_start = (np.cumsum(counts) - counts)[self.listed]
+        nsegs = (counts[self.listed] + SEG - 1) // SEG
+        col_seg = np.concatenate([[0], np.cumsum(nsegs)]).astype(np.int64)
+        self.n_segs = int(col_seg[-1])
+        seg_col = np.repeat(np.arange(len(self.listed)), nsegs)
+        k = np.arange(self.n_segs) - np.repeat(col_seg[:-1], nsegs)
+        seg_ptr = np.concatenate([col_start[seg_col] + SEG * k, [self.nnz]])
+        self.c_rows = ctx.upload(M.rows[order].astype(np.uint32)) if self.nnz else ctx.alloc(4)
+        self.c_vals = ctx.upload(np.ascontiguousarray(M.vals[order])) if self.nnz else ctx.alloc(32)
+        self.seg_ptr = ctx.upload(seg_ptr.astype(np.uint32))
+        self.col_seg = ctx.upload(col_seg.astype(np.uint32))
+        self._pos = {}
+
+    def csr(self):
+        return (self.row_ptr.ptr, self.col.ptr, self.vals.ptr, self.consts.ptr)
+
+    def weighted_columns(self, weights_ptr, n_x, n_in, out_ptr, n_out):
+        """out (n_out scalars over z) = sum_i weights[i] row_i, column c at z position c (c < n_x) or n_in + 3 + c - n_x"""
+        key = (n_x, n_in)
+        if key not in self._pos:
+            pos = np.where(self.listed < n_x, self.listed, self.listed - n_x + n_in + 3)
+            self._pos = {key: self.ctx.upload(pos.astype(np.uint32)) if len(pos) else self.ctx.alloc(4)}
+        self.ctx.cs_colsum(weights_ptr, self.n_rows, self.c_rows.ptr, self.c_vals.ptr, self.seg_ptr.ptr, self.n_segs,
+                           self.col_seg.ptr, self._pos[key].ptr, len(self.listed), out_ptr, n_out)
+
+
+class SparseCircuit:
+    """The circuit as data.  A, B: the affine forms of the left / right wire of each of the m multiplication gates over
+    the columns (x_0..x_{n_x-1}, gamma_0..gamma_{m-1}), as CSR (row_ptr, col, vals, consts) - vals / consts: ints of any
+    sign or size, an integer array, or (nnz, 32) uint8; duplicates add; consts may be left out (zeros).  Row i may only
+    read gamma_j with j < i.  O: the forms of the n_out output gates, same shape (None: no outputs).  text: what stands
+    for str(circuit) (default: the hex SHA-256 of the canonical CSR bytes).
+
+    m = 0 is allowed: f and g are then the constants r_a, r_b (the reference's lagrange_interp_ff of a one-point
+    vector) and z = x + [r_a, r_b, r_a r_b]."""
+
+    def __init__(self, n_x, A, B, O=None, text=None):
+        self.n_x = int(n_x)
+        m = len(A[0]) - 1
+        self.A = _Matrix(A, self.n_x + m, "A")
+        self.B = _Matrix(B, self.n_x + m, "B")
+        if self.B.n_rows != m:
+            raise ValueError("SparseCircuit: A and B must have one row per multiplication gate each")
+        self.O = _Matrix(O if O is not None else ([0], [], [], []), self.n_x + m, "O")
+        self.m, self.n_out = m, self.O.n_rows
+        for M, what in ((self.A, "A"), (self.B, "B")):
+            bad = np.nonzero(M.col >= self.n_x + M.rows)[0]
+            if len(bad):
+                e = bad[np.argmin(M.rows[bad])]
+                raise ValueError(f"SparseCircuit: row {int(M.rows[e])} of {what} reads gamma_{int(M.col[e]) - self.n_x}, "
+                                 f"which is not an earlier gate")
+        self.digest = hashlib.sha256(b"vmpc-ac20/p8/circuit/v1" + b"".join(v.to_bytes(8, "little") for v in
+                                                                             (self.n_x, self.m, self.n_out)) +
+                                     b"".join(M.canonical_bytes() for M in (self.A, self.B, self.O))).digest()
+        self.text = text if text is not None else self.digest.hex()
+        # depth of each multiplication gate and the gates grouped by depth: dependencies point backwards, so one pass
+        # over the gamma entries of A and B in row order (a gate's depth is final before any later gate reads it)
+        depth = [0] * m
+        dep_r = np.concatenate([M.rows[M.col >= self.n_x] for M in (self.A, self.B)])
+        dep_j = np.concatenate([M.col[M.col >= self.n_x] - self.n_x for M in (self.A, self.B)])
+        by_row = np.argsort(dep_r, kind="stable")
+        for r, j in zip(dep_r[by_row].tolist(), dep_j[by_row].tolist()):
+            if depth[j] >= depth[r]:
+                depth[r] = depth[j] + 1
+        self.depth = np.asarray(depth, np.int64)
+        self.level_order = np.argsort(self.depth, kind="stable").astype(np.uint32)
+        self.level_ptr = np.concatenate([[0], np.cumsum(np.bincount(self.depth))]).astype(np.int64) if m else \
+            np.zeros(1, np.int64)
+        self._dev = None
+        self._raw = None
+
+    # the names Protocol 8 reads of a circuit_builder.Circuit
+    @property
+    def input_ct(self):
+        return self.n_x
+
+    @property
+    def mul_ct(self):
+        return self.m
+
+    @property
+    def output_ct(self):
+        return self.n_out
+
+    def __str__(self):
+        return self.text
+
+    def padding(self, n_x=None):
+        """zeros to append to x so that len(z) + 1 is a power of two (circuit_sat_cb.py:46-56)"""
+        z_len = (self.n_x if n_x is None else n_x) + 3 + 2 * self.m
+        return 0 if bin(z_len + 1).count("1") == 1 else (1 << z_len.bit_length()) - z_len - 1
+
+    def pad(self, x):
+        """x with padding(len(x)) zeros appended: inputs no form reads"""
+        return list(x) + [0] * self.padding(len(x))
+
+    @classmethod
+    def from_circuit(cls, circuit):
+        """From a circuit_builder.Circuit (duck-typed), by the rules of construct_affine_form
+        (circuit_builder.py:417-498), each add / scalar-mul gate expanded once."""
+        n = circuit.input_ct
+        by_name, forms = {}, {}
+        for g in circuit.gates:
+            by_name.setdefault(g.output.name, g)
+
+        def is_var(v):
+            return hasattr(v, "input_index")
+
+        def var_form(v):
+            if not is_var(v):
+                return {}, 0 + v
+            if v.input_index is not None:
+                return {v.input_index: 1}, 0
+            child = by_name[v.name]
+            if child.op.name == "mul":
+                return {n + child.mul_index: 1}, 0
+            return forms[id(child)]
+
+        def scaled(form, s):
+            return {c: v * s for c, v in form[0].items()}, form[1] * s
+
+        # gates are in creation order, so a gate's inputs are expanded before it: no recursion, each gate once.
+        # Coefficients stay the Python objects the builder holds (ints of any sign, field elements): the reference
+        # transcript prints them as they are.
+        for g in circuit.gates:
+            name = g.op.name
+            if name == "add":
+                (e0, k0), (e1, k1) = var_form(g.inputs[0]), var_form(g.inputs[1])
+                e = dict(e0)
+                for c, v in e1.items():
+                    e[c] = e.get(c, 0) + v
+                forms[id(g)] = (e, k0 + k1)
+            elif name == "scalar_mul":
+                if is_var(g.inputs[0]):
+                    forms[id(g)] = scaled(var_form(g.inputs[0]), g.inputs[1])
+                elif is_var(g.inputs[1]):
+                    forms[id(g)] = scaled(var_form(g.inputs[1]), g.inputs[0])
+                else:
+                    forms[id(g)] = ({}, g.inputs[0] * g.inputs[1])
+            elif name == "mul":
+                forms[id(g)] = ({n + g.mul_index: 1}, 0)
+            else:
+                raise ValueError(f"gate operation {name!r}")
+
+        def csr(rows):
+            ptr, col, vals, consts = [0], [], [], []
+            for e, k in rows:
+                for c in sorted(e):
+                    col.append(c)
+                    vals.append(int(e[c]))
+                ptr.append(len(col))
+                consts.append(int(k))
+            return ptr, col, vals, consts
+
+        muls = circuit.mul_gates()
+        raw = {"A": [var_form(g.inputs[0]) for g in muls], "B": [var_form(g.inputs[1]) for g in muls],
+               "O": [forms[id(circuit.gates[ix])] for ix in circuit.output_gates]}
+        sc = cls(n, csr(raw["A"]), csr(raw["B"]), csr(raw["O"]), text=str(circuit))
+        sc._raw = raw
+        return sc
+
+    def raw_forms(self):
+        """{"A" | "B" | "O": [({col: coefficient}, constant)]} with the coefficients as Python objects: the builder's own
+        (from_circuit), else the canonical residues as ints"""
+        if self._raw is None:
+            def rows(M):
+                ints = [int.from_bytes(M.vals[i].tobytes(), "little") for i in range(len(M.col))]
+                out = [({}, k) for k in M.const_ints()]
+                for r, c, v in zip(M.rows.tolist(), M.col.tolist(), ints):
+                    out[r][0][c] = v
+                return out
+            self._raw = {"A": rows(self.A), "B": rows(self.B), "O": rows(self.O)}
+        return self._raw
+
+    # ---- device state, made once ------------------------------------------------------------------------------------
+    def device(self):
+        if self._dev is None:
+            ctx = get_context()
+            d = {"ctx": ctx, "A": _DeviceMatrix(ctx, self.A), "B": _DeviceMatrix(ctx, self.B),
+                 "O": _DeviceMatrix(ctx, self.O), "order": ctx.upload(self.level_order) if self.m else ctx.alloc(4)}
+            K = 2 * self.m + 1
+            d["fact"], d["ifact"] = ScalarVector.empty(K + 1, ctx), ScalarVector.empty(K + 1, ctx)
+            ctx.cs_tables(K, d["fact"].ptr, d["ifact"].ptr)
+            self._dev = d
+        return self._dev
+
+
+def as_sparse(circuit):
+    return circuit if isinstance(circuit, SparseCircuit) else SparseCircuit.from_circuit(circuit)
+
+
+# ---- transcript ------------------------------------------------------------------------------------------------------------
+def _mode(transcript):
+    mode = transcript or TRANSCRIPT
+    if mode not in ("compact", "reference"):
+        raise ValueError(f"unknown transcript mode {mode!r}")
+    return mode
+
+
+def _first_digest(z_commitment, circuit, n_in):
+    return hashlib.sha256(b"vmpc-ac20/p8/first/v1" + wire.compress_point(z_commitment) + circuit.digest +
+                          n_in.to_bytes(8, "little")).digest()
+
+
+def first_challenge(digest, order):
+    """the challenge c at which f, g, h are opened, from the first digest"""
+    return int.from_bytes(digest, "little") % order
+
+
+def _second_challenge(digest, ys, outputs, order):
+    h = hashlib.sha256(b"vmpc-ac20/p8/second/v1" + digest)
+    h.update(b"".join((int(v) % order).to_bytes(32, "little") for v in ys))
+    h.update(len(outputs).to_bytes(4, "little") + b"".join((int(v) % order).to_bytes(32, "little") for v in outputs))
+    return int.from_bytes(h.digest(), "little") % order
+
+
+class ChallengeOnNode(ValueError):
+    """the first challenge is one of the interpolation nodes 0..2m (probability about 2m / 2^252): the reference's
+    _recombination_vectors divides by zero there"""
+
+
+def _check_not_node(c, m):
+    if 0 <= c <= 2 * m:
+        raise ChallengeOnNode(f"Protocol 8: the first challenge {c} is an interpolation node (0..{2 * m})")
+
+
+# ---- forms ---------------------------------------------------------------------------------------------------------------------
+class _Forms:
+    """the forms of f(c), g(c), h(c) over z, device-resident, and what L needs of them"""
+
+    def __init__(self, circuit, n_in, c, order):
+        d = circuit.device()
+        ctx, m = d["ctx"], circuit.m
+        self.circuit, self.n_in, self.N, self.order, self.ctx = circuit, n_in, n_in + 3 + 2 * m, order, ctx
+        N = self.N
+        self.lam = ScalarVector.empty(m + 1, ctx)               # nodes 0..m
+        ctx.cs_lagrange(c, m, d["ifact"].ptr, self.lam.ptr)
+        self.H = ScalarVector.empty(N, ctx)                      # zeros, then the vector of the nodes 0..2m
+        ctx.upload_into(self.H.ptr, np.zeros((n_in + 2, 32), np.uint8))
+        ctx.cs_lagrange(c, 2 * m, d["ifact"].ptr, self.H.ptr + 32 * (n_in + 2))
+        self.F, self.G = ScalarVector.empty(N, ctx), ScalarVector.empty(N, ctx)
+        self.k = []
+        for wire_ix, (M, V) in enumerate(((d["A"], self.F), (d["B"], self.G))):
+            M.weighted_columns(self.lam.ptr + 32, circuit.n_x, n_in, V.ptr, N)
+            ctx.copy(V.ptr + 32 * (n_in + wire_ix), self.lam.ptr, 32)
+            self.k.append(ctx.fr_dot(self.lam.ptr + 32, M.consts.ptr, m) if m else 0)
+        self.k.append(0)
+
+    def values(self, z):
+        return [(V.dot(z) + k) % self.order for V, k in zip((self.F, self.G, self.H), self.k)]
+
+    def combine(self, rho, ys, outputs, gf):
+        """L = sum_k rho^k (O_k - out_k) + rho^n_out (F - y1) + rho^(n_out+1) (G - y2) + rho^(n_out+2) (H - y3)"""
+        circuit, order = self.circuit, self.order
+        n_out = circuit.n_out
+        pw = [pow(rho, k, order) for k in range(n_out + 3)]
+        co = ScalarVector.empty(self.N, self.ctx)
+        wts = ScalarVector.from_ints(pw[:n_out], self.ctx)
+        circuit.device()["O"].weighted_columns(wts.ptr, circuit.n_x, self.n_in, co.ptr, self.N)
+        const = sum(p * (k - int(o)) for p, k, o in zip(pw, circuit.O.const_ints(), outputs))
+        for V, k, y, p in zip((self.F, self.G, self.H), self.k, ys, pw[n_out:]):
+            co = V.axpy(p, co)
+            const += p * (k - int(y))
+        return pivot.AffineForm(co, gf(const % order))
+
+
+def _witness_on_device(circuit, x, order, gamma_witness=None):
+    """z = (x, f(0), g(0), h(0), h(1..2m)) as a device vector; draws r_a, r_b from `prng`"""
+    n_in, m, n_x = len(x), circuit.m, circuit.n_x
+    d = circuit.device()
+    ctx = d["ctx"]
+    N = n_in + 3 + 2 * m
+    z = ScalarVector.empty(N, ctx)
+    ctx.upload_into(z.ptr, _ints_to_array([pivot._residue(v) for v in x]))
+    r_a = prng.randrange(1, order)
+    r_b = prng.randrange(1, order)
+    a, b = ScalarVector.empty(m + 1, ctx), ScalarVector.empty(m + 1, ctx)
+    ctx.upload_into(a.ptr + 32 * m, _ints_to_array([r_a]))
+    ctx.upload_into(b.ptr + 32 * m, _ints_to_array([r_b]))
+    g_off = n_in + 3
+    if gamma_witness is not None:
+        if len(gamma_witness) != m:
+            raise ValueError(f"gamma_witness: {m} gate outputs expected")
+        if m:
+            ctx.upload_into(z.ptr + 32 * g_off, _ints_to_array([pivot._residue(v) for v in gamma_witness]))
+            bad = ctx.alloc(4)
+            ctx.cs_triples(d["A"].csr(), d["B"].csr(), None, m, n_x, g_off, z.ptr, a.ptr, b.ptr, 1, bad.ptr)
+            first = int(ctx.download(bad.ptr, 4).view(np.uint32)[0])
+            if first != 0xFFFFFFFF:
+                raise ValueError(f"gamma_witness: multiplication gate {first} is not the product of its wires")
+    else:
+        for lv in range(len(circuit.level_ptr) - 1):
+            lo, hi = int(circuit.level_ptr[lv]), int(circuit.level_ptr[lv + 1])
+            ctx.cs_triples(d["A"].csr(), d["B"].csr(), d["order"].ptr + 4 * lo, hi - lo, n_x, g_off, z.ptr, a.ptr, b.ptr)
+    ctx.cs_extend(a.ptr, b.ptr, m, d["fact"].ptr, d["ifact"].ptr, z.ptr + 32 * n_in)
+    return z
+
+
+# ---- reference transcript (list mode) ----------------------------------------------------------------------------------------
+# The two hashes are pivot.fiat_shamir_hash over the reference's lists (circuit_sat_cb.py:107-111, :149-162) with the
+# reference's element types: the forms' coefficients are Python ints that are never reduced (circuit_builder.py:506-537
+# multiplies the builder's ints by the Lagrange vectors, which recombine.py:31 returns as ints), constants turn into
+# field elements where a field element is subtracted.  The text is O((n_out + 3) N), so this assembly is host code; the
+# device computes z and the Lagrange vectors.  For parity, not for size.
+FIRST_TAG = "First hash circuit satisfiability protocol"
+SECOND_TAG = "Second hash circuit satisfiability protocol"
+
+
+def _typed_forms(circuit, n_in, c):
+    """(linform_f, linform_g, linform_h, circuit_forms) as list-mode forms, typed as the reference's"""
+    d = circuit.device()
+    ctx, m, n_x = d["ctx"], circuit.m, circuit.n_x
+    N = n_in + 3 + 2 * m
+    lam, lam2 = ScalarVector.empty(m + 1, ctx), ScalarVector.empty(2 * m + 1, ctx)
+    ctx.cs_lagrange(c, m, d["ifact"].ptr, lam.ptr)
+    ctx.cs_lagrange(c, 2 * m, d["ifact"].ptr, lam2.ptr)
+    lam, lam2 = lam.to_ints(), lam2.to_ints()
+    raw = circuit.raw_forms()
+
+    def pos(col):
+        return col if col < n_x else n_in + 3 + (col - n_x)
+
+    fg = []
+    for wire_ix, rows in enumerate((raw["A"], raw["B"])):
+        co, const = [0] * N, 0
+        for (e, k), l_j in zip(rows, lam[1:]):
+            for col, v in e.items():
+                co[pos(col)] = co[pos(col)] + v * l_j
+            const = const + k * l_j
+        co[n_in + wire_ix] = 1 * lam[0]
+        fg.append(pivot.AffineForm(co, const))
+    lh = pivot.LinearForm([0] * n_in + [0] * 2 + lam2)
+    circuit_forms = []
+    for e, k in raw["O"]:
+        co = [0] * N
+        for col, v in e.items():
+            co[pos(col)] = v
+        circuit_forms.append(pivot.AffineForm(co, k))
+    return fg[0], fg[1], lh, circuit_forms
+
+
+def _typed_outputs(circuit, x, z_ints, gf):
+    """circuit(x) with the reference's typing: one field element among the inputs makes every gate value a field
+    element (circuit_builder.py:133-172 sums c * v over ALL positions); all-int inputs leave exact, unreduced ints"""
+    n_x, n_in = circuit.n_x, len(x)
+    raw = circuit.raw_forms()
+    if any(not isinstance(v, int) for v in x):
+        gamma = [gf(v) for v in z_ints[n_in + 3:n_in + 3 + circuit.m]]
+        pad = gf(0)
+    else:
+        gamma, pad = [], 0
+        for (ea, ka), (eb, kb) in zip(raw["A"], raw["B"]):
+            w = [sum(v * (x[c] if c < n_x else gamma[c - n_x]) for c, v in e.items()) + k for e, k in ((ea, ka), (eb, kb))]
+            gamma.append(w[0] * w[1])
+    return [sum(v * (x[c] if c < n_x else gamma[c - n_x]) for c, v in e.items()) + k + pad for e, k in raw["O"]]
+
+
+def _reference_prover(generators, circuit, x, z, gf):
+    order, n_in = gf.order, len(x)
+    z_ints = z.to_ints()
+    z_list = list(x) + [gf(v) for v in z_ints[n_in:]]
+    gamma = prng.randrange(1, order)
+    z_commitment = pivot.vector_commitment(z_list, gamma, generators["g"], generators["h"])
+    proof = {"z_commitment": z_commitment}
+    c = pivot.fiat_shamir_hash([z_commitment, circuit.text, FIRST_TAG], order)
+    _check_not_node(c, circuit.m)
+    lf, lg, lh, circuit_forms = _typed_forms(circuit, n_in, c)
+    y1, y2, y3 = lf(z_list), lg(z_list), lh(z_list)
+    assert y1 * y2 == y3
+    proof["y1"], proof["y2"], proof["y3"] = y1, y2, y3
+    outputs = _typed_outputs(circuit, x, z_ints, gf)
+    proof["outputs"] = outputs
+    lin_forms = [form - y for form, y in zip(circuit_forms, outputs)] + [lf - y1, lg - y2, lh - y3]
+    rho = pivot.fiat_shamir_hash([y1, y2, y3, z_commitment, outputs, circuit_forms, lin_forms, SECOND_TAG], order)
+    L = sum((linform_i) * (rho ** i) for i, linform_i in enumerate(lin_forms))
+    proof["L"] = L
+    return proof, z_commitment, L, z_list, gamma
+
+
+def _reference_verifier(proof, circuit, gf, verification):
+    order = gf.order
+    N = len(proof["L"].coeffs)
+    n_in = N - 3 - 2 * circuit.m
+    outputs = proof["outputs"]
+    if n_in < circuit.n_x or len(outputs) != circuit.n_out:
+        verification["L_wellformed_from_Cfgh_forms"] = False
+        return verification, None
+    z_commitment = proof["z_commitment"]
+    c = pivot.fiat_shamir_hash([z_commitment, circuit.text, FIRST_TAG], order)
+    if 0 <= c <= 2 * circuit.m:
+        verification["L_wellformed_from_Cfgh_forms"] = False
+        return verification, None
+    y1, y2, y3 = proof["y1"], proof["y2"], proof["y3"]
+    lf, lg, lh, circuit_forms = _typed_forms(circuit, n_in, c)
+    lin_forms = [form - y for form, y in zip(circuit_forms, outputs)] + [lf - y1, lg - y2, lh - y3]
+    rho = pivot.fiat_shamir_hash([y1, y2, y3, z_commitment, outputs, circuit_forms, lin_forms, SECOND_TAG], order)
+    L = sum((linform_i) * (rho ** i) for i, linform_i in enumerate(lin_forms))
+    verification["L_wellformed_from_Cfgh_forms"] = bool(L == proof["L"])
+    return verification, L
+
+
+# ---- prover -----------------------------------------------------------------------------------------------------------------
+def protocol_8_excl_pivot_prover(generators, circuit, x, gf, use_koe=False, gamma_witness=None, transcript=None):
+    """circuit_sat_cb.py:59-166 for a SparseCircuit (anything else is converted): (proof, z_commitment, L, z, gamma) with
+    z a device ScalarVector and L an AffineForm over device coefficients.  Random draws from `prng` in the reference's
+    order: r_a, r_b, then gamma.  gamma_witness: the gate outputs, if the caller has them - they are checked (one
+    launch) instead of computed (one launch per depth level)."""
+    mode = _mode(transcript)
+    if use_koe or "g" not in generators:
+        raise NotImplementedError("Protocol 8 over a SparseCircuit: the knowledge-of-exponent variant lives in another "
+                                  "field (BN-256) and is not built")
+    circuit = as_sparse(circuit)
+    g, h = generators["g"], generators["h"]
+    order = gf.order
+    assert order == ORDER
+    n_in, m, n_x = len(x), circuit.m, circuit.n_x
+    if n_in < n_x:
+        raise ValueError(f"the circuit has {n_x} inputs, {n_in} given")
+    z = _witness_on_device(circuit, x, order, gamma_witness)
+    d = circuit.device()
+    ctx, g_off = d["ctx"], n_in + 3
+    if mode == "reference":
+        return _reference_prover(generators, circuit, x, z, gf)
+
+    gamma = prng.randrange(1, order)
+    z_commitment = pivot.vector_commitment(z, gamma, g, h)
+    proof = {"z_commitment": z_commitment}
+    digest = _first_digest(z_commitment, circuit, n_in)
+    c = first_challenge(digest, order)
+    _check_not_node(c, m)
+
+    forms = _Forms(circuit, n_in, c, order)
+    y1, y2, y3 = (gf(v) for v in forms.values(z))
+    assert y1 * y2 == y3
+    proof["y1"], proof["y2"], proof["y3"] = y1, y2, y3
+    outputs = []
+    if circuit.n_out:
+        o1 = ScalarVector.empty(circuit.n_out, ctx)      # the kernel's two row sets are both O: one buffer takes both
+        ctx.cs_triples(d["O"].csr(), d["O"].csr(), None, circuit.n_out, n_x, g_off, z.ptr, o1.ptr, o1.ptr, 2)
+        outputs = [gf(v) for v in o1.to_ints()]
+    proof["outputs"] = outputs
+    rho = _second_challenge(digest, (y1, y2, y3), outputs, order)
+    L = forms.combine(rho, (y1, y2, y3), outputs, gf)
+    proof["L"] = L
+    return proof, z_commitment, L, z, gamma
+
+
+def protocol_8_excl_pivot_verifier(proof, circuit, gf, use_koe=False, transcript=None):
+    """circuit_sat_cb.py:169-252: (verification, L); O(nnz + N), nothing quadratic"""
+    mode = _mode(transcript)
+    if use_koe or isinstance(proof.get("z_commitment"), dict):
+        raise NotImplementedError("Protocol 8 over a SparseCircuit: the knowledge-of-exponent variant is not built")
+    circuit = as_sparse(circuit)
+    order = gf.order
+    verification = {}
+    y1, y2, y3 = (int(proof[k]) % order for k in ("y1", "y2", "y3"))
+    verification["y1*y2=y3"] = y1 * y2 % order == y3
+    if not verification["y1*y2=y3"]:
+        return verification, None
+    if mode == "reference":
+        return _reference_verifier(proof, circuit, gf, verification)
+    N = len(proof["L"].coeffs)
+    n_in = N - 3 - 2 * circuit.m
+    outputs = proof["outputs"]
+    if n_in < circuit.n_x or len(outputs) != circuit.n_out:
+        verification["L_wellformed_from_Cfgh_forms"] = False
+        return verification, None
+    digest = _first_digest(proof["z_commitment"], circuit, n_in)
+    c = first_challenge(digest, order)
+    if 0 <= c <= 2 * circuit.m:
+        # no honest prover sends this (ChallengeOnNode); no kernel is launched
+        verification["L_wellformed_from_Cfgh_forms"] = False
+        return verification, None
+    forms = _Forms(circuit, n_in, c, order)
+    rho = _second_challenge(digest, (y1, y2, y3), outputs, order)
+    L = forms.combine(rho, (y1, y2, y3), outputs, gf)
+    theirs = proof["L"]
+    same = int(theirs.constant) % order == int(L.constant) % order and \
+        forms.ctx.cs_first_diff(L.coeffs.ptr, pivot._as_device(theirs.coeffs).ptr, N) is None
+    verification["L_wellformed_from_Cfgh_forms"] = bool(same)
+    return verification, L
+
+
+# Protocol 5 draws its N masks one by one from SystemRandom when it is not handed any: 0.8 s of Python at N = 2^19.
+# From this length on the masks are 252 uniform bits each from os.urandom, uploaded as one array: every value is below
+# l = 2^252 + 2^124.7, and the distance from uniform on [0, l) is 2^-127 per mask.
+MASKS_ON_DEVICE_MIN = 1 << 12
+
+
+def _masks(n, ctx):
+    import os
+    raw = np.frombuffer(os.urandom(32 * n), np.uint8).reshape(n, 32).copy()
+    raw[:, 31] &= 0x0f
+    return ScalarVector.from_array(raw, ctx)
+
+
+def _choice(pivot_choice):
+    return getattr(pivot_choice, "name", pivot_choice)
+
+
+def circuit_sat_prover(generators, circuit, x, gf, pivot_choice="compressed", gamma_witness=None, transcript=None):
+    """circuit_sat_cb.py:255-282 for a SparseCircuit, wholly in this package"""
+    choice = _choice(pivot_choice)
+    if choice == "koe":
+        raise NotImplementedError("PivotChoice.koe over a SparseCircuit: the knowledge-of-exponent pivot lives in "
+                                  "another field (BN-256); Protocol 8 is built over the Ed25519 scalar field")
+    if choice not in ("compressed", "pivot"):
+        raise NotImplementedError
+    mode = _mode(transcript)
+    proof, z_commitment, L, z, gamma = protocol_8_excl_pivot_prover(generators, circuit, x, gf,
+                                                                    gamma_witness=gamma_witness, transcript=mode)
+    y = L(z)
+    if choice == "compressed":
+        r = _masks(len(z), L.coeffs.ctx) if isinstance(z, ScalarVector) and len(z) >= MASKS_ON_DEVICE_MIN else None
+        proof["pivot_proof"] = compressed_pivot.protocol_5_prover(generators, z_commitment, L, y, z, gamma, gf,
+                                                                  transcript=mode, r=r)
+    else:
+        # Protocol 2 is the O(N)-proof pivot and has no device prover: its response IS a vector of N scalars
+        zs = z if isinstance(z, list) else [gf(v) for v in z.to_ints()]
+        proof["pivot_proof"] = pivot.prove_linear_form_eval(generators["g"], generators["h"], z_commitment, L, y, zs,
+                                                            gamma, gf)
+    return proof
+
+
+def circuit_sat_verifier(proof, generators, circuit, gf, pivot_choice="compressed", transcript=None):
+    """circuit_sat_cb.py:285-318 for a SparseCircuit: the verification dict"""
+    choice = _choice(pivot_choice)
+    if choice == "koe":
+        raise NotImplementedError("PivotChoice.koe over a SparseCircuit is not built")
+    if choice not in ("compressed", "pivot"):
+        raise NotImplementedError
+    mode = _mode(transcript)
+    verification, L = protocol_8_excl_pivot_verifier(proof, circuit, gf, transcript=mode)
+    if L is None:
+        return verification
+    if choice == "compressed":
+        ok = compressed_pivot.protocol_5_verifier(generators, proof["z_commitment"], L, gf(0), proof["pivot_proof"], gf,
+                                                  transcript=mode)
+    else:
+        z, phi, c = proof["pivot_proof"]
+        ok = pivot.verify_linear_form_proof(generators["g"], generators["h"], proof["z_commitment"], L, gf(0), z, phi, c)
+    verification["pivot_verification"] = ok
+    return verification
