@@ -1,17 +1,22 @@
-// Host-side harness for csrc/fr_bn.h (GF(n), n the BN-256 group order, and the wide accumulator of the polynomial
-// product).  Built with g++ by tests/test_native_frbn_host.py; reads one command per line on stdin, operands as hex
-// 256-bit values (NOT necessarily below n: every operand goes through frbn_load), and prints one hex residue:
-//     load a            a mod n
+// Host-side harness for csrc/fr256.h as csrc/fr_bn.h (GF(n), n the BN-256 group order; the default) and csrc/fr.h
+// (GF(l), l the Ed25519 order; argument "fr") instantiate it, with the wide accumulator of the sums of products.  Built
+// with g++ by tests/test_native_frbn_host.py; reads one command per line on stdin, operands as hex 256-bit values (every
+// operand goes through the field's load: frbn_load reduces any value mod n, fr_load copies, so GF(l) operands of
+// add / sub / mul / inv must be below l), and prints one hex residue:
+//     load a            a mod n (GF(l): a)
 //     add / sub / mul a b
-//     mac k a1 b1 ... ak bk     frbn_acc_reduce of the accumulator after k frbn_acc_mac calls on the LOADED operands
+//     inv a             a^(m-2): 1 / a, and 0 for 0
+//     mac k a1 b1 ... ak bk     the accumulator reduced after k mac calls on the LOADED operands
 //     macrep r a b      the same after r calls with the one pair (a sum far beyond 512 bits)
 //     macraw r a b      as macrep, on the raw limbs of a and b (values up to 2^256 - 1, the accumulator's worst case)
 #include <cstdio>
 #include <iostream>
+#include <cstring>
 #include <sstream>
 #include <string>
 
 #define VMPC_HD inline
+#include "../../verifiable_mpc_amd/csrc/fr.h"
 #include "../../verifiable_mpc_amd/csrc/fr_bn.h"
 
 static void parse_hex(const std::string &h, uint32_t out[8]) {
@@ -23,7 +28,8 @@ static void parse_hex(const std::string &h, uint32_t out[8]) {
         out[nib / 8] |= v << (4 * (nib % 8));
     }
 }
-static void pr(const frbn &a) {
+template <class F>
+static void pr(const F &a) {
     char buf[16];
     std::string s;
     bool lead = true;
@@ -40,13 +46,15 @@ static void rd_raw(std::istringstream &is, uint32_t w[8]) {
     is >> h;
     parse_hex(h, w);
 }
-static frbn rd(std::istringstream &is) {
+template <class F>
+static F rd(std::istringstream &is) {
     uint32_t w[8];
     rd_raw(is, w);
-    return frbn_load(w);
+    return f256_load<F>(w);
 }
 
-int main() {
+template <class F>
+static int run() {
     std::string line;
     while (std::getline(std::cin, line)) {
         std::istringstream is(line);
@@ -54,19 +62,21 @@ int main() {
         is >> cmd;
         if (cmd == "quit") break;
         if (cmd == "load") {
-            pr(rd(is));
+            pr(rd<F>(is));
         } else if (cmd == "add" || cmd == "sub" || cmd == "mul") {
-            const frbn a = rd(is), b = rd(is);
-            pr(cmd == "add" ? frbn_add(a, b) : cmd == "sub" ? frbn_sub(a, b) : frbn_mul(a, b));
+            const F a = rd<F>(is), b = rd<F>(is);
+            pr(cmd == "add" ? f256_add(a, b) : cmd == "sub" ? f256_sub(a, b) : f256_mul(a, b));
+        } else if (cmd == "inv") {
+            pr(f256_inv(rd<F>(is)));
         } else if (cmd == "mac") {
             int k = 0;
             is >> k;
-            frbn_acc s = frbn_acc_zero();
+            f256_acc s = f256_acc_zero();
             for (int t = 0; t < k; t++) {
-                const frbn a = rd(is), b = rd(is);
-                frbn_acc_mac(s, a.v, b.v);
+                const F a = rd<F>(is), b = rd<F>(is);
+                f256_acc_mac(s, a.v, b.v);
             }
-            pr(frbn_acc_reduce(s));
+            pr(f256_acc_reduce<F>(s));
         } else if (cmd == "macrep" || cmd == "macraw") {
             long r = 0;
             is >> r;
@@ -75,15 +85,17 @@ int main() {
                 rd_raw(is, a);
                 rd_raw(is, b);
             } else {
-                const frbn fa = rd(is), fb = rd(is);
+                const F fa = rd<F>(is), fb = rd<F>(is);
                 for (int i = 0; i < 8; i++) a[i] = fa.v[i], b[i] = fb.v[i];
             }
-            frbn_acc s = frbn_acc_zero();
-            for (long t = 0; t < r; t++) frbn_acc_mac(s, a, b);
-            pr(frbn_acc_reduce(s));
+            f256_acc s = f256_acc_zero();
+            for (long t = 0; t < r; t++) f256_acc_mac(s, a, b);
+            pr(f256_acc_reduce<F>(s));
         } else {
             std::cout << "?\n";
         }
     }
     return 0;
 }
+
+int main(int argc, char **argv) { return argc > 1 && !strcmp(argv[1], "fr") ? run<fr>() : run<frbn>(); }

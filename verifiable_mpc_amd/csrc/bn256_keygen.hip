@@ -10,8 +10,7 @@
 //                                 With Q_j = prod_{k>=j} k = d! / (j-1)!:  1/((j-1)! (d-j)!) = Q_j Q_{d-j+1} / d!^2,
 //                                 so ONE Fermat inversion (of d!) serves all j.  A, B and Q are exclusive prefix
 //                                 products of three generated sequences (s - k forward, s - k backward, k backward):
-//                                 each lane multiplies a run of KG_RUN elements, one workgroup per sequence scans the
-//                                 run products, each lane rescans its run, and a last kernel combines.
+//                                 csrc/fr_scan.h with runs of KG_RUN elements, and a last kernel combines.
 //   vmpc_bn256_qap_colsum_dev     out[c] = sum_e vals[e] basis[rows[e]] over the entries of column c: v_i(s), w_i(s),
 //                                 y_i(s) of a sparse R1CS (basis = l(s)) or of a dense QAP (basis = 1, s, .., s^d, rows
 //                                 = coefficient degrees).  The host cuts the column-ordered entries into items of at most
@@ -23,104 +22,35 @@
 //                                 zero-knowledge tails, for the wires in idx (pynocchio.py:106-154).
 #include "common.h"
 #include "fr_bn.h"
+#include "fr_scan.h"
 
 #define KG_RUN 64       // sequence elements per lane in the scans
-#define KG_SCAN 256     // threads of the run-product scan (one workgroup per sequence)
 #define KG_PARTIAL 0x80000000u
 
-__device__ __forceinline__ frbn kg_small(uint32_t k) {
-    frbn r = frbn_zero();
-    r.v[0] = k;
-    return r;
-}
-
-__device__ __forceinline__ frbn kg_ld(const void *p, long long i) {
-    const uint4 *q = (const uint4 *)((const uint32_t *)p + 8 * i);
-    const uint4 x = q[0], y = q[1];
-    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-    return frbn_load(w);
-}
-
-__device__ __forceinline__ void kg_st(void *p, long long i, const frbn &a) {
-    uint4 *q = (uint4 *)((uint32_t *)p + 8 * i);
-    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
-
-// element k (0 <= k < d) of sequence q: s - (k+1), s - (d-k), d - k
-__device__ __forceinline__ frbn kg_elem(int q, const frbn &s, uint32_t d, uint32_t k) {
-    if (q == 0) return frbn_sub(s, kg_small(k + 1));
-    if (q == 1) return frbn_sub(s, kg_small(d - k));
-    return kg_small(d - k);
-}
-
-// run[q][l] = product of sequence q over [l KG_RUN, (l+1) KG_RUN) n [0, d)
-__global__ void __launch_bounds__(256)
-k_kg_runprod(const uint32_t *__restrict__ s_in, uint32_t d, uint32_t lanes, uint32_t *__restrict__ run) {
-    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-    const int q = blockIdx.y;
-    if (l >= lanes) return;
-    const frbn s = frbn_load(s_in);
-    const uint32_t k0 = l * KG_RUN, k1 = k0 + KG_RUN < d ? k0 + KG_RUN : d;
-    frbn p = kg_elem(q, s, d, k0);
-    for (uint32_t k = k0 + 1; k < k1; k++) p = frbn_mul(p, kg_elem(q, s, d, k));
-    kg_st(run, (long long)q * lanes + l, p);
-}
-
-// one workgroup per sequence: run[q][*] -> its exclusive prefix products, total[q] = the product of all.  Thread t owns
-// a contiguous block of the lanes; the 256 block products are scanned in LDS (Hillis-Steele, log2 256 steps).  The
-// workgroup of sequence 2 (total d!) then writes inv_sq = 1 / d!^2 (one Fermat inversion).
-__global__ void __launch_bounds__(KG_SCAN)
-k_kg_runscan(uint32_t lanes, uint32_t *__restrict__ run, uint32_t *__restrict__ total, uint32_t *__restrict__ inv_sq) {
-    __shared__ frbn buf[2][KG_SCAN];
-    const int t = threadIdx.x, q = blockIdx.x;
-    uint32_t *r = run + 8 * (size_t)q * lanes;
-    const uint32_t per = (lanes + KG_SCAN - 1) / KG_SCAN;
-    const uint32_t b0 = t * per < lanes ? t * per : lanes, b1 = b0 + per < lanes ? b0 + per : lanes;
-    frbn p = frbn_one();
-    for (uint32_t i = b0; i < b1; i++) p = frbn_mul(p, kg_ld(r, i));
-    int cur = 0;
-    buf[cur][t] = p;
-    __syncthreads();
-    for (int off = 1; off < KG_SCAN; off <<= 1) {
-        frbn v = buf[cur][t];
-        if (t >= off) v = frbn_mul(buf[cur][t - off], v);
-        buf[cur ^ 1][t] = v;
-        cur ^= 1;
-        __syncthreads();
+// sequence q (csrc/fr_scan.h), element k (0 <= k < d): s - (k+1), s - (d-k), d - k; s is in device memory
+struct kg_seq {
+    const uint32_t *s;
+    uint32_t d;
+};
+struct kg_seq_bound {
+    frbn s;
+    uint32_t d;
+    __device__ frbn operator()(const frbn &v, uint32_t q, uint32_t k) const {
+        const frbn i = f256_small<frbn>(q ? d - k : k + 1);
+        return frbn_mul(v, q == 2 ? i : frbn_sub(s, i));
     }
-    frbn acc = t ? buf[cur][t - 1] : frbn_one();   // exclusive prefix of this thread's block
-    for (uint32_t i = b0; i < b1; i++) {
-        const frbn x = kg_ld(r, i);
-        kg_st(r, i, acc);
-        acc = frbn_mul(acc, x);
-    }
-    if (t == KG_SCAN - 1) {
-        kg_st(total, q, acc);
-        if (q == 2) {
-            const frbn iv = frbn_inv(acc);
-            kg_st(inv_sq, 0, frbn_mul(iv, iv));
-        }
-    }
-}
+};
+__device__ __forceinline__ kg_seq_bound fr_scan_bind(const kg_seq &a) { return kg_seq_bound{frbn_load(a.s), a.d}; }
 
-// pre[q][k] = exclusive prefix product of sequence q at k (k < d); pre[q][d] = total[q]
-__global__ void __launch_bounds__(256)
-k_kg_runfill(const uint32_t *__restrict__ s_in, uint32_t d, uint32_t lanes, const uint32_t *__restrict__ run,
-             const uint32_t *__restrict__ total, uint32_t *__restrict__ pre) {
-    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-    const int q = blockIdx.y;
-    if (l >= lanes) return;
-    const frbn s = frbn_load(s_in);
-    uint32_t *out = pre + 8 * (size_t)q * (d + 1);
-    frbn v = kg_ld(run, (long long)q * lanes + l);
-    const uint32_t k0 = l * KG_RUN, k1 = k0 + KG_RUN < d ? k0 + KG_RUN : d;
-    for (uint32_t k = k0; k < k1; k++) {
-        kg_st(out, k, v);
-        v = frbn_mul(v, kg_elem(q, s, d, k));
+// sequence 2's total is d!: inv_sq = 1 / d!^2 (one Fermat inversion)
+struct kg_fin {
+    uint32_t *inv_sq;
+    __device__ void operator()(uint32_t q, const frbn &total) const {
+        if (q != 2) return;
+        const frbn iv = frbn_inv(total);
+        f256_st(inv_sq, 0, frbn_mul(iv, iv));
     }
-    if (l == lanes - 1) kg_st(out, d, kg_ld(total, q));
-}
+};
 
 // ell[j-1] = (-1)^(d-j) A_j B_j Q_j Q_{d-j+1} / d!^2 with A_j = pre0[j-1], B_j = pre1[d-j], Q_j = pre2[d-j+1]
 __global__ void __launch_bounds__(256)
@@ -131,13 +61,13 @@ k_kg_combine(uint32_t d, const uint32_t *__restrict__ pre, const uint32_t *__res
     const size_t st = (size_t)d + 1;
     const uint32_t *p0 = pre, *p1 = pre + 8 * st, *p2 = pre + 16 * st;
     const uint32_t j = i + 1;
-    frbn v = frbn_mul(kg_ld(p0, j - 1), kg_ld(p1, d - j));
-    v = frbn_mul(v, kg_ld(p2, d - j + 1));
-    v = frbn_mul(v, kg_ld(p2, j));
-    v = frbn_mul(v, kg_ld(inv_sq, 0));
+    frbn v = frbn_mul(f256_ld<frbn>(p0, j - 1), f256_ld<frbn>(p1, d - j));
+    v = frbn_mul(v, f256_ld<frbn>(p2, d - j + 1));
+    v = frbn_mul(v, f256_ld<frbn>(p2, j));
+    v = frbn_mul(v, f256_ld<frbn>(inv_sq, 0));
     if ((d - j) & 1u) v = frbn_sub(frbn_zero(), v);
-    kg_st(ell, i, v);
-    if (i == 0) kg_st(t_out, 0, kg_ld(p0, d));
+    f256_st(ell, i, v);
+    if (i == 0) f256_st(t_out, 0, f256_ld<frbn>(p0, d));
 }
 
 extern "C" int vmpc_bn256_qap_lagrange_dev(vmpc_ctx *ctx, const void *s, size_t d, void *ell_out, void *t_out) {
@@ -145,25 +75,18 @@ extern "C" int vmpc_bn256_qap_lagrange_dev(vmpc_ctx *ctx, const void *s, size_t 
     if (!ctx || !s || !ell_out || !t_out || d == 0) return VMPC_E_INVAL;
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const uint32_t dd = (uint32_t)d;
-    const uint32_t lanes = (uint32_t)((d + KG_RUN - 1) / KG_RUN);
-    const size_t run_b = 3 * (size_t)lanes * 32, pre_b = 3 * (d + 1) * 32;
-    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(run_b) + vmpc_align(pre_b) + vmpc_align(4 * 32) + 1024));
+    const size_t run_b = fr_scan_run_bytes<KG_RUN>(d, 3), pre_b = 3 * (d + 1) * 32;
+    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(run_b) + vmpc_align(pre_b) + 1024));
     uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, run_b);
     uint32_t *pre = (uint32_t *)vmpc_ws_take(ctx, pre_b);
-    uint32_t *small = (uint32_t *)vmpc_ws_take(ctx, 4 * 32);   // total[3], inv_sq
-    const dim3 g((lanes + 255) / 256, 3);
+    uint32_t *inv_sq = (uint32_t *)vmpc_ws_take(ctx, 32);
     {
         vmpc_stage_scope sc(ctx, "bn_qap_lagrange_scan");
-        k_kg_runprod<<<g, 256, 0, ctx->stream>>>((const uint32_t *)s, dd, lanes, run);
-        VMPC_KERNEL_CHECK();
-        k_kg_runscan<<<3, KG_SCAN, 0, ctx->stream>>>(lanes, run, small, small + 24);
-        VMPC_KERNEL_CHECK();
-        k_kg_runfill<<<g, 256, 0, ctx->stream>>>((const uint32_t *)s, dd, lanes, run, small, pre);
-        VMPC_KERNEL_CHECK();
+        VMPC_CHECK((fr_scan<frbn, KG_RUN>(ctx, kg_seq{(const uint32_t *)s, dd}, dd, 3, run, pre, kg_fin{inv_sq})));
     }
     {
         vmpc_stage_scope sc(ctx, "bn_qap_lagrange_combine");
-        k_kg_combine<<<(unsigned)((d + 255) / 256), 256, 0, ctx->stream>>>(dd, pre, small + 24, (uint32_t *)ell_out,
+        k_kg_combine<<<(unsigned)((d + 255) / 256), 256, 0, ctx->stream>>>(dd, pre, inv_sq, (uint32_t *)ell_out,
                                                                           (uint32_t *)t_out);
         VMPC_KERNEL_CHECK();
     }
@@ -183,14 +106,14 @@ k_kg_colsum(const uint32_t *__restrict__ basis, uint32_t n_basis, const uint32_t
     for (uint64_t e = e0; e < e1 && e < nnz; e++) {
         const uint32_t r = rows[e];
         if (r >= n_basis) continue;
-        const frbn a = kg_ld(vals, (long long)e), b = kg_ld(basis, r);
+        const frbn a = f256_ld<frbn>(vals, (long long)e), b = f256_ld<frbn>(basis, r);
         frbn_acc_mac(acc, a.v, b.v);
     }
     const frbn v = frbn_acc_reduce(acc);
     if (dst & KG_PARTIAL) {
-        if ((dst & ~KG_PARTIAL) < n_partial) kg_st(part, dst & ~KG_PARTIAL, v);
+        if ((dst & ~KG_PARTIAL) < n_partial) f256_st(part, dst & ~KG_PARTIAL, v);
     } else if (dst < n_out) {
-        kg_st(out, dst, v);
+        f256_st(out, dst, v);
     }
 }
 
@@ -203,14 +126,14 @@ k_kg_colfinish(const uint32_t *__restrict__ longs, const uint32_t *__restrict__ 
     const uint32_t col = longs[3 * blockIdx.x], first = longs[3 * blockIdx.x + 1], count = longs[3 * blockIdx.x + 2];
     frbn s = frbn_zero();
     for (uint64_t i = t; i < count; i += 256)
-        if ((uint64_t)first + i < n_partial) s = frbn_add(s, kg_ld(part, (long long)(first + i)));
+        if ((uint64_t)first + i < n_partial) s = frbn_add(s, f256_ld<frbn>(part, (long long)(first + i)));
     red[t] = s;
     __syncthreads();
     for (int h = 128; h > 0; h >>= 1) {
         if (t < h) red[t] = frbn_add(red[t], red[t + h]);
         __syncthreads();
     }
-    if (t == 0 && col < n_out) kg_st(out, col, red[0]);
+    if (t == 0 && col < n_out) f256_st(out, col, red[0]);
 }
 
 extern "C" int vmpc_bn256_qap_colsum_dev(vmpc_ctx *ctx, const void *basis, size_t n_basis, const uint32_t *rows,
@@ -258,15 +181,15 @@ k_kg_exps(const uint32_t *__restrict__ coef, const uint32_t *__restrict__ vwy, u
     if (r >= rows) return;
     frbn c[9];
 #pragma unroll
-    for (int k = 0; k < 9; k++) c[k] = kg_ld(coef, k);
+    for (int k = 0; k < 9; k++) c[k] = f256_ld<frbn>(coef, k);
     frbn e[7];
     if (r < n_idx) {
         const uint64_t i = idx[r];
         frbn v = frbn_zero(), w = frbn_zero(), y = frbn_zero();
         if (i < n_wires) {
-            v = kg_ld(vwy, (long long)i);
-            w = kg_ld(vwy, (long long)(n_wires + i));
-            y = kg_ld(vwy, (long long)(2 * n_wires + i));
+            v = f256_ld<frbn>(vwy, (long long)i);
+            w = f256_ld<frbn>(vwy, (long long)(n_wires + i));
+            y = f256_ld<frbn>(vwy, (long long)(2 * n_wires + i));
         }
         e[0] = frbn_mul(c[0], v);
         e[1] = frbn_mul(c[1], w);
@@ -276,7 +199,7 @@ k_kg_exps(const uint32_t *__restrict__ coef, const uint32_t *__restrict__ vwy, u
         e[5] = frbn_mul(c[5], y);
         e[6] = frbn_add(frbn_add(frbn_mul(c[6], v), frbn_mul(c[7], w)), frbn_mul(c[8], y));
     } else {
-        const frbn t = kg_ld(t_in, 0);
+        const frbn t = f256_ld<frbn>(t_in, 0);
         const int dl = (int)(r - n_idx);   // 0: delta_v, 1: delta_w, 2: delta_y
 #pragma unroll
         for (int k = 0; k < 7; k++) e[k] = frbn_zero();
@@ -295,7 +218,7 @@ k_kg_exps(const uint32_t *__restrict__ coef, const uint32_t *__restrict__ vwy, u
         }
     }
 #pragma unroll
-    for (int k = 0; k < 7; k++) kg_st(out, (long long)(k * rows + r), e[k]);
+    for (int k = 0; k < 7; k++) f256_st(out, (long long)(k * rows + r), e[k]);
 }
 
 extern "C" int vmpc_bn256_keygen_exps_dev(vmpc_ctx *ctx, const void *coef, const void *vwy, size_t n_wires,

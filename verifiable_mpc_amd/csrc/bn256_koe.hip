@@ -40,14 +40,6 @@ __host__ __device__ static inline koe_span koe_tile_span(long long k0, long long
     return s;
 }
 
-__device__ __forceinline__ frbn koe_load_or_zero(const uint32_t *__restrict__ v, long long idx, long long n) {
-    if (idx < 0 || idx >= n) return frbn_zero();
-    const uint4 *p = (const uint4 *)(v + 8 * idx);
-    const uint4 x = p[0], y = p[1];
-    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-    return frbn_load(w);
-}
-
 // grid (tiles, most segments of a tile); dst row y holds the partial sums of every tile's y-th segment
 __global__ void __launch_bounds__(KOE_TILE)
 k_frbn_polymul(const uint32_t *__restrict__ a, long long na, const uint32_t *__restrict__ b, long long nb,
@@ -65,13 +57,13 @@ k_frbn_polymul(const uint32_t *__restrict__ a, long long na, const uint32_t *__r
         if (i0 + KOE_CHUNK <= span.lo || i0 > span.hi) continue;   // (uniform)
         __syncthreads();
         if (t < KOE_CHUNK) {
-            const frbn x = koe_load_or_zero(a, i0 + t, na);
+            const frbn x = f256_ld_or_zero<frbn>(a, i0 + t, na);
 #pragma unroll
             for (int l = 0; l < 8; l++) sA[8 * t + l] = x.v[l];
         }
         // sB word j of a limb row is b[k0 - i0 - (KOE_CHUNK - 1) + j]: lane t at step ii reads j = t + KOE_CHUNK - 1 - ii
         for (int j = t; j < KOE_CHUNK + KOE_TILE - 1; j += KOE_TILE) {
-            const frbn x = koe_load_or_zero(b, k0 - i0 - (KOE_CHUNK - 1) + j, nb);
+            const frbn x = f256_ld_or_zero<frbn>(b, k0 - i0 - (KOE_CHUNK - 1) + j, nb);
 #pragma unroll
             for (int l = 0; l < 8; l++) sB[l * KOE_BROW + j] = x.v[l];
         }

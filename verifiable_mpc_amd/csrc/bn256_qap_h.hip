@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "fr_bn.h"
+#include "fr_scan.h"
 
 #define QH_WG 256
 #define QH_J 4                      // running values per lane and vector
@@ -39,21 +40,7 @@
 #define QH_MAX_GROUPS 32            // j ranges (partials per k) at most
 #define QH_TARGET_WGS 2048
 #define QH_RUN 64                   // sequence elements per lane in the weights' scan
-#define QH_SCAN 256
 #define QH_LEAF 128                 // factors (x - j) per leaf of t's product tree
-
-__device__ __forceinline__ frbn qh_ld(const void *p, long long i) {
-    const uint4 *q = (const uint4 *)((const uint32_t *)p + 8 * i);
-    const uint4 x = q[0], y = q[1];
-    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-    return frbn_load(w);
-}
-
-__device__ __forceinline__ void qh_st(void *p, long long i, const frbn &a) {
-    uint4 *q = (uint4 *)((uint32_t *)p + 8 * i);
-    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
 
 // the sum of x over the 64 lanes (uniform), for lane values below 2^26: rows of 16 by DPP (xor 1, xor 2, half
 // mirror, mirror leave the row's sum in every lane), the four rows by readlane
@@ -99,7 +86,7 @@ k_qh_moments(const uint32_t *__restrict__ u0, const uint32_t *__restrict__ u1, u
 #pragma unroll
             for (int nv = 0; nv < NV; nv++) {
                 const uint32_t *u = nv ? u1 : u0;
-                v[nv][i] = in ? qh_ld(u, idx) : frbn_zero();
+                v[nv][i] = in ? f256_ld<frbn>(u, idx) : frbn_zero();
                 if (k0) v[nv][i] = frbn_mul(v[nv][i], pw);
             }
         }
@@ -160,7 +147,7 @@ k_qh_moments(const uint32_t *__restrict__ u0, const uint32_t *__restrict__ u1, u
         frbn_wide a;
 #pragma unroll
         for (int l = 0; l < 9; l++) a.v[l] = sAcc[nv][k][l];
-        qh_st(nv ? part1 : part0, (long long)g * n_out + k0 + k, frbn_wide_reduce(a));
+        f256_st(nv ? part1 : part0, (long long)g * n_out + k0 + k, frbn_wide_reduce(a));
     }
 }
 
@@ -169,9 +156,9 @@ __global__ void __launch_bounds__(256)
 k_qh_partsum(const uint32_t *__restrict__ part, uint32_t n_out, uint32_t groups, uint32_t *__restrict__ out) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_out) return;
-    frbn s = qh_ld(part, k);
-    for (uint32_t g = 1; g < groups; g++) s = frbn_add(s, qh_ld(part, (long long)g * n_out + k));
-    qh_st(out, k, s);
+    frbn s = f256_ld<frbn>(part, k);
+    for (uint32_t g = 1; g < groups; g++) s = frbn_add(s, f256_ld<frbn>(part, (long long)g * n_out + k));
+    f256_st(out, k, s);
 }
 
 extern "C" int vmpc_bn256_qap_moments_dev(vmpc_ctx *ctx, const void *u0, const void *u1, size_t d, size_t n_out,
@@ -219,63 +206,20 @@ extern "C" int vmpc_bn256_qap_moments_dev(vmpc_ctx *ctx, const void *u0, const v
 }
 
 // ---- the weights 1 / w_j ---------------------------------------------------------------------------------------------
-// E[m] = d (d-1) .. (d-m+1) for m = 0..d (E[d] = d!): exclusive prefix products of e_k = d - k
+// E[m] = d (d-1) .. (d-m+1) for m = 0..d (E[d] = d!): exclusive prefix products of e_k = d - k (csrc/fr_scan.h)
+struct qh_seq {
+    uint32_t d;
+    __device__ frbn operator()(const frbn &v, uint32_t, uint32_t k) const { return frbn_mul_small(v, d - k); }
+};
 
-// run[l] = product of e_k over [l QH_RUN, (l+1) QH_RUN) n [0, d)
-__global__ void __launch_bounds__(256) k_qh_runprod(uint32_t d, uint32_t lanes, uint32_t *__restrict__ run) {
-    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= lanes) return;
-    const uint32_t k0 = l * QH_RUN, k1 = k0 + QH_RUN < d ? k0 + QH_RUN : d;
-    frbn p = frbn_one();
-    for (uint32_t k = k0; k < k1; k++) p = frbn_mul_small(p, d - k);
-    qh_st(run, l, p);
-}
-
-// one workgroup: run[*] -> exclusive prefix products, total = d!, inv_sq = 1 / d!^2 (one Fermat inversion)
-__global__ void __launch_bounds__(QH_SCAN)
-k_qh_runscan(uint32_t lanes, uint32_t *__restrict__ run, uint32_t *__restrict__ total, uint32_t *__restrict__ inv_sq) {
-    __shared__ frbn buf[2][QH_SCAN];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (lanes + QH_SCAN - 1) / QH_SCAN;
-    const uint32_t b0 = t * per < lanes ? t * per : lanes, b1 = b0 + per < lanes ? b0 + per : lanes;
-    frbn p = frbn_one();
-    for (uint32_t i = b0; i < b1; i++) p = frbn_mul(p, qh_ld(run, i));
-    int cur = 0;
-    buf[cur][t] = p;
-    __syncthreads();
-    for (uint32_t off = 1; off < QH_SCAN; off <<= 1) {
-        frbn v = buf[cur][t];
-        if (t >= off) v = frbn_mul(buf[cur][t - off], v);
-        buf[cur ^ 1][t] = v;
-        cur ^= 1;
-        __syncthreads();
+// the total is d!: inv_sq = 1 / d!^2 (one Fermat inversion)
+struct qh_fin {
+    uint32_t *inv_sq;
+    __device__ void operator()(uint32_t, const frbn &total) const {
+        const frbn iv = frbn_inv(total);
+        f256_st(inv_sq, 0, frbn_mul(iv, iv));
     }
-    frbn acc = t ? buf[cur][t - 1] : frbn_one();
-    for (uint32_t i = b0; i < b1; i++) {
-        const frbn x = qh_ld(run, i);
-        qh_st(run, i, acc);
-        acc = frbn_mul(acc, x);
-    }
-    if (t == QH_SCAN - 1) {
-        qh_st(total, 0, acc);
-        const frbn iv = frbn_inv(acc);
-        qh_st(inv_sq, 0, frbn_mul(iv, iv));
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_qh_runfill(uint32_t d, uint32_t lanes, const uint32_t *__restrict__ run, const uint32_t *__restrict__ total,
-             uint32_t *__restrict__ E) {
-    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= lanes) return;
-    frbn v = qh_ld(run, l);
-    const uint32_t k0 = l * QH_RUN, k1 = k0 + QH_RUN < d ? k0 + QH_RUN : d;
-    for (uint32_t k = k0; k < k1; k++) {
-        qh_st(E, k, v);
-        v = frbn_mul_small(v, d - k);
-    }
-    if (l == lanes - 1) qh_st(E, d, qh_ld(total, 0));
-}
+};
 
 // ua[j-1] = a_j f_j, ub[j-1] = b_j f_j, f_j = (-1)^(d-j) E[d-j+1] E[j] / d!^2 = 1 / w_j
 __global__ void __launch_bounds__(256)
@@ -285,30 +229,25 @@ k_qh_weights(uint32_t d, const uint32_t *__restrict__ E, const uint32_t *__restr
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d) return;
     const uint32_t j = i + 1;
-    frbn f = frbn_mul(frbn_mul(qh_ld(E, d - j + 1), qh_ld(E, j)), qh_ld(inv_sq, 0));
+    frbn f = frbn_mul(frbn_mul(f256_ld<frbn>(E, d - j + 1), f256_ld<frbn>(E, j)), f256_ld<frbn>(inv_sq, 0));
     if ((d - j) & 1u) f = frbn_sub(frbn_zero(), f);
-    qh_st(ua, i, frbn_mul(qh_ld(a, i), f));
-    if (b) qh_st(ub, i, frbn_mul(qh_ld(b, i), f));
+    f256_st(ua, i, frbn_mul(f256_ld<frbn>(a, i), f));
+    if (b) f256_st(ub, i, frbn_mul(f256_ld<frbn>(b, i), f));
 }
 
 extern "C" int vmpc_bn256_qap_h_weights_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t d, void *ua, void *ub) {
     if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
     if (!ctx || !a || !ua || (b && !ub) || d == 0) return VMPC_E_INVAL;
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    const uint32_t dd = (uint32_t)d, lanes = (uint32_t)((d + QH_RUN - 1) / QH_RUN);
-    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align((size_t)lanes * 32) + vmpc_align((d + 1) * 32) + 1024));
-    uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, (size_t)lanes * 32);
+    const uint32_t dd = (uint32_t)d;
+    const size_t run_b = fr_scan_run_bytes<QH_RUN>(d, 1);
+    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(run_b) + vmpc_align((d + 1) * 32) + 1024));
+    uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, run_b);
     uint32_t *E = (uint32_t *)vmpc_ws_take(ctx, (d + 1) * 32);
-    uint32_t *small = (uint32_t *)vmpc_ws_take(ctx, 64);   // d!, 1 / d!^2
+    uint32_t *inv_sq = (uint32_t *)vmpc_ws_take(ctx, 32);
     vmpc_stage_scope sc(ctx, "bn_qap_h_weights");
-    const unsigned lb = (lanes + 255) / 256;
-    k_qh_runprod<<<lb, 256, 0, ctx->stream>>>(dd, lanes, run);
-    VMPC_KERNEL_CHECK();
-    k_qh_runscan<<<1, QH_SCAN, 0, ctx->stream>>>(lanes, run, small, small + 8);
-    VMPC_KERNEL_CHECK();
-    k_qh_runfill<<<lb, 256, 0, ctx->stream>>>(dd, lanes, run, small, E);
-    VMPC_KERNEL_CHECK();
-    k_qh_weights<<<(unsigned)((d + 255) / 256), 256, 0, ctx->stream>>>(dd, E, small + 8, (const uint32_t *)a,
+    VMPC_CHECK((fr_scan<frbn, QH_RUN>(ctx, qh_seq{dd}, dd, 1, run, E, qh_fin{inv_sq})));
+    k_qh_weights<<<(unsigned)((d + 255) / 256), 256, 0, ctx->stream>>>(dd, E, inv_sq, (const uint32_t *)a,
                                                                       (const uint32_t *)b, (uint32_t *)ua,
                                                                       (uint32_t *)ub);
     VMPC_KERNEL_CHECK();
@@ -321,11 +260,8 @@ k_qh_check(uint32_t d, const uint32_t *__restrict__ a, const uint32_t *__restric
            uint32_t *__restrict__ first_bad) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d) return;
-    const frbn p = frbn_mul(qh_ld(a, i), qh_ld(b, i)), q = qh_ld(y, i);
-    bool same = true;
-#pragma unroll
-    for (int l = 0; l < 8; l++) same = same && p.v[l] == q.v[l];
-    if (!same) atomicMin(first_bad, i);   // an index, not a field value: the minimum does not depend on the order
+    // an index, not a field value: the minimum does not depend on the order
+    if (!f256_equal(frbn_mul(f256_ld<frbn>(a, i), f256_ld<frbn>(b, i)), f256_ld<frbn>(y, i))) atomicMin(first_bad, i);
 }
 
 extern "C" int vmpc_bn256_qap_check_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t d,
@@ -360,7 +296,7 @@ __global__ void __launch_bounds__(QH_WG) k_qh_tleaf(uint32_t d, uint32_t *__rest
         __syncthreads();
     }
     const uint32_t deg = j1 - j0 + 1;
-    if (t <= deg) qh_st(dst, (long long)l * (QH_LEAF + 1) + t, sP[cur][t]);
+    if (t <= deg) f256_st(dst, (long long)l * (QH_LEAF + 1) + t, sP[cur][t]);
 }
 
 extern "C" int vmpc_bn256_qap_t_coeffs_dev(vmpc_ctx *ctx, size_t d, void *scratch, void *out) {
@@ -422,8 +358,8 @@ k_qh_horner(const uint32_t *__restrict__ coeffs, uint32_t n_coeffs, uint32_t d, 
     if (i >= d) return;
     const uint32_t *c = coeffs + 8 * (size_t)p * n_coeffs;
     frbn acc = frbn_zero();
-    for (uint32_t k = n_coeffs; k-- > 0;) acc = frbn_add(frbn_mul_small(acc, i + 1), qh_ld(c, k));
-    qh_st(out, (long long)p * d + i, acc);
+    for (uint32_t k = n_coeffs; k-- > 0;) acc = frbn_add(frbn_mul_small(acc, i + 1), f256_ld<frbn>(c, k));
+    f256_st(out, (long long)p * d + i, acc);
 }
 
 extern "C" int vmpc_bn256_qap_horner_dev(vmpc_ctx *ctx, const void *coeffs, size_t n_coeffs, size_t n_polys, size_t d,
@@ -448,12 +384,12 @@ k_qh_cmid(uint32_t d, const uint32_t *__restrict__ A, const uint32_t *__restrict
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= d) return;
     const uint32_t i = d - 1 - r;   // C_(i+1)
-    frbn c = i ? qh_ld(P, i - 1) : frbn_zero();
+    frbn c = i ? f256_ld<frbn>(P, i - 1) : frbn_zero();
     if (deltas) {
-        c = frbn_add(c, frbn_mul(qh_ld(deltas, 0), qh_ld(B, i)));
-        c = frbn_add(c, frbn_mul(qh_ld(deltas, 1), qh_ld(A, i)));
+        c = frbn_add(c, frbn_mul(f256_ld<frbn>(deltas, 0), f256_ld<frbn>(B, i)));
+        c = frbn_add(c, frbn_mul(f256_ld<frbn>(deltas, 1), f256_ld<frbn>(A, i)));
     }
-    qh_st(crev, r, c);
+    f256_st(crev, r, c);
 }
 
 // Q = (t_1 .. t_d) * crev: h_e = Q[d-1+e] + delta_v delta_w t_e - [e = 0] delta_y for e < d, h_d = delta_v delta_w t_d
@@ -462,12 +398,12 @@ k_qh_final(uint32_t d, const uint32_t *__restrict__ Q, const uint32_t *__restric
            const uint32_t *__restrict__ deltas, uint32_t *__restrict__ out) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e > d) return;
-    frbn h = e < d ? qh_ld(Q, (long long)d - 1 + e) : frbn_zero();
+    frbn h = e < d ? f256_ld<frbn>(Q, (long long)d - 1 + e) : frbn_zero();
     if (deltas) {
-        h = frbn_add(h, frbn_mul(frbn_mul(qh_ld(deltas, 0), qh_ld(deltas, 1)), qh_ld(tc, e)));
-        if (e == 0) h = frbn_sub(h, qh_ld(deltas, 2));
+        h = frbn_add(h, frbn_mul(frbn_mul(f256_ld<frbn>(deltas, 0), f256_ld<frbn>(deltas, 1)), f256_ld<frbn>(tc, e)));
+        if (e == 0) h = frbn_sub(h, f256_ld<frbn>(deltas, 2));
     }
-    qh_st(out, e, h);
+    f256_st(out, e, h);
 }
 
 extern "C" int vmpc_bn256_qap_h_combine_dev(vmpc_ctx *ctx, const void *A, const void *B, const void *t, size_t d,

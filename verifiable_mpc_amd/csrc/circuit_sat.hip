@@ -8,7 +8,7 @@
 //                             straight into z (gamma_i = h(i + 1)); one launch per depth level.  With check != 0 the
 //                             gammas in z are the caller's and the smallest i with a_i b_i != gamma_i is reported
 //                             (circuit_builder.py:133-151 evaluates the forms one gate after the other in Python).
-//   vmpc_fr_cs_tables_dev     k! and 1 / k! for k <= K: two product scans and ONE inversion.  Everything below is
+//   vmpc_fr_cs_tables_dev     k! and 1 / k! for k <= K: two product scans (csrc/fr_scan.h) and ONE inversion.  Everything below is
 //                             products of these: 1 / k = (k-1)! / k!, the barycentric weights
 //                             w_j = (-1)^(M-j) / ((j-1)! (M-j)!), l(x) = prod_j (x - j) = (x-1)! / (x-M-1)! for x > M.
 //   vmpc_fr_cs_extend_dev     f(x) = l(x) sum_j u_j / (x - j), u_j = v_j w_j, at x = 0 and x = m+2 .. 2m, the same
@@ -20,6 +20,7 @@
 //                             output-stationary, a lane owns one x, chunks of u and the window of T it meets staged in
 //                             LDS (T limb-major, u broadcast), UNREDUCED 8 x 8-limb products added into a 16-limb
 //                             accumulator with per-row carry counters, one Barrett reduction per output and segment.
+//                             The accumulator and the element access are csrc/fr256.h, shared with that kernel.
 //                             f and g share the staged T.  Every x meets every j, so the work per tile is uniform; the
 //                             range of j is cut into segments for occupancy, their partial sums added in a fixed
 //                             order.  Integer sums only: deterministic.
@@ -36,6 +37,7 @@
 //   vmpc_fr_cs_first_diff_dev the smallest i with a[i] != b[i] (the verifier's L == proof["L"])
 #include "common.h"
 #include "fr.h"
+#include "fr_scan.h"
 
 #define CS_WG 256
 #define CS_RUN 32                       // sequence elements per lane in the product scans
@@ -45,111 +47,18 @@
 #define CS_MIN_SEG 256                  // shortest segment of j; a multiple of CS_CHUNK
 #define CS_TARGET_WGS 8192
 
-__device__ __forceinline__ fr cs_ld(const void *p, long long i) {
-    const uint4 *q = (const uint4 *)((const uint32_t *)p + 8 * i);
-    const uint4 x = q[0], y = q[1];
-    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-    return fr_load(w);
-}
-
-__device__ __forceinline__ void cs_st(void *p, long long i, const fr &a) {
-    uint4 *q = (uint4 *)((uint32_t *)p + 8 * i);
-    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
-
-__device__ __forceinline__ fr cs_small(uint32_t k) {
-    fr r = fr_zero();
-    r.v[0] = k;
-    return r;
-}
-
-__device__ __forceinline__ bool cs_same(const fr &a, const fr &b) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int l = 0; l < 8; l++) o |= a.v[l] ^ b.v[l];
-    return o == 0;
-}
-
-// a^(l-2)
-__device__ fr cs_inv(const fr &a) {
-    const uint32_t E[8] = {0x5cf5d3ebu, 0x5812631au, 0xa2f79cd6u, 0x14def9deu, 0u, 0u, 0u, 0x10000000u};
-    fr r = cs_small(1);
-    for (int i = 252; i >= 0; i--) {
-        r = fr_mul(r, r);
-        if ((E[i >> 5] >> (i & 31)) & 1u) r = fr_mul(r, a);
-    }
-    return r;
-}
-
-// sum of unreduced 8 x 8-limb products: value = sum lo[k] 2^(32k) + sum hi[i] 2^(32 (i+8)).  Row i of a product runs
-// its carries through lo[i..i+7] and leaves the carry out of the row in the 64-bit counter hi[i]: good for 2^32 products.
-struct cs_acc {
-    uint32_t lo[16];
-    uint64_t hi[8];
-};
-
-__device__ __forceinline__ cs_acc cs_acc_zero() {
-    cs_acc s;
-#pragma unroll
-    for (int i = 0; i < 16; i++) s.lo[i] = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) s.hi[i] = 0;
-    return s;
-}
-
-__device__ __forceinline__ void cs_acc_mac(cs_acc &s, const uint32_t a[8], const uint32_t b[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        uint64_t c = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            c += (uint64_t)a[i] * b[j] + s.lo[i + j];
-            s.lo[i + j] = (uint32_t)c;
-            c >>= 32;
-        }
-        s.hi[i] += c;
-    }
-}
-
-// the accumulator mod l: 18 limbs, the top 16 reduced first, the two low limbs shifted in (r 2^32 + limb < 2^288)
-__device__ fr cs_acc_reduce(const cs_acc &s) {
-    uint32_t w[18];
-    uint64_t c = 0;
-#pragma unroll
-    for (int k = 0; k < 18; k++) {
-        if (k < 16) c += s.lo[k];
-        if (k >= 8 && k < 16) c += (uint32_t)s.hi[k - 8];
-        if (k >= 9 && k < 17) c += (uint32_t)(s.hi[k - 9] >> 32);
-        w[k] = (uint32_t)c;
-        c >>= 32;
-    }
-    fr r = fr_reduce512(w + 2);
-#pragma unroll
-    for (int k = 1; k >= 0; k--) {
-        uint32_t t[16];
-        t[0] = w[k];
-#pragma unroll
-        for (int i = 0; i < 8; i++) t[i + 1] = r.v[i];
-#pragma unroll
-        for (int i = 9; i < 16; i++) t[i] = 0;
-        r = fr_reduce512(t);
-    }
-    return r;
-}
-
 // ---- multiplication triples ---------------------------------------------------------------------------------------------
 // column c of a form reads z[c] for c < n_x (an input) and z[g_off + c - n_x] otherwise (gamma_(c - n_x))
 __device__ fr cs_row_eval(const uint32_t *__restrict__ rp, const uint32_t *__restrict__ col, const uint32_t *__restrict__ val,
                           const uint32_t *__restrict__ cst, uint32_t row, uint32_t n_x, uint32_t g_off,
                           const uint32_t *__restrict__ z) {
-    cs_acc acc = cs_acc_zero();
+    f256_acc acc = f256_acc_zero();
     for (uint32_t e = rp[row]; e < rp[row + 1]; e++) {
         const uint32_t c = col[e];
-        const fr v = cs_ld(val, e), w = cs_ld(z, c < n_x ? c : g_off + (c - n_x));
-        cs_acc_mac(acc, v.v, w.v);
+        const fr v = f256_ld<fr>(val, e), w = f256_ld<fr>(z, c < n_x ? c : g_off + (c - n_x));
+        f256_acc_mac(acc, v.v, w.v);
     }
-    return fr_add(cs_acc_reduce(acc), cs_ld(cst, row));
+    return fr_add(f256_acc_reduce<fr>(acc), f256_ld<fr>(cst, row));
 }
 
 __global__ void __launch_bounds__(CS_WG)
@@ -163,14 +72,14 @@ k_cs_triples(const uint32_t *__restrict__ a_rp, const uint32_t *__restrict__ a_c
     const uint32_t i = gates ? gates[t] : t;
     const fr a = cs_row_eval(a_rp, a_col, a_val, a_cst, i, n_x, g_off, z);
     const fr b = cs_row_eval(b_rp, b_col, b_val, b_cst, i, n_x, g_off, z);
-    cs_st(a_out, i, a);
-    cs_st(b_out, i, b);
+    f256_st(a_out, i, a);
+    f256_st(b_out, i, b);
     if (check == 2) return;   // the forms' values only (the output rows)
     const fr p = fr_mul(a, b);
     if (check) {
-        if (!cs_same(p, cs_ld(z, (long long)g_off + i))) atomicMin(first_bad, i);   // an index: order does not matter
+        if (!f256_equal(p, f256_ld<fr>(z, (long long)g_off + i))) atomicMin(first_bad, i);   // an index: order does not matter
     } else {
-        cs_st(z, (long long)g_off + i, p);
+        f256_st(z, (long long)g_off + i, p);
     }
 }
 
@@ -195,88 +104,31 @@ extern "C" int vmpc_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, 
     return VMPC_OK;
 }
 
-// ---- inclusive product scans -------------------------------------------------------------------------------------------
-// out[i] = in[0] .. in[i] (rev: in[i] .. in[n-1]).  run: (n + CS_RUN - 1) / CS_RUN scalars of scratch.
-__device__ __forceinline__ uint32_t cs_ix(uint32_t k, uint32_t n, int rev) { return rev ? n - 1 - k : k; }
-
-__global__ void __launch_bounds__(CS_WG)
-k_cs_runprod(const uint32_t *__restrict__ in, uint32_t n, int rev, uint32_t lanes, uint32_t *__restrict__ run) {
-    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= lanes) return;
-    const uint32_t k0 = l * CS_RUN, k1 = k0 + CS_RUN < n ? k0 + CS_RUN : n;
-    fr p = cs_ld(in, cs_ix(k0, n, rev));
-    for (uint32_t k = k0 + 1; k < k1; k++) p = fr_mul(p, cs_ld(in, cs_ix(k, n, rev)));
-    cs_st(run, l, p);
-}
-
-// one workgroup: run[*] -> exclusive prefix products
-__global__ void __launch_bounds__(CS_WG) k_cs_runscan(uint32_t lanes, uint32_t *__restrict__ run) {
-    __shared__ fr buf[2][CS_WG];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (lanes + CS_WG - 1) / CS_WG;
-    const uint32_t b0 = t * per < lanes ? t * per : lanes, b1 = b0 + per < lanes ? b0 + per : lanes;
-    fr p = cs_small(1);
-    for (uint32_t i = b0; i < b1; i++) p = fr_mul(p, cs_ld(run, i));
-    int cur = 0;
-    buf[cur][t] = p;
-    __syncthreads();
-    for (uint32_t off = 1; off < CS_WG; off <<= 1) {
-        fr v = buf[cur][t];
-        if (t >= off) v = fr_mul(buf[cur][t - off], v);
-        buf[cur ^ 1][t] = v;
-        cur ^= 1;
-        __syncthreads();
-    }
-    fr acc = t ? buf[cur][t - 1] : cs_small(1);
-    for (uint32_t i = b0; i < b1; i++) {
-        const fr x = cs_ld(run, i);
-        cs_st(run, i, acc);
-        acc = fr_mul(acc, x);
-    }
-}
-
-__global__ void __launch_bounds__(CS_WG)
-k_cs_runfill(const uint32_t *__restrict__ in, uint32_t n, int rev, uint32_t lanes, const uint32_t *__restrict__ run,
-             uint32_t *__restrict__ out) {
-    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= lanes) return;
-    fr v = cs_ld(run, l);
-    const uint32_t k0 = l * CS_RUN, k1 = k0 + CS_RUN < n ? k0 + CS_RUN : n;
-    for (uint32_t k = k0; k < k1; k++) {
-        const uint32_t i = cs_ix(k, n, rev);
-        v = fr_mul(v, cs_ld(in, i));
-        cs_st(out, i, v);
-    }
-}
-
-static int cs_scan(vmpc_ctx *ctx, const uint32_t *in, uint32_t n, int rev, uint32_t *run, uint32_t *out) {
-    const uint32_t lanes = (n + CS_RUN - 1) / CS_RUN;
-    const unsigned lb = (lanes + CS_WG - 1) / CS_WG;
-    k_cs_runprod<<<lb, CS_WG, 0, ctx->stream>>>(in, n, rev, lanes, run);
-    VMPC_KERNEL_CHECK();
-    k_cs_runscan<<<1, CS_WG, 0, ctx->stream>>>(lanes, run);
-    VMPC_KERNEL_CHECK();
-    k_cs_runfill<<<lb, CS_WG, 0, ctx->stream>>>(in, n, rev, lanes, run, out);
-    VMPC_KERNEL_CHECK();
-    return VMPC_OK;
-}
-static inline size_t cs_run_bytes(size_t n) { return vmpc_align(((n + CS_RUN - 1) / CS_RUN) * 32); }
-
 // ---- factorial tables ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(CS_WG) k_cs_iota(uint32_t n, uint32_t *__restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) cs_st(out, i, cs_small(i ? i : 1));
-}
+// exclusive prefix products (csrc/fr_scan.h) of 1, 2, .., K (k! at index k) and of K, K-1, .., 1 (K! / (K-k)! at index k)
+struct cs_fact_seq {
+    uint32_t K;
+    __device__ fr operator()(const fr &v, uint32_t q, uint32_t k) const {
+        return fr_mul(v, f256_small<fr>(q ? K - k : k + 1));
+    }
+};
 
-// ifact[k] = (1 / K!) (k+1) (k+2) .. K with sfx[k] = k (k+1) .. K; 1 / K! is the one inversion (Fermat), one lane
-__global__ void k_cs_inv1(const uint32_t *__restrict__ x, uint32_t *__restrict__ out) { cs_st(out, 0, cs_inv(cs_ld(x, 0))); }
+// 1 / K! is the one inversion (Fermat), by the thread that holds K!
+struct cs_fact_fin {
+    uint32_t *inv_top;
+    __device__ void operator()(uint32_t q, const fr &total) const {
+        if (q == 0) f256_st(inv_top, 0, f256_inv(total));
+    }
+};
 
+// fact[k] = k!, ifact[k] = (1 / K!) (k+1) (k+2) .. K
 __global__ void __launch_bounds__(CS_WG)
-k_cs_ifact(uint32_t K, const uint32_t *__restrict__ sfx, const uint32_t *__restrict__ inv_top, uint32_t *__restrict__ ifact) {
+k_cs_ifact(uint32_t K, const uint32_t *__restrict__ pre, const uint32_t *__restrict__ inv_top,
+           uint32_t *__restrict__ fact, uint32_t *__restrict__ ifact) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k > K) return;
-    const fr it = cs_ld(inv_top, 0);
-    cs_st(ifact, k, k < K ? fr_mul(it, cs_ld(sfx, k + 1)) : it);
+    f256_st(fact, k, f256_ld<fr>(pre, k));
+    f256_st(ifact, k, fr_mul(f256_ld<fr>(inv_top, 0), f256_ld<fr>(pre, (long long)K + 1 + K - k)));
 }
 
 extern "C" int vmpc_fr_cs_tables_dev(vmpc_ctx *ctx, size_t K, void *fact, void *ifact) {
@@ -284,68 +136,55 @@ extern "C" int vmpc_fr_cs_tables_dev(vmpc_ctx *ctx, size_t K, void *fact, void *
     if (!ctx || !fact || !ifact || K == 0) return VMPC_E_INVAL;
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const uint32_t n = (uint32_t)K + 1;
-    const size_t vec = vmpc_align((size_t)n * 32);
-    VMPC_CHECK(vmpc_ws_reserve(ctx, 2 * vec + cs_run_bytes(n) + 1024));
-    uint32_t *in = (uint32_t *)vmpc_ws_take(ctx, (size_t)n * 32);
-    uint32_t *sfx = (uint32_t *)vmpc_ws_take(ctx, (size_t)n * 32);
-    uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, cs_run_bytes(n));
+    const size_t pre_b = 2 * (size_t)n * 32, run_b = fr_scan_run_bytes<CS_RUN>(K, 2);
+    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(pre_b) + vmpc_align(run_b) + 1024));
+    uint32_t *pre = (uint32_t *)vmpc_ws_take(ctx, pre_b);
+    uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, run_b);
     uint32_t *inv_top = (uint32_t *)vmpc_ws_take(ctx, 32);
     vmpc_stage_scope sc(ctx, "cs_tables");
-    const unsigned blocks = (n + CS_WG - 1) / CS_WG;
-    k_cs_iota<<<blocks, CS_WG, 0, ctx->stream>>>(n, in);
-    VMPC_KERNEL_CHECK();
-    VMPC_CHECK(cs_scan(ctx, in, n, 0, run, (uint32_t *)fact));
-    VMPC_CHECK(cs_scan(ctx, in, n, 1, run, sfx));
-    k_cs_inv1<<<1, 1, 0, ctx->stream>>>((const uint32_t *)fact + 8 * (size_t)K, inv_top);
-    VMPC_KERNEL_CHECK();
-    k_cs_ifact<<<blocks, CS_WG, 0, ctx->stream>>>((uint32_t)K, sfx, inv_top, (uint32_t *)ifact);
+    VMPC_CHECK((fr_scan<fr, CS_RUN>(ctx, cs_fact_seq{(uint32_t)K}, (uint32_t)K, 2, run, pre, cs_fact_fin{inv_top})));
+    k_cs_ifact<<<(n + CS_WG - 1) / CS_WG, CS_WG, 0, ctx->stream>>>((uint32_t)K, pre, inv_top, (uint32_t *)fact,
+                                                                  (uint32_t *)ifact);
     VMPC_KERNEL_CHECK();
     return VMPC_OK;
 }
 
 // ---- Lagrange vector of the nodes 0..K at c -----------------------------------------------------------------------------
-struct cs_arg {
-    uint32_t v[8];
+// exclusive prefix products of c - 0, c - 1, .. (pre) and of c - K, c - (K-1), .. (sfx)
+struct cs_node_seq {
+    fr c;
+    uint32_t K;
+    __device__ fr operator()(const fr &v, uint32_t q, uint32_t k) const {
+        return fr_mul(v, fr_sub(c, f256_small<fr>(q ? K - k : k)));
+    }
 };
 
-__global__ void __launch_bounds__(CS_WG) k_cs_cminus(cs_arg c, uint32_t n, uint32_t *__restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) cs_st(out, i, fr_sub(fr_load(c.v), cs_small(i)));
-}
-
 __global__ void __launch_bounds__(CS_WG)
-k_cs_lagrange(uint32_t K, const uint32_t *__restrict__ pre, const uint32_t *__restrict__ sfx,
-              const uint32_t *__restrict__ ifact, uint32_t *__restrict__ out) {
+k_cs_lagrange(uint32_t K, const uint32_t *__restrict__ pre, const uint32_t *__restrict__ ifact, uint32_t *__restrict__ out) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j > K) return;
-    fr v = fr_mul(cs_ld(ifact, j), cs_ld(ifact, K - j));
-    if (j) v = fr_mul(v, cs_ld(pre, j - 1));
-    if (j < K) v = fr_mul(v, cs_ld(sfx, j + 1));
+    fr v = fr_mul(f256_ld<fr>(ifact, j), f256_ld<fr>(ifact, K - j));
+    v = fr_mul(fr_mul(v, f256_ld<fr>(pre, j)), f256_ld<fr>(pre, (long long)K + 1 + K - j));
     if ((K - j) & 1u) v = fr_neg(v);
-    cs_st(out, j, v);
+    f256_st(out, j, v);
 }
 
 extern "C" int vmpc_fr_cs_lagrange_dev(vmpc_ctx *ctx, const uint8_t c[32], size_t K, const void *ifact, void *out) {
     if (K > 2 * VMPC_FR_CS_MAX_M + 1) return VMPC_E_RANGE;
     if (!ctx || !c || !ifact || !out) return VMPC_E_INVAL;
-    cs_arg ca;
-    memcpy(ca.v, c, 32);
-    if (fr_geq_l(ca.v)) return VMPC_E_NONCANON;
+    fr cv;
+    memcpy(cv.v, c, 32);
+    if (fr_geq_l(cv.v)) return VMPC_E_NONCANON;
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const uint32_t n = (uint32_t)K + 1;
-    const size_t vec = vmpc_align((size_t)n * 32);
-    VMPC_CHECK(vmpc_ws_reserve(ctx, 3 * vec + cs_run_bytes(n) + 1024));
-    uint32_t *in = (uint32_t *)vmpc_ws_take(ctx, (size_t)n * 32);
-    uint32_t *pre = (uint32_t *)vmpc_ws_take(ctx, (size_t)n * 32);
-    uint32_t *sfx = (uint32_t *)vmpc_ws_take(ctx, (size_t)n * 32);
-    uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, cs_run_bytes(n));
+    const size_t pre_b = 2 * (size_t)n * 32, run_b = fr_scan_run_bytes<CS_RUN>(K, 2);
+    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(pre_b) + vmpc_align(run_b) + 1024));
+    uint32_t *pre = (uint32_t *)vmpc_ws_take(ctx, pre_b);
+    uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, run_b);
     vmpc_stage_scope sc(ctx, "cs_lagrange");
-    const unsigned blocks = (n + CS_WG - 1) / CS_WG;
-    k_cs_cminus<<<blocks, CS_WG, 0, ctx->stream>>>(ca, n, in);
-    VMPC_KERNEL_CHECK();
-    VMPC_CHECK(cs_scan(ctx, in, n, 0, run, pre));
-    VMPC_CHECK(cs_scan(ctx, in, n, 1, run, sfx));
-    k_cs_lagrange<<<blocks, CS_WG, 0, ctx->stream>>>((uint32_t)K, pre, sfx, (const uint32_t *)ifact, (uint32_t *)out);
+    VMPC_CHECK((fr_scan<fr, CS_RUN>(ctx, cs_node_seq{cv, (uint32_t)K}, (uint32_t)K, 2, run, pre)));
+    k_cs_lagrange<<<(n + CS_WG - 1) / CS_WG, CS_WG, 0, ctx->stream>>>((uint32_t)K, pre, (const uint32_t *)ifact,
+                                                                     (uint32_t *)out);
     VMPC_KERNEL_CHECK();
     return VMPC_OK;
 }
@@ -359,12 +198,12 @@ k_cs_prep(uint32_t M, uint32_t n_t, const uint32_t *__restrict__ a, const uint32
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < M) {
         const uint32_t j = i + 1;
-        fr w = fr_mul(cs_ld(ifact, j - 1), cs_ld(ifact, M - j));
+        fr w = fr_mul(f256_ld<fr>(ifact, j - 1), f256_ld<fr>(ifact, M - j));
         if ((M - j) & 1u) w = fr_neg(w);
-        cs_st(uf, i, fr_mul(cs_ld(a, i), w));
-        cs_st(ug, i, fr_mul(cs_ld(b, i), w));
+        f256_st(uf, i, fr_mul(f256_ld<fr>(a, i), w));
+        f256_st(ug, i, fr_mul(f256_ld<fr>(b, i), w));
     }
-    if (i < n_t) cs_st(T, i, i ? fr_mul(cs_ld(fact, i - 1), cs_ld(ifact, i)) : fr_zero());
+    if (i < n_t) f256_st(T, i, i ? fr_mul(f256_ld<fr>(fact, i - 1), f256_ld<fr>(ifact, i)) : fr_zero());
 }
 
 // one workgroup: s0[0] = sum_i uf[i] T[i+1], s0[1] = the same for ug (lane t takes i = t, t + 256, ..; the lanes' sums
@@ -374,25 +213,20 @@ k_cs_dot0(uint32_t M, const uint32_t *__restrict__ uf, const uint32_t *__restric
           uint32_t *__restrict__ s0) {
     __shared__ fr part[2][CS_WG];
     const uint32_t t = threadIdx.x;
-    cs_acc af = cs_acc_zero(), ag = cs_acc_zero();
+    f256_acc af = f256_acc_zero(), ag = f256_acc_zero();
     for (uint32_t i = t; i < M; i += CS_WG) {
-        const fr y = cs_ld(T, (long long)i + 1), xf = cs_ld(uf, i), xg = cs_ld(ug, i);
-        cs_acc_mac(af, xf.v, y.v);
-        cs_acc_mac(ag, xg.v, y.v);
+        const fr y = f256_ld<fr>(T, (long long)i + 1), xf = f256_ld<fr>(uf, i), xg = f256_ld<fr>(ug, i);
+        f256_acc_mac(af, xf.v, y.v);
+        f256_acc_mac(ag, xg.v, y.v);
     }
-    part[0][t] = cs_acc_reduce(af);
-    part[1][t] = cs_acc_reduce(ag);
+    part[0][t] = f256_acc_reduce<fr>(af);
+    part[1][t] = f256_acc_reduce<fr>(ag);
     __syncthreads();
     if (t < 2) {
         fr s = part[t][0];
         for (uint32_t i = 1; i < CS_WG; i++) s = fr_add(s, part[t][i]);
-        cs_st(s0, t, s);
+        f256_st(s0, t, s);
     }
-}
-
-__device__ __forceinline__ fr cs_load_or_zero(const uint32_t *__restrict__ v, long long idx, long long n) {
-    if (idx < 0 || idx >= n) return fr_zero();
-    return cs_ld(v, idx);
 }
 
 // grid (tiles, segments).  part_f[s n_out + o] = sum over segment s's i of uf[i] T[k_lo + o - i], o < n_out; part_g alike.
@@ -406,11 +240,11 @@ k_cs_corr(const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, long
     const int t = threadIdx.x;
     const long long o0 = (long long)blockIdx.x * CS_TILE, k0 = k_lo + o0;
     const long long seg_lo = (long long)blockIdx.y * seg;
-    cs_acc accf = cs_acc_zero(), accg = cs_acc_zero();
+    f256_acc accf = f256_acc_zero(), accg = f256_acc_zero();
     for (long long i0 = seg_lo; i0 < seg_lo + seg && i0 < M; i0 += CS_CHUNK) {
         __syncthreads();
         if (t < CS_CHUNK) {
-            const fr x = cs_load_or_zero(uf, i0 + t, M), y = cs_load_or_zero(ug, i0 + t, M);
+            const fr x = f256_ld_or_zero<fr>(uf, i0 + t, M), y = f256_ld_or_zero<fr>(ug, i0 + t, M);
 #pragma unroll
             for (int l = 0; l < 8; l++) {
                 sF[8 * t + l] = x.v[l];
@@ -419,7 +253,7 @@ k_cs_corr(const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, long
         }
         // word j of a limb row is T[k0 - i0 - (CS_CHUNK - 1) + j]: lane t at step ii reads j = t + CS_CHUNK - 1 - ii
         for (int j = t; j < CS_CHUNK + CS_TILE - 1; j += CS_TILE) {
-            const fr x = cs_load_or_zero(T, k0 - i0 - (CS_CHUNK - 1) + j, n_t);
+            const fr x = f256_ld_or_zero<fr>(T, k0 - i0 - (CS_CHUNK - 1) + j, n_t);
 #pragma unroll
             for (int l = 0; l < 8; l++) sT[l * CS_BROW + j] = x.v[l];
         }
@@ -433,14 +267,14 @@ k_cs_corr(const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, long
                 xg[l] = sG[8 * ii + l];
                 y[l] = sT[l * CS_BROW + t + CS_CHUNK - 1 - ii];
             }
-            cs_acc_mac(accf, xf, y);
-            cs_acc_mac(accg, xg, y);
+            f256_acc_mac(accf, xf, y);
+            f256_acc_mac(accg, xg, y);
         }
     }
     const long long o = o0 + t;
     if (o < n_out) {
-        cs_st(part_f, (long long)blockIdx.y * n_out + o, cs_acc_reduce(accf));
-        cs_st(part_g, (long long)blockIdx.y * n_out + o, cs_acc_reduce(accg));
+        f256_st(part_f, (long long)blockIdx.y * n_out + o, f256_acc_reduce<fr>(accf));
+        f256_st(part_g, (long long)blockIdx.y * n_out + o, f256_acc_reduce<fr>(accg));
     }
 }
 
@@ -454,23 +288,23 @@ k_cs_finish(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restri
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t M = m + 1;
     if (o < n_out) {
-        fr sf = cs_ld(part_f, o), sg = cs_ld(part_g, o);
+        fr sf = f256_ld<fr>(part_f, o), sg = f256_ld<fr>(part_g, o);
         for (uint32_t s = 1; s < n_seg; s++) {
-            sf = fr_add(sf, cs_ld(part_f, (long long)s * n_out + o));
-            sg = fr_add(sg, cs_ld(part_g, (long long)s * n_out + o));
+            sf = fr_add(sf, f256_ld<fr>(part_f, (long long)s * n_out + o));
+            sg = fr_add(sg, f256_ld<fr>(part_g, (long long)s * n_out + o));
         }
         const uint32_t x = m + 2 + o;
-        const fr lx = fr_mul(cs_ld(fact, x - 1), cs_ld(ifact, x - M - 1));
-        cs_st(zt, 2 + (long long)x, fr_mul(fr_mul(lx, sf), fr_mul(lx, sg)));
+        const fr lx = fr_mul(f256_ld<fr>(fact, x - 1), f256_ld<fr>(ifact, x - M - 1));
+        f256_st(zt, 2 + (long long)x, fr_mul(fr_mul(lx, sf), fr_mul(lx, sg)));
     } else if (o == n_out) {
         // l(0) = (-1)^M M!, 1 / (0 - j) = -T[j]: f(0) = (-1)^(M+1) M! s0
-        fr l0 = cs_ld(fact, M);
+        fr l0 = f256_ld<fr>(fact, M);
         if (!(M & 1u)) l0 = fr_neg(l0);
-        const fr f0 = fr_mul(l0, cs_ld(s0, 0)), g0 = fr_mul(l0, cs_ld(s0, 1));
-        cs_st(zt, 0, f0);
-        cs_st(zt, 1, g0);
-        cs_st(zt, 2, fr_mul(f0, g0));
-        if (m) cs_st(zt, 2 + (long long)M, fr_mul(cs_ld(a, m), cs_ld(b, m)));   // m = 0: z ends at h(0)
+        const fr f0 = fr_mul(l0, f256_ld<fr>(s0, 0)), g0 = fr_mul(l0, f256_ld<fr>(s0, 1));
+        f256_st(zt, 0, f0);
+        f256_st(zt, 1, g0);
+        f256_st(zt, 2, fr_mul(f0, g0));
+        if (m) f256_st(zt, 2 + (long long)M, fr_mul(f256_ld<fr>(a, m), f256_ld<fr>(b, m)));   // m = 0: z ends at h(0)
     }
 }
 
@@ -524,14 +358,14 @@ k_cs_colseg(const uint32_t *__restrict__ seg_ptr, uint32_t n_segs, const uint32_
             uint32_t *__restrict__ partial) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_segs) return;
-    cs_acc acc = cs_acc_zero();
+    f256_acc acc = f256_acc_zero();
     for (uint32_t e = seg_ptr[s]; e < seg_ptr[s + 1]; e++) {
         const uint32_t r = rows[e];
         if (r >= n_rows) continue;
-        const fr v = cs_ld(vals, e), w = cs_ld(weights, r);
-        cs_acc_mac(acc, v.v, w.v);
+        const fr v = f256_ld<fr>(vals, e), w = f256_ld<fr>(weights, r);
+        f256_acc_mac(acc, v.v, w.v);
     }
-    cs_st(partial, s, cs_acc_reduce(acc));
+    f256_st(partial, s, f256_acc_reduce<fr>(acc));
 }
 
 __global__ void __launch_bounds__(CS_WG)
@@ -542,8 +376,8 @@ k_cs_colsum(const uint32_t *__restrict__ col_seg, const uint32_t *__restrict__ c
     const uint32_t pos = col_pos[c];
     if (pos >= n_out) return;
     fr s = fr_zero();
-    for (uint32_t k = col_seg[c]; k < col_seg[c + 1]; k++) s = fr_add(s, cs_ld(partial, k));
-    cs_st(out, pos, s);
+    for (uint32_t k = col_seg[c]; k < col_seg[c + 1]; k++) s = fr_add(s, f256_ld<fr>(partial, k));
+    f256_st(out, pos, s);
 }
 
 extern "C" int vmpc_fr_cs_colsum_dev(vmpc_ctx *ctx, const void *weights, size_t n_rows, const uint32_t *rows,
@@ -574,7 +408,7 @@ __global__ void __launch_bounds__(CS_WG)
 k_cs_first_diff(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t n, uint32_t *__restrict__ first) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (!cs_same(cs_ld(a, i), cs_ld(b, i))) atomicMin(first, i);
+    if (!f256_equal(f256_ld<fr>(a, i), f256_ld<fr>(b, i))) atomicMin(first, i);
 }
 
 extern "C" int vmpc_fr_cs_first_diff_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, uint32_t *first_diff) {
