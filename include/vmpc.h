@@ -519,6 +519,27 @@ int vmpc_fr_cs_colsum_dev(vmpc_ctx *ctx, const void *weights, size_t n_rows, con
 /* *first_diff (a device uint32) = the smallest i < n with a[i] != b[i], 0xffffffff if none.  No arena. */
 int vmpc_fr_cs_first_diff_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, uint32_t *first_diff);
 
+/* ---- Pi_Nullity (AC20 p. 17-18, verifiable_mpc/ac20/nullity.py:21-40): s dense linear forms over n variables as a
+ * row-major matrix in device memory, row i at rows + 32 i row_stride, 32-byte little-endian elements.  ANY 256-bit
+ * element is accepted and taken mod l (the arithmetic reduces it on the way in); results are canonical.  Caps:
+ * s <= VMPC_FR_ROWS_MAX_S, n and row_stride <= VMPC_FR_ROWS_MAX_N; above them the entries answer VMPC_E_RANGE before
+ * they look at any pointer and write nothing.  row_stride >= n (not read when s <= 1).  Deterministic: integer sums in
+ * a fixed order, no atomics on field values. */
+#define VMPC_FR_ROWS_MAX_S ((size_t)1 << 16)
+#define VMPC_FR_ROWS_MAX_N ((size_t)1 << 30)
+/* out[j] = sum_{i<s} rho^i rows[i][j] for j < n (nullity.py:25 and :32, L = sum_i linform_i * rho**i): one pass over
+ * the matrix, Horner from the last row down; few columns under many rows (n < 65536, s >= 32) are cut into row
+ * segments whose partial rows are combined with rho^(segment length).  rho: a canonical residue (VMPC_E_NONCANON
+ * otherwise).  s = 0: zeros; s = 1: the reduced row.  `out` must not overlap `rows`.  Arena: the partial rows (below
+ * 2^17 scalars). */
+int vmpc_fr_rows_combine_dev(vmpc_ctx *ctx, const void *rows, size_t s, size_t n, size_t row_stride,
+                             const uint8_t rho[32], void *out);
+/* out[i] = sum_{j<n} rows[i][j] x[j] for i < s (device memory, s scalars): every L_i(x) of pivot.py:84-92 in one launch
+ * sequence.  *first_nonzero (a device uint32; may be NULL) = the smallest i with out[i] != 0, 0xffffffff if there is
+ * none.  Arena: at most max(s, 2048) scalars. */
+int vmpc_fr_rows_dot_dev(vmpc_ctx *ctx, const void *rows, size_t s, size_t n, size_t row_stride, const void *x, void *out,
+                         uint32_t *first_nonzero);
+
 /* SHA-256 of every `chunk_bytes`-sized piece of a device buffer (last piece may be short):
  * out_digests[i] = SHA256(data[i*chunk : (i+1)*chunk]), 32 bytes each.  Leaves of the compact
  * transcript's two-level digests; not used by the reference transcript. */

@@ -51,6 +51,7 @@ SYMBOLS = [
     "vmpc_bn256_qap_t_coeffs_dev", "vmpc_bn256_qap_horner_dev", "vmpc_bn256_qap_h_combine_dev",
     "vmpc_fr_cs_triples_dev", "vmpc_fr_cs_tables_dev", "vmpc_fr_cs_extend_dev", "vmpc_fr_cs_lagrange_dev",
     "vmpc_fr_cs_colsum_dev", "vmpc_fr_cs_first_diff_dev",
+    "vmpc_fr_rows_combine_dev", "vmpc_fr_rows_dot_dev",
 ]
 
 
@@ -173,6 +174,8 @@ def load_library():
         "vmpc_fr_cs_lagrange_dev": (i32, [vp, vp, sz, vp, vp]),
         "vmpc_fr_cs_colsum_dev": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, sz]),
         "vmpc_fr_cs_first_diff_dev": (i32, [vp, vp, vp, sz, vp]),
+        "vmpc_fr_rows_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp]),
+        "vmpc_fr_rows_dot_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
         "vmpc_msm_table_fold_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp]),
         "vmpc_msm_table_fold_table_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp, sz, i32, vp]),
         "vmpc_p4_create": (i32, [vp, vp, sz, sz, i32, i32, i32, vp, vp, vp, ctypes.POINTER(vp)]),
@@ -609,10 +612,10 @@ class Context:
         _check(self.lib.vmpc_ctx_profile(self.handle, 1 if enable else 0), "vmpc_ctx_profile")
 
     def profile_read(self, reset=True):
-        names = ctypes.create_string_buffer(2048)
-        ms = (ctypes.c_double * 64)()
-        cnt = (ctypes.c_uint64 * 64)()
-        k = self.lib.vmpc_ctx_profile_read(self.handle, names, 2048, ms, cnt, 64, 1 if reset else 0)
+        names = ctypes.create_string_buffer(4096)      # the library has some 70 stage names of at most 30 characters
+        ms = (ctypes.c_double * 128)()
+        cnt = (ctypes.c_uint64 * 128)()
+        k = self.lib.vmpc_ctx_profile_read(self.handle, names, 4096, ms, cnt, 128, 1 if reset else 0)
         if k < 0:
             _check(k, "vmpc_ctx_profile_read")
         nm = names.value.decode().split(";") if k else []
@@ -830,6 +833,24 @@ class Context:
         _check(self.lib.vmpc_fr_cs_first_diff_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), n,
                                                   ctypes.c_void_p(out.ptr)), "vmpc_fr_cs_first_diff_dev")
         v = int(self.download(out.ptr, 4).view(np.uint32)[0])
+        return None if v == 0xFFFFFFFF else v
+
+    # ---- Pi_Nullity over a dense form matrix (csrc/nullity.hip) ------------------------------------------------------
+    def fr_rows_combine(self, rows_ptr, s, n, row_stride, rho, out_ptr):
+        """out[j] = sum_i rho^i rows[i][j] (n scalars at out_ptr); VmpcError E_RANGE above the library's caps"""
+        rb = ctypes.create_string_buffer(scalar_to_bytes(rho), 32)
+        _check(self.lib.vmpc_fr_rows_combine_dev(self.handle, ctypes.c_void_p(rows_ptr), s, n, row_stride, rb,
+                                                 ctypes.c_void_p(out_ptr)), "vmpc_fr_rows_combine_dev")
+
+    def fr_rows_dot(self, rows_ptr, s, n, row_stride, x_ptr, out_ptr, want_first=True):
+        """out[i] = <rows[i], x> (s scalars at out_ptr); returns the smallest i with out[i] != 0 or None (want_first)"""
+        first = self.alloc(4) if want_first else None
+        _check(self.lib.vmpc_fr_rows_dot_dev(self.handle, ctypes.c_void_p(rows_ptr), s, n, row_stride,
+                                             ctypes.c_void_p(x_ptr), ctypes.c_void_p(out_ptr),
+                                             ctypes.c_void_p(first.ptr) if first else None), "vmpc_fr_rows_dot_dev")
+        if first is None:
+            return None
+        v = int(self.download(first.ptr, 4).view(np.uint32)[0])
         return None if v == 0xFFFFFFFF else v
 
     def _format(self, fn, name, src_ptr, n, per_item_cap, *extra):

@@ -245,6 +245,10 @@ VMPC_HD F f256_inv(const F &a) {
 // of the schoolbook product runs its carry chain through lo[i .. i+7] and drops the carry that leaves the row into
 // hi[i], a 64-bit counter, instead of rippling it to the top - so no limb above the row is touched and nothing is
 // lost: after m products every hi[i] is below m 2^32, i.e. m < 2^32 products never overflow, whatever the field.
+// F256_ACC_MAX_PRODUCTS states that interval for the kernels that accumulate without reducing: a product adds at most
+// 2^32 - 1 (a row's outgoing carry) to a 64-bit counter, and 2^32 (2^32 - 1) < 2^64.
+#define F256_ACC_MAX_PRODUCTS ((uint64_t)1 << 32)
+static_assert(F256_ACC_MAX_PRODUCTS <= UINT64_MAX / 0xFFFFFFFFull, "f256_acc: a carry counter could wrap");
 struct f256_acc {
     uint32_t lo[16];
     uint64_t hi[8];

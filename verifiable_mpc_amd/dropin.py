@@ -20,7 +20,7 @@ to create_generators), so one process can mix groups freely.
 import functools
 import importlib
 
-from . import circuit_sat, compressed_pivot, pivot
+from . import circuit_sat, compressed_pivot, nullity, pivot
 from .groups import is_ed25519_element, is_ed25519_group
 
 _MISSING = object()
@@ -54,6 +54,18 @@ def _always(*args, **kwargs):
     return True
 
 
+# a reference caller knows nothing of `transcript=`: through the seam Pi_Nullity speaks the reference's transcript
+def _prove_nullity(generators, P, lin_forms, x, gamma, gf, transcript="reference", **kwargs):
+    return nullity.prove_nullity_compressed(generators, P, lin_forms, x, gamma, gf, transcript=transcript, **kwargs)
+
+
+def _verify_nullity(generators, P, L, lin_forms, rho, y, proof, gf, transcript="reference"):
+    return nullity.verify_nullity_compressed(generators, P, L, lin_forms, rho, y, proof, gf, transcript=transcript)
+
+
+_OPTIONAL = ("circuit_sat_cb", "nullity")     # modules a copy of the reference may lack (or that need more of MPyC)
+
+
 # (module of the reference, name, this package's function, "is this call ours?")
 _SEAM = [
     ("pivot", "vector_commitment", pivot.vector_commitment, _base_at(3, "h")),
@@ -70,6 +82,9 @@ _SEAM = [
     ("circuit_sat_r1cs", "create_generators", circuit_sat.create_generators, _select_create_generators),
     # the name `from circuit_sat_r1cs import create_generators` left in the caller's namespace
     ("circuit_sat_cb", "create_generators", circuit_sat.create_generators, _select_create_generators),
+    # Pi_Nullity (nullity.py:21-40): its callers reach it through the module object, like the pivots
+    ("nullity", "prove_nullity_compressed", _prove_nullity, _generators_at(0, "generators")),
+    ("nullity", "verify_nullity_compressed", _verify_nullity, _generators_at(0, "generators")),
 ]
 
 
@@ -106,7 +121,7 @@ def install(reference_package="verifiable_mpc.ac20"):
             try:
                 mods[modname] = importlib.import_module(f"{reference_package}.{modname}")
             except ImportError:
-                if modname == "circuit_sat_cb":       # needs more of MPyC than the path itself; optional
+                if modname in _OPTIONAL:
                     mods[modname] = None
                 else:
                     raise
