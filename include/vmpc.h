@@ -432,7 +432,8 @@ int vmpc_bn256_qap_lagrange_dev(vmpc_ctx *ctx, const void *s, size_t d, void *el
  * `items` holds n_items triples (start, end, dst) of uint32 that cover them: entries [start, end) sum to out[dst], or,
  * when bit 31 of dst is set, to partial sum (dst & 0x7fffffff) < n_partial.  `long_cols` holds n_long triples
  * (col, first, count): out[col] = the sum of partial sums first .. first + count - 1.  Rows >= n_basis add nothing;
- * destinations out of range are not written.  Deterministic (no atomics).  Uses the context arena (the partials). */
+ * destinations out of range are not written.  Deterministic (no atomics).  Uses the context arena (the partials).
+ * One implementation with vmpc_fr_cs_colsum_dev (csrc/fr_colsum.h). */
 int vmpc_bn256_qap_colsum_dev(vmpc_ctx *ctx, const void *basis, size_t n_basis, const uint32_t *rows, const void *vals,
                               size_t nnz, const uint32_t *items, size_t n_items, const uint32_t *long_cols,
                               size_t n_long, size_t n_partial, void *out, size_t n_out);
@@ -509,13 +510,14 @@ int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m,
  * circuit_builder.py:548-549); ifact: the table with at least K + 1 entries.  No inversion: exact for every c, a
  * node included (the unit vector).  Arena: 3 K scalars. */
 int vmpc_fr_cs_lagrange_dev(vmpc_ctx *ctx, const uint8_t c[32], size_t K, const void *ifact, void *out);
-/* Transposed sparse mat-vec: out is zeroed (n_out scalars), then out[col_pos[c]] = sum over the entries e of listed
- * column c of vals[e] * weights[rows[e]] (circuit_builder.py:517-545).  Entries are in column order; segment s is
- * entries [seg_ptr[s], seg_ptr[s+1]) (one lane each, so keep them short) and column c owns segments
- * [col_seg[c], col_seg[c+1]).  Rows >= n_rows add nothing, positions >= n_out are not written.  Arena: n_segs scalars. */
+/* Transposed sparse mat-vec: out is zeroed (n_out scalars), then out[dst] = sum over the entries e of a column of
+ * vals[e] * weights[rows[e]] (circuit_builder.py:517-545).  Entries in column order and the plan (items, long_cols,
+ * n_partial) as vmpc_bn256_qap_colsum_dev takes them, over this field: an item's dst is the column's position in out,
+ * so positions that no column maps to stay zero.  Rows >= n_rows add nothing, positions >= n_out are not written.
+ * n_rows <= 2^31 and the plan's bounds as there, else VMPC_E_RANGE.  Arena: n_partial scalars. */
 int vmpc_fr_cs_colsum_dev(vmpc_ctx *ctx, const void *weights, size_t n_rows, const uint32_t *rows, const void *vals,
-                          const uint32_t *seg_ptr, size_t n_segs, const uint32_t *col_seg, const uint32_t *col_pos,
-                          size_t n_cols, void *out, size_t n_out);
+                          size_t nnz, const uint32_t *items, size_t n_items, const uint32_t *long_cols, size_t n_long,
+                          size_t n_partial, void *out, size_t n_out);
 /* *first_diff (a device uint32) = the smallest i < n with a[i] != b[i], 0xffffffff if none.  No arena. */
 int vmpc_fr_cs_first_diff_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, uint32_t *first_diff);
 

@@ -90,7 +90,7 @@ def main():
                 gens = {"g": g, "h": group.generator, "k": vm.Ed25519Point.repeat(group.generator, 12345)}
                 g.precompute([gens["h"], gens["k"]], wide=N >= (1 << 19) - 1)
                 z = vm.ScalarVector.empty(N, ctx)
-                ctx.upload_into(z.ptr, cs._ints_to_array(x))
+                ctx.upload_into(z.ptr, vm.sparse.residue_array(x, group.order))
                 a, b = vm.ScalarVector.from_ints([0] * m + [5], ctx), vm.ScalarVector.from_ints([0] * m + [7], ctx)
                 levels = len(sc.level_ptr) - 1
 
@@ -123,7 +123,7 @@ def main():
                 _, zc, L, zv, gm = p8
                 y = L(zv)
                 row["pivot_prove_ms"], _ = timed(lambda: vm.compressed_pivot.protocol_5_prover(
-                    gens, zc, L, y, zv, gm, gf, transcript="compact", r=cs._masks(N, ctx), rho=12345), reps)
+                    gens, zc, L, y, zv, gm, gf, transcript="compact", r=vm.compressed_pivot.masks(N, ctx), rho=12345), reps)
                 row["p8_excl_pivot_ms"], _ = timed(lambda: cs.protocol_8_excl_pivot_prover(gens, sc, x, gf), reps)
                 proof = cs.circuit_sat_prover(gens, sc, x, gf)          # warm-up
                 row["prove_total_ms"], proof = timed(lambda: cs.circuit_sat_prover(gens, sc, x, gf), reps)

@@ -272,3 +272,73 @@ def test_hash_input_dump_streams_str_of_the_list():
         lg.removeHandler(handler)
     assert records[0].startswith("Method protocol_4_prover: Before fiat_shamir_hash, input_list=\n[[1511")
     assert len(records) > 3 and "".join(r.split("=\n", 1)[1] for r in records) == str(lst)
+
+
+@pytest.mark.parametrize("with_dst", [False, True])
+def test_colsum_plan_covers_every_entry_once(with_dst):
+    """sparse.colsum_plan (the items / long columns of csrc/fr_colsum.h): column lengths on both sides of the 64-entry
+    item and of the finish kernel's 256 lanes, in mixed order, with and without an output permutation"""
+    import numpy as np
+
+    from verifiable_mpc_amd import sparse
+    rng = np.random.default_rng(64)
+    choices = np.array([0, 1, 63, 64, 65, 128, 129, 64 * 256 + 1])
+    lens = np.concatenate([choices, rng.choice(choices[:-1], size=40)])
+    rng.shuffle(lens)
+    n_cols, col_ptr = len(lens), np.concatenate([[0], np.cumsum(lens)])
+    dst = rng.permutation(2 * n_cols)[:n_cols] if with_dst else None
+    where = dst if with_dst else np.arange(n_cols)
+    items, longs, n_partial = sparse.colsum_plan(col_ptr, dst)
+    assert items.dtype == np.uint32 and longs.dtype == np.uint32
+    items, longs = items.astype(np.int64), longs.astype(np.int64)
+    seen = np.zeros(col_ptr[-1], np.int64)
+    for s, e, _ in items:
+        assert 0 <= e - s <= sparse.SEG
+        seen[s:e] += 1
+    assert (seen == 1).all()
+    # the column of each item: a non-empty item's by where it starts; an empty one's (only without dst) is its dst
+    empty = items[:, 1] == items[:, 0]
+    col_of = np.where(empty, items[:, 2], np.searchsorted(col_ptr, items[:, 0], side="right") - 1)
+    assert not (with_dst and empty.any())
+    assert (items[:, 1] <= col_ptr[col_of + 1]).all()           # no item runs past its column
+    partial = (items[:, 2] & sparse.PARTIAL) != 0
+    long_at = {int(d): (int(f), int(c)) for d, f, c in longs}
+    assert len(long_at) == len(longs) == int((lens > sparse.SEG).sum())
+    assert n_partial == sum(c for _, c in long_at.values()) == int(partial.sum())
+    for c in range(n_cols):
+        mine = np.nonzero(col_of == c)[0]
+        if lens[c] == 0:
+            assert len(mine) == (0 if with_dst else 1)          # with dst the position is the caller's to fill
+            assert all(items[i, 0] == items[i, 1] for i in mine)
+        elif lens[c] <= sparse.SEG:
+            assert len(mine) == 1 and items[mine[0], 2] == where[c] and int(where[c]) not in long_at
+        else:
+            first, count = long_at[int(where[c])]
+            assert count == len(mine) == -(-lens[c] // sparse.SEG)
+            assert items[mine, 2].tolist() == [sparse.PARTIAL | (first + k) for k in range(count)]
+            assert np.all(np.diff(items[mine, 0]) == sparse.SEG)
+    assert sparse.colsum_plan([0])[0].shape == (0, 3)
+
+
+def test_sparse_digests_are_the_recorded_ones():
+    """SparseCircuit.digest and a sparse FormMatrix.digest feed every compact-transcript challenge: the hex values were
+    recorded before the CSR code moved to sparse.py.  The forms hold duplicates, a negative value, values >= l, an
+    explicit zero and unsorted columns; the second circuit's B comes as (nnz, 32) bytes with rows >= l, the kind that
+    values_array reduces only when it is told `canonical`."""
+    import numpy as np
+
+    from verifiable_mpc_amd import circuit_sat_gpu, nullity, sparse
+    A = ([0, 2, 4, 7], [1, 0, 0, 2, 3, 0, 3], [5, -3, 2**255 + 7, 1, ed.ELL + 2, 0, -2], [1, -1, ed.ELL])
+    B = ([0, 1, 2, 3], [0, 1, 2], np.array([1, -1, 7], np.int64))
+    O = ([0, 2], [4, 0], [1, 2 * ed.ELL - 1], [9])
+    sc = circuit_sat_gpu.SparseCircuit(2, A, B, O)
+    assert sc.digest.hex() == "6d388fe1c16150859c6d5e9422259ae90806f811087233624a39136724cb99d8"
+    raw = [ed.ELL + 5, 2**256 - 1, ed.ELL - 1, 3]
+    B8 = ([0, 2, 3, 4], [0, 0, 1, 2], np.frombuffer(b"".join(v.to_bytes(32, "little") for v in raw), np.uint8).reshape(-1, 32))
+    sc8 = circuit_sat_gpu.SparseCircuit(2, A, B8, O)
+    assert sc8.digest.hex() == "c1e05838e7fe4cf74e90e1d3a998ef8d49b9d59b5f61a3e2e9d957fdda6b542a"
+    fm = nullity.FormMatrix.__new__(nullity.FormMatrix)         # from_csr also uploads the matrix: not without a GPU
+    fm.sparse = sparse.CanonicalCSR(([0, 3, 3, 5], [4, 0, 4, 2, 1], [1, -1, ed.ELL - 1, 0, 2**256 - 1]), 6, ed.ELL,
+                                    "SparseCircuit: FormMatrix")
+    fm.n, fm.s, fm._digest = 6, fm.sparse.n_rows, None
+    assert fm.digest.hex() == "8f07f25a617bc5fdab77e22d5ebf43a9cf4d1bc28f13a1edbfbf2ffc5df38f3a"

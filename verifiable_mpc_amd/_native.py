@@ -172,7 +172,7 @@ def load_library():
         "vmpc_fr_cs_tables_dev": (i32, [vp, sz, vp, vp]),
         "vmpc_fr_cs_extend_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
         "vmpc_fr_cs_lagrange_dev": (i32, [vp, vp, sz, vp, vp]),
-        "vmpc_fr_cs_colsum_dev": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, sz]),
+        "vmpc_fr_cs_colsum_dev": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_fr_cs_first_diff_dev": (i32, [vp, vp, vp, sz, vp]),
         "vmpc_fr_rows_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp]),
         "vmpc_fr_rows_dot_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
@@ -820,12 +820,17 @@ class Context:
         _check(self.lib.vmpc_fr_cs_lagrange_dev(self.handle, cb, K, ctypes.c_void_p(ifact_ptr), ctypes.c_void_p(out_ptr)),
                "vmpc_fr_cs_lagrange_dev")
 
-    def cs_colsum(self, weights_ptr, n_rows, rows_ptr, vals_ptr, seg_ptr, n_segs, col_seg_ptr, col_pos_ptr, n_cols,
-                  out_ptr, n_out):
+    def _colsum(self, entry, weights_ptr, n_rows, rows_ptr, vals_ptr, nnz, items_ptr, n_items, long_ptr, n_long, n_partial,
+                out_ptr, n_out):
+        """a column-sum plan (sparse.colsum_plan, csrc/fr_colsum.h) through the entry point of one of the two fields"""
         p = ctypes.c_void_p
-        _check(self.lib.vmpc_fr_cs_colsum_dev(self.handle, p(weights_ptr), n_rows, p(rows_ptr), p(vals_ptr), p(seg_ptr),
-                                              n_segs, p(col_seg_ptr), p(col_pos_ptr), n_cols, p(out_ptr), n_out),
-               "vmpc_fr_cs_colsum_dev")
+        _check(getattr(self.lib, entry)(self.handle, p(weights_ptr), n_rows, p(rows_ptr), p(vals_ptr), nnz, p(items_ptr),
+                                        n_items, p(long_ptr), n_long, n_partial, p(out_ptr), n_out), entry)
+
+    def cs_colsum(self, *plan):
+        """out zeroed, then out[dst] = sum of vals[e] * weights[rows[e]] over a column's entries, mod l (include/vmpc.h);
+        plan: the arguments of _colsum after `entry`"""
+        self._colsum("vmpc_fr_cs_colsum_dev", *plan)
 
     def cs_first_diff(self, a_ptr, b_ptr, n):
         """the smallest i with a[i] != b[i], or None"""
@@ -928,14 +933,10 @@ class Context:
         _check(self.lib.vmpc_bn256_qap_lagrange_dev(self.handle, ctypes.c_void_p(s_ptr), d, ctypes.c_void_p(ell_ptr),
                                                     ctypes.c_void_p(t_ptr)), "vmpc_bn256_qap_lagrange_dev")
 
-    def bn256_qap_colsum(self, basis_ptr, n_basis, rows_ptr, vals_ptr, nnz, items_ptr, n_items, long_ptr, n_long,
-                         n_partial, out_ptr, n_out):
-        """out[col] = sum of vals[e] * basis[rows[e]] over a column's entries (include/vmpc.h)"""
-        _check(self.lib.vmpc_bn256_qap_colsum_dev(self.handle, ctypes.c_void_p(basis_ptr), n_basis,
-                                                  ctypes.c_void_p(rows_ptr), ctypes.c_void_p(vals_ptr), nnz,
-                                                  ctypes.c_void_p(items_ptr), n_items, ctypes.c_void_p(long_ptr),
-                                                  n_long, n_partial, ctypes.c_void_p(out_ptr), n_out),
-               "vmpc_bn256_qap_colsum_dev")
+    def bn256_qap_colsum(self, *plan):
+        """out[col] = sum of vals[e] * basis[rows[e]] over a column's entries, mod n (include/vmpc.h); plan: the
+        arguments of _colsum after `entry`"""
+        self._colsum("vmpc_bn256_qap_colsum_dev", *plan)
 
     def bn256_keygen_exps(self, coef_ptr, vwy_ptr, n_wires, t_ptr, idx_ptr, n_idx, out_ptr):
         """the seven exponent vectors (n_idx + 3 scalars each) of the evaluation key's per-wire entries"""

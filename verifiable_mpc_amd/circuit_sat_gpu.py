@@ -22,140 +22,13 @@ from random import SystemRandom
 
 import numpy as np
 
-from . import compressed_pivot, pivot, wire
+from . import compressed_pivot, pivot, sparse, wire
 from .device import ScalarVector, get_context
 from .groups import ORDER
 
 prng = SystemRandom()
 
 TRANSCRIPT = "compact"
-SEG = 64                     # entries per lane of the column sums (long columns are cut)
-
-_ORDER_WORDS = np.array([(ORDER >> (32 * k)) & 0xFFFFFFFF for k in range(8)], dtype=np.int64)
-
-
-def _ints_to_array(vals):
-    return np.frombuffer(b"".join((int(v) % ORDER).to_bytes(32, "little") for v in vals), np.uint8).reshape(-1, 32).copy() \
-        if len(vals) else np.zeros((0, 32), np.uint8)
-
-
-def _values_array(vals):
-    """coefficients -> (nnz, 32) uint8 canonical residues mod l: ints of any sign or size, an integer numpy array, or a
-    (nnz, 32) uint8 array of 256-bit little-endian values (the conventions of pynocchio._values_array, this field)"""
-    if isinstance(vals, np.ndarray) and vals.dtype == np.uint8 and vals.ndim == 2:
-        a = np.ascontiguousarray(vals).copy()
-        big = np.nonzero(a[:, 31] >= 0x10)[0]          # only these can be >= l
-        for i in big.tolist():
-            a[i] = np.frombuffer((int.from_bytes(a[i].tobytes(), "little") % ORDER).to_bytes(32, "little"), np.uint8)
-        return a
-    if isinstance(vals, np.ndarray) and vals.dtype.kind in "iu" and vals.ndim == 1 and vals.dtype.itemsize <= 8:
-        a = vals.astype(np.int64) if vals.dtype.kind == "i" else vals.astype(np.uint64)
-        neg = a < 0 if a.dtype.kind == "i" else np.zeros(len(a), bool)
-        mag = np.where(neg, -a, a).astype(np.uint64)
-        words = np.zeros((len(a), 8), np.int64)
-        words[:, 0] = (mag & np.uint64(0xFFFFFFFF)).astype(np.int64)
-        words[:, 1] = (mag >> np.uint64(32)).astype(np.int64)
-        if neg.any():
-            borrow = np.zeros(int(neg.sum()), np.int64)
-            sub = words[neg]
-            for k in range(8):
-                dk = _ORDER_WORDS[k] - sub[:, k] - borrow
-                borrow = (dk < 0).astype(np.int64)
-                sub[:, k] = dk + (borrow << 32)
-            words[neg] = sub
-        return np.ascontiguousarray(words.astype("<u4")).view(np.uint8).reshape(-1, 32)
-    return _ints_to_array(list(vals))
-
-
-class _Matrix:
-    """affine forms as canonical CSR: entries sorted by (row, col), duplicates added, zeros dropped"""
-
-    def __init__(self, M, n_cols, what):
-        if len(M) == 4:
-            row_ptr, col, vals, consts = M
-        else:
-            (row_ptr, col, vals), consts = M, None
-        row_ptr = np.asarray(row_ptr, np.int64)
-        col = np.asarray(col, np.int64)
-        n_rows = len(row_ptr) - 1
-        if n_rows < 0 or row_ptr[0] != 0 or np.any(np.diff(row_ptr) < 0) or row_ptr[-1] != len(col):
-            raise ValueError(f"SparseCircuit: {what}: row_ptr must rise from 0 to the number of entries")
-        v = _values_array(vals)
-        if len(v) != len(col):
-            raise ValueError(f"SparseCircuit: {what}: one value per entry")
-        if len(col) and (col.min() < 0 or col.max() >= n_cols):
-            raise ValueError(f"SparseCircuit: {what}: column index out of range")
-        rows = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(row_ptr))
-        key = rows * max(n_cols, 1) + col
-        order = np.argsort(key, kind="stable")
-        key, rows, col, v = key[order], rows[order], col[order], v[order]
-        dup = np.nonzero(key[1:] == key[:-1])[0]
-        if len(dup):
-            keep = np.ones(len(key), bool)
-            for i in dup.tolist():          # entry i + 1 repeats entry i: add it into the first of its run
-                first = i
-                while not keep[first]:
-                    first -= 1
-                s = int.from_bytes(v[first].tobytes(), "little") + int.from_bytes(v[i + 1].tobytes(), "little")
-                v[first] = np.frombuffer((s % ORDER).to_bytes(32, "little"), np.uint8)
-                keep[i + 1] = False
-            rows, col, v = rows[keep], col[keep], v[keep]
-        nz = v.any(axis=1) if len(v) else np.zeros(0, bool)
-        rows, col, v = rows[nz], col[nz], v[nz]
-        self.n_rows, self.n_cols = n_rows, n_cols
-        self.rows, self.col, self.vals = rows, col, np.ascontiguousarray(v)
-        self.row_ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n_rows))]).astype(np.int64) \
-            if n_rows else np.zeros(1, np.int64)
-        self.consts = _values_array(consts) if consts is not None else np.zeros((n_rows, 32), np.uint8)
-        if len(self.consts) != n_rows:
-            raise ValueError(f"SparseCircuit: {what}: one constant per row")
-
-    def canonical_bytes(self):
-        return b"".join([self.n_rows.to_bytes(8, "little"), len(self.col).to_bytes(8, "little"),
-                         self.row_ptr.astype("<u8").tobytes(), self.col.astype("<u8").tobytes(), self.vals.tobytes(),
-                         self.consts.tobytes()])
-
-    def const_ints(self):
-        raw = self.consts.tobytes()
-        return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
-
-
-class _DeviceMatrix:
-    """a _Matrix in HBM: CSR for the row evaluation, column order with its segment plan for the transposed product"""
-
-    def __init__(self, ctx, M):
-        self.ctx, self.n_rows, self.nnz = ctx, M.n_rows, len(M.col)
-        self.row_ptr = ctx.upload(M.row_ptr.astype(np.uint32))
-        self.col = ctx.upload(M.col.astype(np.uint32)) if self.nnz else ctx.alloc(4)
-        self.vals = ctx.upload(M.vals) if self.nnz else ctx.alloc(32)
-        self.consts = ScalarVector.from_array(M.consts, ctx) if M.n_rows else ScalarVector.empty(0, ctx)
-        order = np.argsort(M.col, kind="stable")                 # by column, rows ascending inside a column
-        counts = np.bincount(M.col, minlength=M.n_cols) if self.nnz else np.zeros(M.n_cols, np.int64)
-        self.listed = np.nonzero(counts)[0]
-        col_start = (np.cumsum(counts) - counts)[self.listed]
-        nsegs = (counts[self.listed] + SEG - 1) // SEG
-        col_seg = np.concatenate([[0], np.cumsum(nsegs)]).astype(np.int64)
-        self.n_segs = int(col_seg[-1])
-        seg_col = np.repeat(np.arange(len(self.listed)), nsegs)
-        k = np.arange(self.n_segs) - np.repeat(col_seg[:-1], nsegs)
-        seg_ptr = np.concatenate([col_start[seg_col] + SEG * k, [self.nnz]])
-        self.c_rows = ctx.upload(M.rows[order].astype(np.uint32)) if self.nnz else ctx.alloc(4)
-        self.c_vals = ctx.upload(np.ascontiguousarray(M.vals[order])) if self.nnz else ctx.alloc(32)
-        self.seg_ptr = ctx.upload(seg_ptr.astype(np.uint32))
-        self.col_seg = ctx.upload(col_seg.astype(np.uint32))
-        self._pos = {}
-
-    def csr(self):
-        return (self.row_ptr.ptr, self.col.ptr, self.vals.ptr, self.consts.ptr)
-
-    def weighted_columns(self, weights_ptr, n_x, n_in, out_ptr, n_out):
-        """out (n_out scalars over z) = sum_i weights[i] row_i, column c at z position c (c < n_x) or n_in + 3 + c - n_x"""
-        key = (n_x, n_in)
-        if key not in self._pos:
-            pos = np.where(self.listed < n_x, self.listed, self.listed - n_x + n_in + 3)
-            self._pos = {key: self.ctx.upload(pos.astype(np.uint32)) if len(pos) else self.ctx.alloc(4)}
-        self.ctx.cs_colsum(weights_ptr, self.n_rows, self.c_rows.ptr, self.c_vals.ptr, self.seg_ptr.ptr, self.n_segs,
-                           self.col_seg.ptr, self._pos[key].ptr, len(self.listed), out_ptr, n_out)
 
 
 class SparseCircuit:
@@ -171,11 +44,11 @@ class SparseCircuit:
     def __init__(self, n_x, A, B, O=None, text=None):
         self.n_x = int(n_x)
         m = len(A[0]) - 1
-        self.A = _Matrix(A, self.n_x + m, "A")
-        self.B = _Matrix(B, self.n_x + m, "B")
+        self.A = sparse.CanonicalCSR(A, self.n_x + m, ORDER, "SparseCircuit: A")
+        self.B = sparse.CanonicalCSR(B, self.n_x + m, ORDER, "SparseCircuit: B")
         if self.B.n_rows != m:
             raise ValueError("SparseCircuit: A and B must have one row per multiplication gate each")
-        self.O = _Matrix(O if O is not None else ([0], [], [], []), self.n_x + m, "O")
+        self.O = sparse.CanonicalCSR(O if O is not None else ([0], [], [], []), self.n_x + m, ORDER, "SparseCircuit: O")
         self.m, self.n_out = m, self.O.n_rows
         for M, what in ((self.A, "A"), (self.B, "B")):
             bad = np.nonzero(M.col >= self.n_x + M.rows)[0]
@@ -310,8 +183,8 @@ class SparseCircuit:
     def device(self):
         if self._dev is None:
             ctx = get_context()
-            d = {"ctx": ctx, "A": _DeviceMatrix(ctx, self.A), "B": _DeviceMatrix(ctx, self.B),
-                 "O": _DeviceMatrix(ctx, self.O), "order": ctx.upload(self.level_order) if self.m else ctx.alloc(4)}
+            d = {"ctx": ctx, "A": sparse.DeviceMatrix(ctx, self.A), "B": sparse.DeviceMatrix(ctx, self.B),
+                 "O": sparse.DeviceMatrix(ctx, self.O), "order": ctx.upload(self.level_order) if self.m else ctx.alloc(4)}
             K = 2 * self.m + 1
             d["fact"], d["ifact"] = ScalarVector.empty(K + 1, ctx), ScalarVector.empty(K + 1, ctx)
             ctx.cs_tables(K, d["fact"].ptr, d["ifact"].ptr)
@@ -325,10 +198,7 @@ def as_sparse(circuit):
 
 # ---- transcript ------------------------------------------------------------------------------------------------------------
 def _mode(transcript):
-    mode = transcript or TRANSCRIPT
-    if mode not in ("compact", "reference"):
-        raise ValueError(f"unknown transcript mode {mode!r}")
-    return mode
+    return compressed_pivot.transcript_mode(transcript, TRANSCRIPT)
 
 
 def _first_digest(z_commitment, circuit, n_in):
@@ -405,18 +275,18 @@ def _witness_on_device(circuit, x, order, gamma_witness=None):
     ctx = d["ctx"]
     N = n_in + 3 + 2 * m
     z = ScalarVector.empty(N, ctx)
-    ctx.upload_into(z.ptr, _ints_to_array([pivot._residue(v) for v in x]))
+    ctx.upload_into(z.ptr, sparse.residue_array([pivot._residue(v) for v in x], ORDER))
     r_a = prng.randrange(1, order)
     r_b = prng.randrange(1, order)
     a, b = ScalarVector.empty(m + 1, ctx), ScalarVector.empty(m + 1, ctx)
-    ctx.upload_into(a.ptr + 32 * m, _ints_to_array([r_a]))
-    ctx.upload_into(b.ptr + 32 * m, _ints_to_array([r_b]))
+    ctx.upload_into(a.ptr + 32 * m, sparse.residue_array([r_a], ORDER))
+    ctx.upload_into(b.ptr + 32 * m, sparse.residue_array([r_b], ORDER))
     g_off = n_in + 3
     if gamma_witness is not None:
         if len(gamma_witness) != m:
             raise ValueError(f"gamma_witness: {m} gate outputs expected")
         if m:
-            ctx.upload_into(z.ptr + 32 * g_off, _ints_to_array([pivot._residue(v) for v in gamma_witness]))
+            ctx.upload_into(z.ptr + 32 * g_off, sparse.residue_array([pivot._residue(v) for v in gamma_witness], ORDER))
             bad = ctx.alloc(4)
             ctx.cs_triples(d["A"].csr(), d["B"].csr(), None, m, n_x, g_off, z.ptr, a.ptr, b.ptr, 1, bad.ptr)
             first = int(ctx.download(bad.ptr, 4).view(np.uint32)[0])
@@ -615,19 +485,6 @@ def protocol_8_excl_pivot_verifier(proof, circuit, gf, use_koe=False, transcript
     return verification, L
 
 
-# Protocol 5 draws its N masks one by one from SystemRandom when it is not handed any: 0.8 s of Python at N = 2^19.
-# From this length on the masks are 252 uniform bits each from os.urandom, uploaded as one array: every value is below
-# l = 2^252 + 2^124.7, and the distance from uniform on [0, l) is 2^-127 per mask.
-MASKS_ON_DEVICE_MIN = 1 << 12
-
-
-def _masks(n, ctx):
-    import os
-    raw = np.frombuffer(os.urandom(32 * n), np.uint8).reshape(n, 32).copy()
-    raw[:, 31] &= 0x0f
-    return ScalarVector.from_array(raw, ctx)
-
-
 def _choice(pivot_choice):
     return getattr(pivot_choice, "name", pivot_choice)
 
@@ -645,7 +502,8 @@ def circuit_sat_prover(generators, circuit, x, gf, pivot_choice="compressed", ga
                                                                     gamma_witness=gamma_witness, transcript=mode)
     y = L(z)
     if choice == "compressed":
-        r = _masks(len(z), L.coeffs.ctx) if isinstance(z, ScalarVector) and len(z) >= MASKS_ON_DEVICE_MIN else None
+        r = compressed_pivot.masks(len(z), L.coeffs.ctx) if isinstance(z, ScalarVector) and \
+            len(z) >= compressed_pivot.MASKS_ON_DEVICE_MIN else None
         proof["pivot_proof"] = compressed_pivot.protocol_5_prover(generators, z_commitment, L, y, z, gamma, gf,
                                                                   transcript=mode, r=r)
     else:

@@ -25,6 +25,8 @@ import logging
 import os
 from random import SystemRandom
 
+import numpy as np
+
 from . import _native, pivot
 from .device import PointVector, ScalarVector, reduce_scalar
 from .groups import EllipticCurvePoint as EllipticCurveElement
@@ -121,7 +123,6 @@ class _GroupCheck:
 def _valid_group_elements_begin(points):
     """_valid_group_elements with the 253-step ladder (0.9 ms of single-lane latency for the 40 points of a
     2^20 proof) left running on a side stream: the caller goes on and joins the verdict before it accepts."""
-    import numpy as np
     from .device import get_aux_context
     from .groups import ORDER
     try:
@@ -246,13 +247,19 @@ def _challenge(digest, order):
     return int.from_bytes(digest, "little") % order
 
 
+def transcript_mode(transcript, default=None):
+    """`transcript`, or `default` where it is None: "reference" or "compact", anything else is a ValueError"""
+    mode = transcript or default
+    if mode not in ("reference", "compact"):
+        raise ValueError(f"unknown transcript mode {mode!r}")
+    return mode
+
+
 class _Transcript:
     """Challenge source for Protocol 4: reference text hashing or the compact chain."""
 
     def __init__(self, mode, order, state=None):
-        if mode not in ("reference", "compact"):
-            raise ValueError(f"unknown transcript mode {mode!r}")
-        self.mode, self.order, self.state = mode, order, state
+        self.mode, self.order, self.state = transcript_mode(mode), order, state
 
     def round_challenge(self, round_i, A, B, g_hat, k, Q, L_tilde, who="protocol_4_prover"):
         if self.mode == "reference":
@@ -819,6 +826,19 @@ def _extend_form(L, c1):
     if isinstance(L.coeffs, ScalarVector):
         return pivot.LinearForm(L.coeffs.axpy_concat(c1, None, 0))
     return pivot.LinearForm(L.coeffs + [0]) * c1
+
+
+# Protocol 5 draws its N masks one by one from SystemRandom when it is not handed any: 0.8 s of Python at N = 2^19.
+# From this length on its device callers (Protocol 8, Pi_Nullity) hand it masks of 252 uniform bits each from
+# os.urandom, uploaded as one array: every value is below l = 2^252 + 2^124.7, and the distance from uniform on [0, l)
+# is 2^-127 per mask.
+MASKS_ON_DEVICE_MIN = 1 << 12
+
+
+def masks(n, ctx):
+    raw = np.frombuffer(os.urandom(32 * n), np.uint8).reshape(n, 32).copy()
+    raw[:, 31] &= 0x0f
+    return ScalarVector.from_array(raw, ctx)
 
 
 def protocol_5_prover(generators, P, L, y, x, gamma, gf, transcript=None, r=None, rho=None):

@@ -13,19 +13,16 @@
 //                                 csrc/fr_scan.h with runs of KG_RUN elements, and a last kernel combines.
 //   vmpc_bn256_qap_colsum_dev     out[c] = sum_e vals[e] basis[rows[e]] over the entries of column c: v_i(s), w_i(s),
 //                                 y_i(s) of a sparse R1CS (basis = l(s)) or of a dense QAP (basis = 1, s, .., s^d, rows
-//                                 = coefficient degrees).  The host cuts the column-ordered entries into items of at most
-//                                 KG_PIECE entries; one lane sums an item (unreduced products in frbn_acc, one
-//                                 reduction) and writes the column's value, or, for a column of several items, a
-//                                 partial sum that a second kernel adds up (one workgroup per long column, a fixed
-//                                 tree): deterministic, no atomics.
+//                                 = coefficient degrees).  The plan and the kernels are csrc/fr_colsum.h, shared with
+//                                 vmpc_fr_cs_colsum_dev: deterministic, no atomics.
 //   vmpc_bn256_keygen_exps_dev    the seven exponent vectors of the evaluation key's per-wire entries plus their
 //                                 zero-knowledge tails, for the wires in idx (pynocchio.py:106-154).
 #include "common.h"
 #include "fr_bn.h"
+#include "fr_colsum.h"
 #include "fr_scan.h"
 
 #define KG_RUN 64       // sequence elements per lane in the scans
-#define KG_PARTIAL 0x80000000u
 
 // sequence q (csrc/fr_scan.h), element k (0 <= k < d): s - (k+1), s - (d-k), d - k; s is in device memory
 struct kg_seq {
@@ -93,76 +90,15 @@ extern "C" int vmpc_bn256_qap_lagrange_dev(vmpc_ctx *ctx, const void *s, size_t 
     return VMPC_OK;
 }
 
-// one lane per item (start, end, dst): dst < n_out -> out[dst]; dst = KG_PARTIAL | p -> part[p].  Entries whose row
-// is not below n_basis, items that leave [0, nnz) and destinations out of range add / write nothing.
-__global__ void __launch_bounds__(256)
-k_kg_colsum(const uint32_t *__restrict__ basis, uint32_t n_basis, const uint32_t *__restrict__ rows,
-            const uint32_t *__restrict__ vals, uint64_t nnz, const uint32_t *__restrict__ items, uint64_t n_items,
-            uint32_t *__restrict__ part, uint64_t n_partial, uint32_t *__restrict__ out, uint64_t n_out) {
-    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_items) return;
-    const uint32_t e0 = items[3 * k], e1 = items[3 * k + 1], dst = items[3 * k + 2];
-    frbn_acc acc = frbn_acc_zero();
-    for (uint64_t e = e0; e < e1 && e < nnz; e++) {
-        const uint32_t r = rows[e];
-        if (r >= n_basis) continue;
-        const frbn a = f256_ld<frbn>(vals, (long long)e), b = f256_ld<frbn>(basis, r);
-        frbn_acc_mac(acc, a.v, b.v);
-    }
-    const frbn v = frbn_acc_reduce(acc);
-    if (dst & KG_PARTIAL) {
-        if ((dst & ~KG_PARTIAL) < n_partial) f256_st(part, dst & ~KG_PARTIAL, v);
-    } else if (dst < n_out) {
-        f256_st(out, dst, v);
-    }
-}
-
-// one workgroup per long column (col, first, count): out[col] = sum of part[first .. first + count), fixed order
-__global__ void __launch_bounds__(256)
-k_kg_colfinish(const uint32_t *__restrict__ longs, const uint32_t *__restrict__ part, uint64_t n_partial,
-               uint32_t *__restrict__ out, uint64_t n_out) {
-    __shared__ frbn red[256];
-    const int t = threadIdx.x;
-    const uint32_t col = longs[3 * blockIdx.x], first = longs[3 * blockIdx.x + 1], count = longs[3 * blockIdx.x + 2];
-    frbn s = frbn_zero();
-    for (uint64_t i = t; i < count; i += 256)
-        if ((uint64_t)first + i < n_partial) s = frbn_add(s, f256_ld<frbn>(part, (long long)(first + i)));
-    red[t] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (t < h) red[t] = frbn_add(red[t], red[t + h]);
-        __syncthreads();
-    }
-    if (t == 0 && col < n_out) f256_st(out, col, red[0]);
-}
-
 extern "C" int vmpc_bn256_qap_colsum_dev(vmpc_ctx *ctx, const void *basis, size_t n_basis, const uint32_t *rows,
                                          const void *vals, size_t nnz, const uint32_t *items, size_t n_items,
                                          const uint32_t *long_cols, size_t n_long, size_t n_partial, void *out,
                                          size_t n_out) {
-    if (n_basis > VMPC_BN256_QAP_MAX_D + 1 || nnz > 0xFFFFFFFFull || n_partial > 0x7FFFFFFFull ||
-        n_out > 0x7FFFFFFFull || n_long > 0x7FFFFFFFull || n_items > 0xFFFFFFFFull)
-        return VMPC_E_RANGE;
-    if (!ctx || !out || (n_basis && !basis) || (nnz && (!rows || !vals)) || (n_items && !items) ||
-        (n_long && !long_cols))
-        return VMPC_E_INVAL;
-    if (n_items == 0) return VMPC_OK;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    uint32_t *part = nullptr;
-    if (n_partial) {
-        VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(n_partial * 32) + 256));
-        part = (uint32_t *)vmpc_ws_take(ctx, n_partial * 32);
-    }
-    vmpc_stage_scope sc(ctx, "bn_qap_colsum");
-    k_kg_colsum<<<(unsigned)((n_items + 255) / 256), 256, 0, ctx->stream>>>(
-        (const uint32_t *)basis, (uint32_t)n_basis, rows, (const uint32_t *)vals, nnz, items, n_items, part, n_partial,
-        (uint32_t *)out, n_out);
-    VMPC_KERNEL_CHECK();
-    if (n_long) {
-        k_kg_colfinish<<<(unsigned)n_long, 256, 0, ctx->stream>>>(long_cols, part, n_partial, (uint32_t *)out, n_out);
-        VMPC_KERNEL_CHECK();
-    }
-    return VMPC_OK;
+    VMPC_CHECK(fr_colsum_check(ctx, basis, n_basis, VMPC_BN256_QAP_MAX_D + 1, rows, vals, nnz, items, n_items, long_cols,
+                               n_long, n_partial, out, n_out));
+    if (!out) return VMPC_E_INVAL;
+    return fr_colsum<frbn>(ctx, "bn_qap_colsum", false, basis, n_basis, rows, vals, nnz, items, n_items, long_cols, n_long,
+                           n_partial, out, n_out);
 }
 
 // Row r < n_idx, wire i = idx[r], X_i = (v_i, w_i, y_i)(s) read from vwy (v at 0, w at n_wires, y at 2 n_wires); coef =

@@ -7,23 +7,15 @@
 //   k_frbn_powers    scale * z^(i+1): the exponents of the trusted setup (knowledge_of_exponent.py:52-66 reaches them by
 //                    2n sequential scalar multiplications of a point).
 //
-// Product kernel shape: output-stationary.  A workgroup owns a tile of KOE_TILE consecutive output coefficients, one
-// per lane, and one SEGMENT of the index i of a: out[k] += a[i] b[k - i] for i in the segment.  Chunks of KOE_CHUNK
-// coefficients of a and the KOE_CHUNK + KOE_TILE - 1 coefficients of b that the tile meets them with are staged in
-// LDS, reduced mod n on the way in and zero where the index leaves the vector, so the inner loop has no bounds.  b is
-// stored limb-major (lane t reads word t + const of a limb row: consecutive banks), a element-major (every lane reads
-// the same element: a broadcast).  A lane adds unreduced 8 x 8-limb products into frbn_acc and reduces once.
-// The triangle (tiles near k = n meet the whole of a, tiles at the ends almost nothing) is balanced by the segments:
-// a tile is cut into as many workgroups as its i-range has segments, so every workgroup does about the same work;
-// their partial sums (reduced mod n) go to the context arena and k_frbn_polysum adds them.  A product whose tiles all
-// fit one segment is written straight to `out`.
+// Product kernel: the output-stationary tile of csrc/fr_conv.h over one SEGMENT of the index i of a.  The triangle
+// (tiles near k = n meet the whole of a, tiles at the ends almost nothing) is balanced by the segments: a tile is cut
+// into as many workgroups as its i-range has segments; their partial sums (reduced mod n) go to the context arena and
+// k_frbn_polysum adds them.  A product whose tiles all fit one segment is written straight to `out`.
 #include "common.h"
 #include "fr_bn.h"
+#include "fr_conv.h"
 
-#define KOE_TILE 256
-#define KOE_CHUNK 64
-#define KOE_BROW (KOE_CHUNK + KOE_TILE)   // words per limb row of the staged b (KOE_CHUNK + KOE_TILE - 1 used)
-#define KOE_MIN_SEG 256                   // shortest segment; a multiple of KOE_CHUNK
+#define KOE_MIN_SEG 256                   // shortest segment; a multiple of FR_CONV_CHUNK
 #define KOE_TARGET_WGS (1 << 12)          // full-size workgroups a large product is cut into
 
 // [first, last] of the i that tile k0 meets, and how many segments of length seg that range touches
@@ -34,53 +26,31 @@ struct koe_span {
 __host__ __device__ static inline koe_span koe_tile_span(long long k0, long long na, long long nb, long long seg) {
     koe_span s;
     s.lo = k0 - (nb - 1) > 0 ? k0 - (nb - 1) : 0;
-    s.hi = k0 + KOE_TILE - 1 < na - 1 ? k0 + KOE_TILE - 1 : na - 1;
+    s.hi = k0 + FR_CONV_TILE - 1 < na - 1 ? k0 + FR_CONV_TILE - 1 : na - 1;
     s.first_seg = (unsigned)(s.lo / seg);
     s.n_seg = (unsigned)(s.hi / seg) - s.first_seg + 1;
     return s;
 }
 
 // grid (tiles, most segments of a tile); dst row y holds the partial sums of every tile's y-th segment
-__global__ void __launch_bounds__(KOE_TILE)
+__global__ void __launch_bounds__(FR_CONV_TILE)
 k_frbn_polymul(const uint32_t *__restrict__ a, long long na, const uint32_t *__restrict__ b, long long nb,
                long long seg, uint32_t *__restrict__ dst) {
-    __shared__ uint32_t sA[KOE_CHUNK * 8];
-    __shared__ uint32_t sB[8 * KOE_BROW];
-    const int t = threadIdx.x;
+    __shared__ uint32_t sA[1][FR_CONV_CHUNK * 8];
+    __shared__ uint32_t sB[8 * FR_CONV_BROW];
     const long long n_out = na + nb - 1;
-    const long long k0 = (long long)blockIdx.x * KOE_TILE;
+    const long long k0 = (long long)blockIdx.x * FR_CONV_TILE;
     const koe_span span = koe_tile_span(k0, na, nb, seg);
     if (blockIdx.y >= span.n_seg) return;      // (uniform) this tile has fewer segments
     const long long seg_lo = (long long)(span.first_seg + blockIdx.y) * seg;
-    frbn_acc acc = frbn_acc_zero();
-    for (long long i0 = seg_lo; i0 < seg_lo + seg; i0 += KOE_CHUNK) {
-        if (i0 + KOE_CHUNK <= span.lo || i0 > span.hi) continue;   // (uniform)
-        __syncthreads();
-        if (t < KOE_CHUNK) {
-            const frbn x = f256_ld_or_zero<frbn>(a, i0 + t, na);
-#pragma unroll
-            for (int l = 0; l < 8; l++) sA[8 * t + l] = x.v[l];
-        }
-        // sB word j of a limb row is b[k0 - i0 - (KOE_CHUNK - 1) + j]: lane t at step ii reads j = t + KOE_CHUNK - 1 - ii
-        for (int j = t; j < KOE_CHUNK + KOE_TILE - 1; j += KOE_TILE) {
-            const frbn x = f256_ld_or_zero<frbn>(b, k0 - i0 - (KOE_CHUNK - 1) + j, nb);
-#pragma unroll
-            for (int l = 0; l < 8; l++) sB[l * KOE_BROW + j] = x.v[l];
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int ii = 0; ii < KOE_CHUNK; ii++) {
-            uint32_t x[8], y[8];
-#pragma unroll
-            for (int l = 0; l < 8; l++) {
-                x[l] = sA[8 * ii + l];
-                y[l] = sB[l * KOE_BROW + t + KOE_CHUNK - 1 - ii];
-            }
-            frbn_acc_mac(acc, x, y);
-        }
+    const uint32_t *const av[1] = {a};
+    f256_acc acc[1] = {f256_acc_zero()};
+    for (long long i0 = seg_lo; i0 < seg_lo + seg; i0 += FR_CONV_CHUNK) {
+        if (i0 + FR_CONV_CHUNK <= span.lo || i0 > span.hi) continue;   // (uniform)
+        fr_conv_chunk<frbn, 1>(sA, sB, acc, av, na, b, nb, k0, i0);
     }
-    const long long k = k0 + t;
-    if (k < n_out) frbn_store(dst + 8 * ((long long)blockIdx.y * n_out + k), frbn_acc_reduce(acc));
+    const long long k = k0 + threadIdx.x;
+    if (k < n_out) frbn_store(dst + 8 * ((long long)blockIdx.y * n_out + k), frbn_acc_reduce(acc[0]));
 }
 
 __global__ void __launch_bounds__(256)
@@ -89,10 +59,8 @@ k_frbn_polysum(const uint32_t *__restrict__ part, long long na, long long nb, lo
     const long long n_out = na + nb - 1;
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_out) return;
-    const koe_span span = koe_tile_span(k / KOE_TILE * KOE_TILE, na, nb, seg);
-    frbn s = frbn_load(part + 8 * k);
-    for (unsigned y = 1; y < span.n_seg; y++) s = frbn_add(s, frbn_load(part + 8 * ((long long)y * n_out + k)));
-    frbn_store(out + 8 * k, s);
+    const koe_span span = koe_tile_span(k / FR_CONV_TILE * FR_CONV_TILE, na, nb, seg);
+    f256_st(out, k, fr_partsum<frbn>(part, n_out, span.n_seg, k));
 }
 
 // lane g writes out[8g .. 8g+7]: z^(8g+1) by square-and-multiply on the index, then seven products by z
@@ -122,13 +90,13 @@ extern "C" int vmpc_bn256_fr_poly_mul_dev(vmpc_ctx *ctx, const void *a, size_t n
     if (!ctx || !a || !b || !out || na == 0 || nb == 0) return VMPC_E_INVAL;
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const long long n_out = (long long)(na + nb - 1);
-    const unsigned tiles = (unsigned)((n_out + KOE_TILE - 1) / KOE_TILE);
+    const unsigned tiles = (unsigned)((n_out + FR_CONV_TILE - 1) / FR_CONV_TILE);
     // segment length: a power of two that cuts the na * nb products into about KOE_TARGET_WGS workgroups' worth
     long long seg = KOE_MIN_SEG;
-    while (seg * 2 * KOE_TILE * KOE_TARGET_WGS <= (long long)na * (long long)nb) seg *= 2;
+    while (seg * 2 * FR_CONV_TILE * KOE_TARGET_WGS <= (long long)na * (long long)nb) seg *= 2;
     unsigned max_segs = 1;
     for (unsigned t = 0; t < tiles; t++) {
-        const unsigned s = koe_tile_span((long long)t * KOE_TILE, (long long)na, (long long)nb, seg).n_seg;
+        const unsigned s = koe_tile_span((long long)t * FR_CONV_TILE, (long long)na, (long long)nb, seg).n_seg;
         if (s > max_segs) max_segs = s;
     }
     uint32_t *dst = (uint32_t *)out;
@@ -139,7 +107,7 @@ extern "C" int vmpc_bn256_fr_poly_mul_dev(vmpc_ctx *ctx, const void *a, size_t n
     }
     {
         vmpc_stage_scope s(ctx, "bn_fr_poly_mul");
-        k_frbn_polymul<<<dim3(tiles, max_segs), KOE_TILE, 0, ctx->stream>>>(
+        k_frbn_polymul<<<dim3(tiles, max_segs), FR_CONV_TILE, 0, ctx->stream>>>(
             (const uint32_t *)a, (long long)na, (const uint32_t *)b, (long long)nb, seg, dst);
         VMPC_KERNEL_CHECK();
     }

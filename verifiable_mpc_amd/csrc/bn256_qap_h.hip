@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "fr_bn.h"
+#include "fr_conv.h"
 #include "fr_scan.h"
 
 #define QH_WG 256
@@ -151,14 +152,12 @@ k_qh_moments(const uint32_t *__restrict__ u0, const uint32_t *__restrict__ u1, u
     }
 }
 
-// out[k] = part[0][k] + part[1][k] + .. in that order
+// out[k] = part[0][k] + part[1][k] + .. in that order (csrc/fr_conv.h)
 __global__ void __launch_bounds__(256)
 k_qh_partsum(const uint32_t *__restrict__ part, uint32_t n_out, uint32_t groups, uint32_t *__restrict__ out) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_out) return;
-    frbn s = f256_ld<frbn>(part, k);
-    for (uint32_t g = 1; g < groups; g++) s = frbn_add(s, f256_ld<frbn>(part, (long long)g * n_out + k));
-    f256_st(out, k, s);
+    f256_st(out, k, fr_partsum<frbn>(part, n_out, groups, k));
 }
 
 extern "C" int vmpc_bn256_qap_moments_dev(vmpc_ctx *ctx, const void *u0, const void *u1, size_t d, size_t n_out,

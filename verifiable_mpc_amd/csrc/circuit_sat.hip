@@ -11,54 +11,47 @@
 //   vmpc_fr_cs_tables_dev     k! and 1 / k! for k <= K: two product scans (csrc/fr_scan.h) and ONE inversion.  Everything below is
 //                             products of these: 1 / k = (k-1)! / k!, the barycentric weights
 //                             w_j = (-1)^(M-j) / ((j-1)! (M-j)!), l(x) = prod_j (x - j) = (x-1)! / (x-M-1)! for x > M.
-//   vmpc_fr_cs_extend_dev     f(x) = l(x) sum_j u_j / (x - j), u_j = v_j w_j, at x = 0 and x = m+2 .. 2m, the same
-//                             for g, h(x) = f(x) g(x) into z (circuit_sat_r1cs.py:380-388 interpolates and multiplies
+//   vmpc_fr_cs_extend_dev     f(x) = l(x) sum_j u_j / (x - j), u_j = v_j w_j, at x = 0 and x = m+2 .. 2m, the same for
+//                             g, h(x) = f(x) g(x) into z (circuit_sat_r1cs.py:380-388 interpolates and multiplies
 //                             coefficient lists, qap_creator.py:154-164; circuit_sat_cb.py:89 evaluates h 2m times).
-//                             For x > M every 1 / (x - j) is T[x - j], T[k] = 1 / k: the sums are coefficients
-//                             m+1 .. 2m-1 of the product of u (M terms) with T - THE hot kernel, k_cs_corr, m^2
-//                             multiply-accumulates for f and for g.  Shape of k_frbn_polymul (csrc/bn256_koe.hip):
-//                             output-stationary, a lane owns one x, chunks of u and the window of T it meets staged in
-//                             LDS (T limb-major, u broadcast), UNREDUCED 8 x 8-limb products added into a 16-limb
-//                             accumulator with per-row carry counters, one Barrett reduction per output and segment.
-//                             The accumulator and the element access are csrc/fr256.h, shared with that kernel.
-//                             f and g share the staged T.  Every x meets every j, so the work per tile is uniform; the
-//                             range of j is cut into segments for occupancy, their partial sums added in a fixed
-//                             order.  Integer sums only: deterministic.
+//                             For x > M every 1 / (x - j) is T[x - j], T[k] = 1 / k: the sums are coefficients m+1 ..
+//                             2m-1 of the product of u (M terms) with T - THE hot kernel, k_cs_corr, m^2
+//                             multiply-accumulates for f and for g.  The tile of csrc/fr_conv.h, shared with
+//                             k_frbn_polymul (csrc/bn256_koe.hip); f and g share the staged T.  Every x meets every j,
+//                             so the work per tile is uniform; the range of j is cut into segments for occupancy, their
+//                             partial sums added in a fixed order.  Integer sums only: deterministic.
 //   vmpc_fr_cs_lagrange_dev   the Lagrange vector of the nodes 0..K at c (ac20/recombine.py:5-32, a double loop):
 //                             lambda_j = prod_{i != j} (c - i) * (-1)^(K-j) / (j! (K-j)!) - prefix and suffix products
 //                             of (c - i), no inversion at all, so a c on a node cannot divide by zero here (the
 //                             Python caller still refuses it, as the reference does).
-//   vmpc_fr_cs_colsum_dev     out[pos[c]] = sum over the entries e of column c of vals[e] weights[rows[e]]: the
+//   vmpc_fr_cs_colsum_dev     out[dst(c)] = sum over the entries e of column c of vals[e] weights[rows[e]]: the
 //                             transposed sparse mat-vec that turns row weights (the Lagrange vector, powers of rho)
 //                             into the coefficients of the forms of f(c), g(c) and the outputs
-//                             (circuit_builder.py:517-545 builds dense forms per gate).  Columns are cut into
-//                             segments of at most 64 entries, one lane each; a second pass adds a column's partial
-//                             sums in order.  No atomics.
+//                             (circuit_builder.py:517-545 builds dense forms per gate), every other position zero.
+//                             Plan and kernels: csrc/fr_colsum.h, shared with vmpc_bn256_qap_colsum_dev.
 //   vmpc_fr_cs_first_diff_dev the smallest i with a[i] != b[i] (the verifier's L == proof["L"])
 #include "common.h"
 #include "fr.h"
+#include "fr_colsum.h"
+#include "fr_conv.h"
 #include "fr_scan.h"
 
 #define CS_WG 256
 #define CS_RUN 32                       // sequence elements per lane in the product scans
-#define CS_TILE 256                     // outputs per workgroup of k_cs_corr, one per lane
-#define CS_CHUNK 64                     // u_j staged per step
-#define CS_BROW (CS_CHUNK + CS_TILE)    // words per limb row of the staged T
-#define CS_MIN_SEG 256                  // shortest segment of j; a multiple of CS_CHUNK
+#define CS_MIN_SEG 256                  // shortest segment of j; a multiple of FR_CONV_CHUNK
 #define CS_TARGET_WGS 8192
 
 // ---- multiplication triples ---------------------------------------------------------------------------------------------
 // column c of a form reads z[c] for c < n_x (an input) and z[g_off + c - n_x] otherwise (gamma_(c - n_x))
+struct cs_z_map {
+    uint32_t n_x, g_off;
+    __device__ uint32_t operator()(uint32_t c) const { return c < n_x ? c : g_off + (c - n_x); }
+};
+
 __device__ fr cs_row_eval(const uint32_t *__restrict__ rp, const uint32_t *__restrict__ col, const uint32_t *__restrict__ val,
                           const uint32_t *__restrict__ cst, uint32_t row, uint32_t n_x, uint32_t g_off,
                           const uint32_t *__restrict__ z) {
-    f256_acc acc = f256_acc_zero();
-    for (uint32_t e = rp[row]; e < rp[row + 1]; e++) {
-        const uint32_t c = col[e];
-        const fr v = f256_ld<fr>(val, e), w = f256_ld<fr>(z, c < n_x ? c : g_off + (c - n_x));
-        f256_acc_mac(acc, v.v, w.v);
-    }
-    return fr_add(f256_acc_reduce<fr>(acc), f256_ld<fr>(cst, row));
+    return fr_add(fr_sparse_dot<fr>(col, val, rp[row], rp[row + 1], z, cs_z_map{n_x, g_off}), f256_ld<fr>(cst, row));
 }
 
 __global__ void __launch_bounds__(CS_WG)
@@ -230,51 +223,22 @@ k_cs_dot0(uint32_t M, const uint32_t *__restrict__ uf, const uint32_t *__restric
 }
 
 // grid (tiles, segments).  part_f[s n_out + o] = sum over segment s's i of uf[i] T[k_lo + o - i], o < n_out; part_g alike.
-__global__ void __launch_bounds__(CS_TILE)
+__global__ void __launch_bounds__(FR_CONV_TILE)
 k_cs_corr(const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, long long M, const uint32_t *__restrict__ T,
           long long n_t, long long k_lo, long long n_out, long long seg, uint32_t *__restrict__ part_f,
           uint32_t *__restrict__ part_g) {
-    __shared__ uint32_t sF[CS_CHUNK * 8];
-    __shared__ uint32_t sG[CS_CHUNK * 8];
-    __shared__ uint32_t sT[8 * CS_BROW];
-    const int t = threadIdx.x;
-    const long long o0 = (long long)blockIdx.x * CS_TILE, k0 = k_lo + o0;
+    __shared__ uint32_t sU[2][FR_CONV_CHUNK * 8];
+    __shared__ uint32_t sT[8 * FR_CONV_BROW];
+    const long long o0 = (long long)blockIdx.x * FR_CONV_TILE, k0 = k_lo + o0;
     const long long seg_lo = (long long)blockIdx.y * seg;
-    f256_acc accf = f256_acc_zero(), accg = f256_acc_zero();
-    for (long long i0 = seg_lo; i0 < seg_lo + seg && i0 < M; i0 += CS_CHUNK) {
-        __syncthreads();
-        if (t < CS_CHUNK) {
-            const fr x = f256_ld_or_zero<fr>(uf, i0 + t, M), y = f256_ld_or_zero<fr>(ug, i0 + t, M);
-#pragma unroll
-            for (int l = 0; l < 8; l++) {
-                sF[8 * t + l] = x.v[l];
-                sG[8 * t + l] = y.v[l];
-            }
-        }
-        // word j of a limb row is T[k0 - i0 - (CS_CHUNK - 1) + j]: lane t at step ii reads j = t + CS_CHUNK - 1 - ii
-        for (int j = t; j < CS_CHUNK + CS_TILE - 1; j += CS_TILE) {
-            const fr x = f256_ld_or_zero<fr>(T, k0 - i0 - (CS_CHUNK - 1) + j, n_t);
-#pragma unroll
-            for (int l = 0; l < 8; l++) sT[l * CS_BROW + j] = x.v[l];
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int ii = 0; ii < CS_CHUNK; ii++) {
-            uint32_t xf[8], xg[8], y[8];
-#pragma unroll
-            for (int l = 0; l < 8; l++) {
-                xf[l] = sF[8 * ii + l];
-                xg[l] = sG[8 * ii + l];
-                y[l] = sT[l * CS_BROW + t + CS_CHUNK - 1 - ii];
-            }
-            f256_acc_mac(accf, xf, y);
-            f256_acc_mac(accg, xg, y);
-        }
-    }
-    const long long o = o0 + t;
+    const uint32_t *const u[2] = {uf, ug};
+    f256_acc acc[2] = {f256_acc_zero(), f256_acc_zero()};
+    for (long long i0 = seg_lo; i0 < seg_lo + seg && i0 < M; i0 += FR_CONV_CHUNK)
+        fr_conv_chunk<fr, 2>(sU, sT, acc, u, M, T, n_t, k0, i0);
+    const long long o = o0 + threadIdx.x;
     if (o < n_out) {
-        f256_st(part_f, (long long)blockIdx.y * n_out + o, f256_acc_reduce<fr>(accf));
-        f256_st(part_g, (long long)blockIdx.y * n_out + o, f256_acc_reduce<fr>(accg));
+        f256_st(part_f, (long long)blockIdx.y * n_out + o, f256_acc_reduce<fr>(acc[0]));
+        f256_st(part_g, (long long)blockIdx.y * n_out + o, f256_acc_reduce<fr>(acc[1]));
     }
 }
 
@@ -288,11 +252,7 @@ k_cs_finish(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restri
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t M = m + 1;
     if (o < n_out) {
-        fr sf = f256_ld<fr>(part_f, o), sg = f256_ld<fr>(part_g, o);
-        for (uint32_t s = 1; s < n_seg; s++) {
-            sf = fr_add(sf, f256_ld<fr>(part_f, (long long)s * n_out + o));
-            sg = fr_add(sg, f256_ld<fr>(part_g, (long long)s * n_out + o));
-        }
+        const fr sf = fr_partsum<fr>(part_f, n_out, n_seg, o), sg = fr_partsum<fr>(part_g, n_out, n_seg, o);
         const uint32_t x = m + 2 + o;
         const fr lx = fr_mul(f256_ld<fr>(fact, x - 1), f256_ld<fr>(ifact, x - M - 1));
         f256_st(zt, 2 + (long long)x, fr_mul(fr_mul(lx, sf), fr_mul(lx, sg)));
@@ -315,7 +275,7 @@ extern "C" int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const long long M = (long long)m + 1, n_t = 2 * (long long)m + 2;
     const long long n_out = m >= 2 ? (long long)m - 1 : 0, k_lo = (long long)m + 1;
-    const unsigned tiles = (unsigned)((n_out + CS_TILE - 1) / CS_TILE);
+    const unsigned tiles = (unsigned)((n_out + FR_CONV_TILE - 1) / FR_CONV_TILE);
     long long seg = CS_MIN_SEG;
     while ((long long)tiles * ((M + seg - 1) / seg) > CS_TARGET_WGS && seg < M) seg *= 2;
     const unsigned n_seg = (unsigned)((M + seg - 1) / seg);
@@ -338,7 +298,7 @@ extern "C" int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b
     }
     if (n_out) {
         vmpc_stage_scope sc(ctx, "cs_extend_corr");
-        k_cs_corr<<<dim3(tiles, n_seg), CS_TILE, 0, ctx->stream>>>(uf, ug, M, T, n_t, k_lo, n_out, seg, pf, pg);
+        k_cs_corr<<<dim3(tiles, n_seg), FR_CONV_TILE, 0, ctx->stream>>>(uf, ug, M, T, n_t, k_lo, n_out, seg, pf, pg);
         VMPC_KERNEL_CHECK();
     }
     {
@@ -352,55 +312,13 @@ extern "C" int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b
 }
 
 // ---- transposed sparse mat-vec -----------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(CS_WG)
-k_cs_colseg(const uint32_t *__restrict__ seg_ptr, uint32_t n_segs, const uint32_t *__restrict__ rows,
-            const uint32_t *__restrict__ vals, const uint32_t *__restrict__ weights, uint32_t n_rows,
-            uint32_t *__restrict__ partial) {
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n_segs) return;
-    f256_acc acc = f256_acc_zero();
-    for (uint32_t e = seg_ptr[s]; e < seg_ptr[s + 1]; e++) {
-        const uint32_t r = rows[e];
-        if (r >= n_rows) continue;
-        const fr v = f256_ld<fr>(vals, e), w = f256_ld<fr>(weights, r);
-        f256_acc_mac(acc, v.v, w.v);
-    }
-    f256_st(partial, s, f256_acc_reduce<fr>(acc));
-}
-
-__global__ void __launch_bounds__(CS_WG)
-k_cs_colsum(const uint32_t *__restrict__ col_seg, const uint32_t *__restrict__ col_pos, uint32_t n_cols,
-            const uint32_t *__restrict__ partial, uint32_t n_out, uint32_t *__restrict__ out) {
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_cols) return;
-    const uint32_t pos = col_pos[c];
-    if (pos >= n_out) return;
-    fr s = fr_zero();
-    for (uint32_t k = col_seg[c]; k < col_seg[c + 1]; k++) s = fr_add(s, f256_ld<fr>(partial, k));
-    f256_st(out, pos, s);
-}
-
 extern "C" int vmpc_fr_cs_colsum_dev(vmpc_ctx *ctx, const void *weights, size_t n_rows, const uint32_t *rows,
-                                     const void *vals, const uint32_t *seg_ptr, size_t n_segs, const uint32_t *col_seg,
-                                     const uint32_t *col_pos, size_t n_cols, void *out, size_t n_out) {
-    if (n_segs > ((size_t)1 << 31) || n_cols > ((size_t)1 << 31) || n_out > ((size_t)1 << 31) || n_rows > ((size_t)1 << 31))
-        return VMPC_E_RANGE;
-    if (!ctx || (n_out && !out)) return VMPC_E_INVAL;
-    if (n_cols && (!weights || !rows || !vals || !seg_ptr || !col_seg || !col_pos || !n_segs)) return VMPC_E_INVAL;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    vmpc_stage_scope sc(ctx, "cs_colsum");
-    if (n_out) VMPC_HIP_CHECK(hipMemsetAsync(out, 0, n_out * 32, ctx->stream));
-    if (n_cols == 0) return VMPC_OK;
-    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(n_segs * 32) + 256));
-    uint32_t *partial = (uint32_t *)vmpc_ws_take(ctx, n_segs * 32);
-    k_cs_colseg<<<(unsigned)((n_segs + CS_WG - 1) / CS_WG), CS_WG, 0, ctx->stream>>>(
-        seg_ptr, (uint32_t)n_segs, rows, (const uint32_t *)vals, (const uint32_t *)weights, (uint32_t)n_rows, partial);
-    VMPC_KERNEL_CHECK();
-    k_cs_colsum<<<(unsigned)((n_cols + CS_WG - 1) / CS_WG), CS_WG, 0, ctx->stream>>>(col_seg, col_pos, (uint32_t)n_cols,
-                                                                                      partial, (uint32_t)n_out,
-                                                                                      (uint32_t *)out);
-    VMPC_KERNEL_CHECK();
-    return VMPC_OK;
+                                     const void *vals, size_t nnz, const uint32_t *items, size_t n_items,
+                                     const uint32_t *long_cols, size_t n_long, size_t n_partial, void *out, size_t n_out) {
+    VMPC_CHECK(fr_colsum_check(ctx, weights, n_rows, (size_t)1 << 31, rows, vals, nnz, items, n_items, long_cols, n_long,
+                               n_partial, out, n_out));
+    return fr_colsum<fr>(ctx, "cs_colsum", true, weights, n_rows, rows, vals, nnz, items, n_items, long_cols, n_long,
+                         n_partial, out, n_out);      // true: positions that no column maps to stay zero
 }
 
 // ---- comparison --------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ vanish on a committed vector, by opening the one form L = sum_i rho^i L_i with P
 
 The reference composes L with s Python form products and s sums.  Here (csrc/nullity.hip) a dense matrix is combined
 in one pass - a lane per column, Horner over the rows - and all s values L_i(x) come from one launch sequence; sparse
-forms go through the transposed product of csrc/circuit_sat.hip with the weights rho^i.
+forms go through the transposed product of csrc/fr_colsum.h (sparse.DeviceMatrix) with the weights rho^i.
 
 Transcripts, selected by `transcript=` (default: TRANSCRIPT below): "compact" (DESIGN.md section 16 states the bytes;
 tests/nullity_ref.py restates them) - forms, L and x device-resident all the way into the compact Protocol 5 - and
@@ -23,8 +23,7 @@ import hashlib
 
 import numpy as np
 
-from . import circuit_sat_gpu, compressed_pivot, pivot, wire
-from .circuit_sat_gpu import _DeviceMatrix, _Matrix, _ints_to_array, _mode
+from . import compressed_pivot, pivot, sparse, wire
 from .device import ScalarVector, _View, get_context
 from .groups import ORDER, as_point
 
@@ -79,7 +78,7 @@ class FormMatrix:
             if isinstance(f.coeffs, ScalarVector):
                 ctx.copy(buf.ptr + 32 * i * self.n, f.coeffs.ptr, 32 * self.n)
             else:
-                ctx.upload_into(buf.ptr + 32 * i * self.n, _ints_to_array([pivot._residue(c) for c in f.coeffs]))
+                ctx.upload_into(buf.ptr + 32 * i * self.n, sparse.residue_array([pivot._residue(c) for c in f.coeffs], ORDER))
         self._set_dense(buf, self.n, canonical=True)
 
     def _set_dense(self, buf, stride, canonical):
@@ -117,9 +116,9 @@ class FormMatrix:
         self.ctx = ctx or get_context()
         self._digest = None
         self.n = int(n)
-        self.sparse = _Matrix((row_ptr, col, vals), self.n, "FormMatrix")
+        self.sparse = sparse.CanonicalCSR((row_ptr, col, vals), self.n, ORDER, "SparseCircuit: FormMatrix")
         self.s = self.sparse.n_rows
-        self._dev = _DeviceMatrix(self.ctx, self.sparse)
+        self._dev = sparse.DeviceMatrix(self.ctx, self.sparse)
         return self
 
     def __len__(self):
@@ -215,7 +214,7 @@ def _printable(lin_forms):
 def prove_nullity_compressed(generators, P, lin_forms, x, gamma, gf, transcript=None, r=None, mask=None):
     """nullity.py:21-28: (proof, L, y, rho).  `r`, `mask`: Protocol 5's masks (protocol_5_prover's r= and rho=; rho is
     the challenge here), drawn there when None."""
-    mode = _mode(transcript or TRANSCRIPT)
+    mode = compressed_pivot.transcript_mode(transcript, TRANSCRIPT)
     order = gf.order
     if mode == "reference":
         shown = _printable(lin_forms)
@@ -233,8 +232,8 @@ def prove_nullity_compressed(generators, P, lin_forms, x, gamma, gf, transcript=
         L = pivot.LinearForm(fm.combine(rho))
         x = pivot._as_device(x)
         y = gf(L.coeffs.dot(x))
-        if r is None and len(x) >= circuit_sat_gpu.MASKS_ON_DEVICE_MIN:
-            r = circuit_sat_gpu._masks(len(x), fm.ctx)
+        if r is None and len(x) >= compressed_pivot.MASKS_ON_DEVICE_MIN:
+            r = compressed_pivot.masks(len(x), fm.ctx)
     proof = compressed_pivot.protocol_5_prover(generators, P, L, y, x, gamma, gf, transcript=mode, r=r, rho=mask)
     return proof, L, y, rho
 
@@ -242,7 +241,7 @@ def prove_nullity_compressed(generators, P, lin_forms, x, gamma, gf, transcript=
 def verify_nullity_compressed(generators, P, L, lin_forms, rho, y, proof, gf, transcript=None):
     """nullity.py:31-40: a bool.  The compact transcript also refuses a rho that is not the hash of (P, lin_forms):
     the reference takes the challenge as it is handed in, and so does the reference transcript here."""
-    mode = _mode(transcript or TRANSCRIPT)
+    mode = compressed_pivot.transcript_mode(transcript, TRANSCRIPT)
     if mode == "reference" and not _device_forms(lin_forms) and not isinstance(L.coeffs, ScalarVector):
         L_check = _host_combination(lin_forms, rho)
         if not L_check == L:

@@ -41,6 +41,7 @@ import numpy as np
 
 from . import _native
 from .device import get_context
+from .sparse import ColumnPlan, csr_entries
 
 P = 65000549695646603732796438742359905742825358107623003571877145026864184071783
 ORDER = 65000549695646603732796438742359905742570406053903786389881062969044166799969
@@ -796,90 +797,11 @@ class Generators:
         self.g2_w, self.g2_y = _fixed_base_points(ctx, 2, b2, e2.ptr, 2)
 
 
-_PIECE = 64      # column entries one lane of k_kg_colsum sums (csrc/bn256_keygen.hip)
-
-
-def _colsum_plan(col_ptr, piece=_PIECE):
-    """items (start, end, dst) and long columns (col, first partial, count) of vmpc_bn256_qap_colsum_dev for entries in
-    column order (col_ptr: n_cols + 1 offsets); an empty column is one empty item (it writes 0)"""
-    col_ptr = np.asarray(col_ptr, np.int64)
-    lens = np.diff(col_ptr)
-    pieces = np.maximum(1, (lens + piece - 1) // piece)
-    n_items = int(pieces.sum())
-    col_of = np.repeat(np.arange(len(lens), dtype=np.int64), pieces)
-    first_item = np.cumsum(pieces) - pieces
-    start = col_ptr[col_of] + (np.arange(n_items, dtype=np.int64) - first_item[col_of]) * piece
-    end = np.minimum(start + piece, col_ptr[col_of + 1])
-    is_long = pieces > 1
-    is_part = is_long[col_of]
-    part_idx = np.cumsum(is_part) - 1
-    dst = np.where(is_part, 0x80000000 | part_idx, col_of)
-    items = np.stack([start, end, dst], axis=1).astype(np.uint32)
-    long_cols = np.nonzero(is_long)[0]
-    longs = np.stack([long_cols, part_idx[first_item[long_cols]], pieces[long_cols]], axis=1).astype(np.uint32)
-    return items, longs, int(is_part.sum())
-
-
-class _ColumnPlan:
-    """entries of a QAP's 3 (m + 1) (+ 1) columns in column order, on the device, with their colsum plan"""
-
-    def __init__(self, ctx, cols, rows, vals, n_cols):
-        order = np.argsort(cols, kind="stable")
-        counts = np.bincount(cols, minlength=n_cols) if len(cols) else np.zeros(n_cols, np.int64)
-        col_ptr = np.concatenate([[0], np.cumsum(counts)])
-        items, longs, self.n_partial = _colsum_plan(col_ptr)
-        self.ctx, self.nnz, self.n_cols = ctx, len(cols), n_cols
-        self.rows = ctx.upload(np.ascontiguousarray(np.asarray(rows, np.uint32)[order]))
-        self.vals = ctx.upload(np.ascontiguousarray(vals[order])) if len(cols) else ctx.alloc(32)
-        self.items, self.n_items = ctx.upload(items), len(items)
-        self.longs, self.n_long = ctx.upload(longs), len(longs)
-
-    def run(self, basis_ptr, n_basis, out_ptr):
-        self.ctx.bn256_qap_colsum(basis_ptr, n_basis, self.rows.ptr, self.vals.ptr, self.nnz, self.items.ptr,
-                                  self.n_items, self.longs.ptr, self.n_long, self.n_partial, out_ptr, self.n_cols)
-
-
-_ORDER_WORDS = np.array([(ORDER >> (32 * k)) & 0xFFFFFFFF for k in range(8)], dtype=np.int64)
-
-
-def _values_array(vals):
-    """R1CS values -> (nnz, 32) uint8 residues mod ORDER: a (nnz, 32) uint8 array passes through (the device reduces
-    it), an integer array is reduced here (negative entries become ORDER - |v|), anything else goes through ints"""
-    if isinstance(vals, np.ndarray) and vals.dtype == np.uint8 and vals.ndim == 2:
-        return np.ascontiguousarray(vals)
-    if isinstance(vals, np.ndarray) and vals.dtype.kind in "iu" and vals.ndim == 1 and vals.dtype.itemsize <= 8:
-        a = vals.astype(np.int64) if vals.dtype.kind == "i" else vals.astype(np.uint64)
-        neg = a < 0
-        mag = np.where(neg, -a.astype(np.int64), a).astype(np.uint64) if a.dtype.kind == "i" else a
-        words = np.zeros((len(a), 8), np.int64)
-        words[:, 0] = (mag & np.uint64(0xFFFFFFFF)).astype(np.int64)
-        words[:, 1] = (mag >> np.uint64(32)).astype(np.int64)
-        if neg.any():
-            borrow = np.zeros(int(neg.sum()), np.int64)
-            sub = words[neg]
-            for k in range(8):
-                dk = _ORDER_WORDS[k] - sub[:, k] - borrow
-                borrow = (dk < 0).astype(np.int64)
-                sub[:, k] = dk + (borrow << 32)
-            words[neg] = sub
-        return words.astype("<u4").view(np.uint8).reshape(-1, 32)
-    return scalars_to_array([int(v) % ORDER for v in vals])
-
-
 def _matrix_entries(M, n_cols=None):
     """(rows, cols, values (nnz, 32), n_rows, n_cols) of one constraint matrix: a tuple (row_ptr, col, vals) is CSR,
     a list of rows (code_to_r1cs.flatcode_to_r1cs) or a 2-D array is dense"""
     if isinstance(M, tuple):
-        row_ptr, col, vals = M
-        row_ptr = np.asarray(row_ptr, np.int64)
-        col = np.asarray(col, np.int64)
-        n_rows = len(row_ptr) - 1
-        if n_rows < 0 or row_ptr[0] != 0 or np.any(np.diff(row_ptr) < 0) or row_ptr[-1] != len(col):
-            raise ValueError("R1CSQAP: row_ptr must rise from 0 to the number of entries")
-        rows = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(row_ptr))
-        v = _values_array(vals)
-        if len(v) != len(col):
-            raise ValueError("R1CSQAP: one value per entry")
+        rows, col, v, n_rows = csr_entries(*M, ORDER, False, "R1CSQAP")      # values >= ORDER: the device reduces them
         return rows, col, v, n_rows, n_cols
     dense = [[int(x) for x in row] for row in M]
     n_rows = len(dense)
@@ -937,7 +859,7 @@ class R1CSQAP:
     def _plan(self, ctx):
         key = id(ctx)
         if key not in self._plans:
-            self._plans[key] = (ctx, _ColumnPlan(ctx, self._cols, self._rows, self._vals, 3 * (self.m + 1)))
+            self._plans[key] = (ctx, ColumnPlan(ctx, self._cols, self._rows, self._vals, 3 * (self.m + 1)))
         return self._plans[key][1]
 
 
@@ -956,7 +878,7 @@ def _dense_plan(ctx, qap):
                 cols.append(c)
                 ints.append(x)
     vals = scalars_to_array(ints).reshape(-1, 32)
-    return _ColumnPlan(ctx, np.asarray(cols, np.int64), np.asarray(rows, np.int64), vals, len(polys)), top
+    return ColumnPlan(ctx, np.asarray(cols, np.int64), np.asarray(rows, np.int64), vals, len(polys)), top
 
 
 def _scalar_buf(ctx, values):
@@ -1158,7 +1080,7 @@ def _row_plan(ctx, qap):
     """an R1CSQAP's entries in ROW order (a, b, y stacked: 3 d sums), for vmpc_bn256_qap_colsum_dev with basis = c"""
     n_wires = qap.m + 1
     kind, wire = qap._cols // n_wires, qap._cols % n_wires
-    return _ColumnPlan(ctx, qap._rows + kind * qap.d, wire, qap._vals, 3 * qap.d)
+    return ColumnPlan(ctx, qap._rows + kind * qap.d, wire, qap._vals, 3 * qap.d)
 
 
 def _coeff_plan(ctx, qap):
@@ -1175,7 +1097,7 @@ def _coeff_plan(ctx, qap):
                     cols.append(kind * top + k)
                     ints.append(x)
     vals = scalars_to_array(ints).reshape(-1, 32)
-    return _ColumnPlan(ctx, np.asarray(cols, np.int64), np.asarray(rows, np.int64), vals, 3 * top), top
+    return ColumnPlan(ctx, np.asarray(cols, np.int64), np.asarray(rows, np.int64), vals, 3 * top), top
 
 
 def _t_coeffs(ctx, qap):
