@@ -380,6 +380,31 @@ def test_moments_deep_segment(ctx):
         assert got[k] == sum(x * pow(j, k, N) for j, x in enumerate(u, 1)) % N, k
 
 
+def _weights(d):
+    """w_j = (-1)^(d-j) (j-1)! (d-j)! for j = 1..d: factorials in Python"""
+    fact = [1] * (d + 1)
+    for k in range(1, d + 1):
+        fact[k] = fact[k - 1] * k % N
+    return [(-1) ** (d - j) * fact[j - 1] * fact[d - j] % N for j in range(1, d + 1)]
+
+
+@pytest.mark.parametrize("d", [1, 63, 64, 65, 16383, 16384, 16385, 32769])
+def test_weights_at_scan_boundaries(ctx, d):
+    """csrc/fr_scan.h over GF(n) with runs of QH_RUN = 64 elements: d = 63, 64, 65 is a run one short of full, full
+    and a second lane of one element; 16383 / 16384 give 256 lanes (one per scanning thread, the last run short at
+    16383), 16385 gives 257 (two per thread, 127 threads with none, the one that inverts d! among them), 32769 gives 513
+    (three per thread, 85 threads with none).  a random, b all n - 1."""
+    rng = random.Random(8000 + d)
+    a, b = [rng.randrange(N) for _ in range(d)], [N - 1] * d
+    da, db = ctx.upload(K.to_array(a)), ctx.upload(K.to_array(b))
+    ua, ub = ctx.upload(K.to_array([7] * (d + 1))), ctx.upload(K.to_array([7] * (d + 1)))
+    ctx.bn256_qap_h_weights(da.ptr, db.ptr, d, ua.ptr, ub.ptr)
+    inv_w = [pow(wj, -1, N) for wj in _weights(d)]
+    ctx.sync()
+    assert to_ints(ctx.download(ua.ptr, 32 * (d + 1))) == [x * f % N for x, f in zip(a, inv_w)] + [7]
+    assert to_ints(ctx.download(ub.ptr, 32 * (d + 1))) == [x * f % N for x, f in zip(b, inv_w)] + [7]
+
+
 def test_weights_check_and_horner_primitives(ctx):
     d = 130
     rng = random.Random(8)
@@ -387,10 +412,7 @@ def test_weights_check_and_horner_primitives(ctx):
     da, db = ctx.upload(K.to_array(a)), ctx.upload(K.to_array(b))
     ua, ub = ctx.alloc(32 * d), ctx.alloc(32 * d)
     ctx.bn256_qap_h_weights(da.ptr, db.ptr, d, ua.ptr, ub.ptr)
-    fact = [1] * (d + 1)
-    for k in range(1, d + 1):
-        fact[k] = fact[k - 1] * k % N
-    w = [(-1) ** (d - j) * fact[j - 1] * fact[d - j] % N for j in range(1, d + 1)]
+    w = _weights(d)
     ctx.sync()
     assert to_ints(ctx.download(ua.ptr, 32 * d)) == [x * pow(wj, -1, N) % N for x, wj in zip(a, w)]
     assert to_ints(ctx.download(ub.ptr, 32 * d)) == [x * pow(wj, -1, N) % N for x, wj in zip(b, w)]

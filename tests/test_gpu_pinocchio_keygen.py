@@ -272,6 +272,25 @@ def test_special_s_sparse_and_dense(pn, ctx, fx, which):
         assert int.from_bytes(ctx.download(t.ptr, 32).tobytes(), "little") == want_t
 
 
+@pytest.mark.parametrize("d", [1, 63, 64, 65, 16383, 16384, 16385, 32769])
+def test_lagrange_basis_at_scan_boundaries(ctx, d):
+    """csrc/fr_scan.h over GF(n) with runs of KG_RUN = 64 elements, three sequences: d = 63, 64, 65 is a run one short
+    of full, full and a second lane of one element; 16383 / 16384 give 256 lanes (one per scanning thread), 16385 gives
+    257 (two per thread, 127 threads with none, the one that hands on the total among them), 32769 gives 513 (three per
+    thread).  s on a node (16384: the last element of lane 255) turns the products to zero in the middle of a run."""
+    rng = random.Random(6000 + d)
+    ell, t = ctx.alloc(32 * (d + 1)), ctx.alloc(32)
+    for s in [rng.randrange(d + 1, N), 0] + sorted({v for v in (1, 64, 65, 16384, d) if v <= d}):
+        ctx.upload_into(ell.ptr, K.to_array([7] * (d + 1)))
+        sb = ctx.upload(K.to_array([s]))
+        ctx.bn256_qap_lagrange(sb.ptr, d, ell.ptr, t.ptr)
+        ctx.sync()
+        got = [int.from_bytes(r.tobytes(), "little") for r in ctx.download(ell.ptr, 32 * (d + 1)).reshape(-1, 32)]
+        want_ell, want_t = K.lagrange_at(s, d)
+        assert got == want_ell + [7], (d, s)
+        assert int.from_bytes(ctx.download(t.ptr, 32).tobytes(), "little") == want_t, (d, s)
+
+
 def _restated_evalkey(td, ents, n_cols, d, mid):
     v, w, y, t = K.qap_at(*ents, n_cols, d, td.s)
     out = {}

@@ -47,6 +47,31 @@ def test_lagrange_on_a_node_has_no_reference_value():
     assert ref.lagrange_bary(4, 3) == [0, 0, 0, 1, 0]      # the product form is exact there; the prover still refuses
 
 
+@pytest.mark.parametrize("m,top", [(2, False), (258, False), (513, False), (513, True)],
+                         ids=["m2", "m258", "m513", "m513_top"])
+def test_kronecker_convolution_is_the_direct_sum(m, top):
+    """tests/test_gpu_p8_primitives.py takes z_tail_bary's Kronecker route from m = 512 on: it is the double loop, with
+    random values and with every value l - 1 (the largest terms a 66-byte slot has to hold)"""
+    rng = random.Random(5000 + m)
+    a, b = ([ELL - 1] * m,) * 2 if top else ([rng.randrange(ELL) for _ in range(m)], [rng.randrange(ELL) for _ in range(m)])
+    r_a, r_b = (ELL - 1, ELL - 1) if top else (rng.randrange(ELL), rng.randrange(ELL))
+    direct = ref.z_tail_bary(a, b, r_a, r_b, kronecker=False)
+    assert ref.z_tail_bary(a, b, r_a, r_b, kronecker=True) == direct
+    assert len(direct) == 2 * m + 3 and direct[3:3 + m] == [x * y % ELL for x, y in zip(a, b)]
+
+
+@pytest.mark.parametrize("K", [1, 33, 8193])
+def test_lagrange_bary_on_and_off_the_nodes(K):
+    """on a node the product form gives the unit vector (what the GPU test expects of the kernel there); off the nodes
+    it is the reference's double loop"""
+    for c in sorted({j for j in (0, 1, 31, 32, 33, K // 2, K - 1, K) if 0 <= j <= K}):
+        assert ref.lagrange_bary(K, c) == [int(j == c) for j in range(K + 1)], c
+    if K <= 33:
+        rng = random.Random(K)
+        for c in (K + 1, ELL - 1, rng.randrange(K + 1, ELL)):
+            assert ref.lagrange_bary(K, c) == ref.lagrange_naive(K, c), c
+
+
 @pytest.mark.parametrize("seed,n_x,m,n_out", GPU_CASES)
 def test_generator_makes_circuits_the_convention_accepts(seed, n_x, m, n_out):
     rng = random.Random(seed)
