@@ -248,6 +248,13 @@ int vmpc_normalize_dev(vmpc_ctx *ctx, const void *proj, size_t n, void *out_affi
 /* affine (x, y) -> projective (x, y, 1) */
 int vmpc_affine_to_proj_dev(vmpc_ctx *ctx, const void *affine, size_t n, void *out_proj);
 
+/* The GF(l) vector entries from here to vmpc_fr_dot_to_dev (csrc/frvec.hip): out = c * x + y, c * x, <a, b>, the
+ * challenge products and the tail scalars.  Every element of a VECTOR operand (x, y, a, b, z, and `products` from the
+ * second round on) must be a canonical residue < l.  Unlike the host constants (c, tail, the challenges: checked,
+ * VMPC_E_NONCANON) the vectors are NOT checked, and unlike the Pi_Nullity entries below they are not reduced on the way
+ * in: an element is loaded as it is, and a sum is corrected by one subtraction of l only.  With a non-canonical element
+ * the result is unspecified (no fault, no error code, possibly a non-canonical or a wrong residue).  Results of
+ * canonical operands are canonical. */
 int vmpc_fr_axpy_dev(vmpc_ctx *ctx, const uint8_t c[32], const void *x, const void *y, size_t n,
                      void *out);
 int vmpc_fr_scale_dev(vmpc_ctx *ctx, const uint8_t c[32], const void *x, size_t n, void *out);

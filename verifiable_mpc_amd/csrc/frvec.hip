@@ -341,9 +341,11 @@ int vmpc_fr_tail_scalars_block_mem(vmpc_ctx *ctx, const uint8_t newest_challenge
                                    int t, int log2_m0, const void *z, size_t j0, size_t count, void *products,
                                    void *out_a, void *out_b) {
     if (!ctx || t < 0 || t > 40 || log2_m0 < 1 || log2_m0 > 40 || t >= log2_m0 ||
-        (t && !newest_challenge && !challenge_mem) || !z || !products || !out_a || !out_b ||
-        j0 + count > ((size_t)1 << log2_m0))
+        (t && !newest_challenge && !challenge_mem) || !z || !products || !out_a || !out_b)
         return VMPC_E_INVAL;
+    // not j0 + count > m0: that sum wraps for j0 near 2^64
+    const size_t m0 = (size_t)1 << log2_m0;
+    if (j0 > m0 || count > m0 - j0) return VMPC_E_INVAL;
     if (count == 0) return VMPC_OK;
     fr_arg a;
     memset(&a, 0, sizeof a);
