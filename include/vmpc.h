@@ -549,6 +549,27 @@ int vmpc_fr_rows_combine_dev(vmpc_ctx *ctx, const void *rows, size_t s, size_t n
 int vmpc_fr_rows_dot_dev(vmpc_ctx *ctx, const void *rows, size_t s, size_t n, size_t row_stride, const void *x, void *out,
                          uint32_t *first_nonzero);
 
+/* ---- Batch verification of compact Protocol-4/5 proofs over one CRS (csrc/batch_verify.hip).
+ * Proof p < K has `rounds` challenges c_{p,i}, a final response z'_p of 2^low_bits elements and a weight w_p; with
+ * N = 2^(rounds + low_bits) and v_p[j] as vmpc_fr_challenge_products_dev defines it for (c_p, z'_p):
+ *     u_out[j]    = sum_p w_p v_p[j]                          N residues
+ *     dots_out[p] = sum_{j < form_len} w_p v_p[j] forms[p][j]  K residues   (elements from form_len on count as zero)
+ * so that the K final checks (compressed_pivot.py:193-197) become ONE N-term MSM with scalars u.  Everything is in
+ * device memory: challenges_dev K x rounds, zprime_dev K x 2^low_bits, weights_dev K canonical residues (not checked,
+ * as for the vector operands above); forms_dev: K device pointers held in device memory, each to form_len residues
+ * (may be NULL when form_len == 0).  No v_p is written anywhere; results are canonical and bit-reproducible (integer
+ * sums in a fixed order, no atomics).  Caps: K <= VMPC_FR_BATCH_MAX_K, rounds <= VMPC_FR_BATCH_MAX_ROUNDS,
+ * rounds + low_bits <= VMPC_FR_BATCH_MAX_BITS; above them the entry answers VMPC_E_RANGE before it looks at any pointer.
+ * K < 1, a negative count, a missing pointer or form_len > N: VMPC_E_INVAL.  Nothing is launched or written after
+ * either.  Asynchronous on the context's stream.  Arena: K (2^(a+1) + 2^b) + K * segments scalars, a = min(rounds,
+ * (rounds + low_bits) / 2), b = rounds + low_bits - a. */
+#define VMPC_FR_BATCH_MAX_K 4096
+#define VMPC_FR_BATCH_MAX_ROUNDS 20
+#define VMPC_FR_BATCH_MAX_BITS 30
+int vmpc_fr_batch_products_dev(vmpc_ctx *ctx, int K, int rounds, int low_bits, const void *challenges_dev,
+                               const void *zprime_dev, const void *weights_dev, const void *const *forms_dev,
+                               size_t form_len, void *u_out, void *dots_out);
+
 /* SHA-256 of every `chunk_bytes`-sized piece of a device buffer (last piece may be short):
  * out_digests[i] = SHA256(data[i*chunk : (i+1)*chunk]), 32 bytes each.  Leaves of the compact
  * transcript's two-level digests; not used by the reference transcript. */

@@ -51,7 +51,7 @@ SYMBOLS = [
     "vmpc_bn256_qap_t_coeffs_dev", "vmpc_bn256_qap_horner_dev", "vmpc_bn256_qap_h_combine_dev",
     "vmpc_fr_cs_triples_dev", "vmpc_fr_cs_tables_dev", "vmpc_fr_cs_extend_dev", "vmpc_fr_cs_lagrange_dev",
     "vmpc_fr_cs_colsum_dev", "vmpc_fr_cs_first_diff_dev",
-    "vmpc_fr_rows_combine_dev", "vmpc_fr_rows_dot_dev",
+    "vmpc_fr_rows_combine_dev", "vmpc_fr_rows_dot_dev", "vmpc_fr_batch_products_dev",
 ]
 
 
@@ -176,6 +176,7 @@ def load_library():
         "vmpc_fr_cs_first_diff_dev": (i32, [vp, vp, vp, sz, vp]),
         "vmpc_fr_rows_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp]),
         "vmpc_fr_rows_dot_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
+        "vmpc_fr_batch_products_dev": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, sz, vp, vp]),
         "vmpc_msm_table_fold_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp]),
         "vmpc_msm_table_fold_table_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp, sz, i32, vp]),
         "vmpc_p4_create": (i32, [vp, vp, sz, sz, i32, i32, i32, vp, vp, vp, ctypes.POINTER(vp)]),
@@ -857,6 +858,16 @@ class Context:
             return None
         v = int(self.download(first.ptr, 4).view(np.uint32)[0])
         return None if v == 0xFFFFFFFF else v
+
+    # ---- batch verification of compact Protocol-4/5 proofs (csrc/batch_verify.hip) ----------------------------------
+    def fr_batch_products(self, K, rounds, low_bits, challenges_ptr, zprime_ptr, weights_ptr, forms_ptr, form_len,
+                          u_ptr, dots_ptr):
+        """u[j] = sum_p w_p v_p[j] (2^(rounds + low_bits) scalars at u_ptr) and dots[p] = <w_p v_p, forms[p]> (K scalars
+        at dots_ptr); forms_ptr: K device pointers in device memory.  Asynchronous (include/vmpc.h)"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_fr_batch_products_dev(self.handle, K, rounds, low_bits, p(challenges_ptr), p(zprime_ptr),
+                                                   p(weights_ptr), p(forms_ptr), form_len, p(u_ptr), p(dots_ptr)),
+               "vmpc_fr_batch_products_dev")
 
     def _format(self, fn, name, src_ptr, n, per_item_cap, *extra):
         cap = n * per_item_cap + 16

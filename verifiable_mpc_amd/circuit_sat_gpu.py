@@ -533,3 +533,21 @@ def circuit_sat_verifier(proof, generators, circuit, gf, pivot_choice="compresse
         ok = pivot.verify_linear_form_proof(generators["g"], generators["h"], proof["z_commitment"], L, gf(0), z, phi, c)
     verification["pivot_verification"] = ok
     return verification
+
+
+def circuit_sat_verifier_batch(proofs, generators, circuit, gf, transcript=None):
+    """[circuit_sat_verifier(proof, generators, circuit, gf, "compressed", transcript) for proof in proofs] - many inputs
+    of one circuit: Protocol 8's checks per proof, then the proofs that yielded an L in ONE batched pivot verification
+    (compressed_pivot.protocol_5_verifier_batch)"""
+    mode = _mode(transcript)
+    circuit = as_sparse(circuit)
+    out, statements, where = [], [], []
+    for proof in proofs:
+        verification, L = protocol_8_excl_pivot_verifier(proof, circuit, gf, transcript=mode)
+        if L is not None:
+            statements.append((proof["z_commitment"], L, gf(0), proof["pivot_proof"]))
+            where.append(len(out))
+        out.append(verification)
+    for i, ok in zip(where, compressed_pivot.protocol_5_verifier_batch(generators, statements, gf, transcript=mode)):
+        out[i]["pivot_verification"] = ok
+    return out

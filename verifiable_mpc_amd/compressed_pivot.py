@@ -960,3 +960,152 @@ def protocol_5_verifier(generators, P, L, y, proof, gf, transcript=None):
     finally:
         in_group = membership.result()
     return bool(verdict) and in_group
+
+
+# ---- batch verification ---------------------------------------------------------------------------
+
+BATCH_WEIGHT_BITS = 128
+
+
+def batch_unfold_terms(proofs, weights, order):
+    """The terms of sum_p w_p Q_R^(p) as one list: (scalars, points).
+
+    proofs: per proof (q_terms, rounds) with q_terms = [(scalar, point), ...] for Q_0 = sum scalar * point (_LazyQ.terms)
+    and rounds = [(A_i, B_i, c_i), ...]; Q_R = (prod_j c_j) Q_0 + sum_i (prod_{j>i} c_j) (A_i + c_i^2 B_i), the R
+    applications of Q' = A * Q**c * B**(c**2) (compressed_pivot.py:66), as in _unfold_commitment.  Pure: scalars are
+    ints (reduced mod order), points are handed back as they came - 2 R + len(q_terms) terms per proof."""
+    scalars, points = [], []
+    for (q_terms, rounds), w in zip(proofs, weights, strict=True):
+        suffix = int(w) % order
+        for A, B, c in reversed(rounds):
+            scalars += [suffix, suffix * c * c % order]
+            points += [A, B]
+            suffix = suffix * c % order
+        for sc, pt in q_terms:
+            scalars.append(suffix * sc % order)
+            points.append(pt)
+    return scalars, points
+
+
+def _batch_weights(count, order):
+    return [prng.randrange(1, 1 << BATCH_WEIGHT_BITS) for _ in range(count)]
+
+
+class _BatchItem:
+    """what the combined check needs of one proof: challenges, z', c1, the form's coefficients and the terms of Q_R"""
+    __slots__ = ("membership", "rounds", "cs", "z_prime", "c1", "coeffs", "q_terms")
+
+
+def _batch_prepare(generators, k, P, L, y, proof, gf, n, R):
+    """One statement up to (not including) the final check, as protocol_5_verifier does it; the form's digest must have
+    been started.  None: the proof does not have the shape of a proof for this CRS."""
+    order = gf.order
+    try:
+        z_prime = [pivot._residue(v) for v in proof["z_prime"]]
+        t = proof["t"]
+        A = _pt(proof["A"])
+        pairs = [(_pt(proof["A" + str(i)]), _pt(proof["B" + str(i)])) for i in range(R)]
+    except (KeyError, TypeError, ValueError, AttributeError):
+        return None
+    if len(z_prime) != 2 or len(_proof_points(proof)) != 2 * R + 1:
+        return None
+    c0, c1, seed = _p5_challenges("compact", order, generators, t, A, P, L, y, who="protocol_5_verifier")
+    transcript = _p5_setup(generators, k, seed, "compact", order)
+    item = _BatchItem()
+    item.rounds = [(Ai, Bi, transcript.round_challenge(i, Ai, Bi, None, k, None, None)) for i, (Ai, Bi) in enumerate(pairs)]
+    item.cs = [c for _, _, c in item.rounds]
+    item.z_prime, item.c1, item.coeffs = z_prime, c1 % order, L.coeffs
+    item.q_terms = _LazyQ(A, P, k, c0, int(c1 * (c0 * y + t)), order).terms
+    return item
+
+
+def _batch_check(items, weights, g_hat, k, order):
+    """MSM(u, g_hat) + Gamma k == sum_p w_p Q_R^(p) for the given proofs: one K (2 R + 3)-term MSM on the side stream,
+    launched first, one call of the batch kernels, one N-term commitment"""
+    from .device import get_aux_context
+    ctx, aux = g_hat.ctx, get_aux_context()
+    K, R, N = len(items), len(items[0].cs), len(g_hat)
+    scalars, points = batch_unfold_terms([(it.q_terms, it.rounds) for it in items], weights, order)
+    pv = PointVector.from_points(points, aux, keep_proj=False)
+    q_pending = pivot._commit_launch(ScalarVector.from_ints(scalars, aux), 0, pv, Ed25519Point.identity, aux)
+    chal = ScalarVector.from_ints([c for it in items for c in it.cs], ctx)
+    zp = ScalarVector.from_ints([v for it in items for v in it.z_prime], ctx)
+    wts = ScalarVector.from_ints(weights, ctx)
+    forms = ctx.upload(np.array([it.coeffs.ptr for it in items], np.uint64))
+    u, dots = ScalarVector.empty(N, ctx), ScalarVector.empty(K, ctx)
+    for it in items:
+        if it.coeffs.ctx is not ctx:
+            ctx.wait_for(it.coeffs.ctx)
+    ctx.fr_batch_products(K, R, 1, chal.ptr, zp.ptr, wts.ptr, forms.ptr, N - 1, u.ptr, dots.ptr)
+    # Gamma = sum_p c1_p <w_p v_p, L_p || 0>: L~_p = c1_p (L_p || 0) is never formed.  K products, left on the device
+    # like the single verifier's gamma: it is only ever the exponent of k, and the stream is not drained for it
+    gamma = ScalarVector.from_ints([it.c1 for it in items], ctx).dot_dev(dots)
+    pending = pivot._commit_launch(u, gamma, g_hat, k, ctx)
+    return bool(pending.result() == q_pending.result())
+
+
+def _batch_locate(idx, items, weights, check, out, known_bad=False):
+    """out[i] for i in idx by bisection with the same weights: O(b log K) combined checks for b bad proofs"""
+    if not known_bad and check([items[i] for i in idx], [weights[i] for i in idx]):
+        for i in idx:
+            out[i] = True
+        return True
+    if len(idx) == 1:
+        out[idx[0]] = False
+        return False
+    left, right = idx[:len(idx) // 2], idx[len(idx) // 2:]
+    left_ok = _batch_locate(left, items, weights, check, out)
+    # the whole failed: if the left half passes, the right half holds a bad proof - no check of it as a whole
+    _batch_locate(right, items, weights, check, out, known_bad=left_ok)
+    return False
+
+
+def protocol_5_verifier_batch(generators, statements, gf, transcript=None, weights=None):
+    """[protocol_5_verifier(generators, P, L, y, proof, gf, transcript) for (P, L, y, proof) in statements], with ONE
+    N-term MSM for all of them where that is possible (compact transcript, device forms, N = len(g) + 1 >= 4 a power
+    of two): the final checks are linear relations over the same generators, and a combination of them with
+    verifier-chosen 128-bit weights holds only with probability 2^-128 unless each one holds.
+    `weights`: for tests (non-zero, else ValueError); drawn from SystemRandom after all proofs are in hand otherwise.
+    A proof with a point outside the order-l group, or of the wrong shape, is False and enters no combination; a failed
+    combination is bisected down to the bad proofs."""
+    mode = transcript or TRANSCRIPT
+    statements = list(statements)
+    K = len(statements)
+    order = gf.order
+    if weights is not None:
+        weights = [int(w) % order for w in weights]
+        if len(weights) != K:
+            raise ValueError(f"{K} statements, {len(weights)} weights")
+        if any(w == 0 for w in weights):
+            raise ValueError("a zero weight would take its proof out of the combined check")
+    g = generators["g"]
+    n = len(g)
+    N = n + 1
+    lins = [pivot.affine_to_linear(L, y, n) for _, L, y, _ in statements]
+    if mode != "compact" or N < 4 or N & (N - 1) or not all(isinstance(L.coeffs, ScalarVector) for L, _ in lins):
+        return [protocol_5_verifier(generators, P, L, y, proof, gf, transcript=transcript)
+                for P, L, y, proof in statements]
+    h, k = _pt(generators["h"]), _pt(generators["k"])
+    R = N.bit_length() - 2
+    out = [False] * K
+    # as the single verifier orders it: the order-l ladders and the forms' digests of ALL proofs in flight, then the host's
+    # hashing; the verdicts of the ladders are joined before anything is combined (the curve has cofactor 8: parts of
+    # small order in two proofs could otherwise cancel under the weights)
+    checks = [_valid_group_elements_begin([P] + _proof_points(proof)) for P, _, _, proof in statements]
+    live = [i for i in range(K) if checks[i].verdict is not False and len(lins[i][0].coeffs) == n]
+    for i in live:
+        _form_digest_begin(lins[i][0])
+    items = [None] * K
+    for i in live:
+        P, _, _, proof = statements[i]
+        items[i] = _batch_prepare(generators, k, _pt(P), lins[i][0], lins[i][1], proof, gf, n, R)
+    live = [i for i in live if items[i] is not None]
+    in_group = [c.result() for c in checks]
+    live = [i for i in live if in_group[i]]
+    if not live:
+        return out
+    if weights is None:
+        weights = _batch_weights(K, order)
+    g_hat = pivot._points_on_device(g) + [h]
+    _batch_locate(live, items, weights, lambda its, ws: _batch_check(its, ws, g_hat, k, order), out)
+    return out

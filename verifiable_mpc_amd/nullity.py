@@ -258,3 +258,31 @@ def verify_nullity_compressed(generators, P, L, lin_forms, rho, y, proof, gf, tr
         print(MISMATCH)
         return False
     return compressed_pivot.protocol_5_verifier(generators, P, pivot.LinearForm(L_check), y, proof, gf, transcript=mode)
+
+
+def verify_nullity_compressed_batch(generators, items, gf, transcript=None):
+    """[verify_nullity_compressed(generators, P, L, lin_forms, rho, y, proof, gf, transcript) for (P, L, lin_forms, rho,
+    y, proof) in items]: the rho check and the combination of the forms per item as there, then ONE batched pivot
+    verification (compressed_pivot.protocol_5_verifier_batch) for the items that passed them"""
+    mode = compressed_pivot.transcript_mode(transcript, TRANSCRIPT)
+    items = list(items)
+    if mode == "reference":
+        return [verify_nullity_compressed(generators, P, L, lin_forms, rho, y, proof, gf, transcript=mode)
+                for P, L, lin_forms, rho, y, proof in items]
+    out = [False] * len(items)
+    statements, where = [], []
+    for i, (P, L, lin_forms, rho, y, proof) in enumerate(items):
+        fm = as_form_matrix(lin_forms)
+        rho = int(rho) % gf.order
+        if rho != compact_challenge(P, fm.digest, gf.order):
+            continue
+        L_check = fm.combine(rho)
+        theirs = pivot._as_device(L.coeffs)
+        if len(theirs) != fm.n or fm.ctx.cs_first_diff(L_check.ptr, theirs.ptr, fm.n) is not None:
+            print(MISMATCH)
+            continue
+        statements.append((P, pivot.LinearForm(L_check), y, proof))
+        where.append(i)
+    for i, ok in zip(where, compressed_pivot.protocol_5_verifier_batch(generators, statements, gf, transcript=mode)):
+        out[i] = ok
+    return out
