@@ -513,6 +513,11 @@ int vmpc_fr_cs_tables_dev(vmpc_ctx *ctx, size_t K, void *fact, void *ifact);
  * for s segments of j. */
 int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact, const void *ifact,
                           void *z_tail);
+/* The same extension with f and g kept apart, nothing multiplied and no z: f_out[0] = f(0), f_out[1 + o] = f(m + 2 + o)
+ * for o < m - 1, g_out alike; max(m, 1) scalars each.  Linear in a and b, so on Shamir shares of them it gives shares
+ * of f and g at those points (mpc_ac20_cb.py:66-85 interpolates and evaluates share polynomials).  Arena as above. */
+int vmpc_fr_cs_extend_fg_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact, const void *ifact,
+                             void *f_out, void *g_out);
 /* out[j] = the Lagrange basis polynomial of node j among 0..K at c, j = 0..K (ac20/recombine.py:5-32 as called by
  * circuit_builder.py:548-549); ifact: the table with at least K + 1 entries.  No inversion: exact for every c, a
  * node included (the unit vector).  Arena: 3 K scalars. */
@@ -527,6 +532,26 @@ int vmpc_fr_cs_colsum_dev(vmpc_ctx *ctx, const void *weights, size_t n_rows, con
                           size_t n_partial, void *out, size_t n_out);
 /* *first_diff (a device uint32) = the smallest i < n with a[i] != b[i], 0xffffffff if none.  No arena. */
 int vmpc_fr_cs_first_diff_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, uint32_t *first_diff);
+
+/* ---- Shamir sharings of vectors mod l (csrc/mpc_share.hip; verifiable_mpc/ac20/mpc_ac20_cb.py:39-189 through
+ * mpc.schur_prod and mpc._random).  Party q < parties holds the value at node q + 1.  Matrices are row-major in device
+ * memory, row r at base + 32 r stride.  parties <= VMPC_SHARE_MAX_PARTIES, n and the strides <= 2^31: above them the
+ * entries answer VMPC_E_RANGE before they look at any pointer.  Deterministic (no atomics on field values),
+ * asynchronous on the context's stream, no arena. */
+#define VMPC_SHARE_MAX_PARTIES 64
+/* d_i = a_i b_i (b == NULL: a_i); out[q][i] = d_i + sum_{k=1..t} coeffs[k-1][i] (q + 1)^k for q < parties: a fresh
+ * degree-t sharing of every d_i (coeffs: t rows of n scalars, stride n; t = 0 copies d to every row).  The Shamir
+ * dealer, and the local half of a product of shares.  t < parties, out_stride >= n, else VMPC_E_INVAL.  The vector
+ * operands are canonical residues and are not checked (as for vmpc_fr_axpy_dev). */
+int vmpc_fr_share_mul_deal_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, const void *coeffs, size_t t,
+                               size_t parties, void *out, size_t out_stride);
+/* out[dst ? dst[i] : i] = sum_{p < parties} weights[p] parts[p][i] for i < n.  weights: parties x 32 bytes in HOST
+ * memory; dst: n uint32 in device memory or NULL - the caller keeps every dst[i] inside out, positions that no dst[i]
+ * names are left alone.  The products are summed unreduced and reduced once, which is why every operand must be a
+ * canonical residue: a weight >= l is VMPC_E_NONCANON at once; an element of parts >= l leaves its output unwritten
+ * and the next vmpc_ctx_sync answers VMPC_E_NONCANON.  part_stride >= n, else VMPC_E_INVAL. */
+int vmpc_fr_share_combine_dev(vmpc_ctx *ctx, const void *parts, size_t parties, size_t n, size_t part_stride,
+                              const uint8_t *weights, const uint32_t *dst, void *out);
 
 /* ---- Pi_Nullity (AC20 p. 17-18, verifiable_mpc/ac20/nullity.py:21-40): s dense linear forms over n variables as a
  * row-major matrix in device memory, row i at rows + 32 i row_stride, 32-byte little-endian elements.  ANY 256-bit

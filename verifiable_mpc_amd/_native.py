@@ -52,6 +52,7 @@ SYMBOLS = [
     "vmpc_fr_cs_triples_dev", "vmpc_fr_cs_tables_dev", "vmpc_fr_cs_extend_dev", "vmpc_fr_cs_lagrange_dev",
     "vmpc_fr_cs_colsum_dev", "vmpc_fr_cs_first_diff_dev",
     "vmpc_fr_rows_combine_dev", "vmpc_fr_rows_dot_dev", "vmpc_fr_batch_products_dev",
+    "vmpc_fr_cs_extend_fg_dev", "vmpc_fr_share_mul_deal_dev", "vmpc_fr_share_combine_dev",
 ]
 
 
@@ -171,6 +172,9 @@ def load_library():
         "vmpc_fr_cs_triples_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, i32, vp]),
         "vmpc_fr_cs_tables_dev": (i32, [vp, sz, vp, vp]),
         "vmpc_fr_cs_extend_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
+        "vmpc_fr_cs_extend_fg_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
+        "vmpc_fr_share_mul_deal_dev": (i32, [vp, vp, vp, sz, vp, sz, sz, vp, sz]),
+        "vmpc_fr_share_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
         "vmpc_fr_cs_lagrange_dev": (i32, [vp, vp, sz, vp, vp]),
         "vmpc_fr_cs_colsum_dev": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_fr_cs_first_diff_dev": (i32, [vp, vp, vp, sz, vp]),
@@ -815,6 +819,26 @@ class Context:
         p = ctypes.c_void_p
         _check(self.lib.vmpc_fr_cs_extend_dev(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr),
                                               p(z_tail_ptr)), "vmpc_fr_cs_extend_dev")
+
+    def cs_extend_fg(self, a_ptr, b_ptr, m, fact_ptr, ifact_ptr, f_out_ptr, g_out_ptr):
+        """f(0), f(m+2..2m) and g alike, unmultiplied (max(m, 1) scalars each)"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_fr_cs_extend_fg_dev(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr),
+                                                 p(f_out_ptr), p(g_out_ptr)), "vmpc_fr_cs_extend_fg_dev")
+
+    # ---- Shamir sharings of vectors (csrc/mpc_share.hip) -------------------------------------------------------------
+    def share_mul_deal(self, a_ptr, b_ptr, n, coeffs_ptr, t, parties, out_ptr, out_stride):
+        """out[q][i] = a_i b_i (b_ptr None: a_i) + sum_k coeffs[k-1][i] (q + 1)^k, q < parties"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_fr_share_mul_deal_dev(self.handle, p(a_ptr), p(b_ptr), n, p(coeffs_ptr), t, parties,
+                                                   p(out_ptr), out_stride), "vmpc_fr_share_mul_deal_dev")
+
+    def share_combine(self, parts_ptr, parties, n, part_stride, weights, dst_ptr, out_ptr):
+        """out[dst[i]] (dst_ptr None: out[i]) = sum_p weights[p] parts[p][i]; weights: ints"""
+        p = ctypes.c_void_p
+        wb = ctypes.create_string_buffer(b"".join(scalar_to_bytes(w) for w in weights), 32 * max(len(weights), 1))
+        _check(self.lib.vmpc_fr_share_combine_dev(self.handle, p(parts_ptr), parties, n, part_stride, wb, p(dst_ptr),
+                                                  p(out_ptr)), "vmpc_fr_share_combine_dev")
 
     def cs_lagrange(self, c, K, ifact_ptr, out_ptr):
         cb = ctypes.create_string_buffer(scalar_to_bytes(c), 32)

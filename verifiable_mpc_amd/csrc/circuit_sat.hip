@@ -20,6 +20,8 @@
 //                             k_frbn_polymul (csrc/bn256_koe.hip); f and g share the staged T.  Every x meets every j,
 //                             so the work per tile is uniform; the range of j is cut into segments for occupancy, their
 //                             partial sums added in a fixed order.  Integer sums only: deterministic.
+//   vmpc_fr_cs_extend_fg_dev  the same f(x), g(x) left apart and unmultiplied, for a witness that is a vector of Shamir
+//                             shares: the extension is linear in v, the product is the parties' (csrc/mpc_share.hip)
 //   vmpc_fr_cs_lagrange_dev   the Lagrange vector of the nodes 0..K at c (ac20/recombine.py:5-32, a double loop):
 //                             lambda_j = prod_{i != j} (c - i) * (-1)^(K-j) / (j! (K-j)!) - prefix and suffix products
 //                             of (c - i), no inversion at all, so a c on a node cannot divide by zero here (the
@@ -268,10 +270,31 @@ k_cs_finish(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restri
     }
 }
 
-extern "C" int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
-                                     const void *ifact, void *z_tail) {
-    if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
-    if (!ctx || !a || !b || !fact || !ifact || !z_tail) return VMPC_E_INVAL;
+// the same sums with f and g kept apart and nothing multiplied: f_out[0] = f(0), f_out[1 + o] = f(m + 2 + o) for
+// o < n_out, g alike (the shares of a secret-shared witness: a product of shares is not local, csrc/mpc_share.hip)
+__global__ void __launch_bounds__(CS_WG)
+k_cs_finish_fg(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restrict__ part_f,
+               const uint32_t *__restrict__ part_g, const uint32_t *__restrict__ s0, const uint32_t *__restrict__ fact,
+               const uint32_t *__restrict__ ifact, uint32_t *__restrict__ f_out, uint32_t *__restrict__ g_out) {
+    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t M = m + 1;
+    if (o < n_out) {
+        const fr sf = fr_partsum<fr>(part_f, n_out, n_seg, o), sg = fr_partsum<fr>(part_g, n_out, n_seg, o);
+        const uint32_t x = m + 2 + o;
+        const fr lx = fr_mul(f256_ld<fr>(fact, x - 1), f256_ld<fr>(ifact, x - M - 1));
+        f256_st(f_out, 1 + (long long)o, fr_mul(lx, sf));
+        f256_st(g_out, 1 + (long long)o, fr_mul(lx, sg));
+    } else if (o == n_out) {
+        fr l0 = f256_ld<fr>(fact, M);
+        if (!(M & 1u)) l0 = fr_neg(l0);
+        f256_st(f_out, 0, fr_mul(l0, f256_ld<fr>(s0, 0)));
+        f256_st(g_out, 0, fr_mul(l0, f256_ld<fr>(s0, 1)));
+    }
+}
+
+// z_tail: k_cs_finish writes f(0), g(0) and the products; otherwise k_cs_finish_fg writes f_out, g_out
+static int cs_extend(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact, const void *ifact,
+                     void *z_tail, void *f_out, void *g_out) {
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const long long M = (long long)m + 1, n_t = 2 * (long long)m + 2;
     const long long n_out = m >= 2 ? (long long)m - 1 : 0, k_lo = (long long)m + 1;
@@ -303,12 +326,32 @@ extern "C" int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b
     }
     {
         vmpc_stage_scope sc(ctx, "cs_extend_finish");
-        k_cs_finish<<<(unsigned)((n_out + 1 + CS_WG - 1) / CS_WG), CS_WG, 0, ctx->stream>>>(
-            (uint32_t)m, (uint32_t)n_out, n_seg, pf, pg, s0, (const uint32_t *)a, (const uint32_t *)b,
-            (const uint32_t *)fact, (const uint32_t *)ifact, (uint32_t *)z_tail);
+        const unsigned grid = (unsigned)((n_out + 1 + CS_WG - 1) / CS_WG);
+        if (z_tail)
+            k_cs_finish<<<grid, CS_WG, 0, ctx->stream>>>((uint32_t)m, (uint32_t)n_out, n_seg, pf, pg, s0, (const uint32_t *)a,
+                                                         (const uint32_t *)b, (const uint32_t *)fact,
+                                                         (const uint32_t *)ifact, (uint32_t *)z_tail);
+        else
+            k_cs_finish_fg<<<grid, CS_WG, 0, ctx->stream>>>((uint32_t)m, (uint32_t)n_out, n_seg, pf, pg, s0,
+                                                            (const uint32_t *)fact, (const uint32_t *)ifact,
+                                                            (uint32_t *)f_out, (uint32_t *)g_out);
         VMPC_KERNEL_CHECK();
     }
     return VMPC_OK;
+}
+
+extern "C" int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
+                                     const void *ifact, void *z_tail) {
+    if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !fact || !ifact || !z_tail) return VMPC_E_INVAL;
+    return cs_extend(ctx, a, b, m, fact, ifact, z_tail, nullptr, nullptr);
+}
+
+extern "C" int vmpc_fr_cs_extend_fg_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
+                                        const void *ifact, void *f_out, void *g_out) {
+    if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !fact || !ifact || !f_out || !g_out) return VMPC_E_INVAL;
+    return cs_extend(ctx, a, b, m, fact, ifact, nullptr, f_out, g_out);
 }
 
 // ---- transposed sparse mat-vec -----------------------------------------------------------------------------------------
