@@ -33,6 +33,47 @@ def counter_avgs(dirname, counter):
     return {k: (sum(v) / len(v), len(v)) for k, v in rows.items()}
 
 
+def bucket_launches_by_grid(dirname, counter):
+    """k_msm_bucket's counter values, one list per launch grid (threads)"""
+    groups = {}
+    paths = sorted(glob.glob(os.path.join(dirname, "**", "*counter_collection.csv"), recursive=True),
+                   key=os.path.getmtime)
+    for path in paths[-1:]:
+        with open(path) as f:
+            for r in csv.DictReader(f):
+                if r.get("Counter_Name") == counter and "k_msm_bucket" in r["Kernel_Name"] and \
+                        "k_msm_bucket_finish" not in r["Kernel_Name"]:
+                    groups.setdefault(int(r["Grid_Size"]), []).append(float(r["Counter_Value"]))
+    return groups
+
+
+def bucket_plans(n):
+    """The plans bench.py launches k_msm_bucket over at n terms: the launch grid (msm_layout's t_max, rounded up to
+    256-thread workgroups) and the bytes the stage cannot do without - per entry a 128-B table line and a 4-B sorted
+    index, per task a 16-byte record, per bucket a 160-B accumulator written."""
+    def grid(entries, seg, buckets):
+        t_max = entries // seg + min(entries, buckets)
+        return (t_max + 255) // 256 * 256
+    stride = (n + 8191) // 8192 * 8192
+    wide_entries, wide_buckets = 13 * stride, 1 << 19
+    w16_entries, w16_buckets = 16 * n, 16 << 15
+    seg = 64
+    while seg < 1024 and (seg << 18) < w16_entries:          # msm_plan_geometry's segment length
+        seg *= 2
+    wseg = 64
+    while wseg < 1024 and (wseg << 18) < wide_entries:
+        wseg *= 2
+    return {
+        "wide_13_rows": {"grid_threads": grid(wide_entries, wseg, wide_buckets),
+                         "structural_bytes": 13 * n * (128 + 4) + wide_buckets * 160 + wide_buckets * 16,
+                         "note": "13 rows x n terms x (128-B table line + 4-B sorted index) read, 2^19 buckets x "
+                                 "(16-B task record read + 160 B written)"},
+        "16_windows": {"grid_threads": grid(w16_entries, seg, w16_buckets),
+                       "structural_bytes": 16 * n * (128 + 4) + w16_buckets * 160 + w16_buckets * 16,
+                       "note": "16 windows x n terms x (128-B table line + 4-B sorted index) read, 16 x 2^15 buckets "
+                               "x (16-B task record read + 160 B written)"}}
+
+
 def calibration(out, tag):
     """bytes per FETCH_SIZE KiB for the probe's three patterns and two table sizes (scripts/traffic_calibration.py)"""
     d = os.path.join(out, f"pmc_calib_{tag}")
@@ -108,18 +149,44 @@ def main():
         with open(os.path.join(out, f"revision_{tag}.txt")) as f:
             rev = f.read().strip() or None
     if calib and "error" not in calib and "k_msm_bucket" in kernels:
-        # k_msm_bucket's reads are one-lane-per-line gathers from the 128-MiB prepared-generator table plus the
-        # sorted index stream (4 B per entry, in order): apply the factor measured for the gather in this pass
+        # k_msm_bucket's reads are one-lane-per-line gathers from the table plus the sorted index stream (4 B per
+        # entry) and one 16-byte task record per task: apply the factor measured for the gather in this pass.  The
+        # bench launches the kernel over more than one plan (the wide-window table of the headline, the 16-window
+        # commitments it reports beside it); the launch grid tells them apart, and each plan is priced by its own
+        # rows, buckets and record sizes
         key = "gather_random_lines_128MiB"
         fac = calib[key]["bytes_per_FETCH_SIZE_byte"]
+        n = 1 << 20
+        try:
+            with open(os.path.join(out, f"bench_{tag}.json")) as f:
+                n = int(json.loads(f.read().strip().splitlines()[-1]).get("terms_per_gpu", n))
+        except (OSError, ValueError, IndexError):
+            pass
+        fetch_g = bucket_launches_by_grid(os.path.join(out, f"pmc_fetch_{tag}"), "FETCH_SIZE")
+        write_g = bucket_launches_by_grid(os.path.join(out, f"pmc_write_{tag}"), "WRITE_SIZE")
+        plans = {}
+        for name, plan in bucket_plans(n).items():
+            g = plan["grid_threads"]
+            if g not in fetch_g or g not in write_g:
+                continue
+            f_kib, w_kib = sum(fetch_g[g]) / len(fetch_g[g]), sum(write_g[g]) / len(write_g[g])
+            hbm = (fac * f_kib + w_kib) * 1024.0
+            plans[name] = {"launches_FETCH_SIZE": len(fetch_g[g]), "launches_WRITE_SIZE": len(write_g[g]),
+                           "FETCH_SIZE_KiB_avg": f_kib, "WRITE_SIZE_KiB_avg": w_kib, "hbm_bytes_per_launch": hbm,
+                           "structural_bytes": plan["structural_bytes"], "structural_note": plan["note"],
+                           "traffic_over_structural": hbm / plan["structural_bytes"]}
+        # the figure bench.py's roofline entry quotes is the headline plan's (the wide-window table) when the pass
+        # launched it, otherwise the average over every launch priced as 16-window commitments
         kb = kernels["k_msm_bucket"]
-        n, windows = 1 << 20, 16
-        calibrated["k_msm_bucket"] = {
-            "fetch_factor": fac, "factor_from": key,
+        head = plans.get("wide_13_rows") or {
             "hbm_bytes_per_launch": (fac * kb["FETCH_SIZE_KiB_avg"] + kb["WRITE_SIZE_KiB_avg"]) * 1024.0,
-            "structural_bytes": windows * n * (128 + 4) + windows * (1 << 15) * 160,
-            "structural_note": "16 windows x 2^20 terms x (128-B table line + 4-B sorted index) read, "
-                               "16 x 2^15 buckets x 160 B written"}
+            "structural_bytes": bucket_plans(n)["16_windows"]["structural_bytes"],
+            "structural_note": bucket_plans(n)["16_windows"]["note"] + " (all launches averaged)"}
+        calibrated["k_msm_bucket"] = {
+            "fetch_factor": fac, "factor_from": key, "terms": n,
+            "hbm_bytes_per_launch": head["hbm_bytes_per_launch"], "structural_bytes": head["structural_bytes"],
+            "structural_note": head["structural_note"],
+            "traffic_over_structural": head["hbm_bytes_per_launch"] / head["structural_bytes"], "plans": plans}
     sources = {}
     if os.path.exists(os.path.join(out, f"sources_{tag}.txt")):
         with open(os.path.join(out, f"sources_{tag}.txt")) as f:

@@ -30,32 +30,23 @@ gk_prep(const uint32_t *__restrict__ pts, size_t n_total, uint32_t *__restrict__
     C::entry_st(entries + (size_t)C::ENTRY_WORDS * i, a);
 }
 
-// ---- bucket accumulation: one lane per segment (task table from msm_sort_stage) -------------------
+// ---- bucket accumulation: one lane per segment (task records from msm_sort_stage, msm_sort.h) ------
 template <class C>
 __global__ void __launch_bounds__(MSM_BLOCK)
 gk_bucket(const uint32_t *__restrict__ entries, const uint32_t *__restrict__ sorted,
-          const uint32_t *__restrict__ starts, const uint32_t *__restrict__ counts,
-          const uint32_t *__restrict__ nseg, const uint32_t *__restrict__ seg_starts,
-          const uint2 *__restrict__ tasks, const uint32_t *__restrict__ n_tasks, int nb1, int seg, int balanced,
+          const msm_task *__restrict__ tasks, const uint32_t *__restrict__ n_tasks,
           uint32_t *__restrict__ buckets, uint32_t *__restrict__ partial) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= *n_tasks) return;
-    uint2 tk = tasks[t];
-    uint32_t ci = tk.x, sidx = tk.y;
-    const uint32_t ns = nseg[ci];
-    uint32_t lo, len;
-    msm_seg_range(counts[ci], ns, sidx, (uint32_t)seg, balanced, lo, len);      // msm_sort.h
-    lo += starts[ci];
+    const msm_task tk = tasks[t];
+    const uint32_t lo = tk.x, len = tk.y;
     typename C::acc_t acc = C::identity();
     for (uint32_t j = 0; j < len; j++) {
         uint32_t e = sorted[lo + j];
         typename C::entry_t q = C::entry_ld(entries + (size_t)C::ENTRY_WORDS * (e & 0x7fffffffu));
         acc = C::madd(acc, q, (e >> 31) != 0);
     }
-    if (ns == 1)
-        C::acc_st(buckets + (size_t)C::ACC_WORDS * msm_bucket_slot(ci, nb1), acc);
-    else
-        C::acc_st(partial + (size_t)C::ACC_WORDS * (seg_starts[ci] + sidx), acc);
+    C::acc_st(((tk.w & MSM_TASK_SPLIT) ? partial : buckets) + (size_t)C::ACC_WORDS * tk.z, acc);
 }
 
 template <class C, class F>
@@ -307,8 +298,7 @@ template <class C, class F>
 int bn_kernels<C, F>::bucket(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w, const uint32_t *entries) {
     hipStream_t st = ctx->stream;
     gk_bucket<C><<<(unsigned)((w.t_max + MSM_BLOCK - 1) / MSM_BLOCK), MSM_BLOCK, 0, st>>>(
-        entries, w.sorted, w.starts, w.counts, w.nseg, w.seg_starts, w.tasks, w.ctrl + 1, p.nb1,
-        (int)msm_seg_len(p), p.balanced, w.buckets, w.seg_partial);
+        entries, w.sorted, w.tasks, w.ctrl + 1, w.buckets, w.seg_partial);
     VMPC_KERNEL_CHECK();
     gk_finish_light<C, F><<<2 * ctx->cu_count, MSM_BLOCK, 0, st>>>(w.heavy_list, w.ctrl, w.nseg, w.seg_starts,
                                                                   w.seg_partial, p.nb1, w.buckets);

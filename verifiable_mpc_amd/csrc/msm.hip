@@ -15,9 +15,9 @@
 //   reduce   per window: chunked running sums + LDS tree -> sum_b b*B_b partials
 //   final    window sums, Horner over windows (c doublings each), one inversion -> affine
 //
-// HBM traffic is dominated by the 96-B niels gathers (W per term) and the 4-B sorted
-// indices; the algorithmic bytes of SURVEY.md 8d are 96 B per term (32 B scalar + 64 B
-// point).  Arithmetic is 32x32->64 integer multiply-add; no MFMA.
+// HBM traffic is dominated by the niels gathers (one 128-B line per term and window: 96 B of
+// entry, padded to the line) and the 4-B sorted indices; the algorithmic bytes of SURVEY.md 8d
+// are 96 B per term (32 B scalar + 64 B point).  Arithmetic is 32x32->64 integer multiply-add; no MFMA.
 #include <stdlib.h>
 
 #include "common.h"
@@ -56,41 +56,49 @@ __device__ __forceinline__ ge_niels niels_ld(const uint32_t *niels, uint32_t e) 
     return niels_ld_line(niels + NIELS_WORDS * (size_t)(e & 0x7fffffffu));
 }
 
-// one lane = one segment of <= MSM_SEG sorted entries
-#ifndef MSM_IDX_BATCH
-#define MSM_IDX_BATCH 4
-#endif
+// one lane = one segment of a bucket's run of sorted[] (task records: msm_sort.h)
 #ifndef MSM_BUCKET_WAVES
 #define MSM_BUCKET_WAVES 4
 #endif
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK, BLOCK == MSM_BLOCK ? MSM_BUCKET_WAVES : 1)
+// Sorted indices go through LDS, MSM_IDX_WIN at a time.  A lane walks its own run, so the lanes' index loads are one
+// cache line per lane, and between two of a lane's visits to that line the chip streams a table line per resident
+// lane through an L2 that holds about as many: fetched as it is needed, an index line comes from HBM again and again
+// (4 indices per visit: 0.44 GB per 2^20-term wide-window commitment for 54 MB of indices).  Here a lane asks for a
+// whole window of its run in one burst of loads - before its first addition no accumulator or table entry is live,
+// so the burst has the registers - and parks it in its own column of the stage.  The stage is [entry][thread]: the
+// 64 lanes of a wave read 64 consecutive words, one per bank.  32 entries x 256 threads = 32 KB per workgroup, four
+// workgroups per CU in 128 of the 160 KB.
+#define MSM_IDX_WIN 32
+// the first n of N entries from src into the lane's column: one burst of loads off one address, then the LDS stores
+// (slots past the run get zeros that nobody reads)
+template <int N>
+__device__ __forceinline__ void msm_idx_fill(uint32_t *__restrict__ col, const uint32_t *__restrict__ src, uint32_t n) {
+    uint32_t v[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = (uint32_t)k < n ? src[k] : 0u;
+#pragma unroll
+    for (int k = 0; k < N; k++) col[k * MSM_BLOCK] = v[k];
+}
+
+__global__ void __launch_bounds__(MSM_BLOCK, MSM_BUCKET_WAVES)
 k_msm_bucket(const uint32_t *__restrict__ niels, const uint32_t *__restrict__ sorted,
-             const uint32_t *__restrict__ starts, const uint32_t *__restrict__ counts,
-             const uint32_t *__restrict__ nseg, const uint32_t *__restrict__ seg_starts,
-             const uint2 *__restrict__ tasks, const uint32_t *__restrict__ n_tasks, int nb1, int seg, int balanced,
+             const msm_task *__restrict__ tasks, const uint32_t *__restrict__ n_tasks,
              uint32_t *__restrict__ buckets, uint32_t *__restrict__ partial) {
+    __shared__ uint32_t idx_stage[MSM_IDX_WIN * MSM_BLOCK];
+    uint32_t *const col = idx_stage + threadIdx.x;      // this lane's column: nobody else touches it, no barriers
     // grid-stride over the task table: a launch with fewer workgroups than tasks / 256 (persistent form,
     // msm_accumulate) leaves register-file room on every SIMD for other streams' kernels
     // (measured and dropped, round 4: the stage as 2 / 4 / 8 launches over slices of the task table, to give other
     // streams' kernels a way in at every slice boundary - 0.87 / 0.87 / 0.90 ms per commitment against 0.875)
     const uint32_t n_live = *n_tasks;
     for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n_live; t += gridDim.x * blockDim.x) {
-    uint2 tk = tasks[t];
-    uint32_t ci = tk.x, sidx = tk.y;
-    const uint32_t ns = nseg[ci];
-    uint32_t lo, len;
-    msm_seg_range(counts[ci], ns, sidx, (uint32_t)seg, balanced, lo, len);
-    lo += starts[ci];
+    const msm_task tk = tasks[t];              // one 16-byte load: where the run is and where its sum goes (msm_sort.h)
+    const uint32_t *run = sorted + tk.x;
+    const uint32_t len = tk.y;
+    // (tasks are numbered by length, so the lanes of a wave agree on the short burst almost always)
+    if (len <= 8) msm_idx_fill<8>(col, run, len);
+    else msm_idx_fill<MSM_IDX_WIN>(col, run, len);
     ge_ext acc = ge_ext_identity();
-    // Sorted indices in groups of MSM_IDX_BATCH.  A lane walks its own segment, so the lanes' 4-byte index loads
-    // are >= 256 bytes apart - one cache line per lane - and with 2^18 lanes in flight (64 MB of lines in use
-    // against 32 MB of L2) that line has usually left the L2 by the time the lane comes back for its next
-    // index: one index at a time, the kernel moved 3.7 GB per launch over the fabric for 2.2 GB of table lines
-    // and 0.07 GB of indices (profiles/r03a_pmc_summary.json).  Asking for a group's indices back to back lets
-    // them share the line the first request brings in: 3.0 GB (scripts/pmc_ab.sh).  The kernel's TIME does not
-    // change (integer-ALU bound; 8 at a time is slower: registers) - this only stops wasting fabric bandwidth
-    // that the sort kernels of the next commitment in flight can use.
     // The next table entry is requested one addition ahead, but the compiler hoists its sign selection to right
     // behind the load, so in effect the gather latency is hidden by the 4 waves per SIMD, not by this
     // "prefetch".  A hand-scheduled version (inline-asm loads + manual s_waitcnt after the 7 multiplications,
@@ -104,35 +112,26 @@ k_msm_bucket(const uint32_t *__restrict__ niels, const uint32_t *__restrict__ so
     // early both take the same 660 us as this kernel; confined to 3 / 2 / 1 workgroups per CU all of them take 735 /
     // 760-770 / 880 us, with or without prefetch.  It is bound by vector-ALU issue, not by the gather's latency:
     // one wave per SIMD already issues 75 % of what four do.
-    uint32_t ev[MSM_IDX_BATCH];
-#pragma unroll
-    for (int k = 0; k < MSM_IDX_BATCH; k++) ev[k] = sorted[lo + ((uint32_t)k < len ? (uint32_t)k : len - 1)];
-    uint32_t e = ev[0];
-    ge_niels q = niels_ld(niels, e);
-    for (uint32_t j0 = 0; j0 < len; j0 += MSM_IDX_BATCH) {
-        uint32_t en_v[MSM_IDX_BATCH];
-#pragma unroll
-        for (int k = 0; k < MSM_IDX_BATCH; k++) {
-            const uint32_t jj = j0 + MSM_IDX_BATCH + (uint32_t)k;
-            en_v[k] = sorted[lo + (jj < len ? jj : len - 1)];
+    for (uint32_t left = len;;) {
+        const uint32_t n = left < MSM_IDX_WIN ? left : MSM_IDX_WIN;
+        uint32_t e = col[0];
+        ge_niels q = niels_ld(niels, e);
+        for (uint32_t k = 0; k < n; k++) {
+            // (the window's last addition asks for its own line once more: a hit)
+            const uint32_t en = col[(k + 1 < n ? k + 1 : k) * MSM_BLOCK];
+            ge_niels qn = niels_ld(niels, en);
+            acc = ge_madd(acc, ge_niels_select_neg(q, (e >> 31) != 0));
+            e = en;
+            q = qn;
         }
-#pragma unroll
-        for (int k = 0; k < MSM_IDX_BATCH; k++) {
-            if (j0 + (uint32_t)k < len) {
-                const uint32_t en = k + 1 < MSM_IDX_BATCH ? ev[k + 1 < MSM_IDX_BATCH ? k + 1 : 0] : en_v[0];
-                ge_niels qn = niels_ld(niels, en);
-                acc = ge_madd(acc, ge_niels_select_neg(q, (e >> 31) != 0));
-                e = en;
-                q = qn;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < MSM_IDX_BATCH; k++) ev[k] = en_v[k];
+        if (left <= MSM_IDX_WIN) break;
+        // a run longer than the window refills it in place; the accumulator is live now, so eight loads at a time
+        left -= MSM_IDX_WIN;
+        run += MSM_IDX_WIN;
+        for (uint32_t k0 = 0; k0 < MSM_IDX_WIN && k0 < left; k0 += 8)
+            msm_idx_fill<8>(col + k0 * MSM_BLOCK, run + k0, left - k0);
     }
-    if (ns == 1)
-        ext_st(buckets + EXT_WORDS * msm_bucket_slot(ci, nb1), acc);
-    else
-        ext_st(partial + EXT_WORDS * (size_t)(seg_starts[ci] + sidx), acc);
+    ext_st(((tk.w & MSM_TASK_SPLIT) ? partial : buckets) + EXT_WORDS * (size_t)tk.z, acc);
     }
 }
 
@@ -428,17 +427,7 @@ static int msm_accumulate(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w, const uin
         unsigned grid = (unsigned)((w.t_max + MSM_BLOCK - 1) / MSM_BLOCK);
         if (ctx->bucket_wgs_per_cu > 0 && (unsigned)(ctx->bucket_wgs_per_cu * ctx->cu_count) < grid)
             grid = (unsigned)(ctx->bucket_wgs_per_cu * ctx->cu_count);
-        if (ctx->bucket_block == 1024) {
-            // experiment (VMPC_EXPERIMENTAL=1 VMPC_BUCKET_BLOCK=1024): one workgroup fills a CU, so a retiring one frees
-            // a whole CU at once - room for the 1024-thread sort workgroups of the other streams
-            k_msm_bucket<1024><<<(grid + 3) / 4, 1024, 0, bst>>>(
-                entries, w.sorted, w.starts, w.counts, w.nseg, w.seg_starts, w.tasks, w.ctrl + 1, p.nb1,
-                (int)msm_seg_len(p), p.balanced, w.buckets, w.seg_partial);
-        } else {
-            k_msm_bucket<MSM_BLOCK><<<grid, MSM_BLOCK, 0, bst>>>(
-                entries, w.sorted, w.starts, w.counts, w.nseg, w.seg_starts, w.tasks, w.ctrl + 1, p.nb1,
-                (int)msm_seg_len(p), p.balanced, w.buckets, w.seg_partial);
-        }
+        k_msm_bucket<<<grid, MSM_BLOCK, 0, bst>>>(entries, w.sorted, w.tasks, w.ctrl + 1, w.buckets, w.seg_partial);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             ctx->stage_stream = nullptr;

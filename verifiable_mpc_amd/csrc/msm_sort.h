@@ -50,6 +50,15 @@ struct msm_plan {
 inline size_t msm_seg_len(const msm_plan &p) { return (size_t)1 << (MSM_SEG_LOG2 + p.seg_shift); }
 
 
+// One task of the bucket stage = one segment of a bucket's run of sorted[], self-contained: k_msm_plan2 writes it from
+// what it holds in registers (counts, starts, seg_starts of its bucket, read coalesced), and the bucket kernels read
+// nothing else about the bucket - one aligned 16-byte load per lane instead of three 4-byte gathers at a random bucket.
+//   x = first position in sorted[], y = length, z = destination accumulator, w = MSM_TASK_SPLIT or 0
+// The destination indexes `buckets` (msm_bucket_slot) for a bucket that is one segment, and `seg_partial`
+// (seg_starts[ci] + segment) when MSM_TASK_SPLIT says the bucket was cut: the finish kernels add those up.
+typedef uint4 msm_task;
+#define MSM_TASK_SPLIT 1u
+
 struct msm_ws {
     uint32_t *entries;      // prepared points, entry_bytes each
     uint32_t *hist1;        // [W][NC][J] coarse-bin counts per chunk, scanned in place; [hist1_n] = #entries
@@ -60,7 +69,7 @@ struct msm_ws {
     uint32_t *partials;     // W * red_blocks accumulators (msm_reduce_tree: W window sums, then 3 W red_blocks)
     uint32_t *nseg, *seg_starts, *block_hist, *block_base, *heavy_list, *ctrl;
     uint32_t *seg_partial;  // per-segment partial sums, acc_bytes each
-    uint2 *tasks;
+    msm_task *tasks;
     int16_t *digits;        // int32 rows when the plan is `wide`
     void *scan_ws;
     size_t total;
@@ -82,7 +91,7 @@ bool msm_reduce_tree_fits(const msm_plan &p);
 int msm_reduce_tree_split(const msm_plan &p);      // partial results per window that k_msm_final adds (1: none)
 int msm_reduce_tree(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w, hipStream_t st, void *out_packed);
 // recode -> hist1 -> scan -> part1 -> fine -> plan: fills digits, sorted, starts, counts, nseg,
-// seg_starts, heavy_list, tasks, ctrl[0] = #split buckets, ctrl[1] = #tasks
+// seg_starts, heavy_list, tasks (msm_task records), ctrl[0] = #split buckets, ctrl[1] = #tasks
 int msm_sort_stage(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w, const void *scalars, size_t n,
                    const void *extra_scalars, const msm_modulus &modulus);
 int msm_sort_digits(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w);   // the same minus the recoding
@@ -139,4 +148,13 @@ __device__ __forceinline__ void msm_seg_range(uint32_t cnt, uint32_t ns, uint32_
 __device__ __forceinline__ size_t msm_bucket_slot(uint32_t ci, int nb1) {
     uint32_t w = ci / (uint32_t)nb1;
     return (size_t)ci - w - 1;
+}
+
+// segment sidx of bucket ci (cnt entries from sorted[start], ns segments) as a task record
+__device__ __forceinline__ msm_task msm_make_task(uint32_t ci, uint32_t start, uint32_t cnt, uint32_t ns, uint32_t sidx,
+                                                  uint32_t seg, int balanced, uint32_t seg_start, int nb1) {
+    uint32_t off, len;
+    msm_seg_range(cnt, ns, sidx, seg, balanced, off, len);
+    if (ns <= 1) return make_uint4(start + off, len, (uint32_t)msm_bucket_slot(ci, nb1), 0u);
+    return make_uint4(start + off, len, seg_start + sidx, MSM_TASK_SPLIT);
 }

@@ -673,12 +673,15 @@ k_msm_ranks_classes(uint32_t *__restrict__ block_hist, int NC, int W, uint32_t *
 }
 
 // plan, pass 2 (pass 1 is the tail of k_sort_fine): one block per (window, coarse bin), one thread per
-// bucket: task id = first id of the (length, window) cell + this block's first rank in it + a local rank
+// bucket: task id = first id of the (length, window) cell + this block's first rank in it + a local rank.
+// The thread has its bucket's count, start and (when split) partial-sum base from coalesced reads, so the record it
+// writes is complete (msm_sort.h, msm_task): the bucket kernels never look the bucket up again.
 __global__ void __launch_bounds__(512)
-k_msm_plan2(const uint32_t *__restrict__ counts, int NC, int W, int NF, int top_row, int period, int NF_top, int nb1,
+k_msm_plan2(const uint32_t *__restrict__ counts, const uint32_t *__restrict__ starts,
+            const uint32_t *__restrict__ seg_starts, int NC, int W, int NF, int top_row, int period, int NF_top, int nb1,
             int seg_shift, int balanced,
             const uint32_t *__restrict__ class_base, const uint32_t *__restrict__ block_rank,
-            uint2 *__restrict__ tasks) {
+            msm_task *__restrict__ tasks) {
     const uint32_t seg_log = (uint32_t)(MSM_SEG_LOG2 + seg_shift);
     __shared__ uint32_t cur[MSM_SEG + 1], first[MSM_SEG + 1];
     const uint32_t block = blockIdx.x;
@@ -694,22 +697,26 @@ k_msm_plan2(const uint32_t *__restrict__ counts, int NC, int W, int NF, int top_
     const size_t ci = (size_t)w * nb1 + 1 + (size_t)cb * NF + threadIdx.x;
     const uint32_t cnt = counts[ci];
     const uint32_t ns = msm_seg_count(cnt, seg_log);
-    if (balanced) {
-        if (ns) {                               // the bucket's ns equal segments are consecutive tasks of one class
-            const uint32_t bin = msm_seg_class((cnt + ns - 1u) / ns, seg_shift);
-            const uint32_t base = first[bin] + atomicAdd(&cur[bin], ns);
-            for (uint32_t sidx = 0; sidx < ns; sidx++) tasks[base + sidx] = make_uint2((uint32_t)ci, sidx);
-        }
+    if (ns == 0) return;
+    const uint32_t start = starts[ci], seg = 1u << seg_log;
+    const uint32_t seg_start = ns > 1 ? seg_starts[ci] : 0u;        // (written for split buckets only)
+    if (balanced) {                             // the bucket's ns equal segments are consecutive tasks of one class
+        const uint32_t bin = msm_seg_class((cnt + ns - 1u) / ns, seg_shift);
+        const uint32_t base = first[bin] + atomicAdd(&cur[bin], ns);
+        for (uint32_t sidx = 0; sidx < ns; sidx++)
+            tasks[base + sidx] = msm_make_task((uint32_t)ci, start, cnt, ns, sidx, seg, 1, seg_start, nb1);
         return;
     }
-    const uint32_t full = cnt >> seg_log, rem = cnt & ((1u << seg_log) - 1u);
+    const uint32_t full = cnt >> seg_log, rem = cnt & (seg - 1u);
     if (rem) {
         const uint32_t bin = msm_seg_class(rem, seg_shift);
-        tasks[first[bin] + atomicAdd(&cur[bin], 1u)] = make_uint2((uint32_t)ci, full);
+        tasks[first[bin] + atomicAdd(&cur[bin], 1u)] =
+            msm_make_task((uint32_t)ci, start, cnt, ns, full, seg, 0, seg_start, nb1);
     }
     if (full) {
         const uint32_t base = first[MSM_SEG] + atomicAdd(&cur[MSM_SEG], full);
-        for (uint32_t sidx = 0; sidx < full; sidx++) tasks[base + sidx] = make_uint2((uint32_t)ci, sidx);
+        for (uint32_t sidx = 0; sidx < full; sidx++)
+            tasks[base + sidx] = msm_make_task((uint32_t)ci, start, cnt, ns, sidx, seg, 0, seg_start, nb1);
     }
 }
 
@@ -895,7 +902,7 @@ void msm_layout(const msm_plan &p, msm_ws &w, char *base, size_t entry_bytes, si
     w.seg_starts = (uint32_t *)take(nbk * 4);                 // written for split buckets only
     w.heavy_list = (uint32_t *)take(nbk * 4);
     w.ctrl = (uint32_t *)take((16 + (size_t)MSM_SEG * p.W) * 4);
-    w.tasks = (uint2 *)take(w.t_max * 8);
+    w.tasks = (msm_task *)take(w.t_max * sizeof(msm_task));
     w.seg_partial = (uint32_t *)take(w.t_max * acc_bytes);
     size_t scan_n = hist_n;
     if (w.hist1_n > scan_n) scan_n = w.hist1_n;
@@ -1047,8 +1054,9 @@ int msm_sort_digits(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w) {
             k_msm_classes<<<1, 1024, 0, st>>>(w.ctrl, p.W, w.block_base);
             VMPC_KERNEL_CHECK();
         }
-        k_msm_plan2<<<w.plan_blocks, 512, 0, st>>>(w.counts, p.NC, p.W, 1 << p.LB, p.top_row, p.period, 1 << p.LB_top,
-                                                  p.nb1, p.seg_shift, p.balanced, w.block_base, w.block_hist, w.tasks);
+        k_msm_plan2<<<w.plan_blocks, 512, 0, st>>>(w.counts, w.starts, w.seg_starts, p.NC, p.W, 1 << p.LB, p.top_row,
+                                                  p.period, 1 << p.LB_top, p.nb1, p.seg_shift, p.balanced, w.block_base,
+                                                  w.block_hist, w.tasks);
         VMPC_KERNEL_CHECK();
     }
     return VMPC_OK;
