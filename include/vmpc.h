@@ -459,7 +459,7 @@ int vmpc_bn256_keygen_exps_dev(vmpc_ctx *ctx, const void *coef, const void *vwy,
  * 14).  With w_j = t'(j) = (-1)^(d-j) (j-1)! (d-j)!, u_j = a_j / w_j and the moments A_k = sum_j u_j j^(k-1) (B_k from b),
  *     C_k = sum_{i=1..k-1} A_i B_(k-i) + delta_v B_k + delta_w A_k,   h_e = sum_{i=e+1..d} t_i C_(i-e) + delta_v delta_w t_e
  *                                                                            - [e = 0] delta_y      (e = 0..d).
- * Cap for all six entries: d + 1 <= VMPC_BN256_FR_POLY_MAX; above it they answer VMPC_E_RANGE before they look at any
+ * Cap for all seven entries: d + 1 <= VMPC_BN256_FR_POLY_MAX; above it they answer VMPC_E_RANGE before they look at any
  * pointer.  d >= 1. */
 /* out0[k] = sum_{j=1..d} u0[j-1] j^k mod n for k < n_out (n_out <= VMPC_BN256_FR_POLY_MAX), and the same for u1 -> out1
  * when u1 is not NULL (the two share the powers of j).  Replaces nothing the reference has: it stands in for the
@@ -473,6 +473,15 @@ int vmpc_bn256_qap_h_weights_dev(vmpc_ctx *ctx, const void *a, const void *b, si
 /* *first_bad (a device uint32) = the smallest i < d with a[i] * b[i] != y[i] mod n, 0xffffffff if there is none: the
  * check that the reference's demo makes on the remainder of p / qap.t.  No arena. */
 int vmpc_bn256_qap_check_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t d, uint32_t *first_bad);
+/* *out (ONE device scalar) = sum_{j<d} rho^j (a[j] b[j] - y[j]) mod n: the share-side replacement of the check above
+ * (demos/demo_zkp_trinocchio.py:70-72 divides p by qap.t in the clear and drops the remainder; a party that holds only
+ * Shamir shares of the witness has rows that never satisfy a_j b_j = y_j).  On degree-t shares of a satisfying witness
+ * the M parties' results are a degree-2t sharing of 0 for every rho; a violated row makes it nonzero for all but d of
+ * the rho.  rho: a canonical residue in HOST memory (VMPC_E_NONCANON otherwise).  Each lane sums its rows' unreduced
+ * products, workgroup partials go through the arena (at most 64 scalars) and are added in a fixed order:
+ * deterministic, no atomics. */
+int vmpc_bn256_qap_residual_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t d,
+                                const uint8_t rho[32], void *out);
 /* out[0..d] = the coefficients of t(x) = prod_{j=1..d} (x - j), lowest first (qap_creator.r1cs_to_qap_ff builds qap.t by
  * d Poly.__mul__): leaves of 128 factors and a product tree over vmpc_bn256_fr_poly_mul_dev.  scratch: device memory
  * of 2 (d + (d + 127) / 128) scalars (not read when d <= 128).  Uses the context arena as the products do. */
@@ -552,6 +561,22 @@ int vmpc_fr_share_mul_deal_dev(vmpc_ctx *ctx, const void *a, const void *b, size
  * and the next vmpc_ctx_sync answers VMPC_E_NONCANON.  part_stride >= n, else VMPC_E_INVAL. */
 int vmpc_fr_share_combine_dev(vmpc_ctx *ctx, const void *parts, size_t parties, size_t n, size_t part_stride,
                               const uint8_t *weights, const uint32_t *dst, void *out);
+
+/* ---- The same sharings mod n, BN-256's group order, for Pinocchio proofs from a shared witness
+ * (demos/demo_zkp_trinocchio.py:76-93: mpc.gather of the witness and h shares, compute_proof on them, recombination of
+ * the proof elements).  Conventions, caps and VMPC_SHARE_MAX_PARTIES as above. */
+/* vmpc_fr_share_mul_deal_dev over GF(n); the vector operands may be any 32-byte values and are taken mod n.  With
+ * b == NULL the Shamir dealer; with a all zeros and t = 2 t' the dealer of degree-2t' sharings of zero. */
+int vmpc_bn256_fr_share_mul_deal_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, const void *coeffs,
+                                     size_t t, size_t parties, void *out, size_t out_stride);
+/* out[dst ? dst[i] : i] = addend[i] + sum_{p < parties} weights[p] parts[p][i] for i < n; addend: n scalars in device
+ * memory (any 32-byte values, taken mod n) or NULL.  n^2 fills 512 bits - three products of n - 1 still fit 512 bits,
+ * four need 513 - so the products are summed in the wide accumulator of csrc/fr256.h (f256_acc) and reduced once.
+ * Canonicity as for vmpc_fr_share_combine_dev: a weight >= n is VMPC_E_NONCANON at once; an element of parts >= n
+ * leaves its output unwritten and the next vmpc_ctx_sync answers VMPC_E_NONCANON.  part_stride >= n, else
+ * VMPC_E_INVAL. */
+int vmpc_bn256_fr_share_combine_dev(vmpc_ctx *ctx, const void *parts, size_t parties, size_t n, size_t part_stride,
+                                    const uint8_t *weights, const uint32_t *dst, const void *addend, void *out);
 
 /* ---- Pi_Nullity (AC20 p. 17-18, verifiable_mpc/ac20/nullity.py:21-40): s dense linear forms over n variables as a
  * row-major matrix in device memory, row i at rows + 32 i row_stride, 32-byte little-endian elements.  ANY 256-bit

@@ -53,6 +53,7 @@ SYMBOLS = [
     "vmpc_fr_cs_colsum_dev", "vmpc_fr_cs_first_diff_dev",
     "vmpc_fr_rows_combine_dev", "vmpc_fr_rows_dot_dev", "vmpc_fr_batch_products_dev",
     "vmpc_fr_cs_extend_fg_dev", "vmpc_fr_share_mul_deal_dev", "vmpc_fr_share_combine_dev",
+    "vmpc_bn256_fr_share_mul_deal_dev", "vmpc_bn256_fr_share_combine_dev", "vmpc_bn256_qap_residual_dev",
 ]
 
 
@@ -175,6 +176,9 @@ def load_library():
         "vmpc_fr_cs_extend_fg_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
         "vmpc_fr_share_mul_deal_dev": (i32, [vp, vp, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_fr_share_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
+        "vmpc_bn256_fr_share_mul_deal_dev": (i32, [vp, vp, vp, sz, vp, sz, sz, vp, sz]),
+        "vmpc_bn256_fr_share_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp, vp]),
+        "vmpc_bn256_qap_residual_dev": (i32, [vp, vp, vp, vp, sz, vp, vp]),
         "vmpc_fr_cs_lagrange_dev": (i32, [vp, vp, sz, vp, vp]),
         "vmpc_fr_cs_colsum_dev": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_fr_cs_first_diff_dev": (i32, [vp, vp, vp, sz, vp]),
@@ -840,6 +844,20 @@ class Context:
         _check(self.lib.vmpc_fr_share_combine_dev(self.handle, p(parts_ptr), parties, n, part_stride, wb, p(dst_ptr),
                                                   p(out_ptr)), "vmpc_fr_share_combine_dev")
 
+    def bn256_share_mul_deal(self, a_ptr, b_ptr, n, coeffs_ptr, t, parties, out_ptr, out_stride):
+        """share_mul_deal over GF(n), the BN-256 order"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_bn256_fr_share_mul_deal_dev(self.handle, p(a_ptr), p(b_ptr), n, p(coeffs_ptr), t, parties,
+                                                         p(out_ptr), out_stride), "vmpc_bn256_fr_share_mul_deal_dev")
+
+    def bn256_share_combine(self, parts_ptr, parties, n, part_stride, weights, dst_ptr, addend_ptr, out_ptr):
+        """out[dst[i]] (dst_ptr None: out[i]) = addend[i] (addend_ptr None: 0) + sum_p weights[p] parts[p][i] mod n"""
+        p = ctypes.c_void_p
+        wb = ctypes.create_string_buffer(b"".join(scalar_to_bytes(w) for w in weights), 32 * max(len(weights), 1))
+        _check(self.lib.vmpc_bn256_fr_share_combine_dev(self.handle, p(parts_ptr), parties, n, part_stride, wb,
+                                                        p(dst_ptr), p(addend_ptr), p(out_ptr)),
+               "vmpc_bn256_fr_share_combine_dev")
+
     def cs_lagrange(self, c, K, ifact_ptr, out_ptr):
         cb = ctypes.create_string_buffer(scalar_to_bytes(c), 32)
         _check(self.lib.vmpc_fr_cs_lagrange_dev(self.handle, cb, K, ctypes.c_void_p(ifact_ptr), ctypes.c_void_p(out_ptr)),
@@ -997,6 +1015,13 @@ class Context:
         _check(self.lib.vmpc_bn256_qap_check_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr),
                                                  ctypes.c_void_p(y_ptr), d, ctypes.c_void_p(first_bad_ptr)),
                "vmpc_bn256_qap_check_dev")
+
+    def bn256_qap_residual(self, a_ptr, b_ptr, y_ptr, d, rho, out_ptr):
+        """device scalar at out_ptr = sum_{i<d} rho^i (a[i] b[i] - y[i]) mod n; rho: an int below n"""
+        rb = ctypes.create_string_buffer(scalar_to_bytes(rho), 32)
+        _check(self.lib.vmpc_bn256_qap_residual_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr),
+                                                    ctypes.c_void_p(y_ptr), d, rb, ctypes.c_void_p(out_ptr)),
+               "vmpc_bn256_qap_residual_dev")
 
     def bn256_qap_t_coeffs(self, d, scratch_ptr, out_ptr):
         """out[0..d] = coefficients of prod_{j=1..d} (x - j); scratch: 2 (d + ceil(d / 128)) scalars"""

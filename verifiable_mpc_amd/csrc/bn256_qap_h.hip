@@ -22,6 +22,8 @@
 //                                  1 / ((j-1)! (d-j)!) = E_(d-j+1) E_j / d!^2 - prefix products of small integers and ONE
 //                                  inversion, as vmpc_bn256_qap_lagrange_dev does for its Q_j.
 //   vmpc_bn256_qap_check_dev       the smallest j with a_j b_j != y_j
+//   vmpc_bn256_qap_residual_dev    sum_j rho^j (a_j b_j - y_j): what a party holding SHARES of the witness computes in
+//                                  place of the check (its own rows never satisfy a_j b_j = y_j)
 //   vmpc_bn256_qap_t_coeffs_dev    the d + 1 coefficients of t = prod (x - j): leaves of QH_LEAF factors multiplied out
 //                                  in LDS, then a product tree over vmpc_bn256_fr_poly_mul_dev
 //   vmpc_bn256_qap_horner_dev      P(1), .., P(d) of coefficient vectors (the dense QAP form), one lane per point
@@ -32,6 +34,7 @@
 #include "fr_bn.h"
 #include "fr_conv.h"
 #include "fr_scan.h"
+#include "share_combine.h"
 
 #define QH_WG 256
 #define QH_J 4                      // running values per lane and vector
@@ -42,6 +45,7 @@
 #define QH_TARGET_WGS 2048
 #define QH_RUN 64                   // sequence elements per lane in the weights' scan
 #define QH_LEAF 128                 // factors (x - j) per leaf of t's product tree
+#define QH_RES_MAX_WGS 64           // workgroups (partials) of the residual at most: rows beyond 64 x 256 share lanes
 
 // the sum of x over the 64 lanes (uniform), for lane values below 2^26: rows of 16 by DPP (xor 1, xor 2, half
 // mirror, mirror leave the row's sum in every lane), the four rows by readlane
@@ -204,7 +208,7 @@ extern "C" int vmpc_bn256_qap_moments_dev(vmpc_ctx *ctx, const void *u0, const v
     return VMPC_OK;
 }
 
-// ---- the weights 1 / w_j ---------------------------------------------------------------------------------------------
+// ---- the weights 1 / w_j --------------------------------------------------------------------------------------------
 // E[m] = d (d-1) .. (d-m+1) for m = 0..d (E[d] = d!): exclusive prefix products of e_k = d - k (csrc/fr_scan.h)
 struct qh_seq {
     uint32_t d;
@@ -253,7 +257,7 @@ extern "C" int vmpc_bn256_qap_h_weights_dev(vmpc_ctx *ctx, const void *a, const 
     return VMPC_OK;
 }
 
-// ---- the witness check -------------------------------------------------------------------------------------------------
+// ---- the witness check ----------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 k_qh_check(uint32_t d, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ y,
            uint32_t *__restrict__ first_bad) {
@@ -276,7 +280,82 @@ extern "C" int vmpc_bn256_qap_check_dev(vmpc_ctx *ctx, const void *a, const void
     return VMPC_OK;
 }
 
-// ---- t's coefficients --------------------------------------------------------------------------------------------------
+// ---- the residual of a share vector ---------------------------------------------------------------------------------
+struct qh_scalar {
+    uint32_t v[8];
+};
+
+// part[g] = sum over workgroup g's rows i of rho^i (a_i b_i - y_i) mod n, the row at the point j = i + 1 carrying rho^i.
+// Lane L of the grid owns the rows L, L + S, L + 2S, .. (S = all lanes): it starts its power at rho^L (square and
+// multiply) and advances it by rho^S (`step`, from the host), adding the unreduced products into its own f256_acc
+// (at most 2^20 / S of them), reduced once.  The workgroup's 256 residues are added through LDS in a fixed tree.
+__global__ void __launch_bounds__(QH_WG)
+k_qh_residual(uint32_t d, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ y,
+              qh_scalar rho, qh_scalar step, uint32_t *__restrict__ part) {
+    __shared__ frbn sR[QH_WG];
+    const uint32_t t = threadIdx.x, first = blockIdx.x * QH_WG + t, S = gridDim.x * QH_WG;
+    frbn r = frbn_zero();
+    if (first < d) {
+        const frbn rh = f256_copy<frbn>(rho.v), st = f256_copy<frbn>(step.v);
+        frbn pw = frbn_one();
+        if (first) {
+            for (int bit = 31 - __clz(first); bit >= 0; bit--) {
+                pw = frbn_mul(pw, pw);
+                if ((first >> bit) & 1u) pw = frbn_mul(pw, rh);
+            }
+        }
+        frbn_acc acc = frbn_acc_zero();
+        for (uint32_t i = first; i < d; i += S) {
+            const frbn e = frbn_sub(frbn_mul(f256_ld<frbn>(a, i), f256_ld<frbn>(b, i)), f256_ld<frbn>(y, i));
+            frbn_acc_mac(acc, pw.v, e.v);
+            pw = frbn_mul(pw, st);
+        }
+        r = frbn_acc_reduce(acc);
+    }
+    sR[t] = r;
+    __syncthreads();
+    for (uint32_t h = QH_WG / 2; h >= 1; h >>= 1) {
+        if (t < h) sR[t] = frbn_add(sR[t], sR[t + h]);
+        __syncthreads();
+    }
+    if (t == 0) f256_st(part, blockIdx.x, sR[0]);
+}
+
+extern "C" int vmpc_bn256_qap_residual_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t d,
+                                           const uint8_t rho[32], void *out) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !y || !rho || !out || d == 0) return VMPC_E_INVAL;
+    qh_scalar r, step;
+    memcpy(r.v, rho, 32);
+    if (f256_geq_m<frbn>(r.v)) return VMPC_E_NONCANON;
+    size_t groups = (d + QH_WG - 1) / QH_WG;
+    if (groups > QH_RES_MAX_WGS) groups = QH_RES_MAX_WGS;
+    // rho^S for the S = groups x 256 lanes, on the host (S has one or two bits set above the eighth)
+    frbn pw = frbn_one();
+    const frbn rh = f256_copy<frbn>(r.v);
+    for (int bit = 31; bit >= 0; bit--) {
+        pw = frbn_mul(pw, pw);
+        if (((uint32_t)(groups * QH_WG) >> bit) & 1u) pw = frbn_mul(pw, rh);
+    }
+    memcpy(step.v, pw.v, 32);
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(groups * 32) + 256));
+    uint32_t *part = (uint32_t *)vmpc_ws_take(ctx, groups * 32);
+    {
+        vmpc_stage_scope sc(ctx, "bn_qap_residual");
+        k_qh_residual<<<(unsigned)groups, QH_WG, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)a, (const uint32_t *)b,
+                                                                  (const uint32_t *)y, r, step, part);
+        VMPC_KERNEL_CHECK();
+    }
+    {
+        vmpc_stage_scope sc(ctx, "bn_qap_residual_sum");
+        k_qh_partsum<<<1, 256, 0, ctx->stream>>>(part, 1, (uint32_t)groups, (uint32_t *)out);
+        VMPC_KERNEL_CHECK();
+    }
+    return VMPC_OK;
+}
+
+// ---- t's coefficients -----------------------------------------------------------------------------------------------
 // leaf l: prod (x - j) over j = l QH_LEAF + 1 .. min((l+1) QH_LEAF, d), its deg + 1 coefficients at dst + 32 (l QH_LEAF + l)
 // (leaves packed one after the other).  Thread i owns coefficient i: new_i = old_(i-1) - j old_i.
 __global__ void __launch_bounds__(QH_WG) k_qh_tleaf(uint32_t d, uint32_t *__restrict__ dst) {
@@ -349,7 +428,7 @@ extern "C" int vmpc_bn256_qap_t_coeffs_dev(vmpc_ctx *ctx, size_t d, void *scratc
     return VMPC_OK;
 }
 
-// ---- values at the integer points (dense QAP form) --------------------------------------------------------------------
+// ---- values at the integer points (dense QAP form) ------------------------------------------------------------------
 // out[p d + i] = sum_k coeffs[p n_coeffs + k] (i + 1)^k: Horner with small multipliers, one lane per point
 __global__ void __launch_bounds__(256)
 k_qh_horner(const uint32_t *__restrict__ coeffs, uint32_t n_coeffs, uint32_t d, uint32_t *__restrict__ out) {
@@ -374,7 +453,7 @@ extern "C" int vmpc_bn256_qap_horner_dev(vmpc_ctx *ctx, const void *coeffs, size
     return VMPC_OK;
 }
 
-// ---- the combination --------------------------------------------------------------------------------------------------
+// ---- the combination ------------------------------------------------------------------------------------------------
 // A[i] = A_(i+1), B[i] = B_(i+1) (the moments), P = A * B.  crev[r] = C_(d-r) with
 //     C_k = P[k-2] (k >= 2) + delta_v B_k + delta_w A_k
 __global__ void __launch_bounds__(256)

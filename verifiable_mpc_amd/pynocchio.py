@@ -1142,27 +1142,60 @@ def compute_h(qap, c, deltas=None, ctx=None):
     violates a constraint raises ValueError naming the first violated constraint (1-based, the point x = j)."""
     ctx = ctx or get_context()
     d = int(qap.d)
-    if d + 1 > _native.BN256_FR_POLY_MAX:
-        raise ValueError(f"compute_h: d + 1 = {d + 1} exceeds the polynomial product's cap {_native.BN256_FR_POLY_MAX}")
-    c_arr = _witness_array(qap, c)
-    n_wires = len(c_arr)
-    dc = ctx.upload(c_arr) if n_wires else ctx.alloc(32)
-    aby, keep = _row_values(ctx, qap, dc, n_wires)
-    a_ptr, b_ptr, y_ptr = aby.ptr, aby.ptr + 32 * d, aby.ptr + 64 * d
+    aby, keep = _upload_row_values(ctx, qap, c, "compute_h")
     bad = ctx.alloc(4)
-    ctx.bn256_qap_check(a_ptr, b_ptr, y_ptr, d, bad.ptr)
+    ctx.bn256_qap_check(aby.ptr, aby.ptr + 32 * d, aby.ptr + 64 * d, d, bad.ptr)
     ctx.sync()
     first = int(ctx.download(bad.ptr, 4).view("<u4")[0])
     if first != 0xFFFFFFFF:
         raise ValueError(f"compute_h: the witness violates constraint {first + 1} (V(j) W(j) != Y(j) at j = {first + 1})")
+    dd = _scalar_buf(ctx, [deltas.v, deltas.w, deltas.y]) if deltas is not None else None
+    return _h_from_row_values(ctx, qap, aby, keep, dd)
+
+
+def _upload_row_values(ctx, qap, c, who):
+    """c on the device and its row values a || b || y -> (buffer, what must outlive the stream's work on it)"""
+    d = int(qap.d)
+    if d + 1 > _native.BN256_FR_POLY_MAX:
+        raise ValueError(f"{who}: d + 1 = {d + 1} exceeds the polynomial product's cap {_native.BN256_FR_POLY_MAX}")
+    c_arr = _witness_array(qap, c)
+    n_wires = len(c_arr)
+    dc = ctx.upload(c_arr) if n_wires else ctx.alloc(32)
+    aby, keep = _row_values(ctx, qap, dc, n_wires)
+    return aby, (dc,) + tuple(keep)
+
+
+def _h_from_row_values(ctx, qap, aby, keep, dd):
+    """row values -> weights -> moments -> combination; dd: device buffer of the three deltas or
+    None.  Nothing here asks whether the rows satisfy a_j b_j = y_j: the result is the polynomial part of V W / t."""
+    d = int(qap.d)
+    a_ptr, b_ptr = aby.ptr, aby.ptr + 32 * d
     t = _t_coeffs(ctx, qap)
     u = ctx.alloc(32 * 2 * d)
     ctx.bn256_qap_h_weights(a_ptr, b_ptr, d, u.ptr, u.ptr + 32 * d)
     mom = ctx.alloc(32 * 2 * d)
     ctx.bn256_qap_moments(u.ptr, u.ptr + 32 * d, d, d, mom.ptr, mom.ptr + 32 * d)
-    dd = _scalar_buf(ctx, [deltas.v, deltas.w, deltas.y]) if deltas is not None else None
     scratch, out = ctx.alloc(32 * 5 * d), ctx.alloc(32 * (d + 1))
     ctx.bn256_qap_h_combine(mom.ptr, mom.ptr + 32 * d, t.ptr, d, dd.ptr if dd else None, scratch.ptr, out.ptr)
     ctx.sync()      # the temporaries above may be released once the stream has drained
     del keep
-    return HPoly(ctx, out, d + 1 if deltas is not None else max(d - 1, 0))
+    return HPoly(ctx, out, d + 1 if dd is not None else max(d - 1, 0))
+
+
+def compute_h_share(qap, c_share, delta_shares=None, ctx=None):
+    """compute_h for ONE PARTY's Shamir share of the witness (demos/demo_zkp_trinocchio.py:70-79 computes h in the clear
+    and shares its coefficients): the same row values -> weights -> moments -> combination on the party's share vector,
+    WITHOUT the constraint check - a share vector never satisfies a_j b_j = y_j - and without a host read-back before
+    the result.  deg Y < d, so what comes out is the polynomial part of V W / t, which is bilinear in the shares (plus
+    linear in delta_y): from degree-t sharings of c and of the deltas the M parties' results are a degree-2t SHARING of
+    the h that compute_h(qap, c, deltas) gives, coefficient for coefficient - M >= 2t + 1 parties recombine it with the
+    Lagrange weights at 0, no exchange needed.  delta_shares: this party's shares as .v, .w, .y, or a device buffer of
+    those three scalars.  Lengths as compute_h: d + 1 with deltas, max(d - 1, 0) without.  (Whether the shared witness
+    satisfies the constraints is trinocchio.prove's residual check, vmpc_bn256_qap_residual_dev.)"""
+    ctx = ctx or get_context()
+    aby, keep = _upload_row_values(ctx, qap, c_share, "compute_h_share")
+    dd = None
+    if delta_shares is not None:
+        dd = delta_shares if hasattr(delta_shares, "ptr") else \
+            _scalar_buf(ctx, [delta_shares.v, delta_shares.w, delta_shares.y])
+    return _h_from_row_values(ctx, qap, aby, keep, dd)

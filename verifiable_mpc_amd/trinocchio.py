@@ -1,0 +1,283 @@
+"""Counterpart of demos/demo_zkp_trinocchio.py (Trinocchio, Schoenmakers, Veeningen and de Vreede, eprint 2015/480): M
+parties hold Shamir shares of a QAP witness, each computes a Pinocchio proof SHARE on its MI355X, and the shares are
+recombined in the exponent into one proof that the ordinary `pynocchio.verify` accepts.
+
+    c_shares, h_shares            demo_zkp_trinocchio.py:70-79   (h computed in the clear, then shared)
+    compute_proof on the shares   demo_zkp_trinocchio.py:80      pynocchio.compute_proof, unchanged
+    recombination                 demo_zkp_trinocchio.py:86-93   proof[key] = sum_p lambda_p * share_p[key]
+    c_client                      demo_zkp_trinocchio.py:96-98   [1] + opened I/O wires
+
+What differs from the demo: h is never known to anybody.  Each party computes `pynocchio.compute_h_share` on its own
+share vector - the polynomial part of V W / t, bilinear in the shares, so a degree-2t sharing of h that M >= 2t + 1
+parties recombine - and masks it with a fresh degree-2t sharing of zero before anything that
+depends on it leaves the party.  The zero-knowledge deltas the demo leaves as a TODO are degree-t shared randomness and
+ride along.  Whether the SHARED witness satisfies the constraints - the remainder of p / qap.t, which the demo drops
+unchecked - is a random linear combination of the rows' residuals (vmpc_bn256_qap_residual_dev), masked and opened.
+
+The share arithmetic is GF(n), n the BN-256 group order: `Runtime` is mpc_ac20.PartyRuntime's hub, tags and exchange of
+bytes over csrc/mpc_share.hip's GF(n) entries.  A party exchanges (section 19 has the argument):
+
+    check      1. the dealt randomness (deltas, rho) and sharings of zero   2. rho opened   3. the masked residual opened
+    always     (1. as above, when there is anything to deal)   then ONE exchange of the eight proof-share points with
+               the shares of the I/O wires
+
+so 4 exchanges with the check and 2 without (1 when there is nothing to deal: no deltas and an empty h).
+
+Out of scope:
+  * the witness computation on shares (the demo's qap.calculate_witness on secure values): the parties arrive with
+    shares of the WHOLE witness, as with `gamma_witness=` in mpc_circuit_sat;
+  * QAP construction from code (stays with the reference, as for pynocchio);
+  * multi-client Trinocchio (the paper's Alg. 4);
+  * any transport other than the hub: a real runtime moves the same bytes.
+"""
+import time
+import types
+
+import numpy as np
+
+from . import _native
+from . import pynocchio as pn
+from .device import ScalarVector, get_context
+from .mpc_ac20 import LocalHub, PartyRuntime
+
+ORDER = pn.ORDER
+_ORDER_BE = np.frombuffer(ORDER.to_bytes(32, "big"), np.uint8).astype(np.int16)
+
+
+def recombination_vector(xs, x_r=0):
+    """Lagrange coefficients for the nodes xs at x_r, mod n (mpyc.thresha._recombination_vector as
+    demo_zkp_trinocchio.py:88 calls it)."""
+    out = []
+    for i, x_i in enumerate(xs):
+        num = den = 1
+        for j, x_j in enumerate(xs):
+            if i != j:
+                num = num * (x_r - x_j) % ORDER
+                den = den * (x_i - x_j) % ORDER
+        out.append(num * pow(den, ORDER - 2, ORDER) % ORDER)
+    return out
+
+
+def random_residues(rng, count):
+    """(count, 32) uint8 uniform residues mod n from `rng`: 256-bit draws, those >= n rejected (n is 0.56 x 2^256, so
+    reducing instead would make the low residues twice as likely)"""
+    out = np.zeros((0, 32), np.uint8)
+    while len(out) < count:
+        k = 2 * (count - len(out)) + 16
+        arr = np.frombuffer(rng.getrandbits(256 * k).to_bytes(32 * k, "little"), np.uint8).reshape(k, 32)
+        diff = arr[:, ::-1].astype(np.int16) - _ORDER_BE          # most significant byte first
+        first = (diff != 0).argmax(axis=1)
+        below = diff[np.arange(k), first] < 0                     # (a row equal to n has diff 0 everywhere: rejected)
+        out = np.concatenate([out, arr[below]])
+    return np.ascontiguousarray(out[:count])
+
+
+class Runtime(PartyRuntime):
+    """PartyRuntime over GF(n): pid in 0..M-1 holds the share at x = pid + 1.  Share vectors are device vectors of
+    32-byte residues (device.ScalarVector used as a container: its arithmetic is GF(l) and is not used here).
+    A product of two degree-t sharings - h is one - has degree 2t, which M parties recombine only if 2t < M: anything
+    else is refused here, before a context exists."""
+
+    def __init__(self, pid=0, parties=1, threshold=0, rng=None, hub=None, ctx=None):
+        if 2 * threshold >= parties:
+            raise ValueError(f"trinocchio: h is a degree-{2 * threshold} sharing, which {parties} parties cannot "
+                             f"recombine (2 t < M)")
+        super().__init__(pid, parties, threshold, rng, hub)
+        self.gf = None                                              # opened values are plain ints mod n
+        self.weights = recombination_vector(list(range(1, parties + 1)))
+        self.lagrange = self.weights[pid]
+        self.exchanges = 0
+        self.stage_log = None               # a list: prove appends (stage, seconds), each ended by a synchronisation
+        self._ctx = ctx
+
+    def _context(self):
+        return self._ctx or get_context()
+
+    def _stage(self, name, t0):
+        """scripts/trinocchio_probe.py's bracket: the local work since t0 belongs to `name`; -> the new t0"""
+        if self.stage_log is not None:
+            self._context().sync()
+            self.stage_log.append((name, time.perf_counter() - t0))
+        return time.perf_counter()
+
+    def _next_tag(self, kind):
+        self.exchanges += 1                 # every exchange draws exactly one tag
+        return super()._next_tag(kind)
+
+    # what the GF(l) class does with l's arithmetic has no meaning here
+    def _random(self, sectype=None):
+        raise NotImplementedError("trinocchio.Runtime: use random_shares")
+
+    async def schur_prod(self, a, b, out=None, dst=None):
+        raise NotImplementedError("trinocchio.Runtime: no product of shares is needed for a Pinocchio proof")
+
+    def _dealt(self, values, n, degree, ctx):
+        """fresh degree-`degree` sharings of the n device scalars `values` (None: of zero) -> (M, n, 32) host table"""
+        M = self.parties
+        a = values if values is not None else ctx.upload(np.zeros((n, 32), np.uint8))
+        coeffs = ctx.upload(random_residues(self.rng, degree * n)) if degree else None
+        out = ctx.alloc(32 * M * n)
+        ctx.bn256_share_mul_deal(a.ptr, None, n, coeffs.ptr if degree else None, degree, M, out.ptr, n)
+        return ctx.download(out.ptr, 32 * M * n, (M, n, 32))
+
+    async def _deal_round(self, n_rand, n_zero):
+        """ONE exchange that carries both kinds of dealt randomness: every party deals n_rand random values of its own
+        with degree t and n_zero zeros with degree 2t.  -> (the n_rand random shares, combined: a ScalarVector;
+        the n_zero zero sharings as RECEIVED, an M x n_zero device matrix still to be added up - the combination that
+        adds them takes the value to be masked as its addend, see `masked`)"""
+        ctx, M, n = self._context(), self.parties, n_rand + n_zero
+        if n == 0:
+            return ScalarVector.empty(0, ctx), None
+        t0 = time.perf_counter()
+        tables = []
+        if n_rand:
+            tables.append(self._dealt(ctx.upload(random_residues(self.rng, n_rand)), n_rand, self.threshold, ctx))
+        if n_zero:
+            tables.append(self._dealt(None, n_zero, 2 * self.threshold, ctx))
+        table = np.concatenate(tables, axis=1)
+        self._stage("masks", t0)
+        got = await self.exchange_vectors([table[q] for q in range(M)])
+        t0 = time.perf_counter()
+        parts = ctx.upload(np.ascontiguousarray(np.stack(got)))            # M x n
+        rand = ScalarVector.empty(n_rand, ctx)
+        if n_rand:
+            ctx.bn256_share_combine(parts.ptr, M, n_rand, n, [1] * M, None, None, rand.ptr)
+        self._stage("masks", t0)
+        return rand, (_Zeros(parts, n_rand, n_zero, n) if n_zero else None)
+
+    def masked(self, zeros, first, values_ptr, n):
+        """the n device scalars at values_ptr + the zero sharings first .. first + n - 1 of a `_deal_round`, in one
+        combination: the unmasked values are its addend and go nowhere else (values_ptr None: the zero shares alone)"""
+        ctx = self._context()
+        out = ScalarVector.empty(n, ctx)
+        if n:
+            assert first + n <= zeros.n
+            ctx.bn256_share_combine(zeros.parts.ptr + 32 * (zeros.offset + first), self.parties, n, zeros.stride,
+                                    [1] * self.parties, None, values_ptr, out.ptr)
+        return out
+
+    async def random_shares(self, n):
+        """n uniformly random secrets nobody knows, shared with degree `threshold`"""
+        return (await self._deal_round(n, 0))[0]
+
+    async def zero_shares(self, n):
+        """n degree-2t sharings of zero: every party deals zeros with the degree argument 2t, one exchange, the sum of
+        what arrived (a combination with weights 1)"""
+        zeros = (await self._deal_round(0, n))[1]
+        return self.masked(zeros, 0, None, n)
+
+    def _recombined(self, got, n, ctx):
+        t0 = time.perf_counter()
+        parts = ctx.upload(np.ascontiguousarray(np.stack(got)))
+        res = ScalarVector.empty(n, ctx)
+        ctx.bn256_share_combine(parts.ptr, self.parties, n, n, self.weights, None, None, res.ptr)
+        out = res.to_ints()
+        self._stage("exchange", t0)
+        return out
+
+    async def output(self, x):
+        """open a share vector (of any degree below M) to all parties: every party sends its shares, the M-point
+        recombination runs on the device -> list of ints mod n"""
+        n, ctx = len(x), x.ctx
+        if n == 0:
+            return []
+        mine = ctx.download(x.ptr, 32 * n, (n, 32))
+        return self._recombined(await self.exchange_vectors(mine), n, ctx)
+
+    async def exchange_points(self, points, scalars=None):
+        """send this party's BN256Point / BN256TwistPoint elements as bytes, receive everybody's: list over parties of
+        lists of points.  scalars: an (n, 32) uint8 array of shares that rides along in the same exchange; then
+        -> (points, the n opened values)."""
+        raw = [(p.group, p.to_bytes()) for p in points]
+        every = await self.hub.exchange(self.pid, self._next_tag("pts"), (raw, scalars))
+        cls = {1: pn.BN256Point, 2: pn.BN256TwistPoint}
+        pts = [[cls[g].from_bytes(b) for g, b in part[0]] for part in every]
+        if scalars is None:
+            return pts
+        n = len(scalars)
+        return pts, (self._recombined([part[1] for part in every], n, self._context()) if n else [])
+
+
+class _Zeros:
+    """the zero sharings a party received in one deal round: M rows of `n` scalars at column `offset` of `parts`"""
+
+    def __init__(self, parts, offset, n, stride):
+        self.parts, self.offset, self.n, self.stride = parts, offset, n, stride
+
+
+def deal_witness(c, threshold, parties, rng):
+    """Degree-`threshold` Shamir shares mod n of every wire value for parties 1..M, as M (n_wires, 32) uint8 arrays
+    (dealer / test helper: in the demo the shares come from MPyC's input protocol and calculate_witness)."""
+    vals = [int(v) % ORDER for v in c]
+    coeffs = [[rng.randrange(ORDER) for _ in vals] for _ in range(threshold)]
+    out = []
+    for p in range(parties):
+        x = p + 1
+        row = []
+        for i, v in enumerate(vals):
+            acc = 0
+            for k in range(threshold - 1, -1, -1):
+                acc = (acc + coeffs[k][i]) * x % ORDER
+            row.append((acc + v) % ORDER)
+        out.append(_native.ints_to_array(row, 32))
+    return out
+
+
+async def prove(rt, qap, key, c_share, zk=True, check=True):
+    """One party's run of the M-party prover.  rt: this party's Runtime; key: a pynocchio.PreparedKey; c_share: this
+    party's degree-t shares of the witness over qap.indices, an (n_wires, 32) uint8 array or a list of ints.
+    -> (proof, c_client): the proof has the keys and point types of pynocchio.compute_proof's result, c_client is
+    [1] + the opened I/O wires; `pynocchio.verify(qap, verikey, proof, c_client)` takes them unchanged.  Every party
+    returns the same pair.
+
+    zk: jointly random degree-t shared deltas make the proof zero-knowledge (the demo's TODO).
+    check: the parties open a jointly random rho and the masked sum_j rho^j (a_j b_j - y_j) over the shared rows; if it
+    is not zero the shares are not of a satisfying witness (or not consistent sharings at all) and every party raises
+    ValueError("inconsistent shares") before a proof share is exchanged.  A wrong witness passes with probability at
+    most d / n.  Without the check a wrong witness gives a proof whose H check fails."""
+    if not isinstance(key, pn.PreparedKey):
+        raise TypeError("trinocchio.prove: key must be a pynocchio.PreparedKey")
+    ctx, d = key.ctx, int(qap.d)
+    assert rt._context() is ctx, "the runtime and the prepared key share one context"
+    c_arr = pn._witness_array(qap, c_share)
+    n_h = d + 1 if zk else max(d - 1, 0)
+    n_delta, n_check = (3 if zk else 0), (1 if check else 0)
+    # 1. all dealt randomness in one exchange: deltas and rho with degree t, zeros (residual, h) with degree 2t
+    rand, zeros = await rt._deal_round(n_delta + n_check, n_check + n_h)
+    t0 = time.perf_counter()
+    aby, keep = pn._upload_row_values(ctx, qap, c_arr, "trinocchio.prove")
+    t0 = rt._stage("h_share", t0)
+    if check:
+        # 2. rho is opened only now: the shares it tests were fixed before anybody knew it
+        rho = (await rt.output(rand[n_delta:]))[0]
+        t0 = time.perf_counter()
+        res = ScalarVector.empty(1, ctx)
+        ctx.bn256_qap_residual(aby.ptr, aby.ptr + 32 * d, aby.ptr + 64 * d, d, rho, res.ptr)
+        # 3. a degree-2t share of 0 for a satisfying witness: opened under a zero sharing, it tells nothing else
+        masked = rt.masked(zeros, 0, res.ptr, 1)
+        rt._stage("residual", t0)
+        if (await rt.output(masked))[0] != 0:
+            raise ValueError("inconsistent shares")
+        t0 = time.perf_counter()
+    deltas = None
+    if zk:
+        dv, dw, dy = rand[:3].to_ints()          # this party's own shares: compute_proof takes them from the host
+        deltas = types.SimpleNamespace(v=dv, w=dw, y=dy)
+    # compute_h_share's two steps (the row values are shared with the check above)
+    h = pn._h_from_row_values(ctx, qap, aby, keep, rand[:3] if zk else None)
+    assert len(h) == n_h
+    t0 = rt._stage("h_share", t0)
+    if n_h:
+        h = pn.HPoly(ctx, rt.masked(zeros, n_check, h.buf.ptr, n_h), n_h)
+    t0 = rt._stage("masks", t0)
+    share = pn.compute_proof(qap, c_arr, h, key, deltas)
+    rt._stage("proof_share", t0)
+    # 4. the eight points and this party's shares of the I/O wires, one exchange
+    names = list(share)
+    out_ix = int(qap.out_ix)
+    every, opened = await rt.exchange_points([share[k] for k in names], np.ascontiguousarray(c_arr[1:out_ix + 1]))
+    t0 = time.perf_counter()
+    proof = {k: pn.msm(rt.weights, [part[i] for part in every], ctx) for i, k in enumerate(names)}
+    rt._stage("exchange", t0)
+    return proof, [1] + opened
+
