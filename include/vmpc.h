@@ -513,6 +513,19 @@ int vmpc_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint3
                            const void *a_const, const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_vals,
                            const void *b_const, const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset,
                            void *z, void *a_out, void *b_out, int check, uint32_t *first_bad);
+/* vmpc_fr_cs_triples_dev for n_wit witnesses of ONE circuit in one launch (the witness on the grid's y).  The forms and
+ * the gate list are shared; witness w reads and writes z + 32 w z_stride, a_out + 32 w ab_stride and b_out alike (strides
+ * in scalars: z_stride >= the length of z, ab_stride >= the rows' count), and with check = 1 first_bad[w] (n_wit device
+ * words, all set to 0xffffffff by the call) is ITS smallest bad gate.  check = 2: the values of the rows for every
+ * witness, a_out and b_out may be one buffer.  n_wit <= VMPC_FR_CS_MAX_WIT, the strides <= 2^31 and not below what the
+ * call itself addresses (gamma_offset + n_gates, n_gates), else VMPC_E_RANGE; n_wit = 0 or n_gates = 0: VMPC_OK and no
+ * launch.  The bits are those of n_wit single calls.  No arena. */
+#define VMPC_FR_CS_MAX_WIT ((size_t)65535)
+int vmpc_fr_cs_triples_batch_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_vals,
+                                 const void *a_const, const uint32_t *b_row_ptr, const uint32_t *b_col,
+                                 const void *b_vals, const void *b_const, const uint32_t *gates, size_t n_gates,
+                                 size_t n_x, size_t gamma_offset, void *z, size_t z_stride, void *a_out, void *b_out,
+                                 size_t ab_stride, size_t n_wit, int check, uint32_t *first_bad);
 /* fact[k] = k!, ifact[k] = 1 / k! for k = 0..K (K >= 1): two product scans and one inversion.  Arena: 2 K scalars. */
 int vmpc_fr_cs_tables_dev(vmpc_ctx *ctx, size_t K, void *fact, void *ifact);
 /* a, b: M scalars (a_1..a_m, r_a).  Writes z_tail[0] = f(0), [1] = g(0), [2] = h(0), [2 + m + 1] = r_a r_b and
@@ -522,6 +535,17 @@ int vmpc_fr_cs_tables_dev(vmpc_ctx *ctx, size_t K, void *fact, void *ifact);
  * for s segments of j. */
 int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact, const void *ifact,
                           void *z_tail);
+/* vmpc_fr_cs_extend_dev for n_wit witnesses in one launch sequence: a, b are n_wit rows of M scalars, ab_stride >= M
+ * scalars apart, z_tail n_wit rows z_stride >= 2m + 3 scalars apart (strides <= 2^31, n_wit <= VMPC_FR_CS_MAX_WIT, else
+ * VMPC_E_RANGE; n_wit = 0: VMPC_OK, no launch).  The table 1 / k and the weights are computed once, the correlation runs
+ * on a grid (tiles, segments, witnesses), and the segment length is chosen with n_wit counted, so a large batch uses
+ * fewer, longer segments.  Canonical residues: the bits are those of n_wit single calls whatever the segmentation.
+ * Arena: vmpc_fr_cs_extend_batch_bytes(m, n_wit); when it cannot be reserved the error is returned and nothing is
+ * launched. */
+int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m, const void *fact,
+                                const void *ifact, void *z_tail, size_t z_stride, size_t n_wit);
+/* the arena bytes vmpc_fr_cs_extend_batch_dev reserves (0 where the call would answer VMPC_E_RANGE or do nothing) */
+size_t vmpc_fr_cs_extend_batch_bytes(size_t m, size_t n_wit);
 /* The same extension with f and g kept apart, nothing multiplied and no z: f_out[0] = f(0), f_out[1 + o] = f(m + 2 + o)
  * for o < m - 1, g_out alike; max(m, 1) scalars each.  Linear in a and b, so on Shamir shares of them it gives shares
  * of f and g at those points (mpc_ac20_cb.py:66-85 interpolates and evaluates share polynomials).  Arena as above. */

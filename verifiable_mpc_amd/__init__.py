@@ -14,6 +14,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 from . import circuit_sat, circuit_sat_gpu, compressed_pivot, knowledge_of_exponent, nullity, pivot  # noqa: E402,F401
 from .circuit_sat import PivotChoice, circuit_sat_prover, circuit_sat_verifier, create_generators  # noqa: E402,F401
 from .circuit_sat_gpu import SparseCircuit, circuit_sat_verifier_batch  # noqa: E402,F401
+from .circuit_sat_gpu import circuit_sat_prover_batch, protocol_8_excl_pivot_prover_batch  # noqa: E402,F401
 from .compressed_pivot import protocol_5_verifier_batch  # noqa: E402,F401
 from .device import PointVector, ScalarVector, get_context  # noqa: E402,F401
 from .fields import GF  # noqa: E402,F401

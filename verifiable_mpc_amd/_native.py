@@ -54,6 +54,7 @@ SYMBOLS = [
     "vmpc_fr_rows_combine_dev", "vmpc_fr_rows_dot_dev", "vmpc_fr_batch_products_dev",
     "vmpc_fr_cs_extend_fg_dev", "vmpc_fr_share_mul_deal_dev", "vmpc_fr_share_combine_dev",
     "vmpc_bn256_fr_share_mul_deal_dev", "vmpc_bn256_fr_share_combine_dev", "vmpc_bn256_qap_residual_dev",
+    "vmpc_fr_cs_triples_batch_dev", "vmpc_fr_cs_extend_batch_dev", "vmpc_fr_cs_extend_batch_bytes",
 ]
 
 
@@ -172,6 +173,10 @@ def load_library():
         "vmpc_bn256_qap_h_combine_dev": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
         "vmpc_fr_cs_triples_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, i32, vp]),
         "vmpc_fr_cs_tables_dev": (i32, [vp, sz, vp, vp]),
+        "vmpc_fr_cs_triples_batch_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, sz, sz, i32,
+                                               vp]),
+        "vmpc_fr_cs_extend_batch_dev": (i32, [vp, vp, vp, sz, sz, vp, vp, vp, sz, sz]),
+        "vmpc_fr_cs_extend_batch_bytes": (sz, [sz, sz]),
         "vmpc_fr_cs_extend_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
         "vmpc_fr_cs_extend_fg_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
         "vmpc_fr_share_mul_deal_dev": (i32, [vp, vp, vp, sz, vp, sz, sz, vp, sz]),
@@ -807,6 +812,11 @@ class Context:
                                            ctypes.c_void_p(out.ptr)), "vmpc_fr_dot_to_dev")
         return out
 
+    def fr_dot_into(self, a_ptr, b_ptr, n, out_ptr):
+        """inner product into a scalar of the caller's device memory, no synchronisation"""
+        _check(self.lib.vmpc_fr_dot_to_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), n,
+                                           ctypes.c_void_p(out_ptr)), "vmpc_fr_dot_to_dev")
+
     # ---- Protocol 8 from a sparse circuit (csrc/circuit_sat.hip) ------------------------------------------------------
     def cs_triples(self, A, B, gates_ptr, n_gates, n_x, gamma_offset, z_ptr, a_ptr, b_ptr, check=0, first_bad_ptr=None):
         """A, B: (row_ptr, col, vals, consts) device pointers"""
@@ -829,6 +839,26 @@ class Context:
         p = ctypes.c_void_p
         _check(self.lib.vmpc_fr_cs_extend_fg_dev(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr),
                                                  p(f_out_ptr), p(g_out_ptr)), "vmpc_fr_cs_extend_fg_dev")
+
+    def cs_triples_batch(self, A, B, gates_ptr, n_gates, n_x, gamma_offset, z_ptr, z_stride, a_ptr, b_ptr, ab_stride, n_wit,
+                         check=0, first_bad_ptr=None):
+        """cs_triples for n_wit witnesses of one circuit in one launch: rows of z / a / b, strides in scalars;
+        first_bad_ptr: n_wit device words"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_fr_cs_triples_batch_dev(self.handle, p(A[0]), p(A[1]), p(A[2]), p(A[3]), p(B[0]), p(B[1]),
+                                                     p(B[2]), p(B[3]), p(gates_ptr), n_gates, n_x, gamma_offset, p(z_ptr),
+                                                     z_stride, p(a_ptr), p(b_ptr), ab_stride, n_wit, check,
+                                                     p(first_bad_ptr)), "vmpc_fr_cs_triples_batch_dev")
+
+    def cs_extend_batch(self, a_ptr, b_ptr, ab_stride, m, fact_ptr, ifact_ptr, z_tail_ptr, z_stride, n_wit):
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_fr_cs_extend_batch_dev(self.handle, p(a_ptr), p(b_ptr), ab_stride, m, p(fact_ptr),
+                                                    p(ifact_ptr), p(z_tail_ptr), z_stride, n_wit),
+               "vmpc_fr_cs_extend_batch_dev")
+
+    def cs_extend_batch_bytes(self, m, n_wit):
+        """the arena bytes cs_extend_batch reserves for n_wit witnesses"""
+        return int(self.lib.vmpc_fr_cs_extend_batch_bytes(m, n_wit))
 
     # ---- Shamir sharings of vectors (csrc/mpc_share.hip) -------------------------------------------------------------
     def share_mul_deal(self, a_ptr, b_ptr, n, coeffs_ptr, t, parties, out_ptr, out_stride):

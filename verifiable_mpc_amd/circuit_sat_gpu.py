@@ -232,7 +232,9 @@ def _check_not_node(c, m):
 class _Forms:
     """the forms of f(c), g(c), h(c) over z, device-resident, and what L needs of them"""
 
-    def __init__(self, circuit, n_in, c, order):
+    def __init__(self, circuit, n_in, c, order, k_out=None):
+        """k_out: device memory of two scalars that takes the constants of F and G instead of the host, so that nothing
+        waits here; the caller sets self.k once it has read them (the batch prover reads all witnesses' at once)"""
         d = circuit.device()
         ctx, m = d["ctx"], circuit.m
         self.circuit, self.n_in, self.N, self.order, self.ctx = circuit, n_in, n_in + 3 + 2 * m, order, ctx
@@ -247,7 +249,12 @@ class _Forms:
         for wire_ix, (M, V) in enumerate(((d["A"], self.F), (d["B"], self.G))):
             M.weighted_columns(self.lam.ptr + 32, circuit.n_x, n_in, V.ptr, N)
             ctx.copy(V.ptr + 32 * (n_in + wire_ix), self.lam.ptr, 32)
-            self.k.append(ctx.fr_dot(self.lam.ptr + 32, M.consts.ptr, m) if m else 0)
+            if k_out is None:
+                self.k.append(ctx.fr_dot(self.lam.ptr + 32, M.consts.ptr, m) if m else 0)
+            else:
+                self.k.append(None)
+                if m:
+                    ctx.fr_dot_into(self.lam.ptr + 32, M.consts.ptr, m, k_out + 32 * wire_ix)
         self.k.append(0)
 
     def values(self, z):
@@ -551,3 +558,221 @@ def circuit_sat_verifier_batch(proofs, generators, circuit, gf, transcript=None)
     for i, ok in zip(where, compressed_pivot.protocol_5_verifier_batch(generators, statements, gf, transcript=mode)):
         out[i]["pivot_verification"] = ok
     return out
+
+
+# ---- K witnesses of one circuit -------------------------------------------------------------------
+# what one chunk of a batch may hold in Z, the row values and the extension's workspace
+BATCH_BUDGET_BYTES = 1 << 30
+MAX_BATCH = 65535           # VMPC_FR_CS_MAX_WIT of include/vmpc.h
+
+
+def _batch_inputs(xs, n_in):
+    """(K, n_in, rows): rows a (K, n_in, 32) uint8 array of canonical residues, or the caller's device ScalarVector of
+    K n_in scalars.  Only a sequence of input lists is converted integer by integer."""
+    if isinstance(xs, ScalarVector):
+        if n_in is None:
+            raise ValueError("xs on the device: n_in= says where a witness ends")
+        if (n_in == 0 and len(xs)) or (n_in and len(xs) % n_in):
+            raise ValueError(f"xs holds {len(xs)} scalars, not a multiple of n_in = {n_in}")
+        return (len(xs) // n_in if n_in else 0), n_in, xs
+    if isinstance(xs, np.ndarray) and xs.dtype == np.uint8:
+        if xs.ndim != 3 or xs.shape[2] != 32:
+            raise ValueError("xs as an array: (K, n_in, 32) uint8 little-endian residues")
+        rows = np.ascontiguousarray(xs)
+        big = np.argwhere(rows[:, :, 31] >= 0x10)       # l < 2^253: the few values that may not be canonical
+        if len(big):
+            rows = rows.copy()
+            for p, i in big.tolist():
+                v = int.from_bytes(rows[p, i].tobytes(), "little") % ORDER
+                rows[p, i] = np.frombuffer(v.to_bytes(32, "little"), np.uint8)
+        return rows.shape[0], rows.shape[1], rows
+    xs = [list(x) for x in xs]
+    if not xs:
+        return 0, 0, np.zeros((0, 0, 32), np.uint8)
+    if any(len(x) != len(xs[0]) for x in xs):
+        raise ValueError("xs: every witness takes the same number of inputs")
+    rows = [sparse.residue_array([pivot._residue(v) for v in x], ORDER).reshape(len(xs[0]), 32) for x in xs]
+    return len(xs), len(xs[0]), np.stack(rows)
+
+
+def _input_lists(xs, n_in):
+    """xs as K lists of Python values, for the paths that are host list code"""
+    if isinstance(xs, ScalarVector):
+        K, n_in, _ = _batch_inputs(xs, n_in)
+        flat = xs.to_ints()
+        return [flat[p * n_in:(p + 1) * n_in] for p in range(K)]
+    if isinstance(xs, np.ndarray) and xs.dtype == np.uint8:
+        K, n_in, rows = _batch_inputs(xs, n_in)
+        return [[int.from_bytes(rows[p, i].tobytes(), "little") for i in range(n_in)] for p in range(K)]
+    return [list(x) for x in xs]
+
+
+def _batch_bytes(circuit, n_in, k):
+    """device bytes of k witnesses' Z, row values and extension workspace"""
+    m = circuit.m
+    return 32 * k * (n_in + 3 + 2 * m + 2 * (m + 1)) + circuit.device()["ctx"].cs_extend_batch_bytes(m, k)
+
+
+def _chunk_size(circuit, n_in, K):
+    """the most witnesses (<= K) whose _batch_bytes stay within BATCH_BUDGET_BYTES, at least one"""
+    lo, hi = 1, min(K, MAX_BATCH)
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if _batch_bytes(circuit, n_in, mid) <= BATCH_BUDGET_BYTES:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def _witnesses_on_device(circuit, rows, n_in, draws, gamma_witnesses=None, first=0):
+    """Z: the K = len(draws) vectors z of _witness_on_device as consecutive rows of ONE device vector (stride N), for
+    the inputs `rows` (host array or device vector from witness 0 on) and draws [(r_a, r_b, ..)].  Every stage runs
+    once for all K; `first` is only what an error calls witness 0."""
+    K, m, n_x = len(draws), circuit.m, circuit.n_x
+    d = circuit.device()
+    ctx = d["ctx"]
+    M, N, g_off = m + 1, n_in + 3 + 2 * m, n_in + 3
+    Z = ScalarVector.empty(K * N, ctx)
+    a, b = ScalarVector.empty(K * M, ctx), ScalarVector.empty(K * M, ctx)
+    X = rows if isinstance(rows, ScalarVector) else ScalarVector.from_array(rows.reshape(K * n_in, 32), ctx)
+    r = ctx.upload(sparse.residue_array([dr[0] for dr in draws] + [dr[1] for dr in draws], ORDER))
+    G = None
+    if gamma_witnesses is not None and m:
+        G = ctx.upload(sparse.residue_array([pivot._residue(v) for gw in gamma_witnesses for v in gw], ORDER))
+    for p in range(K):
+        ctx.copy(Z.ptr + 32 * p * N, X.ptr + 32 * p * n_in, 32 * n_in)
+        ctx.copy(a.ptr + 32 * (p * M + m), r.ptr + 32 * p, 32)
+        ctx.copy(b.ptr + 32 * (p * M + m), r.ptr + 32 * (K + p), 32)
+        if G is not None:
+            ctx.copy(Z.ptr + 32 * (p * N + g_off), G.ptr + 32 * p * m, 32 * m)
+    if G is not None:
+        bad = ctx.alloc(4 * K)
+        ctx.cs_triples_batch(d["A"].csr(), d["B"].csr(), None, m, n_x, g_off, Z.ptr, N, a.ptr, b.ptr, M, K, 1, bad.ptr)
+        firsts = ctx.download(bad.ptr, 4 * K).view(np.uint32)
+        for p in np.nonzero(firsts != 0xFFFFFFFF)[0][:1].tolist():
+            raise ValueError(f"gamma_witnesses[{first + p}]: multiplication gate {int(firsts[p])} is not the product of "
+                             f"its wires")
+    elif gamma_witnesses is None:
+        for lv in range(len(circuit.level_ptr) - 1):
+            lo, hi = int(circuit.level_ptr[lv]), int(circuit.level_ptr[lv + 1])
+            ctx.cs_triples_batch(d["A"].csr(), d["B"].csr(), d["order"].ptr + 4 * lo, hi - lo, n_x, g_off, Z.ptr, N, a.ptr,
+                                 b.ptr, M, K)
+    ctx.cs_extend_batch(a.ptr, b.ptr, M, m, d["fact"].ptr, d["ifact"].ptr, Z.ptr + 32 * n_in, N, K)
+    return Z
+
+
+def _prove_chunk(generators, circuit, rows, n_in, draws, gamma_witnesses, gf, first):
+    """Protocol 8 without the pivot for the witnesses of one chunk, stage by stage; nothing is read back inside a loop
+    over witnesses"""
+    order, K, m, n_x, n_out = gf.order, len(draws), circuit.m, circuit.n_x, circuit.n_out
+    d = circuit.device()
+    ctx, N, g_off = d["ctx"], n_in + 3 + 2 * m, n_in + 3
+    Z = _witnesses_on_device(circuit, rows, n_in, draws, gamma_witnesses, first)
+    zs = [Z[p * N:(p + 1) * N] for p in range(K)]           # views: each keeps the allocation alive
+    gv, h = pivot._points_on_device(generators["g"]), pivot._as_point(generators["h"])
+    assert len(gv) >= N, "Not enough generators."
+    pending = [pivot._commit_launch(z, dr[2], gv, h, gv.ctx) for z, dr in zip(zs, draws)]
+    commitments = [pc.result() for pc in pending]           # the first waits for all K, the others only copy
+    digests = [_first_digest(zc, circuit, n_in) for zc in commitments]
+    cs = [first_challenge(dg, order) for dg in digests]
+    for p, c in enumerate(cs):
+        if 0 <= c <= 2 * m:
+            raise ChallengeOnNode(f"Protocol 8, witness {first + p}: the first challenge {c} is an interpolation node "
+                                  f"(0..{2 * m})")
+    # per witness F z, G z, H z and the constants of F and G: five scalars, read back together
+    Y = ScalarVector.empty(5 * K, ctx)
+    forms = []
+    for p, (z, c) in enumerate(zip(zs, cs)):
+        f = _Forms(circuit, n_in, c, order, Y.ptr + 32 * (5 * p + 3))
+        for i, V in enumerate((f.F, f.G, f.H)):
+            ctx.fr_dot_into(V.ptr, z.ptr, N, Y.ptr + 32 * (5 * p + i))
+        forms.append(f)
+    o1 = None
+    if n_out:
+        o1 = ScalarVector.empty(K * n_out, ctx)
+        ctx.cs_triples_batch(d["O"].csr(), d["O"].csr(), None, n_out, n_x, g_off, Z.ptr, N, o1.ptr, o1.ptr, n_out, K, 2)
+    ys = Y.to_ints()
+    outs = o1.to_ints() if n_out else []
+    results = []
+    for p, (z, zc, f, dg, dr) in enumerate(zip(zs, commitments, forms, digests, draws)):
+        f.k = [ys[5 * p + 3], ys[5 * p + 4], 0] if m else [0, 0, 0]
+        y1, y2, y3 = (gf((v + k) % order) for v, k in zip(ys[5 * p:5 * p + 3], f.k))
+        assert y1 * y2 == y3
+        proof = {"z_commitment": zc, "y1": y1, "y2": y2, "y3": y3}
+        outputs = [gf(v) for v in outs[p * n_out:(p + 1) * n_out]]
+        proof["outputs"] = outputs
+        rho = _second_challenge(dg, (y1, y2, y3), outputs, order)
+        L = f.combine(rho, (y1, y2, y3), outputs, gf)
+        proof["L"] = L
+        results.append((proof, zc, L, z, dr[2]))
+    return results
+
+
+def protocol_8_excl_pivot_prover_batch(generators, circuit, xs, gf, gamma_witnesses=None, transcript=None, n_in=None):
+    """[protocol_8_excl_pivot_prover(generators, circuit, x, gf, ...) for x in xs] for K inputs of ONE circuit, with the
+    random draws those K calls would make (r_a, r_b, gamma of witness 0, then witness 1, ..: all before the first launch)
+    and so the same proofs - but every stage once for all K: one launch per depth level, one batched extension, K queued
+    commitments read back together, K queued sets of forms whose values are read back together.
+
+    xs: K input lists of one length; a (K, n_in, 32) uint8 array of little-endian residues; or a device ScalarVector of
+    K n_in scalars with n_in=.  gamma_witnesses: K lists of gate outputs, checked in one launch.  Each returned z is a
+    slice of one device vector.  K is cut into chunks of at most BATCH_BUDGET_BYTES of Z, row values and workspace."""
+    mode = _mode(transcript)
+    if "g" not in generators:
+        raise NotImplementedError("Protocol 8 over a SparseCircuit: the knowledge-of-exponent variant lives in another "
+                                  "field (BN-256) and is not built")
+    circuit = as_sparse(circuit)
+    order = gf.order
+    assert order == ORDER
+    if mode == "reference":             # host list code by construction
+        lists = _input_lists(xs, n_in)
+        gws = gamma_witnesses if gamma_witnesses is not None else [None] * len(lists)
+        return [protocol_8_excl_pivot_prover(generators, circuit, x, gf, gamma_witness=gw, transcript=mode)
+                for x, gw in zip(lists, gws)]
+    K, n_in, rows = _batch_inputs(xs, n_in)
+    if K == 0:
+        return []
+    if n_in < circuit.n_x:
+        raise ValueError(f"the circuit has {circuit.n_x} inputs, {n_in} given")
+    if gamma_witnesses is not None:
+        gamma_witnesses = [list(gw) for gw in gamma_witnesses]
+        if len(gamma_witnesses) != K or any(len(gw) != circuit.m for gw in gamma_witnesses):
+            raise ValueError(f"gamma_witnesses: {K} lists of {circuit.m} gate outputs expected")
+    draws = [(prng.randrange(1, order), prng.randrange(1, order), prng.randrange(1, order)) for _ in range(K)]
+    step = _chunk_size(circuit, n_in, K)
+    results = []
+    for lo in range(0, K, step):
+        hi = min(K, lo + step)
+        part = rows[lo * n_in:hi * n_in] if isinstance(rows, ScalarVector) else rows[lo:hi]
+        results += _prove_chunk(generators, circuit, part, n_in, draws[lo:hi],
+                                gamma_witnesses[lo:hi] if gamma_witnesses is not None else None, gf, lo)
+    return results
+
+
+def circuit_sat_prover_batch(generators, circuit, xs, gf, pivot_choice="compressed", gamma_witnesses=None, transcript=None,
+                             n_in=None):
+    """[circuit_sat_prover(generators, circuit, x, gf, pivot_choice, ...) for x in xs]: Protocol 8 for all K witnesses
+    together (protocol_8_excl_pivot_prover_batch), then the compressed pivot per witness, in order.  The plain pivot and
+    the reference transcript are host list code: a loop over circuit_sat_prover."""
+    choice = _choice(pivot_choice)
+    if choice == "koe":
+        raise NotImplementedError("PivotChoice.koe over a SparseCircuit: the knowledge-of-exponent pivot lives in "
+                                  "another field (BN-256); Protocol 8 is built over the Ed25519 scalar field")
+    if choice not in ("compressed", "pivot"):
+        raise NotImplementedError
+    mode = _mode(transcript)
+    if choice == "pivot" or mode == "reference":
+        lists = _input_lists(xs, n_in)
+        gws = gamma_witnesses if gamma_witnesses is not None else [None] * len(lists)
+        return [circuit_sat_prover(generators, circuit, x, gf, pivot_choice, gamma_witness=gw, transcript=mode)
+                for x, gw in zip(lists, gws)]
+    proofs = []
+    for proof, z_commitment, L, z, gamma in protocol_8_excl_pivot_prover_batch(generators, circuit, xs, gf,
+                                                                               gamma_witnesses, mode, n_in):
+        y = L(z)
+        r = compressed_pivot.masks(len(z), L.coeffs.ctx) if len(z) >= compressed_pivot.MASKS_ON_DEVICE_MIN else None
+        proof["pivot_proof"] = compressed_pivot.protocol_5_prover(generators, z_commitment, L, y, z, gamma, gf,
+                                                                  transcript=mode, r=r)
+        proofs.append(proof)
+    return proofs

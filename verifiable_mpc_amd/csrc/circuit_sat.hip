@@ -8,6 +8,8 @@
 //                             straight into z (gamma_i = h(i + 1)); one launch per depth level.  With check != 0 the
 //                             gammas in z are the caller's and the smallest i with a_i b_i != gamma_i is reported
 //                             (circuit_builder.py:133-151 evaluates the forms one gate after the other in Python).
+//   vmpc_fr_cs_triples_batch_dev  the same for K witnesses of ONE circuit in one launch: the witness on blockIdx.y, z and the
+//                             row values K rows of one allocation
 //   vmpc_fr_cs_tables_dev     k! and 1 / k! for k <= K: two product scans (csrc/fr_scan.h) and ONE inversion.  Everything below is
 //                             products of these: 1 / k = (k-1)! / k!, the barycentric weights
 //                             w_j = (-1)^(M-j) / ((j-1)! (M-j)!), l(x) = prod_j (x - j) = (x-1)! / (x-M-1)! for x > M.
@@ -22,6 +24,8 @@
 //                             partial sums added in a fixed order.  Integer sums only: deterministic.
 //   vmpc_fr_cs_extend_fg_dev  the same f(x), g(x) left apart and unmultiplied, for a witness that is a vector of Shamir
 //                             shares: the extension is linear in v, the product is the parties' (csrc/mpc_share.hip)
+//   vmpc_fr_cs_extend_batch_dev  vmpc_fr_cs_extend_dev for K witnesses: T and the weights once, the correlation on a grid
+//                             (tiles, segments, witness), the segment length chosen with K counted
 //   vmpc_fr_cs_lagrange_dev   the Lagrange vector of the nodes 0..K at c (ac20/recombine.py:5-32, a double loop):
 //                             lambda_j = prod_{i != j} (c - i) * (-1)^(K-j) / (j! (K-j)!) - prefix and suffix products
 //                             of (c - i), no inversion at all, so a c on a node cannot divide by zero here (the
@@ -95,6 +99,59 @@ extern "C" int vmpc_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, 
         a_row_ptr, a_col, (const uint32_t *)a_vals, (const uint32_t *)a_const, b_row_ptr, b_col, (const uint32_t *)b_vals,
         (const uint32_t *)b_const, gates, (uint32_t)n_gates, (uint32_t)n_x, (uint32_t)gamma_offset, (uint32_t *)z,
         (uint32_t *)a_out, (uint32_t *)b_out, check, first_bad);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+// the witness on blockIdx.y: the forms and the level's gate list are the circuit's, z / a_out / b_out rows w of K
+// (strides in scalars), first_bad one word per witness.  a_out and b_out may be one buffer (check == 2).
+__global__ void __launch_bounds__(CS_WG)
+k_cs_triples_batch(const uint32_t *__restrict__ a_rp, const uint32_t *__restrict__ a_col, const uint32_t *__restrict__ a_val,
+                   const uint32_t *__restrict__ a_cst, const uint32_t *__restrict__ b_rp, const uint32_t *__restrict__ b_col,
+                   const uint32_t *__restrict__ b_val, const uint32_t *__restrict__ b_cst, const uint32_t *__restrict__ gates,
+                   uint32_t n_gates, uint32_t n_x, uint32_t g_off, uint32_t *z, size_t z_stride, uint32_t *a_out,
+                   uint32_t *b_out, size_t ab_stride, int check, uint32_t *__restrict__ first_bad) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_gates) return;
+    const size_t w = blockIdx.y;
+    z += w * z_stride * 8;
+    a_out += w * ab_stride * 8;
+    b_out += w * ab_stride * 8;
+    const uint32_t i = gates ? gates[t] : t;
+    const fr a = cs_row_eval(a_rp, a_col, a_val, a_cst, i, n_x, g_off, z);
+    const fr b = cs_row_eval(b_rp, b_col, b_val, b_cst, i, n_x, g_off, z);
+    f256_st(a_out, i, a);
+    f256_st(b_out, i, b);
+    if (check == 2) return;
+    const fr p = fr_mul(a, b);
+    if (check) {
+        if (!f256_equal(p, f256_ld<fr>(z, (long long)g_off + i))) atomicMin(first_bad + w, i);
+    } else {
+        f256_st(z, (long long)g_off + i, p);
+    }
+}
+
+extern "C" int vmpc_fr_cs_triples_batch_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col,
+                                            const void *a_vals, const void *a_const, const uint32_t *b_row_ptr,
+                                            const uint32_t *b_col, const void *b_vals, const void *b_const,
+                                            const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset, void *z,
+                                            size_t z_stride, void *a_out, void *b_out, size_t ab_stride, size_t n_wit,
+                                            int check, uint32_t *first_bad) {
+    if (n_gates > VMPC_FR_CS_MAX_M || n_x > ((size_t)1 << 30) || gamma_offset > ((size_t)1 << 30) ||
+        n_wit > VMPC_FR_CS_MAX_WIT || z_stride > ((size_t)1 << 31) || ab_stride > ((size_t)1 << 31) ||
+        (n_gates && n_wit && (z_stride < gamma_offset + (check == 2 ? 0 : n_gates) || ab_stride < n_gates)))
+        return VMPC_E_RANGE;
+    if (!ctx || !a_row_ptr || !b_row_ptr || !a_const || !b_const || !z || !a_out || !b_out || (check == 1 && !first_bad) ||
+        check < 0 || check > 2)
+        return VMPC_E_INVAL;
+    if (n_gates == 0 || n_wit == 0) return VMPC_OK;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope sc(ctx, check ? "cs_triples_batch_check" : "cs_triples_batch");
+    if (check == 1) VMPC_HIP_CHECK(hipMemsetAsync(first_bad, 0xFF, 4 * n_wit, ctx->stream));
+    k_cs_triples_batch<<<dim3((unsigned)((n_gates + CS_WG - 1) / CS_WG), (unsigned)n_wit), CS_WG, 0, ctx->stream>>>(
+        a_row_ptr, a_col, (const uint32_t *)a_vals, (const uint32_t *)a_const, b_row_ptr, b_col, (const uint32_t *)b_vals,
+        (const uint32_t *)b_const, gates, (uint32_t)n_gates, (uint32_t)n_x, (uint32_t)gamma_offset, (uint32_t *)z, z_stride,
+        (uint32_t *)a_out, (uint32_t *)b_out, ab_stride, check, first_bad);
     VMPC_KERNEL_CHECK();
     return VMPC_OK;
 }
@@ -352,6 +409,172 @@ extern "C" int vmpc_fr_cs_extend_fg_dev(vmpc_ctx *ctx, const void *a, const void
     if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
     if (!ctx || !a || !b || !fact || !ifact || !f_out || !g_out) return VMPC_E_INVAL;
     return cs_extend(ctx, a, b, m, fact, ifact, nullptr, f_out, g_out);
+}
+
+// ---- the extension for K witnesses of one circuit ----------------------------------------------------------------------
+// Witness w reads rows w of a, b (ab_stride scalars apart) and writes row w of the z tails (z_stride apart); uf, ug, s0
+// and the partial sums are K rows of the workspace, T and the weights are the circuit's and computed once.
+__global__ void __launch_bounds__(CS_WG)
+k_cs_prep_batch(uint32_t M, uint32_t n_t, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, size_t ab_stride,
+                const uint32_t *__restrict__ fact, const uint32_t *__restrict__ ifact, uint32_t *__restrict__ uf,
+                uint32_t *__restrict__ ug, uint32_t *__restrict__ T) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t w = blockIdx.y;
+    if (i < M) {
+        const uint32_t j = i + 1;
+        fr wt = fr_mul(f256_ld<fr>(ifact, j - 1), f256_ld<fr>(ifact, M - j));
+        if ((M - j) & 1u) wt = fr_neg(wt);
+        f256_st(uf + w * M * 8, i, fr_mul(f256_ld<fr>(a + w * ab_stride * 8, i), wt));
+        f256_st(ug + w * M * 8, i, fr_mul(f256_ld<fr>(b + w * ab_stride * 8, i), wt));
+    }
+    if (w == 0 && i < n_t) f256_st(T, i, i ? fr_mul(f256_ld<fr>(fact, i - 1), f256_ld<fr>(ifact, i)) : fr_zero());
+}
+
+// one workgroup per witness: s0[2 w], s0[2 w + 1] as k_cs_dot0 (the same lanes, the same order)
+__global__ void __launch_bounds__(CS_WG)
+k_cs_dot0_batch(uint32_t M, const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, const uint32_t *__restrict__ T,
+                uint32_t *__restrict__ s0) {
+    __shared__ fr part[2][CS_WG];
+    const uint32_t t = threadIdx.x;
+    const size_t w = blockIdx.x;
+    uf += w * M * 8;
+    ug += w * M * 8;
+    f256_acc af = f256_acc_zero(), ag = f256_acc_zero();
+    for (uint32_t i = t; i < M; i += CS_WG) {
+        const fr y = f256_ld<fr>(T, (long long)i + 1), xf = f256_ld<fr>(uf, i), xg = f256_ld<fr>(ug, i);
+        f256_acc_mac(af, xf.v, y.v);
+        f256_acc_mac(ag, xg.v, y.v);
+    }
+    part[0][t] = f256_acc_reduce<fr>(af);
+    part[1][t] = f256_acc_reduce<fr>(ag);
+    __syncthreads();
+    if (t < 2) {
+        fr s = part[t][0];
+        for (uint32_t i = 1; i < CS_WG; i++) s = fr_add(s, part[t][i]);
+        f256_st(s0, (long long)(2 * w + t), s);
+    }
+}
+
+// grid (tiles, segments, witnesses): k_cs_corr's tile on witness blockIdx.z's uf, ug; its partial sums are rows
+// (w n_seg + s) of part_f, part_g
+__global__ void __launch_bounds__(FR_CONV_TILE)
+k_cs_corr_batch(const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, long long M, const uint32_t *__restrict__ T,
+                long long n_t, long long k_lo, long long n_out, long long seg, uint32_t *__restrict__ part_f,
+                uint32_t *__restrict__ part_g) {
+    __shared__ uint32_t sU[2][FR_CONV_CHUNK * 8];
+    __shared__ uint32_t sT[8 * FR_CONV_BROW];
+    const long long o0 = (long long)blockIdx.x * FR_CONV_TILE, k0 = k_lo + o0;
+    const long long seg_lo = (long long)blockIdx.y * seg;
+    const size_t w = blockIdx.z;
+    const uint32_t *const u[2] = {uf + w * (size_t)M * 8, ug + w * (size_t)M * 8};
+    f256_acc acc[2] = {f256_acc_zero(), f256_acc_zero()};
+    for (long long i0 = seg_lo; i0 < seg_lo + seg && i0 < M; i0 += FR_CONV_CHUNK)
+        fr_conv_chunk<fr, 2>(sU, sT, acc, u, M, T, n_t, k0, i0);
+    const long long o = o0 + threadIdx.x;
+    if (o < n_out) {
+        const long long row = (long long)w * gridDim.y + blockIdx.y;
+        f256_st(part_f, row * n_out + o, f256_acc_reduce<fr>(acc[0]));
+        f256_st(part_g, row * n_out + o, f256_acc_reduce<fr>(acc[1]));
+    }
+}
+
+// grid (outputs, witnesses): k_cs_finish on witness blockIdx.y's partial sums, s0, row values and z tail
+__global__ void __launch_bounds__(CS_WG)
+k_cs_finish_batch(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restrict__ part_f,
+                  const uint32_t *__restrict__ part_g, const uint32_t *__restrict__ s0, const uint32_t *__restrict__ a,
+                  const uint32_t *__restrict__ b, size_t ab_stride, const uint32_t *__restrict__ fact,
+                  const uint32_t *__restrict__ ifact, uint32_t *__restrict__ zt, size_t z_stride) {
+    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t M = m + 1;
+    const size_t w = blockIdx.y;
+    zt += w * z_stride * 8;
+    if (o < n_out) {
+        const size_t rows = w * n_seg * (size_t)n_out * 8;
+        const fr sf = fr_partsum<fr>(part_f + rows, n_out, n_seg, o), sg = fr_partsum<fr>(part_g + rows, n_out, n_seg, o);
+        const uint32_t x = m + 2 + o;
+        const fr lx = fr_mul(f256_ld<fr>(fact, x - 1), f256_ld<fr>(ifact, x - M - 1));
+        f256_st(zt, 2 + (long long)x, fr_mul(fr_mul(lx, sf), fr_mul(lx, sg)));
+    } else if (o == n_out) {
+        fr l0 = f256_ld<fr>(fact, M);
+        if (!(M & 1u)) l0 = fr_neg(l0);
+        const fr f0 = fr_mul(l0, f256_ld<fr>(s0, (long long)(2 * w))), g0 = fr_mul(l0, f256_ld<fr>(s0, (long long)(2 * w + 1)));
+        f256_st(zt, 0, f0);
+        f256_st(zt, 1, g0);
+        f256_st(zt, 2, fr_mul(f0, g0));
+        if (m) f256_st(zt, 2 + (long long)M, fr_mul(f256_ld<fr>(a + w * ab_stride * 8, m), f256_ld<fr>(b + w * ab_stride * 8, m)));
+    }
+}
+
+// The segment length with the witnesses counted: tiles x segments x K workgroups against CS_TARGET_WGS.  K = 1 is
+// cs_extend's choice; a large batch ends at one segment per witness, so the partial sums never exceed K n_out scalars
+// per polynomial beyond what the grid needs.
+struct cs_batch_plan {
+    long long seg;
+    unsigned tiles, n_seg;
+    size_t part_b, total_b;
+};
+
+static cs_batch_plan cs_extend_batch_plan(size_t m, size_t n_wit) {
+    const long long M = (long long)m + 1, n_t = 2 * (long long)m + 2, n_out = m >= 2 ? (long long)m - 1 : 0;
+    cs_batch_plan p;
+    p.tiles = (unsigned)((n_out + FR_CONV_TILE - 1) / FR_CONV_TILE);
+    p.seg = CS_MIN_SEG;
+    while ((long long)p.tiles * ((M + p.seg - 1) / p.seg) * (long long)n_wit > CS_TARGET_WGS && p.seg < M) p.seg *= 2;
+    p.n_seg = (unsigned)((M + p.seg - 1) / p.seg);
+    p.part_b = vmpc_align(n_wit * (size_t)p.n_seg * (size_t)(n_out ? n_out : 1) * 32);
+    p.total_b = 2 * vmpc_align(n_wit * (size_t)M * 32) + vmpc_align((size_t)n_t * 32) + 2 * p.part_b +
+                vmpc_align(n_wit * 64) + 2048;
+    return p;
+}
+
+extern "C" size_t vmpc_fr_cs_extend_batch_bytes(size_t m, size_t n_wit) {
+    if (m > VMPC_FR_CS_MAX_M || n_wit > VMPC_FR_CS_MAX_WIT || n_wit == 0) return 0;
+    return cs_extend_batch_plan(m, n_wit).total_b;
+}
+
+extern "C" int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m,
+                                           const void *fact, const void *ifact, void *z_tail, size_t z_stride,
+                                           size_t n_wit) {
+    if (m > VMPC_FR_CS_MAX_M || n_wit > VMPC_FR_CS_MAX_WIT || ab_stride > ((size_t)1 << 31) ||
+        z_stride > ((size_t)1 << 31) || (n_wit && (ab_stride < m + 1 || z_stride < 2 * m + 3)))
+        return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !fact || !ifact || !z_tail) return VMPC_E_INVAL;
+    if (n_wit == 0) return VMPC_OK;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const long long M = (long long)m + 1, n_t = 2 * (long long)m + 2;
+    const long long n_out = m >= 2 ? (long long)m - 1 : 0, k_lo = (long long)m + 1;
+    const cs_batch_plan p = cs_extend_batch_plan(m, n_wit);
+    VMPC_CHECK(vmpc_ws_reserve(ctx, p.total_b));        // before any launch: a batch too large for the arena does nothing
+    uint32_t *uf = (uint32_t *)vmpc_ws_take(ctx, n_wit * (size_t)M * 32);
+    uint32_t *ug = (uint32_t *)vmpc_ws_take(ctx, n_wit * (size_t)M * 32);
+    uint32_t *T = (uint32_t *)vmpc_ws_take(ctx, (size_t)n_t * 32);
+    uint32_t *pf = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
+    uint32_t *pg = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
+    uint32_t *s0 = (uint32_t *)vmpc_ws_take(ctx, n_wit * 64);
+    const unsigned K = (unsigned)n_wit;
+    {
+        vmpc_stage_scope sc(ctx, "cs_extend_batch_prep");
+        k_cs_prep_batch<<<dim3((unsigned)((n_t + CS_WG - 1) / CS_WG), K), CS_WG, 0, ctx->stream>>>(
+            (uint32_t)M, (uint32_t)n_t, (const uint32_t *)a, (const uint32_t *)b, ab_stride, (const uint32_t *)fact,
+            (const uint32_t *)ifact, uf, ug, T);
+        VMPC_KERNEL_CHECK();
+        k_cs_dot0_batch<<<K, CS_WG, 0, ctx->stream>>>((uint32_t)M, uf, ug, T, s0);
+        VMPC_KERNEL_CHECK();
+    }
+    if (n_out) {
+        vmpc_stage_scope sc(ctx, "cs_extend_batch_corr");
+        k_cs_corr_batch<<<dim3(p.tiles, p.n_seg, K), FR_CONV_TILE, 0, ctx->stream>>>(uf, ug, M, T, n_t, k_lo, n_out, p.seg, pf,
+                                                                                   pg);
+        VMPC_KERNEL_CHECK();
+    }
+    {
+        vmpc_stage_scope sc(ctx, "cs_extend_batch_finish");
+        k_cs_finish_batch<<<dim3((unsigned)((n_out + 1 + CS_WG - 1) / CS_WG), K), CS_WG, 0, ctx->stream>>>(
+            (uint32_t)m, (uint32_t)n_out, p.n_seg, pf, pg, s0, (const uint32_t *)a, (const uint32_t *)b, ab_stride,
+            (const uint32_t *)fact, (const uint32_t *)ifact, (uint32_t *)z_tail, z_stride);
+        VMPC_KERNEL_CHECK();
+    }
+    return VMPC_OK;
 }
 
 // ---- transposed sparse mat-vec -----------------------------------------------------------------------------------------
