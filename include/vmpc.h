@@ -101,6 +101,24 @@ int vmpc_ctx_set_bucket_stream(vmpc_ctx *ctx, void *hip_stream, int wgs_per_cu);
 int vmpc_ctx_set_window(vmpc_ctx *ctx, int c_bits);
 /* the window width and window count the planner uses for an n-term Ed25519 MSM */
 int vmpc_ed25519_msm_plan(vmpc_ctx *ctx, size_t n, int *c_bits, int *windows);
+/* Read-only view of the sort front end (csrc/msm_sort.hip) of the LAST MSM call on this context, for tests: the plan
+ * and the device addresses of the arrays the sort and the segment planning left in the context's workspace.  The
+ * workspace is reset at the start of every call that uses it, so the arrays are valid from the moment the MSM call
+ * has completed (the caller synchronises first) until the next such call; nothing after the sort writes them (the
+ * bucket, finish, reduce and recombination kernels read them only).  A batched BN-256 table MSM leaves the view of its
+ * one shared pass.  VMPC_E_INVAL when no sort has run since the workspace was last reset - in particular when the
+ * last call took the fused short path, which does not use this stage.  Host side only: no launch, no device access.
+ * Element types: digits int16 (int32 when `wide`) [W][n_pad]; tasks uint32[4] records, ctrl[1] of them (<= t_max);
+ * every other array uint32: hist1[hist1_n + 1], counts / starts / nseg / seg_starts / heavy_list [W * nb1],
+ * sorted[hist1[hist1_n]], ctrl[16 + 64 * W]. */
+typedef struct vmpc_sort_view {
+    uint64_t n_total, n_pad, row_stride, hist1_n, t_max;
+    uint32_t top_max_b;
+    int32_t c, W, nb, nb1, period, top_row, LB, LB_top, NC, J, idx_bits, fine_in_entry, fine_cap, seg_shift, balanced,
+        wide, chunks_per_row;
+    const void *digits, *hist1, *counts, *starts, *sorted, *nseg, *seg_starts, *heavy_list, *tasks, *ctrl;
+} vmpc_sort_view;
+int vmpc_msm_sort_view(vmpc_ctx *ctx, vmpc_sort_view *out);
 /* Integer-ALU ceiling of the bucket stage (bench.py roofline leg): mixed additions per second of
  * a register-resident chain on every lane of the chip - the bucket kernel without memory. */
 int vmpc_ed25519_madd_rate(vmpc_ctx *ctx, int iters, double *madds_per_second);

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import ed25519_ref as ed
+from tests.msm_sort_ref import recode
 from tests.test_gpu_cabi import gpu_points, sc_bytes
 from tests.test_gpu_wide_table import ext_affine, stages
 
@@ -39,18 +40,6 @@ def make_ctx(nat, monkeypatch, seg64):
         monkeypatch.setenv("VMPC_EXPERIMENTAL", "1")
         monkeypatch.setenv("VMPC_SEG_SHIFT_MIN", "0")
     return nat.Context(0)
-
-
-def recode(s, c, W, order):
-    """the library's signed digits (msm_recode_term): W digits in [-2^(c-1), 2^(c-1))"""
-    assert s < order
-    half, out, carry = 1 << (c - 1), [], 0
-    for _ in range(W):
-        raw = (s & ((1 << c) - 1)) + carry
-        carry = 1 if raw >= half else 0
-        out.append(raw - (carry << c))
-        s >>= c
-    return out
 
 
 def heavy_vector(rng, L, v, c, W, one_set, order=ELL, n_random=N_RANDOM):

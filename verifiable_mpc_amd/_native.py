@@ -28,7 +28,7 @@ SYMBOLS = [
     "vmpc_backend_info", "vmpc_last_error", "vmpc_ctx_create", "vmpc_ctx_destroy",
     "vmpc_ctx_set_stream", "vmpc_ctx_sync", "vmpc_ctx_set_short_path", "vmpc_ctx_get_short_path", "vmpc_ctx_debug_hold_wait", "vmpc_ctx_query", "vmpc_ctx_wait_for", "vmpc_malloc", "vmpc_free", "vmpc_memcpy_h2d",
     "vmpc_memcpy_d2h", "vmpc_memcpy_d2d", "vmpc_ctx_profile", "vmpc_ctx_profile_read",
-    "vmpc_ctx_set_window", "vmpc_ed25519_msm_plan", "vmpc_ed25519_madd_rate", "vmpc_ed25519_msm", "vmpc_ed25519_fold",
+    "vmpc_ctx_set_window", "vmpc_ed25519_msm_plan", "vmpc_msm_sort_view", "vmpc_ed25519_madd_rate", "vmpc_ed25519_msm", "vmpc_ed25519_fold",
     "vmpc_ed25519_fixed_base_batch", "vmpc_fr_axpy", "vmpc_fr_dot", "vmpc_points_validate_dev",
     "vmpc_msm_dev", "vmpc_msm_table_bytes", "vmpc_msm_table_build_dev", "vmpc_msm_table_dev", "vmpc_msm_table_batch_dev", "vmpc_points_sum_dev", "vmpc_points_sum_many_dev", "vmpc_fixed_base_dev", "vmpc_repeat_dev", "vmpc_fold_dev",
     "vmpc_tree_reduce_dev", "vmpc_normalize_dev", "vmpc_affine_to_proj_dev", "vmpc_fr_axpy_dev",
@@ -56,6 +56,16 @@ SYMBOLS = [
     "vmpc_bn256_fr_share_mul_deal_dev", "vmpc_bn256_fr_share_combine_dev", "vmpc_bn256_qap_residual_dev",
     "vmpc_fr_cs_triples_batch_dev", "vmpc_fr_cs_extend_batch_dev", "vmpc_fr_cs_extend_batch_bytes",
 ]
+
+
+class SortView(ctypes.Structure):
+    """vmpc_sort_view (include/vmpc.h): the plan of the last sort and the device addresses of its arrays"""
+    PLAN_U64 = ("n_total", "n_pad", "row_stride", "hist1_n", "t_max")
+    PLAN_I32 = ("c", "W", "nb", "nb1", "period", "top_row", "LB", "LB_top", "NC", "J", "idx_bits", "fine_in_entry",
+                "fine_cap", "seg_shift", "balanced", "wide", "chunks_per_row")
+    ARRAYS = ("digits", "hist1", "counts", "starts", "sorted", "nseg", "seg_starts", "heavy_list", "tasks", "ctrl")
+    _fields_ = ([(k, ctypes.c_uint64) for k in PLAN_U64] + [("top_max_b", ctypes.c_uint32)] +
+                [(k, ctypes.c_int32) for k in PLAN_I32] + [(k, ctypes.c_void_p) for k in ARRAYS])
 
 
 class VmpcError(RuntimeError):
@@ -107,6 +117,7 @@ def load_library():
         "vmpc_stream_destroy": (i32, [vp]),
         "vmpc_ctx_set_bucket_stream": (i32, [vp, vp, i32]),
         "vmpc_ed25519_msm_plan": (i32, [vp, sz, vp, vp]),
+        "vmpc_msm_sort_view": (i32, [vp, ctypes.POINTER(SortView)]),
         "vmpc_ed25519_madd_rate": (i32, [vp, i32, vp]),
         "vmpc_ed25519_msm": (i32, [vp, vp, sz, vp]),
         "vmpc_ed25519_fold": (i32, [vp, vp, vp, sz, vp]),
@@ -607,6 +618,29 @@ class Context:
         _check(self.lib.vmpc_ed25519_msm_plan(self.handle, int(n), ctypes.byref(c), ctypes.byref(w)),
                "vmpc_ed25519_msm_plan")
         return c.value, w.value
+
+    def msm_sort_view(self):
+        """(plan, arrays) of the sort front end of the last MSM call (csrc/msm_sort.hip), downloaded: the plan as a
+        dict, every array as numpy - digits int16 (int32 for the wide window) [W, n_pad], tasks uint32 [ctrl[1], 4],
+        the others uint32 (sorted trimmed to the number of entries, ctrl to its five counters).  Synchronises.  Raises
+        VmpcError(E_INVAL) when the last call did not sort (the fused short path) or the workspace was reset since."""
+        self.sync()
+        v = SortView()
+        _check(self.lib.vmpc_msm_sort_view(self.handle, ctypes.byref(v)), "vmpc_msm_sort_view")
+        plan = {k: int(getattr(v, k)) for k in SortView.PLAN_U64 + ("top_max_b",) + SortView.PLAN_I32}
+
+        def get(name, count, dtype=np.uint32):
+            nbytes = count * np.dtype(dtype).itemsize
+            return self.download(getattr(v, name), nbytes).view(dtype) if count else np.zeros(0, dtype)
+        W, nbk = plan["W"], plan["W"] * plan["nb1"]
+        arrays = {"digits": get("digits", W * plan["n_pad"], np.int32 if plan["wide"] else np.int16)
+                  .reshape(W, plan["n_pad"]),
+                  "hist1": get("hist1", plan["hist1_n"] + 1), "ctrl": get("ctrl", 16)[:5].copy()}
+        for name in ("counts", "starts", "nseg", "seg_starts", "heavy_list"):
+            arrays[name] = get(name, nbk)
+        arrays["sorted"] = get("sorted", min(int(arrays["hist1"][-1]), W * plan["n_total"]))
+        arrays["tasks"] = get("tasks", 4 * min(int(arrays["ctrl"][1]), plan["t_max"])).reshape(-1, 4)
+        return plan, arrays
 
     def madd_rate(self, iters=400):
         """mixed additions per second of the register-resident ALU ceiling probe"""

@@ -265,6 +265,17 @@ extern "C" int vmpc_ctx_set_window(vmpc_ctx *ctx, int c_bits) {
     return VMPC_OK;
 }
 
+// the record msm_sort_digits left (msm_sort.hip); vmpc_ws_reserve voids it when the arena is handed out again
+extern "C" int vmpc_msm_sort_view(vmpc_ctx *ctx, vmpc_sort_view *out) {
+    if (!ctx || !out) return VMPC_E_INVAL;
+    if (!ctx->sort_view_valid) {
+        snprintf(vmpc_err_buf, sizeof vmpc_err_buf, "no sort has run since the workspace was last reset");
+        return VMPC_E_INVAL;
+    }
+    *out = ctx->sort_view;
+    return VMPC_OK;
+}
+
 int vmpc_pinned_reserve(vmpc_ctx *ctx, size_t bytes) {
     if (ctx->pin && bytes <= ctx->pin_bytes) return VMPC_OK;
     if (ctx->stream_waits) {
@@ -299,6 +310,7 @@ int vmpc_stage_h2d(vmpc_ctx *ctx, void *dst, const void *src, size_t bytes) {
 
 int vmpc_ws_reserve(vmpc_ctx *ctx, size_t total_bytes) {
     ctx->ws_used = 0;
+    ctx->sort_view_valid = false;       // the arena is handed out again: the last sort's arrays are void
     if (total_bytes <= ctx->ws_bytes) return VMPC_OK;
     if (ctx->stream_waits) {
         snprintf(vmpc_err_buf, sizeof vmpc_err_buf, "workspace would grow while the stream waits on the host");

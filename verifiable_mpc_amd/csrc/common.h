@@ -70,6 +70,9 @@ struct vmpc_ctx {
                                    // prover round: each scalar vector is zero on half of its positions): the segment
                                    // length follows the expected number of entries, not the number of positions
     int cu_count = 256;
+    // what the last sort left in the arena (msm_sort_digits records it, vmpc_ws_reserve clears it): vmpc_msm_sort_view
+    vmpc_sort_view sort_view = {};
+    bool sort_view_valid = false;
     hipEvent_t xevent = nullptr;   // cross-context ordering (vmpc_ctx_wait_for)
     // Phase pipelining (vmpc_ctx_set_bucket_stream): the bucket stage of every commitment of this context runs on a
     // stream SHARED by the contexts of a pipeline - bucket kernels then run back to back, one at a time, and the sort

@@ -1059,5 +1059,17 @@ int msm_sort_digits(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w) {
                                                   w.block_hist, w.tasks);
         VMPC_KERNEL_CHECK();
     }
+    {   // what this sort leaves in the arena, for vmpc_msm_sort_view (host side only; nothing later writes these arrays)
+        vmpc_sort_view &v = ctx->sort_view;
+        v.n_total = p.n_total; v.n_pad = p.n_pad; v.row_stride = p.row_stride; v.hist1_n = w.hist1_n; v.t_max = w.t_max;
+        v.top_max_b = p.top_max_b;
+        v.c = p.c; v.W = p.W; v.nb = p.nb; v.nb1 = p.nb1; v.period = p.period; v.top_row = p.top_row;
+        v.LB = p.LB; v.LB_top = p.LB_top; v.NC = p.NC; v.J = p.J; v.idx_bits = p.idx_bits;
+        v.fine_in_entry = p.fine_in_entry; v.fine_cap = p.fine_cap; v.seg_shift = p.seg_shift; v.balanced = p.balanced;
+        v.wide = p.wide; v.chunks_per_row = p.chunks_per_row;
+        v.digits = w.digits; v.hist1 = w.hist1; v.counts = w.counts; v.starts = w.starts; v.sorted = w.sorted;
+        v.nseg = w.nseg; v.seg_starts = w.seg_starts; v.heavy_list = w.heavy_list; v.tasks = w.tasks; v.ctrl = w.ctrl;
+        ctx->sort_view_valid = true;
+    }
     return VMPC_OK;
 }
