@@ -439,6 +439,20 @@ int vmpc_bn256_lincomb_batch(int group, const uint8_t *bases, size_t n_bases, co
 int vmpc_bn256_fr_poly_mul_dev(vmpc_ctx *ctx, const void *a, size_t na, const void *b, size_t nb, void *out);
 /* host-buffer form of the above (own context, synchronous) */
 int vmpc_bn256_fr_poly_mul(const uint8_t *a, size_t na, const uint8_t *b, size_t nb, uint8_t *out);
+/* n_wit products of one shape in one launch sequence: out_w[k - k_lo] = (a_w * b_w)[k] for k in the WINDOW
+ * [k_lo, k_lo + k_cnt) (k_lo + k_cnt <= na + nb - 1), row w of a / b / out at a_stride / b_stride / out_stride scalars
+ * (a_stride >= na, out_stride >= k_cnt; b_stride >= nb, or 0: ONE b for all products).  Only the tiles of 256 outputs that
+ * meet the window are launched and only the window's k_cnt scalars of a row are written - the batched h asks for the
+ * halves P[0 .. d-2] and Q[d-1 .. 2d-2] of its two d x d products.  The segment length is chosen with n_wit counted (a
+ * large batch: fewer, longer segments); canonical residues, so the bits are those of vmpc_bn256_fr_poly_mul_dev whatever
+ * the segmentation.  n_wit <= VMPC_BN256_QAP_MAX_WIT (the product index is a grid dimension), na and nb within the cap
+ * above, strides <= 2^31, else VMPC_E_RANGE before any pointer is looked at; n_wit = 0 or k_cnt = 0: VMPC_OK, no launch.
+ * Arena: vmpc_bn256_fr_poly_mul_batch_bytes(...), reserved before the first launch (0: the product needs none). */
+#define VMPC_BN256_QAP_MAX_WIT ((size_t)65535)
+int vmpc_bn256_fr_poly_mul_batch_dev(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b,
+                                     size_t b_stride, size_t nb, size_t k_lo, size_t k_cnt, void *out, size_t out_stride,
+                                     size_t n_wit);
+size_t vmpc_bn256_fr_poly_mul_batch_bytes(size_t na, size_t nb, size_t k_lo, size_t k_cnt, size_t n_wit);
 /* out[i] = scale * z^(i+1) mod n for i < count (z, scale: one 32-byte device scalar each): the exponents of the
  * trusted setup, which knowledge_of_exponent.py:52-66 reaches by 2n sequential `g1_base ** z` / `g2_base ** z` on the
  * points themselves; here the 2n points are vmpc_bn256_fixed_base_dev of these exponents. */
@@ -513,6 +527,33 @@ int vmpc_bn256_qap_horner_dev(vmpc_ctx *ctx, const void *coeffs, size_t n_coeffs
  * use it has. */
 int vmpc_bn256_qap_h_combine_dev(vmpc_ctx *ctx, const void *A, const void *B, const void *t, size_t d,
                                  const void *deltas, void *scratch, void *out);
+
+/* The same stages for n_wit witnesses of ONE QAP (the batch prover): the witness is a grid dimension,
+ * row w of every per-witness vector lies `stride` scalars after row w - 1 (a stride is at least the row's length and at
+ * most 2^31; scalars of a row beyond its length are never written).  The bits are those of n_wit single calls.
+ * n_wit <= VMPC_BN256_QAP_MAX_WIT and the cap on d as above, else VMPC_E_RANGE before any pointer is looked at; n_wit = 0:
+ * VMPC_OK, no launch.  Deterministic (integer sums in a fixed order, no atomics on field values).  Where an entry uses
+ * the arena it reserves it before its first launch: a batch too large for it does nothing. */
+/* first_bad[w] (n_wit device words) = witness w's smallest bad row, 0xffffffff if none; a, b, y share the stride */
+int vmpc_bn256_qap_check_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t stride, size_t d,
+                                   uint32_t *first_bad, size_t n_wit);
+/* the scan of the factorial prefix products and the inversion ONCE, then one launch for the n_wit rows of ua (and ub) */
+int vmpc_bn256_qap_h_weights_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t d, void *ua,
+                                       void *ub, size_t u_stride, size_t n_wit);
+/* vmpc_bn256_qap_moments_dev's workgroup on a grid (k segments, ranges of j, witnesses).  The number of ranges counts the
+ * witnesses: 2048 / (k segments x n_wit) under the single call's caps - n_wit = 1 is the single plan, a large batch ends
+ * at one range (one partial per k and witness).  Arena: vmpc_bn256_qap_moments_batch_bytes(d, n_out, n_wit) (0 where the
+ * call would answer VMPC_E_RANGE or do nothing). */
+int vmpc_bn256_qap_moments_batch_dev(vmpc_ctx *ctx, const void *u0, const void *u1, size_t u_stride, size_t d,
+                                     size_t n_out, void *out0, void *out1, size_t out_stride, size_t n_wit);
+size_t vmpc_bn256_qap_moments_batch_bytes(size_t d, size_t n_out, size_t n_wit);
+/* out rows (d + 1 scalars, out_stride apart) from the moments' rows A, B (ab_stride apart), t's d + 1 coefficients (the
+ * QAP's, shared) and deltas = n_wit x 3 consecutive scalars (NULL: all zero).  scratch: 3 d scalars per witness.  The two
+ * products go through vmpc_bn256_fr_poly_mul_batch_dev and are asked only for what is read: P[0 .. d-2] of A * B and
+ * Q[d-1 .. 2d-2] of (t_1 .. t_d) * crev, t passed as the shared b.  Arena: the larger of the two products'. */
+int vmpc_bn256_qap_h_combine_batch_dev(vmpc_ctx *ctx, const void *A, const void *B, size_t ab_stride, const void *t,
+                                       size_t d, const void *deltas, void *scratch, void *out, size_t out_stride,
+                                       size_t n_wit);
 
 /* ---- Protocol 8 from a sparse circuit (verifiable_mpc/ac20/circuit_sat_cb.py:59-252), scalars mod l as above ------
  * m multiplication gates, M = m + 1, z = (x, f(0), g(0), h(0), h(1), .., h(2m)); f runs through (j, a_j) for j = 1..m

@@ -49,6 +49,9 @@ SYMBOLS = [
     "vmpc_bn256_qap_lagrange_dev", "vmpc_bn256_qap_colsum_dev", "vmpc_bn256_keygen_exps_dev",
     "vmpc_bn256_qap_moments_dev", "vmpc_bn256_qap_h_weights_dev", "vmpc_bn256_qap_check_dev",
     "vmpc_bn256_qap_t_coeffs_dev", "vmpc_bn256_qap_horner_dev", "vmpc_bn256_qap_h_combine_dev",
+    "vmpc_bn256_qap_check_batch_dev", "vmpc_bn256_qap_h_weights_batch_dev", "vmpc_bn256_qap_moments_batch_dev",
+    "vmpc_bn256_qap_moments_batch_bytes", "vmpc_bn256_qap_h_combine_batch_dev", "vmpc_bn256_fr_poly_mul_batch_dev",
+    "vmpc_bn256_fr_poly_mul_batch_bytes",
     "vmpc_fr_cs_triples_dev", "vmpc_fr_cs_tables_dev", "vmpc_fr_cs_extend_dev", "vmpc_fr_cs_lagrange_dev",
     "vmpc_fr_cs_colsum_dev", "vmpc_fr_cs_first_diff_dev",
     "vmpc_fr_rows_combine_dev", "vmpc_fr_rows_dot_dev", "vmpc_fr_batch_products_dev",
@@ -182,6 +185,13 @@ def load_library():
         "vmpc_bn256_qap_t_coeffs_dev": (i32, [vp, sz, vp, vp]),
         "vmpc_bn256_qap_horner_dev": (i32, [vp, vp, sz, sz, sz, vp]),
         "vmpc_bn256_qap_h_combine_dev": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
+        "vmpc_bn256_qap_check_batch_dev": (i32, [vp, vp, vp, vp, sz, sz, vp, sz]),
+        "vmpc_bn256_qap_h_weights_batch_dev": (i32, [vp, vp, vp, sz, sz, vp, vp, sz, sz]),
+        "vmpc_bn256_qap_moments_batch_dev": (i32, [vp, vp, vp, sz, sz, sz, vp, vp, sz, sz]),
+        "vmpc_bn256_qap_moments_batch_bytes": (sz, [sz, sz, sz]),
+        "vmpc_bn256_qap_h_combine_batch_dev": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, sz]),
+        "vmpc_bn256_fr_poly_mul_batch_dev": (i32, [vp, vp, sz, sz, vp, sz, sz, sz, sz, vp, sz, sz]),
+        "vmpc_bn256_fr_poly_mul_batch_bytes": (sz, [sz, sz, sz, sz, sz]),
         "vmpc_fr_cs_triples_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, i32, vp]),
         "vmpc_fr_cs_tables_dev": (i32, [vp, sz, vp, vp]),
         "vmpc_fr_cs_triples_batch_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, sz, sz, i32,
@@ -1104,6 +1114,43 @@ class Context:
                                                      ctypes.c_void_p(scratch_ptr), ctypes.c_void_p(out_ptr)),
                "vmpc_bn256_qap_h_combine_dev")
 
+    # ---- the same stages for n_wit witnesses of one QAP (rows a stride in scalars apart; include/vmpc.h) ----------
+    def bn256_qap_check_batch(self, a_ptr, b_ptr, y_ptr, stride, d, first_bad_ptr, n_wit):
+        """n_wit device uint32 at first_bad_ptr: each witness's smallest bad row, 0xffffffff if none"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_bn256_qap_check_batch_dev(self.handle, p(a_ptr), p(b_ptr), p(y_ptr), stride, d,
+                                                       p(first_bad_ptr), n_wit), "vmpc_bn256_qap_check_batch_dev")
+
+    def bn256_qap_h_weights_batch(self, a_ptr, b_ptr, ab_stride, d, ua_ptr, ub_ptr, u_stride, n_wit):
+        """bn256_qap_h_weights for n_wit rows; the factorial scan and the inversion run once"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_bn256_qap_h_weights_batch_dev(self.handle, p(a_ptr), p(b_ptr), ab_stride, d, p(ua_ptr),
+                                                           p(ub_ptr), u_stride, n_wit),
+               "vmpc_bn256_qap_h_weights_batch_dev")
+
+    def bn256_qap_moments_batch(self, u0_ptr, u1_ptr, u_stride, d, n_out, out0_ptr, out1_ptr, out_stride, n_wit):
+        """bn256_qap_moments for n_wit rows in one launch, the ranges of j chosen with n_wit counted"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_bn256_qap_moments_batch_dev(self.handle, p(u0_ptr), p(u1_ptr), u_stride, d, n_out,
+                                                         p(out0_ptr), p(out1_ptr), out_stride, n_wit),
+               "vmpc_bn256_qap_moments_batch_dev")
+
+    def bn256_qap_h_combine_batch(self, a_ptr, b_ptr, ab_stride, t_ptr, d, deltas_ptr, scratch_ptr, out_ptr, out_stride,
+                                  n_wit):
+        """n_wit rows of h (d + 1 scalars each) from the moments' rows, t and n_wit x 3 deltas (0 / None: none);
+        scratch: 3 d scalars per witness"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_bn256_qap_h_combine_batch_dev(self.handle, p(a_ptr), p(b_ptr), ab_stride, p(t_ptr), d,
+                                                           p(deltas_ptr), p(scratch_ptr), p(out_ptr), out_stride, n_wit),
+               "vmpc_bn256_qap_h_combine_batch_dev")
+
+    def bn256_fr_poly_mul_batch(self, a_ptr, a_stride, na, b_ptr, b_stride, nb, k_lo, k_cnt, out_ptr, out_stride, n_wit):
+        """out_w[k - k_lo] = (a_w * b_w)[k] for k in [k_lo, k_lo + k_cnt); b_stride 0: one b for all n_wit products"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_bn256_fr_poly_mul_batch_dev(self.handle, p(a_ptr), a_stride, na, p(b_ptr), b_stride, nb,
+                                                         k_lo, k_cnt, p(out_ptr), out_stride, n_wit),
+               "vmpc_bn256_fr_poly_mul_batch_dev")
+
     def bn256_validate(self, group, points_ptr, n):
         bad = ctypes.c_uint64()
         _check(self.lib.vmpc_bn256_validate_dev(self.handle, group, ctypes.c_void_p(points_ptr), n,
@@ -1443,6 +1490,17 @@ def bn256_msm(group, scalars, points):
 
 
 BN256_FR_POLY_MAX = 1 << 20      # VMPC_BN256_FR_POLY_MAX of include/vmpc.h
+BN256_QAP_MAX_WIT = 65535        # VMPC_BN256_QAP_MAX_WIT
+
+
+def bn256_qap_moments_batch_bytes(d, n_out, n_wit):
+    """the arena bytes Context.bn256_qap_moments_batch reserves (host arithmetic: no GPU, no context)"""
+    return int(load_library().vmpc_bn256_qap_moments_batch_bytes(d, n_out, n_wit))
+
+
+def bn256_fr_poly_mul_batch_bytes(na, nb, k_lo, k_cnt, n_wit):
+    """the arena bytes Context.bn256_fr_poly_mul_batch reserves (0: none)"""
+    return int(load_library().vmpc_bn256_fr_poly_mul_batch_bytes(na, nb, k_lo, k_cnt, n_wit))
 
 
 def bn256_fr_poly_mul(a, b):

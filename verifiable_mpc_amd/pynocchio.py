@@ -18,6 +18,12 @@ The prover's h = (V W - Y) / t comes from the R1CS row values at the witness (cs
 whose coefficients are the moments sum_j (a_j / t'(j)) j^k of the weighted row values, and h is a correlation of t's
 coefficients with the low half of the two series' product.  The result stays on the device for compute_proof.
 
+    compute_h_batch, compute_proof_batch, prove_batch    (no counterpart in the reference)
+
+K witnesses of ONE QAP: exactly the results of K compute_h / compute_proof calls, with every stage of h run once for all
+K - the witness on the grid, the launch plans chosen with K counted - and the K proofs' uploads, synchronisations,
+downloads and inversions shared.  What verify_batch takes.
+
     Trapdoor, SampleDeltas, Generators        verifiable_mpc/trinocchio/pynocchio.py:36-69 (draws from `prng`)
     generate_evalkey, generate_verikey        verifiable_mpc/trinocchio/pynocchio.py:101-200
     PreparedKey.generate                      PreparedKey(qap, generate_evalkey(...)) without a host round trip
@@ -188,6 +194,34 @@ def _from_jacobian_many_g1(raws):
         j += 1
         zi2 = zi * zi % P
         out.append(BN256Point((X * zi2 % P, Y * zi2 % P * zi % P)))
+    return out
+
+
+def _from_jacobian_many_g2(raws):
+    """several twist sums (X : Y : Z) over F_p[i] -> affine, ONE modular inversion for all of them: 1 / Z = conj(Z) / N(Z)
+    with the norms N(Z) = Z.re^2 + Z.im^2 in F_p inverted together (Montgomery's trick)"""
+    vals = [[int.from_bytes(r[32 * i:32 * i + 32], "little") for i in range(6)] for r in raws]
+    norms = [(v[4] * v[4] + v[5] * v[5]) % P for v in vals if v[4] or v[5]]
+    prefix, run = [], 1
+    for n in norms:
+        prefix.append(run)
+        run = run * n % P
+    inv = pow(run, P - 2, P) if norms else 0
+    ninv = [0] * len(norms)
+    for i in range(len(norms) - 1, -1, -1):
+        ninv[i] = inv * prefix[i] % P
+        inv = inv * norms[i] % P
+    mul = lambda a, b: ((a[0] * b[0] - a[1] * b[1]) % P, (a[0] * b[1] + a[1] * b[0]) % P)
+    out, j = [], 0
+    for v in vals:
+        if not (v[4] or v[5]):
+            out.append(BN256TwistPoint(None))
+            continue
+        zi = (v[4] * ninv[j] % P, (-v[5] * ninv[j]) % P)
+        j += 1
+        zi2 = mul(zi, zi)
+        x, y = mul((v[0], v[1]), zi2), mul(mul((v[2], v[3]), zi2), zi)
+        out.append(BN256TwistPoint((x[0], x[1], y[0], y[1])))
     return out
 
 
@@ -466,6 +500,122 @@ def compute_proof(qap, c, h, evalkey, deltas=None):
             zk((dv, "r_v*beta*t*g1"), (dw, "r_w*beta*t*g1"), (dy, "r_y*beta*t*g1"))),
         "h*g1": msm(h_scalars, h_points),
     }
+
+
+def _compute_proof_batch_prepared(key, cs, hs, deltas):
+    """K proofs over a prepared key, stage-major: ONE upload of the K scalar vectors c_mid || (delta_v, delta_w, delta_y),
+    then K six-key passes on the main stream, K twist sums on aux 20 (with deltas each over c_mid || delta_w, put together
+    by two device copies on that stream) and K h sums on aux 21, queued without a host wait in between (the table sums
+    do not synchronise), one synchronisation per stream, one download of all 8 K Jacobian results and two shared
+    inversions (7 K G1 results, K twist results).  The MSM kernels are the single path's; what the batch saves is the
+    per-proof conversion, upload, synchronisation, download and inversion."""
+    from .device import get_aux_context
+    ctx, K = key.ctx, len(cs)
+    if deltas is not None and key.zk_missing:
+        raise KeyError("zero-knowledge deltas given but the prepared key lacks "
+                       + ", ".join(sorted(n for names in key.zk_missing.values() for n in names)))
+    n_mid = len(key.mid)
+    zk = deltas is not None
+    n_shared = n_mid + (3 if zk else 0)
+    n_twist = n_mid + (1 if zk else 0)
+    rows = max(n_shared, 1)
+    host = np.zeros((K * rows, 32), np.uint8)
+    for w, c in enumerate(cs):
+        if isinstance(c, np.ndarray):
+            c_all = _native.as_bytes_array(c, 32)
+            c_mid = c_all if _mid_is_identity(key, len(c_all)) else c_all[key.mid_index]
+        else:
+            c_mid = scalars_to_array([c[i] for i in key.mid])
+        host[w * rows:w * rows + n_mid] = c_mid
+        if zk:
+            dv = _native.ints_to_array([int(getattr(deltas[w], d)) % ORDER for d in _DELTAS], 32)
+            host[w * rows + n_mid:w * rows + n_shared] = dv
+    head = ctx.upload(host)
+    twist_sc = ctx.alloc(32 * K * n_twist) if zk else head
+    twist_stride = 32 * (n_twist if zk else rows)
+    g1 = [key.vectors[name] for name in _SHARED_G1]
+    tables = [v.table.ptr for v in g1]
+    twist_name = next(name for name in _ELEMENTS if name not in _SHARED_G1)
+    tv, hv = key.vectors[twist_name], key.vectors["h*g1"]
+    # one result buffer for the three streams: per witness six G1 sums, the h sum (96 bytes each), the twist sum (192)
+    n_g1, per = len(g1), 96 * (len(g1) + 1) + 192
+    out = ctx.alloc(per * K)
+    twist_ctx, h_ctx = get_aux_context(20), get_aux_context(21)
+    twist_ctx.wait_for(ctx)               # `head` and `out` come from the main stream
+    h_ctx.wait_for(ctx)
+    for w in range(K):
+        if zk:      # c_mid || delta_w out of the witness's row c_mid || (delta_v, delta_w, delta_y)
+            if n_mid:
+                twist_ctx.copy(twist_sc.ptr + twist_stride * w, head.ptr + 32 * rows * w, 32 * n_mid)
+            twist_ctx.copy(twist_sc.ptr + twist_stride * w + 32 * n_mid, head.ptr + 32 * (rows * w + n_mid + 1), 32)
+        twist_ctx.bn256_table_msm(2, tv.table.ptr, tv.n, twist_sc.ptr + twist_stride * w, n_twist, None,
+                                  out.ptr + per * w + 96 * (n_g1 + 1))
+    for w in range(K):
+        ctx.bn256_table_msm_multi(1, tables, g1[0].n, head.ptr + 32 * rows * w, n_shared, out.ptr + per * w)
+    # h: a compute_h_batch result is read where it lies; anything else is converted and uploaded once, on h's stream
+    keep = []
+    if K and all(isinstance(h, HPoly) for h in hs):
+        for src in {id(h.ctx): h.ctx for h in hs}.values():
+            h_ctx.wait_for(src)
+        h_ptrs = [(h.buf.ptr if len(h) else head.ptr, len(h)) for h in hs]
+    else:
+        arrs = []
+        for h in hs:
+            if isinstance(h, HPoly):
+                arrs.append(scalars_to_array(h.coeffs))
+            else:
+                hc = h if isinstance(h, (np.ndarray, list)) else h.coeffs
+                arrs.append(scalars_to_array(hc if isinstance(hc, np.ndarray) else [hc[i] for i in range(len(h))]))
+        offs = np.concatenate([[0], np.cumsum([len(a) for a in arrs])]).astype(np.int64)
+        hb = h_ctx.upload(np.concatenate(arrs) if offs[-1] else np.zeros((1, 32), np.uint8))
+        keep.append(hb)
+        h_ptrs = [(hb.ptr + 32 * int(offs[w]), len(arrs[w])) for w in range(K)]
+    for w, (ptr, n) in enumerate(h_ptrs):
+        assert n <= hv.n
+        h_ctx.bn256_table_msm(1, hv.table.ptr, hv.n, ptr, n, None, out.ptr + per * w + 96 * n_g1)
+    ctx.sync()
+    twist_ctx.sync()
+    h_ctx.sync()
+    raw = ctx.download(out.ptr, per * K).tobytes()
+    del keep
+    pts1 = _from_jacobian_many_g1([raw[per * w + 96 * i:per * w + 96 * i + 96] for w in range(K) for i in range(n_g1 + 1)])
+    pts2 = _from_jacobian_many_g2([raw[per * w + 96 * (n_g1 + 1):per * (w + 1)] for w in range(K)])
+    proofs = []
+    for w in range(K):
+        el = dict(zip(_SHARED_G1 + ("h*g1",), pts1[(n_g1 + 1) * w:(n_g1 + 1) * (w + 1)]))
+        el[twist_name] = pts2[w]
+        proofs.append({name: el[name] for name in list(_ELEMENTS) + ["h*g1"]})
+    return proofs
+
+
+def compute_proof_batch(qap, cs, hs, key, deltas=None):
+    """[compute_proof(qap, cs[w], hs[w], key, deltas[w]) for w in range(K)], point for point.  Over a PreparedKey the K
+    proofs share one upload, one synchronisation per stream, one download and the host inversions
+    (_compute_proof_batch_prepared); over an evalkey dict this loops over compute_proof.  cs: K witnesses as compute_proof
+    takes them, or one (K, n_wires, 32) uint8 array; hs: compute_h_batch's result (read in place on the device) or K of
+    anything compute_proof accepts; deltas: None, or K objects with .v .w .y."""
+    cs = list(cs)
+    hs = list(hs)
+    deltas = None if deltas is None else list(deltas)
+    K = len(cs)
+    if len(hs) != K or (deltas is not None and len(deltas) != K):
+        raise ValueError("compute_proof_batch: one h (and one set of deltas) per witness")
+    if K == 0:
+        return []
+    if isinstance(key, PreparedKey):
+        return _compute_proof_batch_prepared(key, cs, hs, deltas)
+    return [compute_proof(qap, cs[w], hs[w], key, None if deltas is None else deltas[w]) for w in range(K)]
+
+
+def prove_batch(qap, cs, key, deltas=None):
+    """K proofs of one circuit: compute_h_batch, then compute_proof_batch on its device-resident result -> a list of K
+    proof dicts, the counterpart of verify_batch.  key: a PreparedKey (or an evalkey dict: the proofs are then made one
+    by one).  A witness that violates a constraint raises ValueError before any proof work starts."""
+    ctx = key.ctx if isinstance(key, PreparedKey) else None
+    cs = cs if isinstance(cs, np.ndarray) else list(cs)
+    deltas = None if deltas is None else list(deltas)
+    hs = compute_h_batch(qap, cs, deltas, ctx=ctx)
+    return compute_proof_batch(qap, cs, hs, key, deltas)
 
 
 # ---- the pairing and the verifier (trinocchio/pynocchio.py:67-72, 276-325; csrc/bn256_pairing.hip) ----------------
@@ -1039,7 +1189,8 @@ PreparedKey.generate = classmethod(_prepared_generate)
 
 class HPoly:
     """compute_h's result: h's coefficients in device memory (`buf`, 32 bytes each, lowest first, `len()` of them, made
-    on `ctx`'s stream).  `.coeffs` downloads them once, as Python ints - what the reference's Poly offers."""
+    on `ctx`'s stream).  `.coeffs` downloads them once, as Python ints - what the reference's Poly offers.  `buf` is
+    anything with a `.ptr` that keeps the memory alive: a whole buffer, or compute_h_batch's view into its K rows."""
 
     def __init__(self, ctx, buf, n):
         self.ctx, self.buf, self._n, self._coeffs = ctx, buf, n, None
@@ -1199,3 +1350,152 @@ def compute_h_share(qap, c_share, delta_shares=None, ctx=None):
         dd = delta_shares if hasattr(delta_shares, "ptr") else \
             _scalar_buf(ctx, [delta_shares.v, delta_shares.w, delta_shares.y])
     return _h_from_row_values(ctx, qap, aby, keep, dd)
+
+
+# ---- h for K witnesses of one QAP -------------------------------------------------------------
+
+BATCH_BUDGET_BYTES = 1 << 30     # device bytes one chunk of a batch may hold at a time (compute_h_batch)
+
+
+class _BufferView:
+    """`nbytes` of a device buffer from byte `offset` on; holds the buffer"""
+    __slots__ = ("base", "ptr", "nbytes")
+
+    def __init__(self, base, offset, nbytes):
+        self.base, self.ptr, self.nbytes = base, base.ptr + offset, nbytes
+
+
+def witness_batch_array(n_wires, cs, indices=None):
+    """K witnesses -> (K, n_wires, 32) uint8: `cs` is that array already (any 32-byte values), or K witnesses as
+    compute_h takes them (each indexable by `indices`, default range(n_wires), or an (n_wires, 32) array).  A witness
+    with another number of rows raises ValueError.  Pure: needs no device."""
+    if isinstance(cs, np.ndarray) and cs.ndim == 3:
+        arr = np.ascontiguousarray(cs, dtype=np.uint8)
+        if arr.shape[1:] != (n_wires, 32):
+            raise ValueError(f"compute_h_batch: the witnesses have {arr.shape[1]} rows of {arr.shape[2]} bytes, the QAP "
+                             f"{n_wires} wires of 32")
+        return arr
+    cs = list(cs)
+    out = np.empty((len(cs), n_wires, 32), np.uint8)
+    idx = range(n_wires) if indices is None else indices
+    for w, c in enumerate(cs):
+        if isinstance(c, np.ndarray):
+            a = _native.as_bytes_array(c, 32)
+            if len(a) != n_wires:
+                raise ValueError(f"compute_h_batch: witness {w} has {len(a)} rows, the QAP {n_wires} wires")
+        else:
+            if isinstance(c, (list, tuple)) and len(c) != n_wires:
+                raise ValueError(f"compute_h_batch: witness {w} has {len(c)} rows, the QAP {n_wires} wires")
+            a = scalars_to_array([c[i] for i in idx])
+        out[w] = a
+    return out
+
+
+def plan_chunks(k, budget, cost):
+    """[(start, stop), ..]: 0..k cut into consecutive chunks, each the longest whose cost(n) (device bytes of n witnesses,
+    non-decreasing in n) stays within `budget` - but never empty: a budget below one witness gives one witness per
+    chunk.  Pure."""
+    chunks, start = [], 0
+    while start < k:
+        lo, hi = 1, k - start               # the largest n in [1, hi] with cost(n) <= budget, 1 if there is none
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if cost(mid) <= budget:
+                lo = mid
+            else:
+                hi = mid - 1
+        chunks.append((start, start + lo))
+        start += lo
+    return chunks
+
+
+def h_batch_bytes(d, n_wires, n_coef, n):
+    """device bytes compute_h_batch holds for a chunk of n witnesses: per witness the witness itself, the row values
+    (3 d), the weighted rows (2 d), the moments (2 d), the combination's scratch (3 d) and, for a dense QAP, 3 n_coef
+    coefficients; plus the arenas of the moments and of the two half products"""
+    if n == 0:
+        return 0
+    per = 32 * (n_wires + 10 * d + 3 * n_coef)
+    arena = max(_native.bn256_qap_moments_batch_bytes(d, d, n),
+                _native.bn256_fr_poly_mul_batch_bytes(d, d, 0, d - 1, n),
+                _native.bn256_fr_poly_mul_batch_bytes(d, d, d - 1, d, n))
+    return per * n + arena
+
+
+def compute_h_batch(qap, cs, deltas=None, ctx=None):
+    """[compute_h(qap, cs[w], deltas[w]) for w in range(K)], coefficient for coefficient and length included, with every
+    stage run once for all K (csrc/bn256_qap_h.hip's *_batch_dev entries).  cs: K witnesses as compute_h takes them, or
+    one (K, n_wires, 32) uint8 array (uploaded as it is); deltas: None, or K objects with .v .w .y.  -> a list of K HPoly,
+    each a view into ONE device buffer of K rows of d + 1 scalars, which it keeps alive; compute_proof and
+    compute_proof_batch read them in place.
+    Stage-major: upload, K queued runs of the row-value plan, ONE check launch and one read of K words - a violated
+    witness raises ValueError naming the lowest bad witness (0-based) and its first violated constraint (1-based) before
+    weights, moments or products are launched - then weights, moments, combination and one synchronisation.  K is cut
+    into consecutive chunks that hold at most BATCH_BUDGET_BYTES of device memory each (plan_chunks, h_batch_bytes); a
+    chunk boundary changes no value."""
+    ctx = ctx or get_context()
+    d = int(qap.d)
+    if d + 1 > _native.BN256_FR_POLY_MAX:
+        raise ValueError(f"compute_h_batch: d + 1 = {d + 1} exceeds the polynomial product's cap "
+                         f"{_native.BN256_FR_POLY_MAX}")
+    n_wires = len(qap.indices)
+    arr = witness_batch_array(n_wires, cs, qap.indices)
+    K = len(arr)
+    deltas = None if deltas is None else list(deltas)
+    if deltas is not None and len(deltas) != K:
+        raise ValueError("compute_h_batch: one set of deltas per witness")
+    if K == 0:
+        return []
+    sparse = isinstance(qap, R1CSQAP)
+    if sparse:
+        plan, top = _per_ctx(qap, "rows", ctx, lambda: _row_plan(ctx, qap)), 0
+    else:
+        plan, top = _per_ctx(qap, "coeffs", ctx, lambda: _coeff_plan(ctx, qap))
+    t = _t_coeffs(ctx, qap)
+    stride = d + 1
+    out = ctx.alloc(32 * stride * K)
+    chunks = plan_chunks(K, BATCH_BUDGET_BYTES, lambda n: h_batch_bytes(d, n_wires, top, n))
+    for lo, hi in chunks:
+        n = min(hi - lo, _native.BN256_QAP_MAX_WIT)
+        for a in range(lo, hi, n):
+            _h_batch_chunk(ctx, qap, arr[a:min(a + n, hi)], None if deltas is None else deltas[a:min(a + n, hi)], a,
+                           plan, top, t, out.ptr + 32 * stride * a, stride)
+    n_h = d + 1 if deltas is not None else max(d - 1, 0)
+    return [HPoly(ctx, _BufferView(out, 32 * stride * w, 32 * stride), n_h) for w in range(K)]
+
+
+def _h_batch_chunk(ctx, qap, arr, deltas, first, plan, top, t, out_ptr, out_stride):
+    """one chunk of compute_h_batch: n witnesses (arr) -> n rows of h at out_ptr; `first`: the chunk's first witness"""
+    n, n_wires, d = len(arr), arr.shape[1], int(qap.d)
+    dc = ctx.upload(arr) if n_wires else ctx.alloc(32)
+    aby = ctx.alloc(32 * 3 * d * n)
+    if isinstance(qap, R1CSQAP):
+        coef = None
+        for w in range(n):                       # K queued runs of the single path's plan, no host wait between them
+            plan.run(dc.ptr + 32 * n_wires * w, n_wires, aby.ptr + 32 * 3 * d * w)
+    else:
+        coef = ctx.alloc(32 * 3 * top * n)
+        for w in range(n):
+            plan.run(dc.ptr + 32 * n_wires * w, n_wires, coef.ptr + 32 * 3 * top * w)
+            ctx.bn256_qap_horner(coef.ptr + 32 * 3 * top * w, top, 3, d, aby.ptr + 32 * 3 * d * w)
+    bad = ctx.alloc(4 * n)
+    ctx.bn256_qap_check_batch(aby.ptr, aby.ptr + 32 * d, aby.ptr + 64 * d, 3 * d, d, bad.ptr, n)
+    ctx.sync()
+    words = ctx.download(bad.ptr, 4 * n).view("<u4")
+    viol = np.nonzero(words != 0xFFFFFFFF)[0]
+    if len(viol):
+        w, j = int(viol[0]), int(words[viol[0]]) + 1
+        raise ValueError(f"compute_h_batch: witness {first + w} violates constraint {j} "
+                         f"(V(j) W(j) != Y(j) at j = {j})")
+    dd = None
+    if deltas is not None:
+        dd = _scalar_buf(ctx, [getattr(dl, name) for dl in deltas for name in _DELTAS])
+    u = ctx.alloc(32 * 2 * d * n)                # rows ua || ub, stride 2 d; the moments alike
+    ctx.bn256_qap_h_weights_batch(aby.ptr, aby.ptr + 32 * d, 3 * d, d, u.ptr, u.ptr + 32 * d, 2 * d, n)
+    mom = ctx.alloc(32 * 2 * d * n)
+    ctx.bn256_qap_moments_batch(u.ptr, u.ptr + 32 * d, 2 * d, d, d, mom.ptr, mom.ptr + 32 * d, 2 * d, n)
+    scratch = ctx.alloc(32 * 3 * d * n)
+    ctx.bn256_qap_h_combine_batch(mom.ptr, mom.ptr + 32 * d, 2 * d, t.ptr, d, dd.ptr if dd else None, scratch.ptr,
+                                  out_ptr, out_stride, n)
+    ctx.sync()      # the temporaries above may be released once the stream has drained
+    del dc, aby, coef, bad, dd, u, mom, scratch
