@@ -434,7 +434,8 @@ int vmpc_bn256_lincomb_batch(int group, const uint8_t *bases, size_t n_bases, co
  * prover's c_poly = c_poly_lhs * c_poly_rhs of knowledge_of_exponent.py:121-123 (verifiable_mpc/tools/qap_creator.py
  * Poly.__mul__, O(n^2) Python).  na, nb >= 1.  Cap: na and nb at most VMPC_BN256_FR_POLY_MAX each; above it the
  * entry answers VMPC_E_RANGE before it looks at any pointer and writes nothing.  `out` must not overlap a or b.
- * Uses the context arena (partial sums of a large product). */
+ * Uses the context arena (partial sums of a large product).  It is vmpc_bn256_fr_poly_mul_batch_dev's window
+ * [0, na + nb - 1) of one product: one kernel, one planner (csrc/bn256_koe.hip). */
 #define VMPC_BN256_FR_POLY_MAX ((size_t)1 << 20)
 int vmpc_bn256_fr_poly_mul_dev(vmpc_ctx *ctx, const void *a, size_t na, const void *b, size_t nb, void *out);
 /* host-buffer form of the above (own context, synchronous) */
@@ -444,8 +445,8 @@ int vmpc_bn256_fr_poly_mul(const uint8_t *a, size_t na, const uint8_t *b, size_t
  * (a_stride >= na, out_stride >= k_cnt; b_stride >= nb, or 0: ONE b for all products).  Only the tiles of 256 outputs that
  * meet the window are launched and only the window's k_cnt scalars of a row are written - the batched h asks for the
  * halves P[0 .. d-2] and Q[d-1 .. 2d-2] of its two d x d products.  The segment length is chosen with n_wit counted (a
- * large batch: fewer, longer segments); canonical residues, so the bits are those of vmpc_bn256_fr_poly_mul_dev whatever
- * the segmentation.  n_wit <= VMPC_BN256_QAP_MAX_WIT (the product index is a grid dimension), na and nb within the cap
+ * large batch: fewer, longer segments); canonical residues, so the bits do not depend on the segmentation.
+ * n_wit <= VMPC_BN256_QAP_MAX_WIT (the product index is a grid dimension), na and nb within the cap
  * above, strides <= 2^31, else VMPC_E_RANGE before any pointer is looked at; n_wit = 0 or k_cnt = 0: VMPC_OK, no launch.
  * Arena: vmpc_bn256_fr_poly_mul_batch_bytes(...), reserved before the first launch (0: the product needs none). */
 #define VMPC_BN256_QAP_MAX_WIT ((size_t)65535)
@@ -523,14 +524,15 @@ int vmpc_bn256_qap_t_coeffs_dev(vmpc_ctx *ctx, size_t d, void *scratch, void *ou
 int vmpc_bn256_qap_horner_dev(vmpc_ctx *ctx, const void *coeffs, size_t n_coeffs, size_t n_polys, size_t d, void *out);
 /* out[0..d] = h_0 .. h_d as above (pynocchio.py:212-225: p / qap.t plus compute_h_zk_terms) from the moments
  * A[i] = A_(i+1), B[i] = B_(i+1) (i < d), t's d + 1 coefficients and deltas = (delta_v, delta_w, delta_y) (NULL: all
- * zero).  scratch: device memory of 5 d scalars.  Two d x d products through vmpc_bn256_fr_poly_mul_dev, whose arena
- * use it has. */
+ * zero).  scratch: device memory of 5 d scalars, of which 3 d are used.  It is vmpc_bn256_qap_h_combine_batch_dev for one
+ * witness: the halves P[0 .. d-2] and Q[d-1 .. 2d-2] of two d x d products, and that entry's arena. */
 int vmpc_bn256_qap_h_combine_dev(vmpc_ctx *ctx, const void *A, const void *B, const void *t, size_t d,
                                  const void *deltas, void *scratch, void *out);
 
 /* The same stages for n_wit witnesses of ONE QAP (the batch prover): the witness is a grid dimension,
  * row w of every per-witness vector lies `stride` scalars after row w - 1 (a stride is at least the row's length and at
- * most 2^31; scalars of a row beyond its length are never written).  The bits are those of n_wit single calls.
+ * most 2^31; scalars of a row beyond its length are never written).  Each single entry above is its batch entry with
+ * n_wit = 1 - one kernel and one host implementation per stage - so the bits are those of n_wit single calls.
  * n_wit <= VMPC_BN256_QAP_MAX_WIT and the cap on d as above, else VMPC_E_RANGE before any pointer is looked at; n_wit = 0:
  * VMPC_OK, no launch.  Deterministic (integer sums in a fixed order, no atomics on field values).  Where an entry uses
  * the arena it reserves it before its first launch: a batch too large for it does nothing. */
@@ -540,8 +542,8 @@ int vmpc_bn256_qap_check_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, 
 /* the scan of the factorial prefix products and the inversion ONCE, then one launch for the n_wit rows of ua (and ub) */
 int vmpc_bn256_qap_h_weights_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t d, void *ua,
                                        void *ub, size_t u_stride, size_t n_wit);
-/* vmpc_bn256_qap_moments_dev's workgroup on a grid (k segments, ranges of j, witnesses).  The number of ranges counts the
- * witnesses: 2048 / (k segments x n_wit) under the single call's caps - n_wit = 1 is the single plan, a large batch ends
+/* The moments on a grid (k segments, ranges of j, witnesses).  The number of ranges counts the witnesses:
+ * 2048 / (k segments x n_wit), at most 32 and at most one per 1024 j - a large batch ends
  * at one range (one partial per k and witness).  Arena: vmpc_bn256_qap_moments_batch_bytes(d, n_out, n_wit) (0 where the
  * call would answer VMPC_E_RANGE or do nothing). */
 int vmpc_bn256_qap_moments_batch_dev(vmpc_ctx *ctx, const void *u0, const void *u1, size_t u_stride, size_t d,
@@ -572,7 +574,8 @@ int vmpc_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint3
                            const void *a_const, const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_vals,
                            const void *b_const, const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset,
                            void *z, void *a_out, void *b_out, int check, uint32_t *first_bad);
-/* vmpc_fr_cs_triples_dev for n_wit witnesses of ONE circuit in one launch (the witness on the grid's y).  The forms and
+/* vmpc_fr_cs_triples_dev for n_wit witnesses of ONE circuit in one launch (the witness on the grid's y; the single entry
+ * is this one with n_wit = 1).  The forms and
  * the gate list are shared; witness w reads and writes z + 32 w z_stride, a_out + 32 w ab_stride and b_out alike (strides
  * in scalars: z_stride >= the length of z, ab_stride >= the rows' count), and with check = 1 first_bad[w] (n_wit device
  * words, all set to 0xffffffff by the call) is ITS smallest bad gate.  check = 2: the values of the rows for every
@@ -594,8 +597,9 @@ int vmpc_fr_cs_tables_dev(vmpc_ctx *ctx, size_t K, void *fact, void *ifact);
  * for s segments of j. */
 int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact, const void *ifact,
                           void *z_tail);
-/* vmpc_fr_cs_extend_dev for n_wit witnesses in one launch sequence: a, b are n_wit rows of M scalars, ab_stride >= M
- * scalars apart, z_tail n_wit rows z_stride >= 2m + 3 scalars apart (strides <= 2^31, n_wit <= VMPC_FR_CS_MAX_WIT, else
+/* vmpc_fr_cs_extend_dev for n_wit witnesses in one launch sequence (the single entry is this one with n_wit = 1):
+ * a, b are n_wit rows of M scalars, ab_stride >= M scalars apart, z_tail n_wit rows z_stride >= 2m + 3 scalars apart
+ * (strides <= 2^31, n_wit <= VMPC_FR_CS_MAX_WIT, else
  * VMPC_E_RANGE; n_wit = 0: VMPC_OK, no launch).  The table 1 / k and the weights are computed once, the correlation runs
  * on a grid (tiles, segments, witnesses), and the segment length is chosen with n_wit counted, so a large batch uses
  * fewer, longer segments.  Canonical residues: the bits are those of n_wit single calls whatever the segmentation.

@@ -15,7 +15,7 @@ for all K (`*_batch_ms`) and done K times the single way (`*_single_ms`):
                   protocol_8_excl_pivot_prover
     prove         circuit_sat_prover_batch against K circuit_sat_prover
 
-The single path is untouched by the batch prover, so its columns are what the parent revision does."""
+The single entries run the batch entries' kernels with K = 1 (csrc/circuit_sat.hip)."""
 import argparse
 import json
 import os

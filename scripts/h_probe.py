@@ -10,8 +10,8 @@ device synchronisation, all in ONE process:
   check         vmpc_bn256_qap_check_dev
   weights       vmpc_bn256_qap_h_weights_dev (both vectors)
   moments       vmpc_bn256_qap_moments_dev, both vectors, n_out = d
-  product       vmpc_bn256_fr_poly_mul_dev at d x d - the yardstick, the entry as it stands; combine runs it twice
-  combine       vmpc_bn256_qap_h_combine_dev (two products and two elementwise kernels)
+  product       vmpc_bn256_fr_poly_mul_dev at d x d - the yardstick, the entry as it stands
+  combine       vmpc_bn256_qap_h_combine_dev (the halves it reads of two such products and two elementwise kernels)
   compute_h     the whole call, witness upload, check and its host read-back included
   compute_proof over a synthetic prepared key, h read from the device
 and derived: non_product = compute_h - 2 product (what the acceptance ratio of DESIGN.md section 14 compares with one

@@ -15,8 +15,8 @@ the single way (`*_single_ms`):
                                        the sums cost what a generated key's cost), h read in place on the device
     prove                              prove_batch against K x (compute_h, compute_proof)
 
-Every batch result is compared with the single one before its line is written (`equal`).  The single path is untouched
-by the batch prover, so its columns are what the parent revision does."""
+Every batch result is compared with the single one before its line is written (`equal`).  The single entries run the
+batch entries' kernels with K = 1, so at K = 1 the two columns of a stage time the same launches."""
 import argparse
 import json
 import os

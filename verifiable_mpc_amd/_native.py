@@ -1108,7 +1108,8 @@ class Context:
                                                   ctypes.c_void_p(out_ptr)), "vmpc_bn256_qap_horner_dev")
 
     def bn256_qap_h_combine(self, a_ptr, b_ptr, t_ptr, d, deltas_ptr, scratch_ptr, out_ptr):
-        """out[0..d] = h from the moments, t's coefficients and the three deltas (0 / None: none); scratch: 5 d scalars"""
+        """out[0..d] = h from the moments, t's coefficients and the three deltas (0 / None: none); scratch: 5 d scalars, of which
+        3 d are used (bn256_qap_h_combine_batch with n_wit = 1)"""
         _check(self.lib.vmpc_bn256_qap_h_combine_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr),
                                                      ctypes.c_void_p(t_ptr), d, ctypes.c_void_p(deltas_ptr),
                                                      ctypes.c_void_p(scratch_ptr), ctypes.c_void_p(out_ptr)),

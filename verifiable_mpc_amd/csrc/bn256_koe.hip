@@ -12,11 +12,11 @@
 // into as many workgroups as its i-range has segments; their partial sums (reduced mod n) go to the context arena and
 // k_frbn_polysum adds them.  A product whose tiles all fit one segment is written straight to `out`.
 //
-//   k_frbn_polymul_batch   the same tile for K products a_w * b_w of one shape (grid z = w; a stride of 0 between the b
-//                    rows: one b for all), restricted to a WINDOW [k_lo, k_lo + k_cnt) of the outputs: only the tiles
-//                    that meet the window are launched and only the window is written, at out_w[k - k_lo].  The segment
-//                    length counts K, so a large batch ends at one or two partial sums per output
-//                    (vmpc_bn256_fr_poly_mul_batch_dev; the two half products of csrc/bn256_qap_h.hip's batched h).
+// The kernel takes K products a_w * b_w of one shape (grid z = w; a stride of 0 between the b rows: one b for all)
+// and a WINDOW [k_lo, k_lo + k_cnt) of the outputs: only the tiles that meet the window are launched and only the window
+// is written, at out_w[k - k_lo].  The segment length counts K, so a large batch ends at one or two partial sums per
+// output (vmpc_bn256_fr_poly_mul_batch_dev; the two half products of csrc/bn256_qap_h.hip's h).
+// vmpc_bn256_fr_poly_mul_dev is the whole window of one product: both entries call koe_poly_mul.
 #include "common.h"
 #include "fr_bn.h"
 #include "fr_conv.h"
@@ -38,44 +38,13 @@ __host__ __device__ static inline koe_span koe_tile_span(long long k0, long long
     return s;
 }
 
-// grid (tiles, most segments of a tile); dst row y holds the partial sums of every tile's y-th segment
-__global__ void __launch_bounds__(FR_CONV_TILE)
-k_frbn_polymul(const uint32_t *__restrict__ a, long long na, const uint32_t *__restrict__ b, long long nb,
-               long long seg, uint32_t *__restrict__ dst) {
-    __shared__ uint32_t sA[1][FR_CONV_CHUNK * 8];
-    __shared__ uint32_t sB[8 * FR_CONV_BROW];
-    const long long n_out = na + nb - 1;
-    const long long k0 = (long long)blockIdx.x * FR_CONV_TILE;
-    const koe_span span = koe_tile_span(k0, na, nb, seg);
-    if (blockIdx.y >= span.n_seg) return;      // (uniform) this tile has fewer segments
-    const long long seg_lo = (long long)(span.first_seg + blockIdx.y) * seg;
-    const uint32_t *const av[1] = {a};
-    f256_acc acc[1] = {f256_acc_zero()};
-    for (long long i0 = seg_lo; i0 < seg_lo + seg; i0 += FR_CONV_CHUNK) {
-        if (i0 + FR_CONV_CHUNK <= span.lo || i0 > span.hi) continue;   // (uniform)
-        fr_conv_chunk<frbn, 1>(sA, sB, acc, av, na, b, nb, k0, i0);
-    }
-    const long long k = k0 + threadIdx.x;
-    if (k < n_out) frbn_store(dst + 8 * ((long long)blockIdx.y * n_out + k), frbn_acc_reduce(acc[0]));
-}
-
-__global__ void __launch_bounds__(256)
-k_frbn_polysum(const uint32_t *__restrict__ part, long long na, long long nb, long long seg,
-               uint32_t *__restrict__ out) {
-    const long long n_out = na + nb - 1;
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_out) return;
-    const koe_span span = koe_tile_span(k / FR_CONV_TILE * FR_CONV_TILE, na, nb, seg);
-    f256_st(out, k, fr_partsum<frbn>(part, n_out, span.n_seg, k));
-}
-
 // grid (tiles of the window, most segments of a tile, products).  Tile x covers the outputs (tile_lo + x) FR_CONV_TILE ..;
 // output k of product w and segment y goes to dst[w wit_stride + y seg_stride + k - base_k] if k is in the window
 // [k_lo, k_hi).  Straight to `out`: seg_stride = 0 (one segment), base_k = k_lo, wit_stride = the caller's row stride.
 __global__ void __launch_bounds__(FR_CONV_TILE)
-k_frbn_polymul_batch(const uint32_t *__restrict__ a, size_t a_stride, long long na, const uint32_t *__restrict__ b,
-                     size_t b_stride, long long nb, long long seg, unsigned tile_lo, long long k_lo, long long k_hi,
-                     long long base_k, uint32_t *__restrict__ dst, size_t wit_stride, size_t seg_stride) {
+k_frbn_polymul(const uint32_t *__restrict__ a, size_t a_stride, long long na, const uint32_t *__restrict__ b,
+               size_t b_stride, long long nb, long long seg, unsigned tile_lo, long long k_lo, long long k_hi,
+               long long base_k, uint32_t *__restrict__ dst, size_t wit_stride, size_t seg_stride) {
     __shared__ uint32_t sA[1][FR_CONV_CHUNK * 8];
     __shared__ uint32_t sB[8 * FR_CONV_BROW];
     const long long k0 = (long long)(tile_lo + blockIdx.x) * FR_CONV_TILE;
@@ -97,9 +66,9 @@ k_frbn_polymul_batch(const uint32_t *__restrict__ a, size_t a_stride, long long 
 
 // grid (window outputs, products): out_w[k - k_lo] = the sum of tile (k / FR_CONV_TILE)'s partial sums at k
 __global__ void __launch_bounds__(256)
-k_frbn_polysum_batch(const uint32_t *__restrict__ part, size_t wit_stride, size_t seg_stride, long long base_k, long long na,
-                     long long nb, long long seg, long long k_lo, long long k_hi, uint32_t *__restrict__ out,
-                     size_t out_stride) {
+k_frbn_polysum(const uint32_t *__restrict__ part, size_t wit_stride, size_t seg_stride, long long base_k, long long na,
+               long long nb, long long seg, long long k_lo, long long k_hi, uint32_t *__restrict__ out,
+               size_t out_stride) {
     const long long k = k_lo + (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= k_hi) return;
     const size_t w = blockIdx.y;
@@ -129,44 +98,9 @@ k_frbn_powers(const uint32_t *__restrict__ z_in, const uint32_t *__restrict__ sc
     }
 }
 
-extern "C" int vmpc_bn256_fr_poly_mul_dev(vmpc_ctx *ctx, const void *a, size_t na, const void *b, size_t nb,
-                                          void *out) {
-    if (na > VMPC_BN256_FR_POLY_MAX || nb > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
-    if (!ctx || !a || !b || !out || na == 0 || nb == 0) return VMPC_E_INVAL;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    const long long n_out = (long long)(na + nb - 1);
-    const unsigned tiles = (unsigned)((n_out + FR_CONV_TILE - 1) / FR_CONV_TILE);
-    // segment length: a power of two that cuts the na * nb products into about KOE_TARGET_WGS workgroups' worth
-    long long seg = KOE_MIN_SEG;
-    while (seg * 2 * FR_CONV_TILE * KOE_TARGET_WGS <= (long long)na * (long long)nb) seg *= 2;
-    unsigned max_segs = 1;
-    for (unsigned t = 0; t < tiles; t++) {
-        const unsigned s = koe_tile_span((long long)t * FR_CONV_TILE, (long long)na, (long long)nb, seg).n_seg;
-        if (s > max_segs) max_segs = s;
-    }
-    uint32_t *dst = (uint32_t *)out;
-    if (max_segs > 1) {
-        const size_t bytes = (size_t)max_segs * (size_t)n_out * 32;
-        VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(bytes) + 256));
-        dst = (uint32_t *)vmpc_ws_take(ctx, bytes);
-    }
-    {
-        vmpc_stage_scope s(ctx, "bn_fr_poly_mul");
-        k_frbn_polymul<<<dim3(tiles, max_segs), FR_CONV_TILE, 0, ctx->stream>>>(
-            (const uint32_t *)a, (long long)na, (const uint32_t *)b, (long long)nb, seg, dst);
-        VMPC_KERNEL_CHECK();
-    }
-    if (max_segs > 1) {
-        vmpc_stage_scope s(ctx, "bn_fr_poly_sum");
-        k_frbn_polysum<<<(unsigned)((n_out + 255) / 256), 256, 0, ctx->stream>>>(dst, (long long)na, (long long)nb, seg,
-                                                                                (uint32_t *)out);
-        VMPC_KERNEL_CHECK();
-    }
-    return VMPC_OK;
-}
-
-// The plan of a batched product: the tiles that meet the window, the segment length with the products counted (K = 1:
-// vmpc_bn256_fr_poly_mul_dev's choice; more products, longer segments - fewer partial sums each), the arena
+// The plan of a product: the tiles that meet the window; the segment length, a power of two that cuts the na * nb * K
+// products into about KOE_TARGET_WGS workgroups' worth (more products, longer segments - fewer partial sums each) and
+// stops once a segment holds the whole of a; the arena
 struct koe_batch_plan {
     long long seg;
     unsigned tile_lo, tiles, max_segs;
@@ -192,6 +126,43 @@ static koe_batch_plan koe_batch_plan_of(size_t na, size_t nb, size_t k_lo, size_
     return p;
 }
 
+// n_wit >= 1 products of a non-empty window, checked by the entries
+static int koe_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b, size_t b_stride, size_t nb,
+                        size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit) {
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const koe_batch_plan p = koe_batch_plan_of(na, nb, k_lo, k_cnt, n_wit);
+    const long long lo = (long long)k_lo, hi = (long long)(k_lo + k_cnt);
+    const long long base = p.max_segs > 1 ? (long long)p.tile_lo * FR_CONV_TILE : lo;
+    const size_t wit_stride = p.max_segs > 1 ? p.max_segs * p.cols : out_stride;
+    uint32_t *dst = (uint32_t *)out;
+    if (p.max_segs > 1) {
+        VMPC_CHECK(vmpc_ws_reserve(ctx, p.bytes));      // before any launch
+        dst = (uint32_t *)vmpc_ws_take(ctx, n_wit * p.max_segs * p.cols * 32);
+    }
+    {
+        vmpc_stage_scope s(ctx, "bn_fr_poly_mul");
+        k_frbn_polymul<<<dim3(p.tiles, p.max_segs, (unsigned)n_wit), FR_CONV_TILE, 0, ctx->stream>>>(
+            (const uint32_t *)a, a_stride, (long long)na, (const uint32_t *)b, b_stride, (long long)nb, p.seg, p.tile_lo, lo,
+            hi, base, dst, wit_stride, p.max_segs > 1 ? p.cols : 0);
+        VMPC_KERNEL_CHECK();
+    }
+    if (p.max_segs > 1) {
+        vmpc_stage_scope s(ctx, "bn_fr_poly_sum");
+        k_frbn_polysum<<<dim3((unsigned)((k_cnt + 255) / 256), (unsigned)n_wit), 256, 0, ctx->stream>>>(
+            dst, wit_stride, p.cols, base, (long long)na, (long long)nb, p.seg, lo, hi, (uint32_t *)out, out_stride);
+        VMPC_KERNEL_CHECK();
+    }
+    return VMPC_OK;
+}
+
+// the whole product: the window [0, na + nb - 1) of one pair
+extern "C" int vmpc_bn256_fr_poly_mul_dev(vmpc_ctx *ctx, const void *a, size_t na, const void *b, size_t nb,
+                                          void *out) {
+    if (na > VMPC_BN256_FR_POLY_MAX || nb > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !out || na == 0 || nb == 0) return VMPC_E_INVAL;
+    return koe_poly_mul(ctx, a, na, na, b, nb, nb, 0, na + nb - 1, out, na + nb - 1, 1);
+}
+
 static bool koe_batch_in_range(size_t na, size_t nb, size_t k_lo, size_t k_cnt, size_t n_wit) {
     return n_wit <= VMPC_BN256_QAP_MAX_WIT && na <= VMPC_BN256_FR_POLY_MAX && nb <= VMPC_BN256_FR_POLY_MAX &&
            k_lo <= 2 * VMPC_BN256_FR_POLY_MAX && k_cnt <= 2 * VMPC_BN256_FR_POLY_MAX &&
@@ -212,30 +183,7 @@ extern "C" int vmpc_bn256_fr_poly_mul_batch_dev(vmpc_ctx *ctx, const void *a, si
         return VMPC_E_RANGE;
     if (!ctx || !a || !b || !out || na == 0 || nb == 0) return VMPC_E_INVAL;
     if (n_wit == 0 || k_cnt == 0) return VMPC_OK;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    const koe_batch_plan p = koe_batch_plan_of(na, nb, k_lo, k_cnt, n_wit);
-    const long long lo = (long long)k_lo, hi = (long long)(k_lo + k_cnt);
-    const long long base = p.max_segs > 1 ? (long long)p.tile_lo * FR_CONV_TILE : lo;
-    const size_t wit_stride = p.max_segs > 1 ? p.max_segs * p.cols : out_stride;
-    uint32_t *dst = (uint32_t *)out;
-    if (p.max_segs > 1) {
-        VMPC_CHECK(vmpc_ws_reserve(ctx, p.bytes));      // before any launch
-        dst = (uint32_t *)vmpc_ws_take(ctx, n_wit * p.max_segs * p.cols * 32);
-    }
-    {
-        vmpc_stage_scope s(ctx, "bn_fr_poly_mul_batch");
-        k_frbn_polymul_batch<<<dim3(p.tiles, p.max_segs, (unsigned)n_wit), FR_CONV_TILE, 0, ctx->stream>>>(
-            (const uint32_t *)a, a_stride, (long long)na, (const uint32_t *)b, b_stride, (long long)nb, p.seg, p.tile_lo, lo,
-            hi, base, dst, wit_stride, p.max_segs > 1 ? p.cols : 0);
-        VMPC_KERNEL_CHECK();
-    }
-    if (p.max_segs > 1) {
-        vmpc_stage_scope s(ctx, "bn_fr_poly_sum_batch");
-        k_frbn_polysum_batch<<<dim3((unsigned)((k_cnt + 255) / 256), (unsigned)n_wit), 256, 0, ctx->stream>>>(
-            dst, wit_stride, p.cols, base, (long long)na, (long long)nb, p.seg, lo, hi, (uint32_t *)out, out_stride);
-        VMPC_KERNEL_CHECK();
-    }
-    return VMPC_OK;
+    return koe_poly_mul(ctx, a, a_stride, na, b, b_stride, nb, k_lo, k_cnt, out, out_stride, n_wit);
 }
 
 extern "C" int vmpc_bn256_fr_powers_dev(vmpc_ctx *ctx, const void *z, const void *scale, size_t count, void *out) {

@@ -27,12 +27,16 @@
 //   vmpc_bn256_qap_t_coeffs_dev    the d + 1 coefficients of t = prod (x - j): leaves of QH_LEAF factors multiplied out
 //                                  in LDS, then a product tree over vmpc_bn256_fr_poly_mul_dev
 //   vmpc_bn256_qap_horner_dev      P(1), .., P(d) of coefficient vectors (the dense QAP form), one lane per point
-//   vmpc_bn256_qap_h_combine_dev   moments, t, deltas -> h (two products through vmpc_bn256_fr_poly_mul_dev)
+//   vmpc_bn256_qap_h_combine_dev   moments, t, deltas -> h (the halves that it reads of two products, through
+//                                  vmpc_bn256_fr_poly_mul_batch_dev)
 //
-// For K witnesses of one QAP every stage has a *_batch_dev form with the witness on the grid and
-// rows a stride apart: the check writes one word per witness, the weights run their scan and inversion ONCE, the moments
-// count K when they cut j into ranges (K = 1: the single plan; a large batch: one range, one partial per k), and the
-// combination asks vmpc_bn256_fr_poly_mul_batch_dev only for the halves of its two products that it reads.
+// For K witnesses of one QAP the moments, the weights, the check and the combination have a
+// *_batch_dev entry with rows a stride apart.  Each of these stages is ONE kernel with the witness on the grid's last
+// dimension and ONE static host function (qh_moments, qh_weights, qh_check, qh_combine) that plans, reserves and
+// launches; the single entry and the batch entry check their own arguments and call it, the single one with K = 1.
+// The check writes one word per witness, the weights run their scan and inversion ONCE, the moments count K when they
+// cut j into ranges (a large batch: one range, one partial per k), and the combination asks
+// vmpc_bn256_fr_poly_mul_batch_dev only for P[0 .. d-2] and Q[d-1 .. 2d-2] of its two products.
 #include <vector>
 
 #include "common.h"
@@ -64,7 +68,7 @@ __device__ __forceinline__ uint32_t qh_wave_sum(uint32_t x) {
            (uint32_t)__builtin_amdgcn_readlane((int)x, 32) + (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
 }
 
-// grid (k segments, j groups).  part[v][(g n_out + k)] = sum over group g's j of u_v[j-1] j^k mod n.
+// One workgroup of the grid (k segments, j groups).  part[v][(g n_out + k)] = sum over group g's j of u_v[j-1] j^k mod n.
 // Bounds: j <= d < 2^21 (frbn_mul_small); a lane's QH_J values sum below 2^258 (ten 26-bit pieces), 64 lanes' pieces
 // below 2^32, a wave total below 2^264, four waves and at most 2^10 chunks below 2^276 < 2^288 (frbn_wide).
 template <int NV>
@@ -162,81 +166,22 @@ qh_moments_wg(const uint32_t *__restrict__ u0, const uint32_t *__restrict__ u1, 
     }
 }
 
-template <int NV>
-__global__ void __launch_bounds__(QH_WG)
-k_qh_moments(const uint32_t *__restrict__ u0, const uint32_t *__restrict__ u1, uint32_t d, uint32_t n_out, uint32_t ks,
-             uint32_t chunks_per_group, uint32_t *__restrict__ part0, uint32_t *__restrict__ part1) {
-    qh_moments_wg<NV>(u0, u1, d, n_out, ks, chunks_per_group, part0, part1);
-}
-
-// grid (k segments, j groups, witnesses): the same workgroup on witness blockIdx.z's rows of u0, u1 (u_stride scalars
+// grid (k segments, j groups, witnesses): the workgroup above on witness blockIdx.z's rows of u0, u1 (u_stride scalars
 // apart) and its `groups` x n_out partials
 template <int NV>
 __global__ void __launch_bounds__(QH_WG)
-k_qh_moments_batch(const uint32_t *__restrict__ u0, const uint32_t *__restrict__ u1, size_t u_stride, uint32_t d,
-                   uint32_t n_out, uint32_t ks, uint32_t chunks_per_group, uint32_t *__restrict__ part0,
-                   uint32_t *__restrict__ part1) {
+k_qh_moments(const uint32_t *__restrict__ u0, const uint32_t *__restrict__ u1, size_t u_stride, uint32_t d, uint32_t n_out,
+             uint32_t ks, uint32_t chunks_per_group, uint32_t *__restrict__ part0, uint32_t *__restrict__ part1) {
     const size_t w = blockIdx.z, rows = 8 * w * gridDim.y * (size_t)n_out;
     qh_moments_wg<NV>(u0 + 8 * w * u_stride, NV > 1 ? u1 + 8 * w * u_stride : nullptr, d, n_out, ks, chunks_per_group,
                       part0 + rows, part1 + rows);
 }
 
-// out[k] = part[0][k] + part[1][k] + .. in that order (csrc/fr_conv.h)
+// grid (outputs, witnesses, vectors): witness y's partials of vector z, added in the order part[0][k] + part[1][k] + ..
+// (csrc/fr_conv.h), into its row of out0 / out1
 __global__ void __launch_bounds__(256)
-k_qh_partsum(const uint32_t *__restrict__ part, uint32_t n_out, uint32_t groups, uint32_t *__restrict__ out) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_out) return;
-    f256_st(out, k, fr_partsum<frbn>(part, n_out, groups, k));
-}
-
-extern "C" int vmpc_bn256_qap_moments_dev(vmpc_ctx *ctx, const void *u0, const void *u1, size_t d, size_t n_out,
-                                          void *out0, void *out1) {
-    if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_out > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
-    if (!ctx || !u0 || !out0 || (u1 && !out1) || d == 0) return VMPC_E_INVAL;
-    if (n_out == 0) return VMPC_OK;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    const int nv = u1 ? 2 : 1;
-    const uint32_t ks = (uint32_t)(n_out >= QH_KS ? QH_KS : (n_out + QH_KB - 1) / QH_KB * QH_KB);
-    const uint32_t n_kseg = (uint32_t)((n_out + ks - 1) / ks);
-    const uint32_t n_chunks = (uint32_t)((d + QH_CHUNK - 1) / QH_CHUNK);
-    uint32_t groups = QH_TARGET_WGS / n_kseg;
-    if (groups < 1) groups = 1;
-    if (groups > QH_MAX_GROUPS) groups = QH_MAX_GROUPS;
-    if (groups > n_chunks) groups = n_chunks;
-    const uint32_t cpg = (n_chunks + groups - 1) / groups;
-    groups = (n_chunks + cpg - 1) / cpg;
-    const size_t part_b = (size_t)groups * n_out * 32;
-    VMPC_CHECK(vmpc_ws_reserve(ctx, 2 * vmpc_align(part_b) + 512));
-    uint32_t *part0 = (uint32_t *)vmpc_ws_take(ctx, part_b);
-    uint32_t *part1 = (uint32_t *)vmpc_ws_take(ctx, part_b);
-    {
-        vmpc_stage_scope sc(ctx, "bn_qap_moments");
-        const dim3 grid(n_kseg, groups);
-        if (nv == 2)
-            k_qh_moments<2><<<grid, QH_WG, 0, ctx->stream>>>((const uint32_t *)u0, (const uint32_t *)u1, (uint32_t)d,
-                                                             (uint32_t)n_out, ks, cpg, part0, part1);
-        else
-            k_qh_moments<1><<<grid, QH_WG, 0, ctx->stream>>>((const uint32_t *)u0, nullptr, (uint32_t)d,
-                                                             (uint32_t)n_out, ks, cpg, part0, part1);
-        VMPC_KERNEL_CHECK();
-    }
-    {
-        vmpc_stage_scope sc(ctx, "bn_qap_moments_sum");
-        const unsigned blocks = (unsigned)((n_out + 255) / 256);
-        k_qh_partsum<<<blocks, 256, 0, ctx->stream>>>(part0, (uint32_t)n_out, groups, (uint32_t *)out0);
-        VMPC_KERNEL_CHECK();
-        if (nv == 2) {
-            k_qh_partsum<<<blocks, 256, 0, ctx->stream>>>(part1, (uint32_t)n_out, groups, (uint32_t *)out1);
-            VMPC_KERNEL_CHECK();
-        }
-    }
-    return VMPC_OK;
-}
-
-// grid (outputs, witnesses, vectors): k_qh_partsum on witness y's partials of vector z -> its row of out0 / out1
-__global__ void __launch_bounds__(256)
-k_qh_partsum_batch(const uint32_t *__restrict__ part0, const uint32_t *__restrict__ part1, uint32_t n_out, uint32_t groups,
-                   uint32_t *__restrict__ out0, uint32_t *__restrict__ out1, size_t out_stride) {
+k_qh_partsum(const uint32_t *__restrict__ part0, const uint32_t *__restrict__ part1, uint32_t n_out, uint32_t groups,
+             uint32_t *__restrict__ out0, uint32_t *__restrict__ out1, size_t out_stride) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_out) return;
     const size_t w = blockIdx.y;
@@ -244,8 +189,8 @@ k_qh_partsum_batch(const uint32_t *__restrict__ part0, const uint32_t *__restric
     f256_st((blockIdx.z ? out1 : out0) + 8 * w * out_stride, k, fr_partsum<frbn>(part, n_out, groups, k));
 }
 
-// The ranges of j with the witnesses counted: k segments x groups x K workgroups against QH_TARGET_WGS under the single
-// call's caps.  K = 1 is vmpc_bn256_qap_moments_dev's plan; a large batch ends at one range, one partial per k and witness.
+// The ranges of j with the witnesses counted: k segments x groups x K workgroups against QH_TARGET_WGS, at most
+// QH_MAX_GROUPS.  A large batch ends at one range, one partial per k and witness.
 struct qh_batch_plan {
     uint32_t ks, n_kseg, groups, cpg;
     size_t part_b, total_b;
@@ -267,6 +212,43 @@ static qh_batch_plan qh_moments_batch_plan(size_t d, size_t n_out, size_t n_wit)
     return p;
 }
 
+// n_wit >= 1 witnesses and n_out >= 1, checked by the entries; one witness may come with strides 0
+static int qh_moments(vmpc_ctx *ctx, const void *u0, const void *u1, size_t u_stride, size_t d, size_t n_out, void *out0,
+                      void *out1, size_t out_stride, size_t n_wit) {
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const qh_batch_plan p = qh_moments_batch_plan(d, n_out, n_wit);
+    VMPC_CHECK(vmpc_ws_reserve(ctx, p.total_b));        // before any launch
+    uint32_t *part0 = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
+    uint32_t *part1 = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
+    const unsigned K = (unsigned)n_wit;
+    {
+        vmpc_stage_scope sc(ctx, "bn_qap_moments");
+        const dim3 grid(p.n_kseg, p.groups, K);
+        if (u1)
+            k_qh_moments<2><<<grid, QH_WG, 0, ctx->stream>>>((const uint32_t *)u0, (const uint32_t *)u1, u_stride,
+                                                             (uint32_t)d, (uint32_t)n_out, p.ks, p.cpg, part0, part1);
+        else
+            k_qh_moments<1><<<grid, QH_WG, 0, ctx->stream>>>((const uint32_t *)u0, nullptr, u_stride, (uint32_t)d,
+                                                             (uint32_t)n_out, p.ks, p.cpg, part0, part1);
+        VMPC_KERNEL_CHECK();
+    }
+    {
+        vmpc_stage_scope sc(ctx, "bn_qap_moments_sum");
+        k_qh_partsum<<<dim3((unsigned)((n_out + 255) / 256), K, u1 ? 2 : 1), 256, 0, ctx->stream>>>(
+            part0, part1, (uint32_t)n_out, p.groups, (uint32_t *)out0, (uint32_t *)out1, out_stride);
+        VMPC_KERNEL_CHECK();
+    }
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_bn256_qap_moments_dev(vmpc_ctx *ctx, const void *u0, const void *u1, size_t d, size_t n_out,
+                                          void *out0, void *out1) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_out > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !u0 || !out0 || (u1 && !out1) || d == 0) return VMPC_E_INVAL;
+    if (n_out == 0) return VMPC_OK;
+    return qh_moments(ctx, u0, u1, 0, d, n_out, out0, out1, 0, 1);
+}
+
 extern "C" size_t vmpc_bn256_qap_moments_batch_bytes(size_t d, size_t n_out, size_t n_wit) {
     if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_out > VMPC_BN256_FR_POLY_MAX || n_wit > VMPC_BN256_QAP_MAX_WIT || d == 0 ||
         n_out == 0 || n_wit == 0)
@@ -281,30 +263,7 @@ extern "C" int vmpc_bn256_qap_moments_batch_dev(vmpc_ctx *ctx, const void *u0, c
         return VMPC_E_RANGE;
     if (!ctx || !u0 || !out0 || (u1 && !out1) || d == 0) return VMPC_E_INVAL;
     if (n_out == 0 || n_wit == 0) return VMPC_OK;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    const qh_batch_plan p = qh_moments_batch_plan(d, n_out, n_wit);
-    VMPC_CHECK(vmpc_ws_reserve(ctx, p.total_b));        // before any launch
-    uint32_t *part0 = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
-    uint32_t *part1 = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
-    const unsigned K = (unsigned)n_wit;
-    {
-        vmpc_stage_scope sc(ctx, "bn_qap_moments_batch");
-        const dim3 grid(p.n_kseg, p.groups, K);
-        if (u1)
-            k_qh_moments_batch<2><<<grid, QH_WG, 0, ctx->stream>>>((const uint32_t *)u0, (const uint32_t *)u1, u_stride,
-                                                                   (uint32_t)d, (uint32_t)n_out, p.ks, p.cpg, part0, part1);
-        else
-            k_qh_moments_batch<1><<<grid, QH_WG, 0, ctx->stream>>>((const uint32_t *)u0, nullptr, u_stride, (uint32_t)d,
-                                                                   (uint32_t)n_out, p.ks, p.cpg, part0, part1);
-        VMPC_KERNEL_CHECK();
-    }
-    {
-        vmpc_stage_scope sc(ctx, "bn_qap_moments_batch_sum");
-        k_qh_partsum_batch<<<dim3((unsigned)((n_out + 255) / 256), K, u1 ? 2 : 1), 256, 0, ctx->stream>>>(
-            part0, part1, (uint32_t)n_out, p.groups, (uint32_t *)out0, (uint32_t *)out1, out_stride);
-        VMPC_KERNEL_CHECK();
-    }
-    return VMPC_OK;
+    return qh_moments(ctx, u0, u1, u_stride, d, n_out, out0, out1, out_stride, n_wit);
 }
 
 // ---- the weights 1 / w_j --------------------------------------------------------------------------------------------
@@ -323,44 +282,12 @@ struct qh_fin {
     }
 };
 
-// ua[j-1] = a_j f_j, ub[j-1] = b_j f_j, f_j = (-1)^(d-j) E[d-j+1] E[j] / d!^2 = 1 / w_j
+// grid (rows, witnesses): ua[j-1] = a_j f_j, ub[j-1] = b_j f_j on witness blockIdx.y's rows, f_j = (-1)^(d-j) E[d-j+1]
+// E[j] / d!^2 = 1 / w_j; E and inv_sq are the QAP's, computed once
 __global__ void __launch_bounds__(256)
 k_qh_weights(uint32_t d, const uint32_t *__restrict__ E, const uint32_t *__restrict__ inv_sq,
-             const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ ua,
-             uint32_t *__restrict__ ub) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= d) return;
-    const uint32_t j = i + 1;
-    frbn f = frbn_mul(frbn_mul(f256_ld<frbn>(E, d - j + 1), f256_ld<frbn>(E, j)), f256_ld<frbn>(inv_sq, 0));
-    if ((d - j) & 1u) f = frbn_sub(frbn_zero(), f);
-    f256_st(ua, i, frbn_mul(f256_ld<frbn>(a, i), f));
-    if (b) f256_st(ub, i, frbn_mul(f256_ld<frbn>(b, i), f));
-}
-
-extern "C" int vmpc_bn256_qap_h_weights_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t d, void *ua, void *ub) {
-    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
-    if (!ctx || !a || !ua || (b && !ub) || d == 0) return VMPC_E_INVAL;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    const uint32_t dd = (uint32_t)d;
-    const size_t run_b = fr_scan_run_bytes<QH_RUN>(d, 1);
-    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(run_b) + vmpc_align((d + 1) * 32) + 1024));
-    uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, run_b);
-    uint32_t *E = (uint32_t *)vmpc_ws_take(ctx, (d + 1) * 32);
-    uint32_t *inv_sq = (uint32_t *)vmpc_ws_take(ctx, 32);
-    vmpc_stage_scope sc(ctx, "bn_qap_h_weights");
-    VMPC_CHECK((fr_scan<frbn, QH_RUN>(ctx, qh_seq{dd}, dd, 1, run, E, qh_fin{inv_sq})));
-    k_qh_weights<<<(unsigned)((d + 255) / 256), 256, 0, ctx->stream>>>(dd, E, inv_sq, (const uint32_t *)a,
-                                                                      (const uint32_t *)b, (uint32_t *)ua,
-                                                                      (uint32_t *)ub);
-    VMPC_KERNEL_CHECK();
-    return VMPC_OK;
-}
-
-// grid (rows, witnesses): k_qh_weights on witness blockIdx.y's rows; E and inv_sq are the QAP's, computed once
-__global__ void __launch_bounds__(256)
-k_qh_weights_batch(uint32_t d, const uint32_t *__restrict__ E, const uint32_t *__restrict__ inv_sq,
-                   const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, size_t ab_stride,
-                   uint32_t *__restrict__ ua, uint32_t *__restrict__ ub, size_t u_stride) {
+             const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, size_t ab_stride,
+             uint32_t *__restrict__ ua, uint32_t *__restrict__ ub, size_t u_stride) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d) return;
     const size_t w = blockIdx.y;
@@ -371,13 +298,9 @@ k_qh_weights_batch(uint32_t d, const uint32_t *__restrict__ E, const uint32_t *_
     if (b) f256_st(ub + 8 * w * u_stride, i, frbn_mul(f256_ld<frbn>(b + 8 * w * ab_stride, i), f));
 }
 
-extern "C" int vmpc_bn256_qap_h_weights_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t d,
-                                                  void *ua, void *ub, size_t u_stride, size_t n_wit) {
-    if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_wit > VMPC_BN256_QAP_MAX_WIT || ab_stride > QH_MAX_STRIDE ||
-        u_stride > QH_MAX_STRIDE || (n_wit && (ab_stride < d || u_stride < d)))
-        return VMPC_E_RANGE;
-    if (!ctx || !a || !ua || (b && !ub) || d == 0) return VMPC_E_INVAL;
-    if (n_wit == 0) return VMPC_OK;
+// n_wit >= 1 witnesses, checked by the entries; one witness may come with strides 0
+static int qh_weights(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t d, void *ua, void *ub,
+                      size_t u_stride, size_t n_wit) {
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const uint32_t dd = (uint32_t)d;
     const size_t run_b = fr_scan_run_bytes<QH_RUN>(d, 1);
@@ -385,46 +308,60 @@ extern "C" int vmpc_bn256_qap_h_weights_batch_dev(vmpc_ctx *ctx, const void *a, 
     uint32_t *run = (uint32_t *)vmpc_ws_take(ctx, run_b);
     uint32_t *E = (uint32_t *)vmpc_ws_take(ctx, (d + 1) * 32);
     uint32_t *inv_sq = (uint32_t *)vmpc_ws_take(ctx, 32);
-    vmpc_stage_scope sc(ctx, "bn_qap_h_weights_batch");
+    vmpc_stage_scope sc(ctx, "bn_qap_h_weights");
     VMPC_CHECK((fr_scan<frbn, QH_RUN>(ctx, qh_seq{dd}, dd, 1, run, E, qh_fin{inv_sq})));
-    k_qh_weights_batch<<<dim3((unsigned)((d + 255) / 256), (unsigned)n_wit), 256, 0, ctx->stream>>>(
+    k_qh_weights<<<dim3((unsigned)((d + 255) / 256), (unsigned)n_wit), 256, 0, ctx->stream>>>(
         dd, E, inv_sq, (const uint32_t *)a, (const uint32_t *)b, ab_stride, (uint32_t *)ua, (uint32_t *)ub, u_stride);
     VMPC_KERNEL_CHECK();
     return VMPC_OK;
 }
 
+extern "C" int vmpc_bn256_qap_h_weights_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t d, void *ua, void *ub) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !a || !ua || (b && !ub) || d == 0) return VMPC_E_INVAL;
+    return qh_weights(ctx, a, b, 0, d, ua, ub, 0, 1);
+}
+
+extern "C" int vmpc_bn256_qap_h_weights_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t d,
+                                                  void *ua, void *ub, size_t u_stride, size_t n_wit) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_wit > VMPC_BN256_QAP_MAX_WIT || ab_stride > QH_MAX_STRIDE ||
+        u_stride > QH_MAX_STRIDE || (n_wit && (ab_stride < d || u_stride < d)))
+        return VMPC_E_RANGE;
+    if (!ctx || !a || !ua || (b && !ub) || d == 0) return VMPC_E_INVAL;
+    if (n_wit == 0) return VMPC_OK;
+    return qh_weights(ctx, a, b, ab_stride, d, ua, ub, u_stride, n_wit);
+}
+
 // ---- the witness check ----------------------------------------------------------------------------------------------
+// grid (rows, witnesses): first_bad[w] = witness w's smallest bad row (rows `stride` scalars apart)
 __global__ void __launch_bounds__(256)
 k_qh_check(uint32_t d, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ y,
-           uint32_t *__restrict__ first_bad) {
+           size_t stride, uint32_t *__restrict__ first_bad) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d) return;
+    const size_t w = blockIdx.y, off = 8 * w * stride;
     // an index, not a field value: the minimum does not depend on the order
-    if (!f256_equal(frbn_mul(f256_ld<frbn>(a, i), f256_ld<frbn>(b, i)), f256_ld<frbn>(y, i))) atomicMin(first_bad, i);
+    if (!f256_equal(frbn_mul(f256_ld<frbn>(a + off, i), f256_ld<frbn>(b + off, i)), f256_ld<frbn>(y + off, i)))
+        atomicMin(first_bad + w, i);
+}
+
+// n_wit >= 1 witnesses, checked by the entries; one witness may come with stride 0
+static int qh_check(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t stride, size_t d,
+                    uint32_t *first_bad, size_t n_wit) {
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope sc(ctx, "bn_qap_check");
+    VMPC_HIP_CHECK(hipMemsetAsync(first_bad, 0xFF, 4 * n_wit, ctx->stream));
+    k_qh_check<<<dim3((unsigned)((d + 255) / 256), (unsigned)n_wit), 256, 0, ctx->stream>>>(
+        (uint32_t)d, (const uint32_t *)a, (const uint32_t *)b, (const uint32_t *)y, stride, first_bad);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
 }
 
 extern "C" int vmpc_bn256_qap_check_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t d,
                                         uint32_t *first_bad) {
     if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
     if (!ctx || !a || !b || !y || !first_bad || d == 0) return VMPC_E_INVAL;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    vmpc_stage_scope sc(ctx, "bn_qap_check");
-    VMPC_HIP_CHECK(hipMemsetAsync(first_bad, 0xFF, 4, ctx->stream));
-    k_qh_check<<<(unsigned)((d + 255) / 256), 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)a,
-                                                                    (const uint32_t *)b, (const uint32_t *)y, first_bad);
-    VMPC_KERNEL_CHECK();
-    return VMPC_OK;
-}
-
-// grid (rows, witnesses): first_bad[w] = witness w's smallest bad row
-__global__ void __launch_bounds__(256)
-k_qh_check_batch(uint32_t d, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b,
-                 const uint32_t *__restrict__ y, size_t stride, uint32_t *__restrict__ first_bad) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= d) return;
-    const size_t w = blockIdx.y, off = 8 * w * stride;
-    if (!f256_equal(frbn_mul(f256_ld<frbn>(a + off, i), f256_ld<frbn>(b + off, i)), f256_ld<frbn>(y + off, i)))
-        atomicMin(first_bad + w, i);     // an index, as in k_qh_check
+    return qh_check(ctx, a, b, y, 0, d, first_bad, 1);
 }
 
 extern "C" int vmpc_bn256_qap_check_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t stride,
@@ -434,13 +371,7 @@ extern "C" int vmpc_bn256_qap_check_batch_dev(vmpc_ctx *ctx, const void *a, cons
         return VMPC_E_RANGE;
     if (!ctx || !a || !b || !y || !first_bad || d == 0) return VMPC_E_INVAL;
     if (n_wit == 0) return VMPC_OK;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    vmpc_stage_scope sc(ctx, "bn_qap_check_batch");
-    VMPC_HIP_CHECK(hipMemsetAsync(first_bad, 0xFF, 4 * n_wit, ctx->stream));
-    k_qh_check_batch<<<dim3((unsigned)((d + 255) / 256), (unsigned)n_wit), 256, 0, ctx->stream>>>(
-        (uint32_t)d, (const uint32_t *)a, (const uint32_t *)b, (const uint32_t *)y, stride, first_bad);
-    VMPC_KERNEL_CHECK();
-    return VMPC_OK;
+    return qh_check(ctx, a, b, y, stride, d, first_bad, n_wit);
 }
 
 // ---- the residual of a share vector ---------------------------------------------------------------------------------
@@ -512,7 +443,7 @@ extern "C" int vmpc_bn256_qap_residual_dev(vmpc_ctx *ctx, const void *a, const v
     }
     {
         vmpc_stage_scope sc(ctx, "bn_qap_residual_sum");
-        k_qh_partsum<<<1, 256, 0, ctx->stream>>>(part, 1, (uint32_t)groups, (uint32_t *)out);
+        k_qh_partsum<<<1, 256, 0, ctx->stream>>>(part, nullptr, 1, (uint32_t)groups, (uint32_t *)out, nullptr, 0);
         VMPC_KERNEL_CHECK();
     }
     return VMPC_OK;
@@ -619,65 +550,11 @@ extern "C" int vmpc_bn256_qap_horner_dev(vmpc_ctx *ctx, const void *coeffs, size
 // ---- the combination ------------------------------------------------------------------------------------------------
 // A[i] = A_(i+1), B[i] = B_(i+1) (the moments), P = A * B.  crev[r] = C_(d-r) with
 //     C_k = P[k-2] (k >= 2) + delta_v B_k + delta_w A_k
+// grid (r, witnesses): witness blockIdx.y's moments (ab_stride apart), its three deltas and its row of the scratch
+// (sc_stride apart: P at 0, crev at d).  P holds only P[0 .. d-2], all that C_2 .. C_d read.
 __global__ void __launch_bounds__(256)
-k_qh_cmid(uint32_t d, const uint32_t *__restrict__ A, const uint32_t *__restrict__ B, const uint32_t *__restrict__ P,
-          const uint32_t *__restrict__ deltas, uint32_t *__restrict__ crev) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= d) return;
-    const uint32_t i = d - 1 - r;   // C_(i+1)
-    frbn c = i ? f256_ld<frbn>(P, i - 1) : frbn_zero();
-    if (deltas) {
-        c = frbn_add(c, frbn_mul(f256_ld<frbn>(deltas, 0), f256_ld<frbn>(B, i)));
-        c = frbn_add(c, frbn_mul(f256_ld<frbn>(deltas, 1), f256_ld<frbn>(A, i)));
-    }
-    f256_st(crev, r, c);
-}
-
-// Q = (t_1 .. t_d) * crev: h_e = Q[d-1+e] + delta_v delta_w t_e - [e = 0] delta_y for e < d, h_d = delta_v delta_w t_d
-__global__ void __launch_bounds__(256)
-k_qh_final(uint32_t d, const uint32_t *__restrict__ Q, const uint32_t *__restrict__ tc,
-           const uint32_t *__restrict__ deltas, uint32_t *__restrict__ out) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e > d) return;
-    frbn h = e < d ? f256_ld<frbn>(Q, (long long)d - 1 + e) : frbn_zero();
-    if (deltas) {
-        h = frbn_add(h, frbn_mul(frbn_mul(f256_ld<frbn>(deltas, 0), f256_ld<frbn>(deltas, 1)), f256_ld<frbn>(tc, e)));
-        if (e == 0) h = frbn_sub(h, f256_ld<frbn>(deltas, 2));
-    }
-    f256_st(out, e, h);
-}
-
-extern "C" int vmpc_bn256_qap_h_combine_dev(vmpc_ctx *ctx, const void *A, const void *B, const void *t, size_t d,
-                                            const void *deltas, void *scratch, void *out) {
-    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
-    if (!ctx || !A || !B || !t || !scratch || !out || d == 0) return VMPC_E_INVAL;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    // scratch: P (2d - 1), crev (d), Q (2d - 1)
-    char *P = (char *)scratch, *crev = P + 32 * (2 * d - 1), *Q = crev + 32 * d;
-    const unsigned blocks = (unsigned)((d + 1 + 255) / 256);
-    VMPC_CHECK(vmpc_bn256_fr_poly_mul_dev(ctx, A, d, B, d, P));
-    {
-        vmpc_stage_scope sc(ctx, "bn_qap_h_cmid");
-        k_qh_cmid<<<blocks, 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)A, (const uint32_t *)B,
-                                                   (const uint32_t *)P, (const uint32_t *)deltas, (uint32_t *)crev);
-        VMPC_KERNEL_CHECK();
-    }
-    VMPC_CHECK(vmpc_bn256_fr_poly_mul_dev(ctx, (const char *)t + 32, d, crev, d, Q));
-    {
-        vmpc_stage_scope sc(ctx, "bn_qap_h_final");
-        k_qh_final<<<blocks, 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)Q, (const uint32_t *)t,
-                                                    (const uint32_t *)deltas, (uint32_t *)out);
-        VMPC_KERNEL_CHECK();
-    }
-    return VMPC_OK;
-}
-
-// ---- the combination for K witnesses --------------------------------------------------------------------------------
-// grid (r, witnesses): k_qh_cmid on witness blockIdx.y's moments (ab_stride apart), its three deltas and its row of the
-// scratch (sc_stride apart: P at 0, crev at d).  P holds only P[0 .. d-2], all that C_2 .. C_d read.
-__global__ void __launch_bounds__(256)
-k_qh_cmid_batch(uint32_t d, const uint32_t *__restrict__ A, const uint32_t *__restrict__ B, size_t ab_stride,
-                const uint32_t *__restrict__ deltas, uint32_t *__restrict__ scratch, size_t sc_stride) {
+k_qh_cmid(uint32_t d, const uint32_t *__restrict__ A, const uint32_t *__restrict__ B, size_t ab_stride,
+          const uint32_t *__restrict__ deltas, uint32_t *__restrict__ scratch, size_t sc_stride) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= d) return;
     const size_t w = blockIdx.y;
@@ -692,10 +569,11 @@ k_qh_cmid_batch(uint32_t d, const uint32_t *__restrict__ A, const uint32_t *__re
     f256_st(scratch + 8 * (w * sc_stride + d), r, c);
 }
 
-// grid (e, witnesses): k_qh_final; Q holds only the window Q[d-1 .. 2d-2] of the second product, at index 0
+// Q = (t_1 .. t_d) * crev: h_e = Q[d-1+e] + delta_v delta_w t_e - [e = 0] delta_y for e < d, h_d = delta_v delta_w t_d.
+// grid (e, witnesses); the scratch row holds only the window Q[d-1 .. 2d-2] of the second product, at 2 d.
 __global__ void __launch_bounds__(256)
-k_qh_final_batch(uint32_t d, const uint32_t *__restrict__ scratch, size_t sc_stride, const uint32_t *__restrict__ tc,
-                 const uint32_t *__restrict__ deltas, uint32_t *__restrict__ out, size_t out_stride) {
+k_qh_final(uint32_t d, const uint32_t *__restrict__ scratch, size_t sc_stride, const uint32_t *__restrict__ tc,
+           const uint32_t *__restrict__ deltas, uint32_t *__restrict__ out, size_t out_stride) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e > d) return;
     const size_t w = blockIdx.y;
@@ -709,14 +587,9 @@ k_qh_final_batch(uint32_t d, const uint32_t *__restrict__ scratch, size_t sc_str
     f256_st(out + 8 * w * out_stride, e, h);
 }
 
-extern "C" int vmpc_bn256_qap_h_combine_batch_dev(vmpc_ctx *ctx, const void *A, const void *B, size_t ab_stride,
-                                                  const void *t, size_t d, const void *deltas, void *scratch, void *out,
-                                                  size_t out_stride, size_t n_wit) {
-    if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_wit > VMPC_BN256_QAP_MAX_WIT || ab_stride > QH_MAX_STRIDE ||
-        out_stride > QH_MAX_STRIDE || (n_wit && (ab_stride < d || out_stride < d + 1)))
-        return VMPC_E_RANGE;
-    if (!ctx || !A || !B || !t || !scratch || !out || d == 0) return VMPC_E_INVAL;
-    if (n_wit == 0) return VMPC_OK;
+// n_wit >= 1 witnesses with ab_stride >= d, checked by the entries
+static int qh_combine(vmpc_ctx *ctx, const void *A, const void *B, size_t ab_stride, const void *t, size_t d,
+                      const void *deltas, void *scratch, void *out, size_t out_stride, size_t n_wit) {
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     // scratch row of a witness: P[0 .. d-2] (d - 1, one unused), crev (d), Q[d-1 .. 2d-2] (d)
     const size_t sc = 3 * d;
@@ -728,17 +601,35 @@ extern "C" int vmpc_bn256_qap_h_combine_batch_dev(vmpc_ctx *ctx, const void *A, 
     const dim3 grid((unsigned)((d + 1 + 255) / 256), (unsigned)n_wit);
     VMPC_CHECK(vmpc_bn256_fr_poly_mul_batch_dev(ctx, A, ab_stride, d, B, ab_stride, d, 0, d - 1, P, sc, n_wit));
     {
-        vmpc_stage_scope s(ctx, "bn_qap_h_cmid_batch");
-        k_qh_cmid_batch<<<grid, 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)A, (const uint32_t *)B, ab_stride,
-                                                       (const uint32_t *)deltas, (uint32_t *)scratch, sc);
+        vmpc_stage_scope s(ctx, "bn_qap_h_cmid");
+        k_qh_cmid<<<grid, 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)A, (const uint32_t *)B, ab_stride,
+                                                 (const uint32_t *)deltas, (uint32_t *)scratch, sc);
         VMPC_KERNEL_CHECK();
     }
     VMPC_CHECK(vmpc_bn256_fr_poly_mul_batch_dev(ctx, crev, sc, d, (const char *)t + 32, 0, d, d - 1, d, Q, sc, n_wit));
     {
-        vmpc_stage_scope s(ctx, "bn_qap_h_final_batch");
-        k_qh_final_batch<<<grid, 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)scratch, sc, (const uint32_t *)t,
-                                                        (const uint32_t *)deltas, (uint32_t *)out, out_stride);
+        vmpc_stage_scope s(ctx, "bn_qap_h_final");
+        k_qh_final<<<grid, 256, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)scratch, sc, (const uint32_t *)t,
+                                                  (const uint32_t *)deltas, (uint32_t *)out, out_stride);
         VMPC_KERNEL_CHECK();
     }
     return VMPC_OK;
+}
+
+extern "C" int vmpc_bn256_qap_h_combine_dev(vmpc_ctx *ctx, const void *A, const void *B, const void *t, size_t d,
+                                            const void *deltas, void *scratch, void *out) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !A || !B || !t || !scratch || !out || d == 0) return VMPC_E_INVAL;
+    return qh_combine(ctx, A, B, d, t, d, deltas, scratch, out, d + 1, 1);
+}
+
+extern "C" int vmpc_bn256_qap_h_combine_batch_dev(vmpc_ctx *ctx, const void *A, const void *B, size_t ab_stride,
+                                                  const void *t, size_t d, const void *deltas, void *scratch, void *out,
+                                                  size_t out_stride, size_t n_wit) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_wit > VMPC_BN256_QAP_MAX_WIT || ab_stride > QH_MAX_STRIDE ||
+        out_stride > QH_MAX_STRIDE || (n_wit && (ab_stride < d || out_stride < d + 1)))
+        return VMPC_E_RANGE;
+    if (!ctx || !A || !B || !t || !scratch || !out || d == 0) return VMPC_E_INVAL;
+    if (n_wit == 0) return VMPC_OK;
+    return qh_combine(ctx, A, B, ab_stride, t, d, deltas, scratch, out, out_stride, n_wit);
 }

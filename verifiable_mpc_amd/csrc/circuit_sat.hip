@@ -9,7 +9,8 @@
 //                             gammas in z are the caller's and the smallest i with a_i b_i != gamma_i is reported
 //                             (circuit_builder.py:133-151 evaluates the forms one gate after the other in Python).
 //   vmpc_fr_cs_triples_batch_dev  the same for K witnesses of ONE circuit in one launch: the witness on blockIdx.y, z and the
-//                             row values K rows of one allocation
+//                             row values K rows of one allocation.  The single entry is K = 1 of
+//                             the same kernel and host function, as for the extension below.
 //   vmpc_fr_cs_tables_dev     k! and 1 / k! for k <= K: two product scans (csrc/fr_scan.h) and ONE inversion.  Everything below is
 //                             products of these: 1 / k = (k-1)! / k!, the barycentric weights
 //                             w_j = (-1)^(M-j) / ((j-1)! (M-j)!), l(x) = prod_j (x - j) = (x-1)! / (x-M-1)! for x > M.
@@ -25,7 +26,8 @@
 //   vmpc_fr_cs_extend_fg_dev  the same f(x), g(x) left apart and unmultiplied, for a witness that is a vector of Shamir
 //                             shares: the extension is linear in v, the product is the parties' (csrc/mpc_share.hip)
 //   vmpc_fr_cs_extend_batch_dev  vmpc_fr_cs_extend_dev for K witnesses: T and the weights once, the correlation on a grid
-//                             (tiles, segments, witness), the segment length chosen with K counted
+//                             (tiles, segments, witness), the segment length chosen with K counted.  cs_extend() is the
+//                             one implementation of all three entries; the two single ones pass K = 1.
 //   vmpc_fr_cs_lagrange_dev   the Lagrange vector of the nodes 0..K at c (ac20/recombine.py:5-32, a double loop):
 //                             lambda_j = prod_{i != j} (c - i) * (-1)^(K-j) / (j! (K-j)!) - prefix and suffix products
 //                             of (c - i), no inversion at all, so a c on a node cannot divide by zero here (the
@@ -60,14 +62,20 @@ __device__ fr cs_row_eval(const uint32_t *__restrict__ rp, const uint32_t *__res
     return fr_add(fr_sparse_dot<fr>(col, val, rp[row], rp[row + 1], z, cs_z_map{n_x, g_off}), f256_ld<fr>(cst, row));
 }
 
+// grid (gates, witnesses): the forms and the level's gate list are the circuit's, z / a_out / b_out rows w of K (strides
+// in scalars), first_bad one word per witness.  a_out and b_out may be one buffer (check == 2): no __restrict__ on them.
 __global__ void __launch_bounds__(CS_WG)
 k_cs_triples(const uint32_t *__restrict__ a_rp, const uint32_t *__restrict__ a_col, const uint32_t *__restrict__ a_val,
              const uint32_t *__restrict__ a_cst, const uint32_t *__restrict__ b_rp, const uint32_t *__restrict__ b_col,
              const uint32_t *__restrict__ b_val, const uint32_t *__restrict__ b_cst, const uint32_t *__restrict__ gates,
-             uint32_t n_gates, uint32_t n_x, uint32_t g_off, uint32_t *z, uint32_t *__restrict__ a_out,
-             uint32_t *__restrict__ b_out, int check, uint32_t *__restrict__ first_bad) {
+             uint32_t n_gates, uint32_t n_x, uint32_t g_off, uint32_t *z, size_t z_stride, uint32_t *a_out,
+             uint32_t *b_out, size_t ab_stride, int check, uint32_t *__restrict__ first_bad) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_gates) return;
+    const size_t w = blockIdx.y;
+    z += w * z_stride * 8;
+    a_out += w * ab_stride * 8;
+    b_out += w * ab_stride * 8;
     const uint32_t i = gates ? gates[t] : t;
     const fr a = cs_row_eval(a_rp, a_col, a_val, a_cst, i, n_x, g_off, z);
     const fr b = cs_row_eval(b_rp, b_col, b_val, b_cst, i, n_x, g_off, z);
@@ -76,10 +84,27 @@ k_cs_triples(const uint32_t *__restrict__ a_rp, const uint32_t *__restrict__ a_c
     if (check == 2) return;   // the forms' values only (the output rows)
     const fr p = fr_mul(a, b);
     if (check) {
-        if (!f256_equal(p, f256_ld<fr>(z, (long long)g_off + i))) atomicMin(first_bad, i);   // an index: order does not matter
+        if (!f256_equal(p, f256_ld<fr>(z, (long long)g_off + i))) atomicMin(first_bad + w, i);   // an index: order does not matter
     } else {
         f256_st(z, (long long)g_off + i, p);
     }
+}
+
+// n_wit >= 1 witnesses, checked by the entries; one witness may come with strides 0
+static int cs_triples(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_vals,
+                      const void *a_const, const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_vals,
+                      const void *b_const, const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset, void *z,
+                      size_t z_stride, void *a_out, void *b_out, size_t ab_stride, size_t n_wit, int check,
+                      uint32_t *first_bad) {
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope sc(ctx, check ? "cs_triples_check" : "cs_triples");
+    if (check == 1) VMPC_HIP_CHECK(hipMemsetAsync(first_bad, 0xFF, 4 * n_wit, ctx->stream));
+    k_cs_triples<<<dim3((unsigned)((n_gates + CS_WG - 1) / CS_WG), (unsigned)n_wit), CS_WG, 0, ctx->stream>>>(
+        a_row_ptr, a_col, (const uint32_t *)a_vals, (const uint32_t *)a_const, b_row_ptr, b_col, (const uint32_t *)b_vals,
+        (const uint32_t *)b_const, gates, (uint32_t)n_gates, (uint32_t)n_x, (uint32_t)gamma_offset, (uint32_t *)z, z_stride,
+        (uint32_t *)a_out, (uint32_t *)b_out, ab_stride, check, first_bad);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
 }
 
 extern "C" int vmpc_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_vals,
@@ -92,43 +117,8 @@ extern "C" int vmpc_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, 
         check < 0 || check > 2)
         return VMPC_E_INVAL;
     if (n_gates == 0) return VMPC_OK;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    vmpc_stage_scope sc(ctx, check ? "cs_triples_check" : "cs_triples");
-    if (check == 1) VMPC_HIP_CHECK(hipMemsetAsync(first_bad, 0xFF, 4, ctx->stream));
-    k_cs_triples<<<(unsigned)((n_gates + CS_WG - 1) / CS_WG), CS_WG, 0, ctx->stream>>>(
-        a_row_ptr, a_col, (const uint32_t *)a_vals, (const uint32_t *)a_const, b_row_ptr, b_col, (const uint32_t *)b_vals,
-        (const uint32_t *)b_const, gates, (uint32_t)n_gates, (uint32_t)n_x, (uint32_t)gamma_offset, (uint32_t *)z,
-        (uint32_t *)a_out, (uint32_t *)b_out, check, first_bad);
-    VMPC_KERNEL_CHECK();
-    return VMPC_OK;
-}
-
-// the witness on blockIdx.y: the forms and the level's gate list are the circuit's, z / a_out / b_out rows w of K
-// (strides in scalars), first_bad one word per witness.  a_out and b_out may be one buffer (check == 2).
-__global__ void __launch_bounds__(CS_WG)
-k_cs_triples_batch(const uint32_t *__restrict__ a_rp, const uint32_t *__restrict__ a_col, const uint32_t *__restrict__ a_val,
-                   const uint32_t *__restrict__ a_cst, const uint32_t *__restrict__ b_rp, const uint32_t *__restrict__ b_col,
-                   const uint32_t *__restrict__ b_val, const uint32_t *__restrict__ b_cst, const uint32_t *__restrict__ gates,
-                   uint32_t n_gates, uint32_t n_x, uint32_t g_off, uint32_t *z, size_t z_stride, uint32_t *a_out,
-                   uint32_t *b_out, size_t ab_stride, int check, uint32_t *__restrict__ first_bad) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_gates) return;
-    const size_t w = blockIdx.y;
-    z += w * z_stride * 8;
-    a_out += w * ab_stride * 8;
-    b_out += w * ab_stride * 8;
-    const uint32_t i = gates ? gates[t] : t;
-    const fr a = cs_row_eval(a_rp, a_col, a_val, a_cst, i, n_x, g_off, z);
-    const fr b = cs_row_eval(b_rp, b_col, b_val, b_cst, i, n_x, g_off, z);
-    f256_st(a_out, i, a);
-    f256_st(b_out, i, b);
-    if (check == 2) return;
-    const fr p = fr_mul(a, b);
-    if (check) {
-        if (!f256_equal(p, f256_ld<fr>(z, (long long)g_off + i))) atomicMin(first_bad + w, i);
-    } else {
-        f256_st(z, (long long)g_off + i, p);
-    }
+    return cs_triples(ctx, a_row_ptr, a_col, a_vals, a_const, b_row_ptr, b_col, b_vals, b_const, gates, n_gates, n_x,
+                      gamma_offset, z, 0, a_out, b_out, 0, 1, check, first_bad);
 }
 
 extern "C" int vmpc_fr_cs_triples_batch_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col,
@@ -145,15 +135,8 @@ extern "C" int vmpc_fr_cs_triples_batch_dev(vmpc_ctx *ctx, const uint32_t *a_row
         check < 0 || check > 2)
         return VMPC_E_INVAL;
     if (n_gates == 0 || n_wit == 0) return VMPC_OK;
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    vmpc_stage_scope sc(ctx, check ? "cs_triples_batch_check" : "cs_triples_batch");
-    if (check == 1) VMPC_HIP_CHECK(hipMemsetAsync(first_bad, 0xFF, 4 * n_wit, ctx->stream));
-    k_cs_triples_batch<<<dim3((unsigned)((n_gates + CS_WG - 1) / CS_WG), (unsigned)n_wit), CS_WG, 0, ctx->stream>>>(
-        a_row_ptr, a_col, (const uint32_t *)a_vals, (const uint32_t *)a_const, b_row_ptr, b_col, (const uint32_t *)b_vals,
-        (const uint32_t *)b_const, gates, (uint32_t)n_gates, (uint32_t)n_x, (uint32_t)gamma_offset, (uint32_t *)z, z_stride,
-        (uint32_t *)a_out, (uint32_t *)b_out, ab_stride, check, first_bad);
-    VMPC_KERNEL_CHECK();
-    return VMPC_OK;
+    return cs_triples(ctx, a_row_ptr, a_col, a_vals, a_const, b_row_ptr, b_col, b_vals, b_const, gates, n_gates, n_x,
+                      gamma_offset, z, z_stride, a_out, b_out, ab_stride, n_wit, check, first_bad);
 }
 
 // ---- factorial tables ---------------------------------------------------------------------------------------------------
@@ -243,181 +226,14 @@ extern "C" int vmpc_fr_cs_lagrange_dev(vmpc_ctx *ctx, const uint8_t c[32], size_
 
 // ---- extension of f, g to 0 and m+2 .. 2m ------------------------------------------------------------------------------
 // uf[j-1] = a[j-1] w_j, ug[j-1] = b[j-1] w_j (j = 1..M); T[k] = 1 / k (k = 1..n_t-1), T[0] = 0
+// Every kernel of the extension takes the witness from the grid's last dimension: witness w reads rows w of a, b
+// (ab_stride scalars apart) and writes row w of the z tails (z_stride apart); uf, ug, s0 and the partial sums are K rows
+// of the workspace, T and the weights are the circuit's and computed once.
+// grid (max(M, n_t), witnesses); T by witness 0 only
 __global__ void __launch_bounds__(CS_WG)
-k_cs_prep(uint32_t M, uint32_t n_t, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b,
+k_cs_prep(uint32_t M, uint32_t n_t, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, size_t ab_stride,
           const uint32_t *__restrict__ fact, const uint32_t *__restrict__ ifact, uint32_t *__restrict__ uf,
           uint32_t *__restrict__ ug, uint32_t *__restrict__ T) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < M) {
-        const uint32_t j = i + 1;
-        fr w = fr_mul(f256_ld<fr>(ifact, j - 1), f256_ld<fr>(ifact, M - j));
-        if ((M - j) & 1u) w = fr_neg(w);
-        f256_st(uf, i, fr_mul(f256_ld<fr>(a, i), w));
-        f256_st(ug, i, fr_mul(f256_ld<fr>(b, i), w));
-    }
-    if (i < n_t) f256_st(T, i, i ? fr_mul(f256_ld<fr>(fact, i - 1), f256_ld<fr>(ifact, i)) : fr_zero());
-}
-
-// one workgroup: s0[0] = sum_i uf[i] T[i+1], s0[1] = the same for ug (lane t takes i = t, t + 256, ..; the lanes' sums
-// are added in lane order)
-__global__ void __launch_bounds__(CS_WG)
-k_cs_dot0(uint32_t M, const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, const uint32_t *__restrict__ T,
-          uint32_t *__restrict__ s0) {
-    __shared__ fr part[2][CS_WG];
-    const uint32_t t = threadIdx.x;
-    f256_acc af = f256_acc_zero(), ag = f256_acc_zero();
-    for (uint32_t i = t; i < M; i += CS_WG) {
-        const fr y = f256_ld<fr>(T, (long long)i + 1), xf = f256_ld<fr>(uf, i), xg = f256_ld<fr>(ug, i);
-        f256_acc_mac(af, xf.v, y.v);
-        f256_acc_mac(ag, xg.v, y.v);
-    }
-    part[0][t] = f256_acc_reduce<fr>(af);
-    part[1][t] = f256_acc_reduce<fr>(ag);
-    __syncthreads();
-    if (t < 2) {
-        fr s = part[t][0];
-        for (uint32_t i = 1; i < CS_WG; i++) s = fr_add(s, part[t][i]);
-        f256_st(s0, t, s);
-    }
-}
-
-// grid (tiles, segments).  part_f[s n_out + o] = sum over segment s's i of uf[i] T[k_lo + o - i], o < n_out; part_g alike.
-__global__ void __launch_bounds__(FR_CONV_TILE)
-k_cs_corr(const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, long long M, const uint32_t *__restrict__ T,
-          long long n_t, long long k_lo, long long n_out, long long seg, uint32_t *__restrict__ part_f,
-          uint32_t *__restrict__ part_g) {
-    __shared__ uint32_t sU[2][FR_CONV_CHUNK * 8];
-    __shared__ uint32_t sT[8 * FR_CONV_BROW];
-    const long long o0 = (long long)blockIdx.x * FR_CONV_TILE, k0 = k_lo + o0;
-    const long long seg_lo = (long long)blockIdx.y * seg;
-    const uint32_t *const u[2] = {uf, ug};
-    f256_acc acc[2] = {f256_acc_zero(), f256_acc_zero()};
-    for (long long i0 = seg_lo; i0 < seg_lo + seg && i0 < M; i0 += FR_CONV_CHUNK)
-        fr_conv_chunk<fr, 2>(sU, sT, acc, u, M, T, n_t, k0, i0);
-    const long long o = o0 + threadIdx.x;
-    if (o < n_out) {
-        f256_st(part_f, (long long)blockIdx.y * n_out + o, f256_acc_reduce<fr>(acc[0]));
-        f256_st(part_g, (long long)blockIdx.y * n_out + o, f256_acc_reduce<fr>(acc[1]));
-    }
-}
-
-// zt = z + n: zt[0] = f(0), zt[1] = g(0), zt[2] = h(0), zt[2 + x] = h(x).  Lane o < n_out: x = m + 2 + o; lane n_out:
-// x = 0 and h(m + 1) = r_a r_b.
-__global__ void __launch_bounds__(CS_WG)
-k_cs_finish(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restrict__ part_f,
-            const uint32_t *__restrict__ part_g, const uint32_t *__restrict__ s0, const uint32_t *__restrict__ a,
-            const uint32_t *__restrict__ b, const uint32_t *__restrict__ fact, const uint32_t *__restrict__ ifact,
-            uint32_t *__restrict__ zt) {
-    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t M = m + 1;
-    if (o < n_out) {
-        const fr sf = fr_partsum<fr>(part_f, n_out, n_seg, o), sg = fr_partsum<fr>(part_g, n_out, n_seg, o);
-        const uint32_t x = m + 2 + o;
-        const fr lx = fr_mul(f256_ld<fr>(fact, x - 1), f256_ld<fr>(ifact, x - M - 1));
-        f256_st(zt, 2 + (long long)x, fr_mul(fr_mul(lx, sf), fr_mul(lx, sg)));
-    } else if (o == n_out) {
-        // l(0) = (-1)^M M!, 1 / (0 - j) = -T[j]: f(0) = (-1)^(M+1) M! s0
-        fr l0 = f256_ld<fr>(fact, M);
-        if (!(M & 1u)) l0 = fr_neg(l0);
-        const fr f0 = fr_mul(l0, f256_ld<fr>(s0, 0)), g0 = fr_mul(l0, f256_ld<fr>(s0, 1));
-        f256_st(zt, 0, f0);
-        f256_st(zt, 1, g0);
-        f256_st(zt, 2, fr_mul(f0, g0));
-        if (m) f256_st(zt, 2 + (long long)M, fr_mul(f256_ld<fr>(a, m), f256_ld<fr>(b, m)));   // m = 0: z ends at h(0)
-    }
-}
-
-// the same sums with f and g kept apart and nothing multiplied: f_out[0] = f(0), f_out[1 + o] = f(m + 2 + o) for
-// o < n_out, g alike (the shares of a secret-shared witness: a product of shares is not local, csrc/mpc_share.hip)
-__global__ void __launch_bounds__(CS_WG)
-k_cs_finish_fg(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restrict__ part_f,
-               const uint32_t *__restrict__ part_g, const uint32_t *__restrict__ s0, const uint32_t *__restrict__ fact,
-               const uint32_t *__restrict__ ifact, uint32_t *__restrict__ f_out, uint32_t *__restrict__ g_out) {
-    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t M = m + 1;
-    if (o < n_out) {
-        const fr sf = fr_partsum<fr>(part_f, n_out, n_seg, o), sg = fr_partsum<fr>(part_g, n_out, n_seg, o);
-        const uint32_t x = m + 2 + o;
-        const fr lx = fr_mul(f256_ld<fr>(fact, x - 1), f256_ld<fr>(ifact, x - M - 1));
-        f256_st(f_out, 1 + (long long)o, fr_mul(lx, sf));
-        f256_st(g_out, 1 + (long long)o, fr_mul(lx, sg));
-    } else if (o == n_out) {
-        fr l0 = f256_ld<fr>(fact, M);
-        if (!(M & 1u)) l0 = fr_neg(l0);
-        f256_st(f_out, 0, fr_mul(l0, f256_ld<fr>(s0, 0)));
-        f256_st(g_out, 0, fr_mul(l0, f256_ld<fr>(s0, 1)));
-    }
-}
-
-// z_tail: k_cs_finish writes f(0), g(0) and the products; otherwise k_cs_finish_fg writes f_out, g_out
-static int cs_extend(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact, const void *ifact,
-                     void *z_tail, void *f_out, void *g_out) {
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    const long long M = (long long)m + 1, n_t = 2 * (long long)m + 2;
-    const long long n_out = m >= 2 ? (long long)m - 1 : 0, k_lo = (long long)m + 1;
-    const unsigned tiles = (unsigned)((n_out + FR_CONV_TILE - 1) / FR_CONV_TILE);
-    long long seg = CS_MIN_SEG;
-    while ((long long)tiles * ((M + seg - 1) / seg) > CS_TARGET_WGS && seg < M) seg *= 2;
-    const unsigned n_seg = (unsigned)((M + seg - 1) / seg);
-    const size_t part_b = vmpc_align((size_t)n_seg * (size_t)(n_out ? n_out : 1) * 32);
-    VMPC_CHECK(vmpc_ws_reserve(ctx, 2 * vmpc_align((size_t)M * 32) + vmpc_align((size_t)n_t * 32) + 2 * part_b + 2048));
-    uint32_t *uf = (uint32_t *)vmpc_ws_take(ctx, (size_t)M * 32);
-    uint32_t *ug = (uint32_t *)vmpc_ws_take(ctx, (size_t)M * 32);
-    uint32_t *T = (uint32_t *)vmpc_ws_take(ctx, (size_t)n_t * 32);
-    uint32_t *pf = (uint32_t *)vmpc_ws_take(ctx, part_b);
-    uint32_t *pg = (uint32_t *)vmpc_ws_take(ctx, part_b);
-    uint32_t *s0 = (uint32_t *)vmpc_ws_take(ctx, 64);
-    {
-        vmpc_stage_scope sc(ctx, "cs_extend_prep");
-        k_cs_prep<<<(unsigned)((n_t + CS_WG - 1) / CS_WG), CS_WG, 0, ctx->stream>>>(
-            (uint32_t)M, (uint32_t)n_t, (const uint32_t *)a, (const uint32_t *)b, (const uint32_t *)fact,
-            (const uint32_t *)ifact, uf, ug, T);
-        VMPC_KERNEL_CHECK();
-        k_cs_dot0<<<1, CS_WG, 0, ctx->stream>>>((uint32_t)M, uf, ug, T, s0);
-        VMPC_KERNEL_CHECK();
-    }
-    if (n_out) {
-        vmpc_stage_scope sc(ctx, "cs_extend_corr");
-        k_cs_corr<<<dim3(tiles, n_seg), FR_CONV_TILE, 0, ctx->stream>>>(uf, ug, M, T, n_t, k_lo, n_out, seg, pf, pg);
-        VMPC_KERNEL_CHECK();
-    }
-    {
-        vmpc_stage_scope sc(ctx, "cs_extend_finish");
-        const unsigned grid = (unsigned)((n_out + 1 + CS_WG - 1) / CS_WG);
-        if (z_tail)
-            k_cs_finish<<<grid, CS_WG, 0, ctx->stream>>>((uint32_t)m, (uint32_t)n_out, n_seg, pf, pg, s0, (const uint32_t *)a,
-                                                         (const uint32_t *)b, (const uint32_t *)fact,
-                                                         (const uint32_t *)ifact, (uint32_t *)z_tail);
-        else
-            k_cs_finish_fg<<<grid, CS_WG, 0, ctx->stream>>>((uint32_t)m, (uint32_t)n_out, n_seg, pf, pg, s0,
-                                                            (const uint32_t *)fact, (const uint32_t *)ifact,
-                                                            (uint32_t *)f_out, (uint32_t *)g_out);
-        VMPC_KERNEL_CHECK();
-    }
-    return VMPC_OK;
-}
-
-extern "C" int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
-                                     const void *ifact, void *z_tail) {
-    if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
-    if (!ctx || !a || !b || !fact || !ifact || !z_tail) return VMPC_E_INVAL;
-    return cs_extend(ctx, a, b, m, fact, ifact, z_tail, nullptr, nullptr);
-}
-
-extern "C" int vmpc_fr_cs_extend_fg_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
-                                        const void *ifact, void *f_out, void *g_out) {
-    if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
-    if (!ctx || !a || !b || !fact || !ifact || !f_out || !g_out) return VMPC_E_INVAL;
-    return cs_extend(ctx, a, b, m, fact, ifact, nullptr, f_out, g_out);
-}
-
-// ---- the extension for K witnesses of one circuit ----------------------------------------------------------------------
-// Witness w reads rows w of a, b (ab_stride scalars apart) and writes row w of the z tails (z_stride apart); uf, ug, s0
-// and the partial sums are K rows of the workspace, T and the weights are the circuit's and computed once.
-__global__ void __launch_bounds__(CS_WG)
-k_cs_prep_batch(uint32_t M, uint32_t n_t, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, size_t ab_stride,
-                const uint32_t *__restrict__ fact, const uint32_t *__restrict__ ifact, uint32_t *__restrict__ uf,
-                uint32_t *__restrict__ ug, uint32_t *__restrict__ T) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const size_t w = blockIdx.y;
     if (i < M) {
@@ -430,10 +246,11 @@ k_cs_prep_batch(uint32_t M, uint32_t n_t, const uint32_t *__restrict__ a, const 
     if (w == 0 && i < n_t) f256_st(T, i, i ? fr_mul(f256_ld<fr>(fact, i - 1), f256_ld<fr>(ifact, i)) : fr_zero());
 }
 
-// one workgroup per witness: s0[2 w], s0[2 w + 1] as k_cs_dot0 (the same lanes, the same order)
+// one workgroup per witness: s0[2 w] = sum_i uf[i] T[i+1], s0[2 w + 1] = the same for ug (lane t takes i = t, t + 256,
+// ..; the lanes' sums are added in lane order)
 __global__ void __launch_bounds__(CS_WG)
-k_cs_dot0_batch(uint32_t M, const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, const uint32_t *__restrict__ T,
-                uint32_t *__restrict__ s0) {
+k_cs_dot0(uint32_t M, const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, const uint32_t *__restrict__ T,
+          uint32_t *__restrict__ s0) {
     __shared__ fr part[2][CS_WG];
     const uint32_t t = threadIdx.x;
     const size_t w = blockIdx.x;
@@ -455,12 +272,12 @@ k_cs_dot0_batch(uint32_t M, const uint32_t *__restrict__ uf, const uint32_t *__r
     }
 }
 
-// grid (tiles, segments, witnesses): k_cs_corr's tile on witness blockIdx.z's uf, ug; its partial sums are rows
-// (w n_seg + s) of part_f, part_g
+// grid (tiles, segments, witnesses).  Row (w n_seg + s) of part_f: part_f[row n_out + o] = sum over segment s's i of
+// uf_w[i] T[k_lo + o - i], o < n_out; part_g alike.
 __global__ void __launch_bounds__(FR_CONV_TILE)
-k_cs_corr_batch(const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, long long M, const uint32_t *__restrict__ T,
-                long long n_t, long long k_lo, long long n_out, long long seg, uint32_t *__restrict__ part_f,
-                uint32_t *__restrict__ part_g) {
+k_cs_corr(const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug, long long M, const uint32_t *__restrict__ T,
+          long long n_t, long long k_lo, long long n_out, long long seg, uint32_t *__restrict__ part_f,
+          uint32_t *__restrict__ part_g) {
     __shared__ uint32_t sU[2][FR_CONV_CHUNK * 8];
     __shared__ uint32_t sT[8 * FR_CONV_BROW];
     const long long o0 = (long long)blockIdx.x * FR_CONV_TILE, k0 = k_lo + o0;
@@ -478,12 +295,13 @@ k_cs_corr_batch(const uint32_t *__restrict__ uf, const uint32_t *__restrict__ ug
     }
 }
 
-// grid (outputs, witnesses): k_cs_finish on witness blockIdx.y's partial sums, s0, row values and z tail
+// grid (outputs, witnesses).  zt = z + n of witness w: zt[0] = f(0), zt[1] = g(0), zt[2] = h(0), zt[2 + x] = h(x).
+// Lane o < n_out: x = m + 2 + o; lane n_out: x = 0 and h(m + 1) = r_a r_b.
 __global__ void __launch_bounds__(CS_WG)
-k_cs_finish_batch(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restrict__ part_f,
-                  const uint32_t *__restrict__ part_g, const uint32_t *__restrict__ s0, const uint32_t *__restrict__ a,
-                  const uint32_t *__restrict__ b, size_t ab_stride, const uint32_t *__restrict__ fact,
-                  const uint32_t *__restrict__ ifact, uint32_t *__restrict__ zt, size_t z_stride) {
+k_cs_finish(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restrict__ part_f,
+            const uint32_t *__restrict__ part_g, const uint32_t *__restrict__ s0, const uint32_t *__restrict__ a,
+            const uint32_t *__restrict__ b, size_t ab_stride, const uint32_t *__restrict__ fact,
+            const uint32_t *__restrict__ ifact, uint32_t *__restrict__ zt, size_t z_stride) {
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t M = m + 1;
     const size_t w = blockIdx.y;
@@ -495,19 +313,44 @@ k_cs_finish_batch(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__
         const fr lx = fr_mul(f256_ld<fr>(fact, x - 1), f256_ld<fr>(ifact, x - M - 1));
         f256_st(zt, 2 + (long long)x, fr_mul(fr_mul(lx, sf), fr_mul(lx, sg)));
     } else if (o == n_out) {
+        // l(0) = (-1)^M M!, 1 / (0 - j) = -T[j]: f(0) = (-1)^(M+1) M! s0
         fr l0 = f256_ld<fr>(fact, M);
         if (!(M & 1u)) l0 = fr_neg(l0);
         const fr f0 = fr_mul(l0, f256_ld<fr>(s0, (long long)(2 * w))), g0 = fr_mul(l0, f256_ld<fr>(s0, (long long)(2 * w + 1)));
         f256_st(zt, 0, f0);
         f256_st(zt, 1, g0);
         f256_st(zt, 2, fr_mul(f0, g0));
+        // m = 0: z ends at h(0)
         if (m) f256_st(zt, 2 + (long long)M, fr_mul(f256_ld<fr>(a + w * ab_stride * 8, m), f256_ld<fr>(b + w * ab_stride * 8, m)));
     }
 }
 
-// The segment length with the witnesses counted: tiles x segments x K workgroups against CS_TARGET_WGS.  K = 1 is
-// cs_extend's choice; a large batch ends at one segment per witness, so the partial sums never exceed K n_out scalars
-// per polynomial beyond what the grid needs.
+// the same sums of ONE witness with f and g kept apart and nothing multiplied: f_out[0] = f(0), f_out[1 + o] =
+// f(m + 2 + o) for o < n_out, g alike (the shares of a secret-shared witness: a product of shares is not local,
+// csrc/mpc_share.hip)
+__global__ void __launch_bounds__(CS_WG)
+k_cs_finish_fg(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__restrict__ part_f,
+               const uint32_t *__restrict__ part_g, const uint32_t *__restrict__ s0, const uint32_t *__restrict__ fact,
+               const uint32_t *__restrict__ ifact, uint32_t *__restrict__ f_out, uint32_t *__restrict__ g_out) {
+    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t M = m + 1;
+    if (o < n_out) {
+        const fr sf = fr_partsum<fr>(part_f, n_out, n_seg, o), sg = fr_partsum<fr>(part_g, n_out, n_seg, o);
+        const uint32_t x = m + 2 + o;
+        const fr lx = fr_mul(f256_ld<fr>(fact, x - 1), f256_ld<fr>(ifact, x - M - 1));
+        f256_st(f_out, 1 + (long long)o, fr_mul(lx, sf));
+        f256_st(g_out, 1 + (long long)o, fr_mul(lx, sg));
+    } else if (o == n_out) {
+        fr l0 = f256_ld<fr>(fact, M);
+        if (!(M & 1u)) l0 = fr_neg(l0);
+        f256_st(f_out, 0, fr_mul(l0, f256_ld<fr>(s0, 0)));
+        f256_st(g_out, 0, fr_mul(l0, f256_ld<fr>(s0, 1)));
+    }
+}
+
+// The segment length with the witnesses counted: tiles x segments x K workgroups against CS_TARGET_WGS.  A large batch
+// ends at one segment per witness, so the partial sums never exceed K n_out scalars per polynomial beyond what the grid
+// needs.
 struct cs_batch_plan {
     long long seg;
     unsigned tiles, n_seg;
@@ -527,19 +370,10 @@ static cs_batch_plan cs_extend_batch_plan(size_t m, size_t n_wit) {
     return p;
 }
 
-extern "C" size_t vmpc_fr_cs_extend_batch_bytes(size_t m, size_t n_wit) {
-    if (m > VMPC_FR_CS_MAX_M || n_wit > VMPC_FR_CS_MAX_WIT || n_wit == 0) return 0;
-    return cs_extend_batch_plan(m, n_wit).total_b;
-}
-
-extern "C" int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m,
-                                           const void *fact, const void *ifact, void *z_tail, size_t z_stride,
-                                           size_t n_wit) {
-    if (m > VMPC_FR_CS_MAX_M || n_wit > VMPC_FR_CS_MAX_WIT || ab_stride > ((size_t)1 << 31) ||
-        z_stride > ((size_t)1 << 31) || (n_wit && (ab_stride < m + 1 || z_stride < 2 * m + 3)))
-        return VMPC_E_RANGE;
-    if (!ctx || !a || !b || !fact || !ifact || !z_tail) return VMPC_E_INVAL;
-    if (n_wit == 0) return VMPC_OK;
+// n_wit >= 1 witnesses, checked by the entries.  z_tail: k_cs_finish writes f(0), g(0) and the products of every
+// witness; otherwise (one witness) k_cs_finish_fg writes f_out, g_out.
+static int cs_extend(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m, const void *fact,
+                     const void *ifact, void *z_tail, size_t z_stride, void *f_out, void *g_out, size_t n_wit) {
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const long long M = (long long)m + 1, n_t = 2 * (long long)m + 2;
     const long long n_out = m >= 2 ? (long long)m - 1 : 0, k_lo = (long long)m + 1;
@@ -553,28 +387,63 @@ extern "C" int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const v
     uint32_t *s0 = (uint32_t *)vmpc_ws_take(ctx, n_wit * 64);
     const unsigned K = (unsigned)n_wit;
     {
-        vmpc_stage_scope sc(ctx, "cs_extend_batch_prep");
-        k_cs_prep_batch<<<dim3((unsigned)((n_t + CS_WG - 1) / CS_WG), K), CS_WG, 0, ctx->stream>>>(
+        vmpc_stage_scope sc(ctx, "cs_extend_prep");
+        k_cs_prep<<<dim3((unsigned)((n_t + CS_WG - 1) / CS_WG), K), CS_WG, 0, ctx->stream>>>(
             (uint32_t)M, (uint32_t)n_t, (const uint32_t *)a, (const uint32_t *)b, ab_stride, (const uint32_t *)fact,
             (const uint32_t *)ifact, uf, ug, T);
         VMPC_KERNEL_CHECK();
-        k_cs_dot0_batch<<<K, CS_WG, 0, ctx->stream>>>((uint32_t)M, uf, ug, T, s0);
+        k_cs_dot0<<<K, CS_WG, 0, ctx->stream>>>((uint32_t)M, uf, ug, T, s0);
         VMPC_KERNEL_CHECK();
     }
     if (n_out) {
-        vmpc_stage_scope sc(ctx, "cs_extend_batch_corr");
-        k_cs_corr_batch<<<dim3(p.tiles, p.n_seg, K), FR_CONV_TILE, 0, ctx->stream>>>(uf, ug, M, T, n_t, k_lo, n_out, p.seg, pf,
-                                                                                   pg);
+        vmpc_stage_scope sc(ctx, "cs_extend_corr");
+        k_cs_corr<<<dim3(p.tiles, p.n_seg, K), FR_CONV_TILE, 0, ctx->stream>>>(uf, ug, M, T, n_t, k_lo, n_out, p.seg, pf, pg);
         VMPC_KERNEL_CHECK();
     }
     {
-        vmpc_stage_scope sc(ctx, "cs_extend_batch_finish");
-        k_cs_finish_batch<<<dim3((unsigned)((n_out + 1 + CS_WG - 1) / CS_WG), K), CS_WG, 0, ctx->stream>>>(
-            (uint32_t)m, (uint32_t)n_out, p.n_seg, pf, pg, s0, (const uint32_t *)a, (const uint32_t *)b, ab_stride,
-            (const uint32_t *)fact, (const uint32_t *)ifact, (uint32_t *)z_tail, z_stride);
+        vmpc_stage_scope sc(ctx, "cs_extend_finish");
+        const unsigned grid = (unsigned)((n_out + 1 + CS_WG - 1) / CS_WG);
+        if (z_tail)
+            k_cs_finish<<<dim3(grid, K), CS_WG, 0, ctx->stream>>>(
+                (uint32_t)m, (uint32_t)n_out, p.n_seg, pf, pg, s0, (const uint32_t *)a, (const uint32_t *)b, ab_stride,
+                (const uint32_t *)fact, (const uint32_t *)ifact, (uint32_t *)z_tail, z_stride);
+        else
+            k_cs_finish_fg<<<grid, CS_WG, 0, ctx->stream>>>((uint32_t)m, (uint32_t)n_out, p.n_seg, pf, pg, s0,
+                                                            (const uint32_t *)fact, (const uint32_t *)ifact,
+                                                            (uint32_t *)f_out, (uint32_t *)g_out);
         VMPC_KERNEL_CHECK();
     }
     return VMPC_OK;
+}
+
+extern "C" int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
+                                     const void *ifact, void *z_tail) {
+    if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !fact || !ifact || !z_tail) return VMPC_E_INVAL;
+    return cs_extend(ctx, a, b, 0, m, fact, ifact, z_tail, 0, nullptr, nullptr, 1);
+}
+
+extern "C" int vmpc_fr_cs_extend_fg_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
+                                        const void *ifact, void *f_out, void *g_out) {
+    if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !fact || !ifact || !f_out || !g_out) return VMPC_E_INVAL;
+    return cs_extend(ctx, a, b, 0, m, fact, ifact, nullptr, 0, f_out, g_out, 1);
+}
+
+extern "C" size_t vmpc_fr_cs_extend_batch_bytes(size_t m, size_t n_wit) {
+    if (m > VMPC_FR_CS_MAX_M || n_wit > VMPC_FR_CS_MAX_WIT || n_wit == 0) return 0;
+    return cs_extend_batch_plan(m, n_wit).total_b;
+}
+
+extern "C" int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m,
+                                           const void *fact, const void *ifact, void *z_tail, size_t z_stride,
+                                           size_t n_wit) {
+    if (m > VMPC_FR_CS_MAX_M || n_wit > VMPC_FR_CS_MAX_WIT || ab_stride > ((size_t)1 << 31) ||
+        z_stride > ((size_t)1 << 31) || (n_wit && (ab_stride < m + 1 || z_stride < 2 * m + 3)))
+        return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !fact || !ifact || !z_tail) return VMPC_E_INVAL;
+    if (n_wit == 0) return VMPC_OK;
+    return cs_extend(ctx, a, b, ab_stride, m, fact, ifact, z_tail, z_stride, nullptr, nullptr, n_wit);
 }
 
 // ---- transposed sparse mat-vec -----------------------------------------------------------------------------------------

@@ -1316,19 +1316,27 @@ def _upload_row_values(ctx, qap, c, who):
     return aby, (dc,) + tuple(keep)
 
 
-def _h_from_row_values(ctx, qap, aby, keep, dd):
-    """row values -> weights -> moments -> combination; dd: device buffer of the three deltas or
-    None.  Nothing here asks whether the rows satisfy a_j b_j = y_j: the result is the polynomial part of V W / t."""
-    d = int(qap.d)
-    a_ptr, b_ptr = aby.ptr, aby.ptr + 32 * d
-    t = _t_coeffs(ctx, qap)
-    u = ctx.alloc(32 * 2 * d)
-    ctx.bn256_qap_h_weights(a_ptr, b_ptr, d, u.ptr, u.ptr + 32 * d)
-    mom = ctx.alloc(32 * 2 * d)
-    ctx.bn256_qap_moments(u.ptr, u.ptr + 32 * d, d, d, mom.ptr, mom.ptr + 32 * d)
-    scratch, out = ctx.alloc(32 * 5 * d), ctx.alloc(32 * (d + 1))
-    ctx.bn256_qap_h_combine(mom.ptr, mom.ptr + 32 * d, t.ptr, d, dd.ptr if dd else None, scratch.ptr, out.ptr)
+def _h_rows(ctx, d, t, aby_ptr, n, dd, out_ptr, out_stride):
+    """weights -> moments -> combination for n rows a || b || y, 3 d scalars apart, at aby_ptr ->
+    n rows of h at out_ptr; dd: device buffer of the rows' three deltas each, or None.  Ends with the stream drained,
+    so the caller may release what the rows were made from."""
+    u = ctx.alloc(32 * 2 * d * n)                # rows ua || ub, stride 2 d; the moments alike
+    ctx.bn256_qap_h_weights_batch(aby_ptr, aby_ptr + 32 * d, 3 * d, d, u.ptr, u.ptr + 32 * d, 2 * d, n)
+    mom = ctx.alloc(32 * 2 * d * n)
+    ctx.bn256_qap_moments_batch(u.ptr, u.ptr + 32 * d, 2 * d, d, d, mom.ptr, mom.ptr + 32 * d, 2 * d, n)
+    scratch = ctx.alloc(32 * 3 * d * n)
+    ctx.bn256_qap_h_combine_batch(mom.ptr, mom.ptr + 32 * d, 2 * d, t.ptr, d, dd.ptr if dd else None, scratch.ptr,
+                                  out_ptr, out_stride, n)
     ctx.sync()      # the temporaries above may be released once the stream has drained
+
+
+def _h_from_row_values(ctx, qap, aby, keep, dd):
+    """one witness's row values -> h; dd: device buffer of the three deltas or None.  Nothing here asks whether the
+    rows satisfy a_j b_j = y_j: the result is the polynomial part of V W / t."""
+    d = int(qap.d)
+    t = _t_coeffs(ctx, qap)
+    out = ctx.alloc(32 * (d + 1))
+    _h_rows(ctx, d, t, aby.ptr, 1, dd, out.ptr, d + 1)
     del keep
     return HPoly(ctx, out, d + 1 if dd is not None else max(d - 1, 0))
 
@@ -1490,12 +1498,5 @@ def _h_batch_chunk(ctx, qap, arr, deltas, first, plan, top, t, out_ptr, out_stri
     dd = None
     if deltas is not None:
         dd = _scalar_buf(ctx, [getattr(dl, name) for dl in deltas for name in _DELTAS])
-    u = ctx.alloc(32 * 2 * d * n)                # rows ua || ub, stride 2 d; the moments alike
-    ctx.bn256_qap_h_weights_batch(aby.ptr, aby.ptr + 32 * d, 3 * d, d, u.ptr, u.ptr + 32 * d, 2 * d, n)
-    mom = ctx.alloc(32 * 2 * d * n)
-    ctx.bn256_qap_moments_batch(u.ptr, u.ptr + 32 * d, 2 * d, d, d, mom.ptr, mom.ptr + 32 * d, 2 * d, n)
-    scratch = ctx.alloc(32 * 3 * d * n)
-    ctx.bn256_qap_h_combine_batch(mom.ptr, mom.ptr + 32 * d, 2 * d, t.ptr, d, dd.ptr if dd else None, scratch.ptr,
-                                  out_ptr, out_stride, n)
-    ctx.sync()      # the temporaries above may be released once the stream has drained
-    del dc, aby, coef, bad, dd, u, mom, scratch
+    _h_rows(ctx, d, t, aby.ptr, n, dd, out_ptr, out_stride)
+    del dc, aby, coef, bad, dd
