@@ -557,6 +557,42 @@ int vmpc_bn256_qap_h_combine_batch_dev(vmpc_ctx *ctx, const void *A, const void 
                                        size_t d, const void *deltas, void *scratch, void *out, size_t out_stride,
                                        size_t n_wit);
 
+/* ---- Pinocchio witnesses from the R1CS (the reference's QAP.calculate_witness / code_to_r1cs.assign_variables walk flat
+ * code), scalars mod n ----
+ * n_wit witnesses of ONE "program-shaped" R1CS from their inputs.  The plan (pynocchio.SolvePlan, all arrays in DEVICE
+ * memory except level_ptr) lists the d rows in LEVEL order - the rows of level k are level_ptr[k] .. level_ptr[k+1]-1
+ * and read only wires that the inputs or earlier levels define: one CSR per matrix (row_ptr of d + 1 words, col, 32-byte
+ * canonical vals; the new wire's own entry left out), and per row its kind (0: a check row, a b = y; 1: the new wire
+ * stands in Y, c_s = (a b - y) inv; 2: in V, c_s = (y / b - a) inv; 3: in W, c_s = (y / a - b) inv), the new wire
+ * (0xffffffff for a check row) and inv, the inverse of the new wire's coefficient (32 bytes).  level_ptr_dev is the
+ * device copy of level_ptr (n_levels + 1 words), which the call reads on the HOST to plan its launches.
+ * c: n_wit rows of m + 1 slots, c_stride scalars apart; the caller has put the inputs into slots 1..n_in (any 32-byte
+ * values).  On return slot 0 is 1 and every slot 0..m a canonical residue, the inputs' included; nothing beyond slot m
+ * of a row is written.  first_bad (n_wit device words, all set to 0xffffffff by the call): the smallest level-order
+ * position of a row of the witness that FAILED - a zero divisor (kinds 2, 3) or a check row with a b != y; that row is
+ * the root cause, everything before it was sound.  A failed row faults nothing: it stores 0 or nothing, the call
+ * completes and the witness's later slots are unspecified.  An integer minimum on that word is the only atomic; field
+ * values never go through one and the result does not depend on scheduling.
+ * Launches: a level of at least wide_rows rows gets a launch of its own (rows on x, witnesses on y); a maximal run of
+ * consecutive narrower levels is ONE launch (a workgroup per witness walks the levels, a workgroup barrier between
+ * them; nothing is synchronised between workgroups).  The call's first launch also prepares slot 0 and the inputs and
+ * therefore always has the run's shape, a wide level 0 included.  wide_rows = 0: the library's rule (257 rows,
+ * whatever n_wit: a level that a run's 256 lanes cannot take in one step); 1: one launch per level; SIZE_MAX: one launch.  The bits of the result are the same for every
+ * wide_rows.  n_wit > VMPC_BN256_R1CS_MAX_WIT, c_stride < m + 1 or > 2^31, n_in > m: VMPC_E_RANGE before any pointer is
+ * looked at; n_wit = 0 or n_levels = 0: VMPC_OK, no launch.  Runs on the context's stream, synchronises nothing.  No
+ * arena. */
+#define VMPC_BN256_R1CS_MAX_WIT ((size_t)65535)
+int vmpc_bn256_r1cs_solve_batch_dev(vmpc_ctx *ctx, const uint32_t *v_row_ptr, const uint32_t *v_col, const void *v_vals,
+                                    const uint32_t *w_row_ptr, const uint32_t *w_col, const void *w_vals,
+                                    const uint32_t *y_row_ptr, const uint32_t *y_col, const void *y_vals,
+                                    const uint32_t *kind, const uint32_t *wire, const void *inv,
+                                    const uint32_t *level_ptr_dev, const uint32_t *level_ptr /* HOST */, size_t n_levels,
+                                    size_t n_in, size_t m, void *c, size_t c_stride, size_t n_wit, size_t wide_rows,
+                                    uint32_t *first_bad);
+/* the number of kernel launches that call makes (host arithmetic on the level table, by the function the call itself
+ * schedules with; 0 where it launches nothing) */
+size_t vmpc_bn256_r1cs_solve_launches(const uint32_t *level_ptr, size_t n_levels, size_t n_wit, size_t wide_rows);
+
 /* ---- Protocol 8 from a sparse circuit (verifiable_mpc/ac20/circuit_sat_cb.py:59-252), scalars mod l as above ------
  * m multiplication gates, M = m + 1, z = (x, f(0), g(0), h(0), h(1), .., h(2m)); f runs through (j, a_j) for j = 1..m
  * and (m + 1, r_a), g alike (circuit_sat_r1cs.py:380-388).  m <= VMPC_FR_CS_MAX_M: above it the entries answer

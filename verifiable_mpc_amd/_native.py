@@ -58,6 +58,7 @@ SYMBOLS = [
     "vmpc_fr_cs_extend_fg_dev", "vmpc_fr_share_mul_deal_dev", "vmpc_fr_share_combine_dev",
     "vmpc_bn256_fr_share_mul_deal_dev", "vmpc_bn256_fr_share_combine_dev", "vmpc_bn256_qap_residual_dev",
     "vmpc_fr_cs_triples_batch_dev", "vmpc_fr_cs_extend_batch_dev", "vmpc_fr_cs_extend_batch_bytes",
+    "vmpc_bn256_r1cs_solve_batch_dev", "vmpc_bn256_r1cs_solve_launches",
 ]
 
 
@@ -199,6 +200,8 @@ def load_library():
         "vmpc_fr_cs_extend_batch_dev": (i32, [vp, vp, vp, sz, sz, vp, vp, vp, sz, sz]),
         "vmpc_fr_cs_extend_batch_bytes": (sz, [sz, sz]),
         "vmpc_fr_cs_extend_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
+        "vmpc_bn256_r1cs_solve_batch_dev": (i32, [vp] * 15 + [sz, sz, sz, vp, sz, sz, sz, vp]),
+        "vmpc_bn256_r1cs_solve_launches": (sz, [vp, sz, sz, sz]),
         "vmpc_fr_cs_extend_fg_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
         "vmpc_fr_share_mul_deal_dev": (i32, [vp, vp, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_fr_share_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
@@ -1152,6 +1155,16 @@ class Context:
                                                          k_lo, k_cnt, p(out_ptr), out_stride, n_wit),
                "vmpc_bn256_fr_poly_mul_batch_dev")
 
+    def bn256_r1cs_solve_batch(self, plan_ptrs, level_ptr, n_in, m, c_ptr, c_stride, n_wit, wide_rows, first_bad_ptr):
+        """n_wit witnesses of one R1CS from their inputs (include/vmpc.h).  plan_ptrs: the 13 device addresses V, W, Y
+        (row_ptr, col, vals each), kind, wire, inv, level table; level_ptr: the level table as a host uint32 array"""
+        p = ctypes.c_void_p
+        lp = np.ascontiguousarray(level_ptr, dtype=np.uint32)
+        assert len(plan_ptrs) == 13
+        _check(self.lib.vmpc_bn256_r1cs_solve_batch_dev(self.handle, *[p(x) for x in plan_ptrs], _np_ptr(lp), len(lp) - 1,
+                                                        n_in, m, p(c_ptr), c_stride, n_wit, wide_rows, p(first_bad_ptr)),
+               "vmpc_bn256_r1cs_solve_batch_dev")
+
     def bn256_validate(self, group, points_ptr, n):
         bad = ctypes.c_uint64()
         _check(self.lib.vmpc_bn256_validate_dev(self.handle, group, ctypes.c_void_p(points_ptr), n,
@@ -1492,6 +1505,14 @@ def bn256_msm(group, scalars, points):
 
 BN256_FR_POLY_MAX = 1 << 20      # VMPC_BN256_FR_POLY_MAX of include/vmpc.h
 BN256_QAP_MAX_WIT = 65535        # VMPC_BN256_QAP_MAX_WIT
+BN256_R1CS_MAX_WIT = 65535       # VMPC_BN256_R1CS_MAX_WIT
+R1CS_WIDE_ALL = ctypes.c_size_t(-1).value      # wide_rows = SIZE_MAX: every level in one launch
+
+
+def bn256_r1cs_solve_launches(level_ptr, n_wit, wide_rows=0):
+    """the kernel launches Context.bn256_r1cs_solve_batch makes for this level table (host arithmetic: no GPU)"""
+    lp = np.ascontiguousarray(level_ptr, dtype=np.uint32)
+    return int(load_library().vmpc_bn256_r1cs_solve_launches(_np_ptr(lp), len(lp) - 1, n_wit, wide_rows))
 
 
 def bn256_qap_moments_batch_bytes(d, n_out, n_wit):

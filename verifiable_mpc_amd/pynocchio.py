@@ -9,7 +9,8 @@ zero-knowledge case, adds `delta * evalkey[<t term>]`.  Here every element is ON
 (csrc/bn256.hip) with the zero-knowledge terms appended as extra (scalar, point) pairs.
 Keys and proofs hold `BN256Point` / `BN256TwistPoint` objects (affine coordinates); foreign
 points (e.g. MPyC's Jacobian elements) are accepted if they expose `.normalize()` and three
-indexable coordinates.  QAP construction from code stays with the reference (out of scope).
+indexable coordinates.  QAP construction from code stays with the reference (out of scope, SURVEY.md 2 rows 10, 13);
+the witness of a sparse R1CS is computed here (calculate_witness below).
 
     compute_h        verifiable_mpc/trinocchio/pynocchio.py:203-225 (compute_p_poly, p / qap.t, compute_h_zk_terms)
 
@@ -23,6 +24,12 @@ coefficients with the low half of the two series' product.  The result stays on 
 K witnesses of ONE QAP: exactly the results of K compute_h / compute_proof calls, with every stage of h run once for all
 K - the witness on the grid, the launch plans chosen with K counted - and the K proofs' uploads, synchronisations,
 downloads and inversions shared.  What verify_batch takes.
+
+    calculate_witness, calculate_witness_batch, prove_batch_inputs, SolvePlan    (tools/code_to_qap.py QAP.calculate_witness)
+
+The witness from the inputs, for one input vector or K of them in one call: a host plan orders the rows of an R1CSQAP by
+depth level from the matrices alone, and csrc/bn256_r1cs_solve.hip solves level by level on the device - runs of narrow
+levels inside one launch, wide levels in launches of their own.
 
     Trapdoor, SampleDeltas, Generators        verifiable_mpc/trinocchio/pynocchio.py:36-69 (draws from `prng`)
     generate_evalkey, generate_verikey        verifiable_mpc/trinocchio/pynocchio.py:101-200
@@ -1500,3 +1507,218 @@ def _h_batch_chunk(ctx, qap, arr, deltas, first, plan, top, t, out_ptr, out_stri
         dd = _scalar_buf(ctx, [getattr(dl, name) for dl in deltas for name in _DELTAS])
     _h_rows(ctx, d, t, aby.ptr, n, dd, out_ptr, out_stride)
     del dc, aby, coef, bad, dd
+
+
+# ---- the witness from the inputs (code_to_qap.QAP.calculate_witness; csrc/bn256_r1cs_solve.hip) ----
+
+KIND_CHECK, KIND_Y, KIND_A, KIND_B = 0, 1, 2, 3
+_NO_WIRE = 0xFFFFFFFF
+
+
+class SolvePlan:
+    """How to compute every wire of a "program-shaped" R1CS from wire 0 (the constant 1) and the inputs, wires
+    1 .. n_in: SolvePlan(qap, n_in), made once per (R1CSQAP, n_in) and kept on the QAP.  Pure host work on the constraint
+    matrices alone - no device, no flat code.
+
+    Rounds: a round visits the rows not yet placed in ascending row index.  A row whose support (V, W and Y together,
+    duplicate entries added first, entries that are 0 mod the order ignored) has no unknown wire is a CHECK row of the
+    round; a row with exactly one unknown wire s that no earlier row of the round defines DEFINES s; any other row waits.
+    The wires a round defines are known after it.  A round is one LEVEL: the depth is minimal and the order
+    deterministic.  The new wire must stand in exactly one of V, W, Y of its defining row, which gives the row's kind,
+    with a, b, y the row's dot products over the known wires:
+        KIND_Y   c_s = (a b - y) / gamma      every +, - and * row of the reference's flattener
+        KIND_A   c_s = (y / b - a) / alpha    its `set` rows (b = wire 0, Y empty) and `/` rows (b the divisor)
+        KIND_B   c_s = (y / a - b) / beta
+    ValueError (1-based constraint numbers): a new wire in two of V, W, Y of its defining row; rows left with two or
+    more unknown wires (the lowest is named); a wire that no row defines and that is no input (the lowest); n_in > m.
+
+    level_ptr (n_levels + 1), and per row in level order: row (the original 0-based row), kind, wire (the new wire,
+    0xffffffff for a check row), inv (ints: the inverse of the new wire's coefficient, 0 for a check row); csr: per
+    matrix "V", "W", "Y" (row_ptr, col, vals as ints) in that order with the new wire's own entry removed."""
+
+    def __new__(cls, qap, n_in):
+        if not isinstance(qap, R1CSQAP):
+            raise TypeError("SolvePlan needs the sparse R1CS, not interpolated polynomials: build the QAP as "
+                            "R1CSQAP(V, W, Y, out_ix)")
+        n_in = int(n_in)
+        cache = qap.__dict__.setdefault("_solve_plans", {})
+        if n_in not in cache:
+            plan = object.__new__(cls)
+            plan._build(qap, n_in)
+            cache[n_in] = plan
+        return cache[n_in]
+
+    def _build(self, qap, n_in):
+        m, d, n_wires = qap.m, qap.d, qap.m + 1
+        if not 0 <= n_in <= m:
+            raise ValueError(f"SolvePlan: n_in = {n_in} inputs, the QAP has m = {m} wires beside the constant")
+        # rows[j] = [{wire: coefficient} for V, W, Y], duplicates added, zeros dropped
+        raw = qap._vals.tobytes()
+        rows = [[{}, {}, {}] for _ in range(d)]
+        for e, (j, col) in enumerate(zip(qap._rows.tolist(), qap._cols.tolist())):
+            mat = rows[j][col // n_wires]
+            wire = col % n_wires
+            mat[wire] = mat.get(wire, 0) + int.from_bytes(raw[32 * e:32 * e + 32], "little")
+        users = [[] for _ in range(n_wires)]
+        unknown = [0] * d
+        for j, mats in enumerate(rows):
+            for mat in mats:
+                for wire in [w for w, x in mat.items() if x % ORDER == 0]:
+                    del mat[wire]
+                for wire in mat:
+                    mat[wire] %= ORDER
+            for wire in set().union(*mats):
+                users[wire].append(j)
+                unknown[j] += wire > n_in
+        known = [i <= n_in for i in range(n_wires)]
+        level_ptr, order, kinds, wires, invs = [0], [], [], [], []
+        ready = [j for j in range(d) if unknown[j] <= 1]
+        while ready:
+            defined, waiting = {}, []
+            for j in ready:                                   # ascending row index
+                if unknown[j] == 0:
+                    order.append(j), kinds.append(KIND_CHECK), wires.append(_NO_WIRE), invs.append(0)
+                    continue
+                s = next(w for w in set().union(*rows[j]) if not known[w])
+                if s in defined:
+                    waiting.append(j)                        # a check row of a later round
+                    continue
+                where = [k for k in range(3) if s in rows[j][k]]
+                if len(where) != 1:
+                    raise ValueError(f"SolvePlan: constraint {j + 1} is not linear in wire {s}, the wire it would define "
+                                     f"(it stands in {' and '.join('VWY'[k] for k in where)})")
+                defined[s] = j
+                order.append(j), kinds.append((KIND_A, KIND_B, KIND_Y)[where[0]]), wires.append(s)
+                invs.append(pow(rows[j][where[0]].pop(s), -1, ORDER))
+            level_ptr.append(len(order))
+            nxt = set(waiting)
+            for s in defined:
+                known[s] = True
+            for s in defined:
+                for j in users[s]:
+                    if j != defined[s]:
+                        unknown[j] -= 1
+                        if unknown[j] <= 1:
+                            nxt.add(j)
+            for j in defined.values():
+                unknown[j] = -1
+            placed = set(order[level_ptr[-2]:])
+            ready = sorted(j for j in nxt if j not in placed and unknown[j] >= 0)
+        if len(order) < d:
+            placed = set(order)
+            j = min(j for j in range(d) if j not in placed)
+            raise ValueError(f"SolvePlan: constraint {j + 1} keeps {unknown[j]} unknown wires: the R1CS is not "
+                             f"program-shaped (every row must define at most one new wire)")
+        if not all(known):
+            raise ValueError(f"SolvePlan: no constraint defines wire {known.index(False)} and it is not an input")
+        self.n_in, self.m, self.d = n_in, m, d
+        self.n_levels = len(level_ptr) - 1
+        self.level_ptr = np.asarray(level_ptr, np.uint32)
+        self.row = np.asarray(order, np.uint32)
+        self.kind = np.asarray(kinds, np.uint32)
+        self.wire = np.asarray(wires, np.uint32)
+        self.inv = invs
+        self.csr = {}
+        for k, name in enumerate("VWY"):
+            ptr, col, vals = [0], [], []
+            for j in order:
+                for wire in sorted(rows[j][k]):
+                    col.append(wire)
+                    vals.append(rows[j][k][wire])
+                ptr.append(len(col))
+            self.csr[name] = (ptr, col, vals)
+
+    def device(self, ctx):
+        """the plan's arrays on `ctx`, uploaded once per context -> (13 device addresses as
+        Context.bn256_r1cs_solve_batch takes them, the buffers that hold them)"""
+        def make():
+            bufs = []
+            for name in "VWY":
+                ptr, col, vals = self.csr[name]
+                bufs += [ctx.upload(np.asarray(ptr, np.uint32)), ctx.upload(np.asarray(col + [0], np.uint32)),
+                         ctx.upload(scalars_to_array(vals + [0]))]
+            bufs += [ctx.upload(self.kind), ctx.upload(self.wire), ctx.upload(scalars_to_array(self.inv)),
+                     ctx.upload(self.level_ptr)]
+            ctx.sync()
+            return [b.ptr for b in bufs], bufs
+        cache = self.__dict__.setdefault("_device", {})
+        if id(ctx) not in cache:
+            cache[id(ctx)] = (ctx, make())
+        return cache[id(ctx)][1]
+
+
+def witness_batch_bytes(n_wires, n):
+    """device bytes calculate_witness_batch holds for a chunk of n witnesses: the witnesses and one status word each"""
+    return (32 * n_wires + 4) * n
+
+
+def _input_rows(inputs):
+    """K input vectors -> (K, n_in, 32) uint8 (any 32-byte values pass as they are; ints are reduced)"""
+    if isinstance(inputs, np.ndarray) and inputs.ndim == 3:
+        arr = np.ascontiguousarray(inputs, dtype=np.uint8)
+        if arr.shape[2] != 32:
+            raise ValueError(f"calculate_witness_batch: inputs of {arr.shape[2]} bytes, scalars have 32")
+        return arr
+    inputs = [list(x) for x in inputs]
+    if len({len(x) for x in inputs}) > 1:
+        raise ValueError("calculate_witness_batch: every witness takes the same number of inputs")
+    n_in = len(inputs[0]) if inputs else 0
+    return scalars_to_array([v for x in inputs for v in x]).reshape(len(inputs), n_in, 32)
+
+
+def calculate_witness_batch(qap, inputs, ctx=None, wide_rows=0):
+    """K witnesses of one R1CSQAP from K input vectors -> (K, n_wires, 32) uint8 canonical residues, row w = wire 0 (the
+    constant 1), the inputs of witness w in wires 1 .. n_in, every other wire computed on the device: what compute_h_batch,
+    compute_proof_batch, prove_batch and verify_batch take.  inputs: K sequences of n_in ints / field elements, or one
+    (K, n_in, 32) uint8 array (uploaded as it is; values >= the order are reduced on the device).
+    One upload, ONE solve for all K (SolvePlan's levels; narrow levels fused into single launches, wide_rows as in
+    include/vmpc.h, 0 = the library's rule), one synchronisation, one read of the K status words, one download.  K is cut
+    into chunks of at most BATCH_BUDGET_BYTES (plan_chunks, witness_batch_bytes) and VMPC_BN256_R1CS_MAX_WIT witnesses; a
+    chunk boundary changes no value.  A division by zero or a violated check row raises ValueError naming the lowest
+    bad witness (0-based) and, of its rows, the first that failed in solve order (1-based constraint)."""
+    if not isinstance(qap, R1CSQAP):
+        SolvePlan(qap, 0)                   # raises the TypeError that says what to pass
+    arr = _input_rows(inputs)
+    K, n_in = arr.shape[0], arr.shape[1]
+    n_wires = qap.m + 1
+    out = np.zeros((K, n_wires, 32), np.uint8)
+    if K == 0:
+        return out
+    plan = SolvePlan(qap, n_in)
+    ctx = ctx or get_context()
+    ptrs, _ = plan.device(ctx)
+    out[:, 1:n_in + 1] = arr
+    for lo, hi in plan_chunks(K, BATCH_BUDGET_BYTES, lambda n: witness_batch_bytes(n_wires, n)):
+        step = min(hi - lo, _native.BN256_R1CS_MAX_WIT)
+        for a in range(lo, hi, step):
+            b = min(a + step, hi)
+            dc, bad = ctx.upload(out[a:b]), ctx.alloc(4 * (b - a))
+            ctx.bn256_r1cs_solve_batch(ptrs, plan.level_ptr, n_in, qap.m, dc.ptr, n_wires, b - a, wide_rows, bad.ptr)
+            ctx.sync()
+            words = ctx.download(bad.ptr, 4 * (b - a)).view("<u4")
+            viol = np.nonzero(words != 0xFFFFFFFF)[0]
+            if len(viol):
+                w, pos = a + int(viol[0]), int(words[viol[0]])
+                j = int(plan.row[pos]) + 1
+                if plan.kind[pos] == KIND_CHECK:
+                    raise ValueError(f"calculate_witness_batch: witness {w} violates constraint {j} "
+                                     f"(V(j) W(j) != Y(j) at j = {j})")
+                raise ValueError(f"calculate_witness_batch: witness {w}: division by zero in constraint {j}")
+            out[a:b] = ctx.download(dc.ptr, 32 * n_wires * (b - a)).reshape(b - a, n_wires, 32)
+            del dc, bad
+    return out
+
+
+def calculate_witness(qap, inputs, ctx=None):
+    """The reference's QAP.calculate_witness(inputs): the witness as a list of ints, c[0] == 1, the len(inputs) inputs
+    in wires 1 .. len(inputs) - computed on the device from the R1CS (calculate_witness_batch with K = 1)."""
+    raw = calculate_witness_batch(qap, [list(inputs)], ctx=ctx)[0].tobytes()
+    return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(len(raw) // 32)]
+
+
+def prove_batch_inputs(qap, inputs, key, deltas=None):
+    """prove_batch from the inputs: calculate_witness_batch, then prove_batch on its witnesses -> (K proof dicts, the
+    (K, n_wires, 32) witness array, of which verify / verify_batch read the io wires)."""
+    ctx = key.ctx if isinstance(key, PreparedKey) else None
+    cs = calculate_witness_batch(qap, inputs, ctx=ctx)
+    return prove_batch(qap, cs, key, deltas), cs

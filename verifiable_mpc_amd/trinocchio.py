@@ -24,8 +24,9 @@ bytes over csrc/mpc_share.hip's GF(n) entries.  A party exchanges (section 19 ha
 so 4 exchanges with the check and 2 without (1 when there is nothing to deal: no deltas and an empty h).
 
 Out of scope:
-  * the witness computation on shares (the demo's qap.calculate_witness on secure values): the parties arrive with
-    shares of the WHOLE witness, as with `gamma_witness=` in mpc_circuit_sat;
+  * the witness computation ON SHARES (the demo's qap.calculate_witness on secure values needs a multiplication protocol
+    per level): the parties arrive with shares of the WHOLE witness, as with `gamma_witness=` in mpc_circuit_sat.  In
+    the clear the witness comes from pynocchio.calculate_witness / calculate_witness_batch (DESIGN.md section 22);
   * QAP construction from code (stays with the reference, as for pynocchio);
   * multi-client Trinocchio (the paper's Alg. 4);
   * any transport other than the hub: a real runtime moves the same bytes.
