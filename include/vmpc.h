@@ -757,6 +757,22 @@ int vmpc_sha256_chunks_dev(vmpc_ctx *ctx, const void *data, size_t nbytes, size_
 int vmpc_msm_table_fold_dev(vmpc_ctx *ctx, const void *table, size_t table_n, size_t table_extra, int rows,
                             size_t n_cols, int k, const uint8_t *scalars, void *out_affine);
 
+/* The plan vmpc_msm_table_fold_dev / _table_dev make for (rows, n_cols, k, scalars) on this context, for tests
+ * (csrc/fold_jump_plan.h; the calls above go through the same code).  Digit position p of a scalar - n_digits signed
+ * digits of digit_bits bits, 8 or, for 16 rows or under VMPC_FOLD_JUMP_DIGITS=4, 4 - uses table row p / O at offset
+ * p % O; the walk is launched as grid_x x grid_y workgroups of 256 lanes, n_blocks of the grid_x with work, grid_y = S
+ * lanes sharing the schedule of one (output, offset).  sched_out: NULL, or room for sched_capacity_words >= sched_words
+ * = O * e1 words: per offset the number of entries, the entries by |digit| descending (bits 0..7 = scalar index,
+ * 8..12 = row, 15 = negate, 16..23 = |digit|) and a closing 0.  VMPC_E_NONCANON for a scalar >= l.  Host side only:
+ * no launch, no device access, nothing taken from the workspace. */
+typedef struct vmpc_fold_plan {
+    int32_t digit_bits, n_digits, O, e1, S;
+    uint32_t n_blocks, grid_x, grid_y;
+    uint64_t m_out, sched_words;
+} vmpc_fold_plan;
+int vmpc_msm_table_fold_plan(vmpc_ctx *ctx, int rows, size_t n_cols, int k, const uint8_t *scalars,
+                             vmpc_fold_plan *out, uint32_t *sched_out, size_t sched_capacity_words);
+
 /* the same fold, leaving the folded vector's own fixed-base table (out_rows rows, the n_extra device points
  * extra_affine_points as its extras; size: vmpc_msm_table_bytes(n_cols >> k, n_extra, out_rows)) instead of the
  * vector - what a prover that keeps committing to the folded generators wants (vmpc_p4_round uses it) */

@@ -38,7 +38,7 @@ SYMBOLS = [
     "vmpc_sha256_chunks_dev", "vmpc_fr_challenge_products_dev", "vmpc_fr_tail_scalars_dev", "vmpc_fr_tail_scalars_inc_dev", "vmpc_fr_tail_scalars_block_dev",
     "vmpc_bn256_g1_msm", "vmpc_bn256_g2_msm", "vmpc_bn256_g1_msm_dev", "vmpc_bn256_g2_msm_dev",
     "vmpc_bn256_validate_dev", "vmpc_bn256_fixed_base_dev",
-    "vmpc_msm_table_fold_dev", "vmpc_msm_table_fold_table_dev", "vmpc_p4_create", "vmpc_p4_create_opts", "vmpc_p4_prefold", "vmpc_p4_set_commit_table", "vmpc_p4_round", "vmpc_p4_round_begin", "vmpc_p4_round_end", "vmpc_p4_finish", "vmpc_p4_run_compact", "vmpc_p4_destroy", "vmpc_bn256_table_bytes", "vmpc_bn256_table_build_dev", "vmpc_bn256_table_msm_dev", "vmpc_bn256_table_msm_multi_dev",
+    "vmpc_msm_table_fold_dev", "vmpc_msm_table_fold_table_dev", "vmpc_msm_table_fold_plan", "vmpc_p4_create", "vmpc_p4_create_opts", "vmpc_p4_prefold", "vmpc_p4_set_commit_table", "vmpc_p4_round", "vmpc_p4_round_begin", "vmpc_p4_round_end", "vmpc_p4_finish", "vmpc_p4_run_compact", "vmpc_p4_destroy", "vmpc_bn256_table_bytes", "vmpc_bn256_table_build_dev", "vmpc_bn256_table_msm_dev", "vmpc_bn256_table_msm_multi_dev",
     "vmpc_comm_unique_id", "vmpc_comm_create_rccl", "vmpc_comm_create_callback", "vmpc_comm_destroy", "vmpc_comm_info",
     "vmpc_comm_allgather_dev", "vmpc_comm_points_allsum_dev", "vmpc_p4_create_sharded", "vmpc_gather_probe_dev", "vmpc_bn256_madd_rate",
     "vmpc_stream_create", "vmpc_stream_destroy", "vmpc_ctx_set_bucket_stream",
@@ -70,6 +70,15 @@ class SortView(ctypes.Structure):
     ARRAYS = ("digits", "hist1", "counts", "starts", "sorted", "nseg", "seg_starts", "heavy_list", "tasks", "ctrl")
     _fields_ = ([(k, ctypes.c_uint64) for k in PLAN_U64] + [("top_max_b", ctypes.c_uint32)] +
                 [(k, ctypes.c_int32) for k in PLAN_I32] + [(k, ctypes.c_void_p) for k in ARRAYS])
+
+
+class FoldPlan(ctypes.Structure):
+    """vmpc_fold_plan (include/vmpc.h): the geometry of a fold jump (csrc/fold_jump_plan.h)"""
+    I32 = ("digit_bits", "n_digits", "O", "e1", "S")
+    U32 = ("n_blocks", "grid_x", "grid_y")
+    U64 = ("m_out", "sched_words")
+    _fields_ = ([(k, ctypes.c_int32) for k in I32] + [(k, ctypes.c_uint32) for k in U32] +
+                [(k, ctypes.c_uint64) for k in U64])
 
 
 class VmpcError(RuntimeError):
@@ -216,6 +225,7 @@ def load_library():
         "vmpc_fr_batch_products_dev": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, sz, vp, vp]),
         "vmpc_msm_table_fold_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp]),
         "vmpc_msm_table_fold_table_dev": (i32, [vp, vp, sz, sz, i32, sz, i32, vp, vp, sz, i32, vp]),
+        "vmpc_msm_table_fold_plan": (i32, [vp, i32, sz, i32, vp, ctypes.POINTER(FoldPlan), vp, sz]),
         "vmpc_p4_create": (i32, [vp, vp, sz, sz, i32, i32, i32, vp, vp, vp, ctypes.POINTER(vp)]),
         "vmpc_p4_set_commit_table": (i32, [vp, vp, i32]),
         "vmpc_p4_create_opts": (i32, [vp, vp, sz, sz, i32, i32, i32, vp, vp, vp, i32, i32, ctypes.POINTER(vp)]),
@@ -749,6 +759,22 @@ class Context:
                                                       n_cols, k, raw, ctypes.c_void_p(extras_ptr), n_extra, out_rows,
                                                       ctypes.c_void_p(out.ptr)), "vmpc_msm_table_fold_table_dev")
         return out
+
+    def msm_table_fold_plan(self, rows, n_cols, scalars):
+        """(geometry, schedule) of the fold jump msm_table_fold / _table would run for these arguments on this context:
+        the geometry as a dict, the schedule as uint32 [O, e1] (csrc/fold_jump_plan.h).  Host side only."""
+        k = len(scalars).bit_length() - 1
+        assert len(scalars) == 1 << k
+        raw = ctypes.create_string_buffer(b"".join(scalar_to_bytes(v) for v in scalars), 32 << k)
+        g = FoldPlan()
+        _check(self.lib.vmpc_msm_table_fold_plan(self.handle, rows, n_cols, k, raw, ctypes.byref(g), None, 0),
+               "vmpc_msm_table_fold_plan")
+        sched = np.zeros(int(g.sched_words), np.uint32)
+        _check(self.lib.vmpc_msm_table_fold_plan(self.handle, rows, n_cols, k, raw, ctypes.byref(g),
+                                                 sched.ctypes.data_as(ctypes.c_void_p), sched.size),
+               "vmpc_msm_table_fold_plan")
+        geo = {name: int(getattr(g, name)) for name in FoldPlan.I32 + FoldPlan.U32 + FoldPlan.U64}
+        return geo, sched.reshape(geo["O"], geo["e1"])
 
     def points_sum(self, ext_ptr, m, out_ext_ptr=None, out_affine_ptr=None):
         _check(self.lib.vmpc_points_sum_dev(self.handle, ctypes.c_void_p(ext_ptr), m,

@@ -20,12 +20,10 @@
 #include <vector>
 
 #include "common.h"
+#include "fold_jump_plan.h"
 #include "fr.h"
 #include "ptio.h"
 #include "quad.h"
-
-#define FJ_BLOCK 256
-#define FJ_WAVES (FJ_BLOCK / 64)
 
 int vmpc_normalize_launch(vmpc_ctx *ctx, const void *proj, size_t n, void *out_affine);   // exact.hip
 
@@ -205,55 +203,19 @@ __global__ void k_copy_columns(const uint4 *__restrict__ src, size_t row_vecs, u
 static int table_fold(vmpc_ctx *ctx, const void *table, size_t table_n, size_t table_extra, int rows, size_t n_cols,
                       int k, const uint8_t *scalars, void *out_affine, void *out_table, int out_rows,
                       const void *out_extra, size_t out_n_extra, const void *extras_block = nullptr) {
-    if (!ctx || !table || !scalars || (!out_affine && !out_table) || k < 1 || k > 6 || n_cols < ((size_t)1 << k) ||
-        (n_cols & (n_cols - 1)) || n_cols > table_n + table_extra ||
-        !(rows == 1 || rows == 2 || rows == 4 || rows == 8 || rows == 16))
+    if (!ctx || !table || !scalars || (!out_affine && !out_table) || !fold_jump_args_ok(rows, n_cols, k) ||
+        n_cols > table_n + table_extra)
         return VMPC_E_INVAL;
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t stride = (table_n + table_extra + 7) & ~(size_t)7;       // msm.hip: msm_table_stride
-    const size_t m_out = n_cols >> k;
-    // digit width: 8 bits where a row still holds at least one offset per wave of a workgroup (rows <= 8: the CRS
-    // table of a 2^20-generator proof) - half the lanes and table reads of the 4-bit form (k_fold_jump8); else 4
-    int digit_bits = (rows <= 8 && ctx->fold_jump_digit_bits != 4) ? 8 : 4;
-    const int n_digits = 256 / digit_bits, half = 1 << (digit_bits - 1), per_word = 32 / digit_bits;
-    const int B = 1 << k, O = n_digits / rows, e1 = rows * B + 2;
-    // the shared schedule: signed digits of the 2^k scalars, per offset sorted by |digit| descending
-    std::vector<uint32_t> sched((size_t)O * e1, 0);
-    {
-        std::vector<std::vector<uint32_t>> by_value((size_t)O * (half + 1));
-        for (int b = 0; b < B; b++) {
-            uint32_t w[8];
-            memcpy(w, scalars + 32 * b, 32);
-            if (fr_geq_l(w)) return VMPC_E_NONCANON;
-            uint32_t carry = 0;
-            for (int p = 0; p < n_digits; p++) {
-                uint32_t raw = ((w[p / per_word] >> (digit_bits * (p % per_word))) & (uint32_t)(2 * half - 1)) + carry;
-                int d = (int)raw;
-                carry = 0;
-                if (raw >= (uint32_t)half) {
-                    d = (int)raw - 2 * half;
-                    carry = 1;
-                }
-                if (d == 0) continue;
-                const uint32_t v = (uint32_t)(d < 0 ? -d : d);
-                by_value[(size_t)(p % O) * (half + 1) + v].push_back((uint32_t)b | ((uint32_t)(p / O) << 8) |
-                                                                     ((d < 0 ? 1u : 0u) << 15) | (v << 16));
-            }
-        }
-        for (int o = 0; o < O; o++) {
-            uint32_t *dst = sched.data() + (size_t)o * e1;
-            uint32_t n = 0;
-            for (int v = half; v >= 1; v--)
-                for (uint32_t ent : by_value[(size_t)o * (half + 1) + v]) dst[1 + n++] = ent;
-            dst[0] = n;
-        }
-    }
+    // the plan - digit width, geometry, the shared schedule of signed digits - is host code of its own
+    // (fold_jump_plan.h; vmpc_msm_table_fold_plan hands the same plan out)
+    const fold_jump_geometry geo = fold_jump_plan_geometry(rows, n_cols, k, ctx->fold_jump_digit_bits);
+    const size_t m_out = geo.m_out;
+    const int digit_bits = geo.digit_bits, O = geo.O, e1 = geo.e1, S = geo.S;
+    std::vector<uint32_t> sched;
+    if (!fold_jump_plan_schedule(geo, k, scalars, sched)) return VMPC_E_NONCANON;
     const size_t sched_bytes = (sched.size() * 4 + 255) & ~(size_t)255;
-    // short vectors: S lanes share an (output, offset) schedule so that up to 2^17 lanes are at work
-    int S = 1;
-    // (2^16 / 2^17 / 2^18 lanes: 4.03 / 4.04 / 4.02 ms for the fold of a 2^20-generator proof, 2^19: 4.40 - the pass
-    // is bound by its 8 GB of table reads, 64 x 128 bytes per generator, not by the lanes at work)
-    while (S < 16 && m_out * (size_t)O * S * 2 <= ((size_t)1 << 17) && rows * B / (S * 2) >= 8) S *= 2;
     const size_t partial_bytes = 2 * m_out * (size_t)O * S * EXT_WORDS * 4;      // slots, then k_fold_jump's parking
     const size_t proj_bytes = (m_out * 96 + 255) & ~(size_t)255;
     VMPC_CHECK(vmpc_ws_reserve(ctx, sched_bytes + partial_bytes + proj_bytes));
@@ -262,8 +224,7 @@ static int table_fold(vmpc_ctx *ctx, const void *table, size_t table_n, size_t t
     uint32_t *d_partial = (uint32_t *)(ws + sched_bytes + proj_bytes);
     vmpc_stage_scope s(ctx, "table_fold");
     VMPC_CHECK(vmpc_stage_h2d(ctx, d_sched, sched.data(), sched.size() * 4));
-    const unsigned n_blocks = (unsigned)(((m_out + 63) / 64) * (size_t)(O / FJ_WAVES));
-    const unsigned grid = ((n_blocks + 7) / 8) * 8;
+    const unsigned n_blocks = geo.n_blocks, grid = geo.grid_x;
     if (digit_bits == 8)
         k_fold_jump8<<<dim3(grid, (unsigned)S), FJ_BLOCK, 0, ctx->stream>>>((const uint32_t *)table, stride, m_out, O, e1,
                                                                             d_sched, n_blocks, d_partial);
@@ -290,6 +251,22 @@ static int table_fold(vmpc_ctx *ctx, const void *table, size_t table_n, size_t t
         return VMPC_OK;
     }
     return vmpc_msm_table_build_extras(ctx, m_out, out_extra, out_n_extra, out_rows, out_table);
+}
+
+// The plan table_fold() would make for these arguments on this context - the same two calls into fold_jump_plan.h.
+// Host side only: no launch, nothing taken from the workspace.
+extern "C" int vmpc_msm_table_fold_plan(vmpc_ctx *ctx, int rows, size_t n_cols, int k, const uint8_t *scalars,
+                                        vmpc_fold_plan *out, uint32_t *sched_out, size_t sched_capacity_words) {
+    if (!ctx || !scalars || !out || !fold_jump_args_ok(rows, n_cols, k)) return VMPC_E_INVAL;
+    const fold_jump_geometry geo = fold_jump_plan_geometry(rows, n_cols, k, ctx->fold_jump_digit_bits);
+    std::vector<uint32_t> sched;
+    if (!fold_jump_plan_schedule(geo, k, scalars, sched)) return VMPC_E_NONCANON;
+    if (sched_out && sched_capacity_words < sched.size()) return VMPC_E_INVAL;
+    out->digit_bits = geo.digit_bits, out->n_digits = geo.n_digits, out->O = geo.O, out->e1 = geo.e1, out->S = geo.S;
+    out->n_blocks = geo.n_blocks, out->grid_x = geo.grid_x, out->grid_y = (uint32_t)geo.S;
+    out->m_out = geo.m_out, out->sched_words = sched.size();
+    if (sched_out) memcpy(sched_out, sched.data(), sched.size() * 4);
+    return VMPC_OK;
 }
 
 extern "C" int vmpc_msm_table_fold_dev(vmpc_ctx *ctx, const void *table, size_t table_n, size_t table_extra, int rows,

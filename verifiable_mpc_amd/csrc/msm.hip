@@ -619,6 +619,7 @@ extern "C" int vmpc_msm_table_build_dev(vmpc_ctx *ctx, const void *affine_points
 int vmpc_msm_table_build_extras(vmpc_ctx *ctx, size_t n, const void *extra_affine_points, size_t n_extra, int rows,
                                 void *table) {
     const size_t stride = msm_table_stride(n + n_extra, rows);
+    if (stride == n) return VMPC_OK;     // no extras and no padding (n a multiple of 8): nothing to fill, and no empty grid
     k_msm_table_build<<<(unsigned)((stride - n + MSM_BLOCK - 1) / MSM_BLOCK), MSM_BLOCK, 0, ctx->stream>>>(
         nullptr, n, (const uint32_t *)extra_affine_points, n + n_extra, stride, rows, n, (uint32_t *)table);
     VMPC_KERNEL_CHECK();
