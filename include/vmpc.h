@@ -701,6 +701,34 @@ int vmpc_bn256_fr_share_mul_deal_dev(vmpc_ctx *ctx, const void *a, const void *b
 int vmpc_bn256_fr_share_combine_dev(vmpc_ctx *ctx, const void *parts, size_t parties, size_t n, size_t part_stride,
                                     const uint8_t *weights, const uint32_t *dst, const void *addend, void *out);
 
+/* ---- The R1CS solve on shares mod n (demos/demo_zkp_trinocchio.py:70: qap.calculate_witness on secure values, one
+ * MPyC multiplication per `*` line of the flat code, tools/code_to_r1cs.py:253-274; csrc/bn256_r1cs_share.hip, DESIGN.md
+ * section 23).  One party's two halves of a ROUND: the product rows r0 .. r1-1 of a plan in the layout of
+ * vmpc_bn256_r1cs_solve_batch_dev (pynocchio.ShareSolvePlan; all plan arrays in DEVICE memory) on n_wit share vectors c,
+ * c_stride scalars apart, slot 0 = 1 and every slot that the rows read a canonical residue.  With n_r = r1 - r0 the
+ * element of row i and witness w is e = w n_r + (i - r0), n_e = n_wit n_r.  The rows that need no exchange run through
+ * vmpc_bn256_r1cs_solve_batch_dev itself, which computes a party's share of a linear row's wire unchanged.
+ * parties > VMPC_SHARE_MAX_PARTIES, n_wit > VMPC_BN256_R1CS_MAX_WIT, a stride or n_e above 2^31, c_stride < m + 1:
+ * VMPC_E_RANGE before any pointer is looked at; t >= parties, a table stride below n_e, r1 < r0, a null pointer where
+ * there is work: VMPC_E_INVAL; an empty range or n_wit = 0: VMPC_OK, no launch.  One lane per (row, witness),
+ * deterministic (no atomics on field values), asynchronous on the context's stream, no arena. */
+/* d = (V_i . c_w)(W_i . c_w), this party's degree-2t share of the product, and a fresh degree-t sharing of it:
+ * out[q][e] = d + sum_{k=1..t} coeffs[k-1][e] (q + 1)^k for q < parties (coeffs: t rows of n_e scalars, stride n_e;
+ * out: `parties` rows, out_stride apart; t = 0 copies d to every row).  d itself is written nowhere. */
+int vmpc_bn256_r1cs_share_mul_deal_dev(vmpc_ctx *ctx, const uint32_t *v_row_ptr, const uint32_t *v_col,
+                                       const void *v_vals, const uint32_t *w_row_ptr, const uint32_t *w_col,
+                                       const void *w_vals, size_t r0, size_t r1, size_t m, const void *c, size_t c_stride,
+                                       size_t n_wit, const void *coeffs, size_t t, size_t parties, void *out,
+                                       size_t out_stride);
+/* After the exchange: c_w[wire_i] = (sum_{p < parties} weights[p] parts[p][e] - Y_i . c_w) inv_i, the sum in the wide
+ * accumulator of csrc/fr256.h, reduced once; an inverse of 1 is not multiplied.  weights: parties x 32 bytes in HOST
+ * memory.  Canonicity as for vmpc_bn256_fr_share_combine_dev: a weight >= n is VMPC_E_NONCANON at once; an element of
+ * parts >= n leaves its wire unwritten and the next vmpc_ctx_sync answers VMPC_E_NONCANON. */
+int vmpc_bn256_r1cs_share_finish_dev(vmpc_ctx *ctx, const uint32_t *y_row_ptr, const uint32_t *y_col, const void *y_vals,
+                                     const uint32_t *wire, const void *inv, size_t r0, size_t r1, size_t m,
+                                     const void *parts, size_t parties, size_t part_stride,
+                                     const uint8_t *weights /* HOST */, void *c, size_t c_stride, size_t n_wit);
+
 /* ---- Pi_Nullity (AC20 p. 17-18, verifiable_mpc/ac20/nullity.py:21-40): s dense linear forms over n variables as a
  * row-major matrix in device memory, row i at rows + 32 i row_stride, 32-byte little-endian elements.  ANY 256-bit
  * element is accepted and taken mod l (the arithmetic reduces it on the way in); results are canonical.  Caps:

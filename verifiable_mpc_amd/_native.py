@@ -59,6 +59,7 @@ SYMBOLS = [
     "vmpc_bn256_fr_share_mul_deal_dev", "vmpc_bn256_fr_share_combine_dev", "vmpc_bn256_qap_residual_dev",
     "vmpc_fr_cs_triples_batch_dev", "vmpc_fr_cs_extend_batch_dev", "vmpc_fr_cs_extend_batch_bytes",
     "vmpc_bn256_r1cs_solve_batch_dev", "vmpc_bn256_r1cs_solve_launches",
+    "vmpc_bn256_r1cs_share_mul_deal_dev", "vmpc_bn256_r1cs_share_finish_dev",
 ]
 
 
@@ -211,6 +212,8 @@ def load_library():
         "vmpc_fr_cs_extend_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
         "vmpc_bn256_r1cs_solve_batch_dev": (i32, [vp] * 15 + [sz, sz, sz, vp, sz, sz, sz, vp]),
         "vmpc_bn256_r1cs_solve_launches": (sz, [vp, sz, sz, sz]),
+        "vmpc_bn256_r1cs_share_mul_deal_dev": (i32, [vp] * 7 + [sz, sz, sz, vp, sz, sz, vp, sz, sz, vp, sz]),
+        "vmpc_bn256_r1cs_share_finish_dev": (i32, [vp] * 6 + [sz, sz, sz, vp, sz, sz, vp, vp, sz, sz]),
         "vmpc_fr_cs_extend_fg_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
         "vmpc_fr_share_mul_deal_dev": (i32, [vp, vp, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_fr_share_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
@@ -1190,6 +1193,29 @@ class Context:
         _check(self.lib.vmpc_bn256_r1cs_solve_batch_dev(self.handle, *[p(x) for x in plan_ptrs], _np_ptr(lp), len(lp) - 1,
                                                         n_in, m, p(c_ptr), c_stride, n_wit, wide_rows, p(first_bad_ptr)),
                "vmpc_bn256_r1cs_solve_batch_dev")
+
+    def bn256_r1cs_share_mul_deal(self, plan_ptrs, r0, r1, m, c_ptr, c_stride, n_wit, coeffs_ptr, t, parties, out_ptr,
+                                  out_stride):
+        """the product rows r0 .. r1-1 of a share plan on n_wit share vectors, dealt afresh with degree t (include/vmpc.h):
+        out[q][w (r1 - r0) + i - r0] = (V_i . c_w)(W_i . c_w) + sum_k coeffs[k-1][.] (q + 1)^k.  plan_ptrs: the 13
+        device addresses of bn256_r1cs_solve_batch, of which V's and W's are read"""
+        p = ctypes.c_void_p
+        assert len(plan_ptrs) == 13
+        _check(self.lib.vmpc_bn256_r1cs_share_mul_deal_dev(self.handle, *[p(x) for x in plan_ptrs[:6]], r0, r1, m, p(c_ptr),
+                                                           c_stride, n_wit, p(coeffs_ptr), t, parties, p(out_ptr),
+                                                           out_stride), "vmpc_bn256_r1cs_share_mul_deal_dev")
+
+    def bn256_r1cs_share_finish(self, plan_ptrs, r0, r1, m, parts_ptr, parties, part_stride, weights, c_ptr, c_stride,
+                                n_wit):
+        """after the exchange: c_w[wire_i] = (sum_p weights[p] parts[p][.] - Y_i . c_w) inv_i for the same rows; weights:
+        ints.  plan_ptrs as above, of which Y's, wire and inv are read"""
+        p = ctypes.c_void_p
+        assert len(plan_ptrs) == 13
+        wb = ctypes.create_string_buffer(b"".join(scalar_to_bytes(w) for w in weights), 32 * max(len(weights), 1))
+        y, wire, inv = plan_ptrs[6:9], plan_ptrs[10], plan_ptrs[11]
+        _check(self.lib.vmpc_bn256_r1cs_share_finish_dev(self.handle, *[p(x) for x in y], p(wire), p(inv), r0, r1, m,
+                                                         p(parts_ptr), parties, part_stride, wb, p(c_ptr), c_stride,
+                                                         n_wit), "vmpc_bn256_r1cs_share_finish_dev")
 
     def bn256_validate(self, group, points_ptr, n):
         bad = ctypes.c_uint64()

@@ -1647,6 +1647,136 @@ class SolvePlan:
         return cache[id(ctx)][1]
 
 
+class ShareSolvePlan:
+    """SolvePlan's rows in the order of a solve on Shamir SHARES of the wires, where only a product of two shared
+    values costs an exchange (trinocchio.calculate_witness_shares): ShareSolvePlan(qap, n_in), made
+    once per (R1CSQAP, n_in) from SolvePlan(qap, n_in) and kept on the QAP.  Which row defines which wire, its kind, its
+    inverse coefficient and its stored entries are SolvePlan's; only the order differs.  Pure host work.
+
+    Wire 0 is public (every party's share of the constant 1 is 1), so a dot whose stored entries all sit on wire 0, or
+    an empty dot, is a public constant.  A defining row is
+        LINEAR    a KIND_Y row whose V entries or W entries are a subset of {wire 0}, or a KIND_A / KIND_B row whose
+                  divisor side is: the row's own formula on a party's share vector gives its share of the new wire;
+        PRODUCT   a KIND_Y row with a shared wire in both V and W: one multiplication of shares, one exchange.
+    ValueError (1-based constraint numbers): a KIND_A / KIND_B row whose divisor has a shared wire ("division by a
+    shared value": it needs an inversion protocol with two more exchanges and is out of scope); a constant divisor that
+    is 0 mod the order.  SolvePlan's check rows are left out (n_checks counts them): trinocchio.prove tests every row
+    through the masked residual.
+
+    Depth mu: 0 for wire 0 and the inputs; a linear row gives its wire the largest mu among its stored entries (0 where
+    it has none), a product row 1 + that.  n_rounds = the largest mu.  The solve runs the phases
+    L_0, P_1, L_1, .., P_D, L_D: P_r the product rows of depth r in ascending row index, ONE exchange; L_r the linear
+    rows of depth r in sub-levels (a row's sub-level is 1 + the largest sub-level of a linear wire of the same depth that
+    it reads, 0 where it reads none), ascending row index within a sub-level; L_r may be empty.
+
+    The arrays hold the linear rows first, phase by phase, then the product rows, round by round - so the local phases
+    are sub-ranges of ONE level table, as vmpc_bn256_r1cs_solve_batch_dev takes them:
+        local_level_ptr   (n_local_levels + 1) positions: sub-level k is rows local_level_ptr[k] .. local_level_ptr[k+1]-1
+        phase_ptr         (n_rounds + 2): L_r is the sub-levels phase_ptr[r] .. phase_ptr[r+1]-1
+        round_ptr         (n_rounds + 1): P_r is rows n_linear + round_ptr[r-1] .. n_linear + round_ptr[r]-1
+        row, kind, wire, inv, csr   per row in that order, as SolvePlan's."""
+
+    def __new__(cls, qap, n_in):
+        base = SolvePlan(qap, n_in)                     # the TypeError for a reference QAP is SolvePlan's
+        cache = qap.__dict__.setdefault("_share_solve_plans", {})
+        if base.n_in not in cache:
+            plan = object.__new__(cls)
+            plan._build(base)
+            cache[base.n_in] = plan
+        return cache[base.n_in]
+
+    def _build(self, base):
+        rows = len(base.row)
+        entries = []                                    # per SolvePlan position: the stored columns of V, W, Y
+        for name in "VWY":
+            ptr, col, _ = base.csr[name]
+            entries.append([col[ptr[i]:ptr[i + 1]] for i in range(rows)])
+        shared = lambda cols: any(w != 0 for w in cols)
+        mu = {w: 0 for w in range(base.n_in + 1)}
+        sub = {}                                        # linear-defined wire -> its sub-level
+        linear, product = {}, {}                        # (mu, sub-level) / mu -> positions
+        for i in range(rows):                           # level order: every entry read was defined before
+            kind, j = int(base.kind[i]), int(base.row[i]) + 1
+            if kind == KIND_CHECK:
+                continue
+            v, w, y = entries[0][i], entries[1][i], entries[2][i]
+            read = v + w + y
+            depth = max((mu[s] for s in read), default=0)
+            if kind == KIND_Y:
+                is_product = shared(v) and shared(w)
+            else:
+                is_product = False
+                k = 1 if kind == KIND_A else 0
+                if shared(entries[k][i]):
+                    raise ValueError(f"ShareSolvePlan: division by a shared value in constraint {j} (the solve on shares "
+                                     f"multiplies shared values but does not invert them)")
+                if not entries[k][i]:                   # stored coefficients are non-zero residues: only an empty dot is 0
+                    raise ValueError(f"ShareSolvePlan: division by the constant 0 in constraint {j}")
+            s = int(base.wire[i])
+            if is_product:
+                mu[s] = depth + 1
+                product.setdefault(depth + 1, []).append(i)
+            else:
+                mu[s] = depth
+                sub[s] = max((sub[x] + 1 for x in read if mu[x] == depth and x in sub), default=0)
+                linear.setdefault((depth, sub[s]), []).append(i)
+        by_row = lambda pos: sorted(pos, key=lambda i: int(base.row[i]))
+        self.n_rounds = D = max(product, default=0)
+        order, local_level_ptr, phase_ptr = [], [0], [0]
+        for r in range(D + 1):
+            k = 0
+            while (r, k) in linear:
+                order += by_row(linear[r, k])
+                local_level_ptr.append(len(order))
+                k += 1
+            phase_ptr.append(len(local_level_ptr) - 1)
+        self.n_linear = len(order)
+        round_ptr = [0]
+        for r in range(1, D + 1):
+            order += by_row(product[r])
+            round_ptr.append(len(order) - self.n_linear)
+        self.n_in, self.m, self.d = base.n_in, base.m, base.d
+        self.n_checks = int((base.kind == KIND_CHECK).sum())
+        self.local_level_ptr = np.asarray(local_level_ptr, np.uint32)
+        self.phase_ptr = np.asarray(phase_ptr, np.uint32)
+        self.round_ptr = np.asarray(round_ptr, np.uint32)
+        self.n_local_levels = len(local_level_ptr) - 1
+        idx = np.asarray(order, np.int64)
+        self.row, self.kind, self.wire = base.row[idx], base.kind[idx], base.wire[idx]
+        self.inv = [base.inv[i] for i in order]
+        self.csr = {}
+        for name in "VWY":
+            bptr, bcol, bvals = base.csr[name]
+            ptr, col, vals = [0], [], []
+            for i in order:
+                col += bcol[bptr[i]:bptr[i + 1]]
+                vals += bvals[bptr[i]:bptr[i + 1]]
+                ptr.append(len(col))
+            self.csr[name] = (ptr, col, vals)
+
+    def round_rows(self, r):
+        """(r0, r1): the positions of P_r, r = 1 .. n_rounds"""
+        return self.n_linear + int(self.round_ptr[r - 1]), self.n_linear + int(self.round_ptr[r])
+
+    def device(self, ctx):
+        """the plan's arrays on `ctx`, uploaded once per context -> (13 device addresses in SolvePlan.device's order, the
+        last one local_level_ptr's; the buffers that hold them)"""
+        def make():
+            bufs = []
+            for name in "VWY":
+                ptr, col, vals = self.csr[name]
+                bufs += [ctx.upload(np.asarray(ptr, np.uint32)), ctx.upload(np.asarray(col + [0], np.uint32)),
+                         ctx.upload(scalars_to_array(vals + [0]))]
+            bufs += [ctx.upload(np.append(self.kind, np.uint32(0))), ctx.upload(np.append(self.wire, np.uint32(0))),
+                     ctx.upload(scalars_to_array(self.inv + [0])), ctx.upload(self.local_level_ptr)]
+            ctx.sync()
+            return [b.ptr for b in bufs], bufs
+        cache = self.__dict__.setdefault("_device", {})
+        if id(ctx) not in cache:
+            cache[id(ctx)] = (ctx, make())
+        return cache[id(ctx)][1]
+
+
 def witness_batch_bytes(n_wires, n):
     """device bytes calculate_witness_batch holds for a chunk of n witnesses: the witnesses and one status word each"""
     return (32 * n_wires + 4) * n

@@ -23,10 +23,18 @@ bytes over csrc/mpc_share.hip's GF(n) entries.  A party exchanges (section 19 ha
 
 so 4 exchanges with the check and 2 without (1 when there is nothing to deal: no deltas and an empty h).
 
+    shares of the inputs only     demo_zkp_trinocchio.py:42,70   calculate_witness_shares, prove_inputs
+
+`prove` starts from shares of the WHOLE witness (as with `gamma_witness=` in mpc_circuit_sat).  `calculate_witness_shares`
+makes them from shares of the inputs alone, as the demo's qap.calculate_witness on secure values does: the rows that
+need no communication run locally, every multiplicative depth of the circuit costs one more exchange (DESIGN.md
+section 23), and `prove_inputs` is the two in a row.  In the clear the witness comes from pynocchio.calculate_witness /
+calculate_witness_batch.
+
 Out of scope:
-  * the witness computation ON SHARES (the demo's qap.calculate_witness on secure values needs a multiplication protocol
-    per level): the parties arrive with shares of the WHOLE witness, as with `gamma_witness=` in mpc_circuit_sat.  In
-    the clear the witness comes from pynocchio.calculate_witness / calculate_witness_batch (DESIGN.md section 22);
+  * a division by a shared value in the witness computation on shares (it needs an inversion protocol with two more
+    exchanges; pynocchio.ShareSolvePlan refuses such a circuit), inputs that are partly public, and parties that
+    deviate from the protocol;
   * QAP construction from code (stays with the reference, as for pynocchio);
   * multi-client Trinocchio (the paper's Alg. 4);
   * any transport other than the hub: a real runtime moves the same bytes.
@@ -222,6 +230,94 @@ def deal_witness(c, threshold, parties, rng):
             row.append((acc + v) % ORDER)
         out.append(_native.ints_to_array(row, 32))
     return out
+
+
+def _input_share_rows(x_share):
+    """this party's input shares -> ((K, n_in, 32) uint8 canonical residues, whether the caller gave K vectors)"""
+    if isinstance(x_share, np.ndarray) and x_share.dtype == np.uint8 and x_share.ndim in (2, 3):
+        arr = np.ascontiguousarray(x_share if x_share.ndim == 3 else x_share[None])
+        if arr.shape[2] != 32:
+            raise ValueError(f"calculate_witness_shares: shares of {arr.shape[2]} bytes, scalars have 32")
+        diff = arr.reshape(-1, 32)[:, ::-1].astype(np.int16) - _ORDER_BE          # most significant byte first
+        first = (diff != 0).argmax(axis=1)
+        if len(diff) and (diff[np.arange(len(diff)), first] >= 0).any():
+            raise ValueError("calculate_witness_shares: a share is a residue mod n, below n")
+        return arr, x_share.ndim == 3
+    x = [int(v) for v in x_share]
+    return pn.scalars_to_array(x).reshape(1, len(x), 32), False
+
+
+async def calculate_witness_shares(rt, qap, x_share, ctx=None, wide_rows=0):
+    """One party's run of the M-party R1CS solve (demo_zkp_trinocchio.py:70, qap.calculate_witness on secure values):
+    from this party's degree-t shares of the INPUTS alone to its degree-t shares of every wire, with no wire ever opened.
+    x_share: a list of ints, an (n_in, 32) uint8 array, or a (K, n_in, 32) array for K input vectors of one R1CS (array
+    elements are residues below n).  -> (n_wires, 32) or (K, n_wires, 32) uint8, slot 0 = 1: what `prove` takes.
+
+    pynocchio.ShareSolvePlan orders the rows: for r = 0 .. D the linear rows of depth r run locally through
+    vmpc_bn256_r1cs_solve_batch_dev on the share vector (`wide_rows` as there), then for r < D the product rows of depth
+    r + 1 cost ONE exchange - the party multiplies its shares, deals the degree-2t product afresh with degree t
+    (vmpc_bn256_r1cs_share_mul_deal_dev; the product itself is stored nowhere), sends every party its row, and
+    recombines what arrives with the M-point weights (vmpc_bn256_r1cs_share_finish_dev).  Exactly plan.n_rounds
+    exchanges, whatever K is; a circuit without a product of shared values exchanges nothing.  A division by a shared
+    value is ShareSolvePlan's ValueError, raised before any device call or exchange.  Whether the inputs satisfy the
+    circuit's check rows is not tested here: prove(check=True) tests every row."""
+    arr, many = _input_share_rows(x_share)
+    K, n_in = arr.shape[0], arr.shape[1]
+    plan = pn.ShareSolvePlan(qap, n_in)
+    if K > _native.BN256_R1CS_MAX_WIT:
+        raise ValueError(f"calculate_witness_shares: {K} input vectors, one call takes {_native.BN256_R1CS_MAX_WIT}")
+    n_wires, M, t, D = qap.m + 1, rt.parties, rt.threshold, plan.n_rounds
+    host = np.zeros((K, n_wires, 32), np.uint8)
+    host[:, 0, 0] = 1
+    host[:, 1:n_in + 1] = arr
+    if K == 0:
+        return host
+    ctx = ctx or rt._context()
+    ptrs, _ = plan.device(ctx)
+    t0 = time.perf_counter()
+    dc, bad = ctx.upload(host), ctx.alloc(4 * K * (D + 1))
+    t0 = rt._stage("upload", t0)
+    for r in range(D + 1):
+        lv0, lv1 = int(plan.phase_ptr[r]), int(plan.phase_ptr[r + 1])
+        # L_r: a sub-range of the local level table, its device copy moved along; the call sets its K status words
+        ctx.bn256_r1cs_solve_batch(ptrs[:12] + [ptrs[12] + 4 * lv0], plan.local_level_ptr[lv0:lv1 + 1], n_in, qap.m,
+                                   dc.ptr, n_wires, K, wide_rows, bad.ptr + 4 * K * r)
+        t0 = rt._stage("local", t0)
+        if r == D:
+            break
+        r0, r1 = plan.round_rows(r + 1)
+        n_e = K * (r1 - r0)
+        coeffs = ctx.upload(random_residues(rt.rng, t * n_e)) if t else None
+        t0 = rt._stage("coeffs", t0)
+        table = ctx.alloc(32 * M * n_e)
+        ctx.bn256_r1cs_share_mul_deal(ptrs, r0, r1, qap.m, dc.ptr, n_wires, K, coeffs.ptr if t else None, t, M,
+                                      table.ptr, n_e)
+        t0 = rt._stage("mul_deal", t0)
+        dealt = ctx.download(table.ptr, 32 * M * n_e, (M, n_e, 32))
+        t0 = rt._stage("download", t0)
+        got = await rt.exchange_vectors([dealt[q] for q in range(M)])
+        t0 = rt._stage("exchange", t0)
+        parts = ctx.upload(np.ascontiguousarray(np.stack(got)))
+        t0 = rt._stage("upload", t0)
+        ctx.bn256_r1cs_share_finish(ptrs, r0, r1, qap.m, parts.ptr, M, n_e, rt.weights, dc.ptr, n_wires, K)
+        t0 = rt._stage("finish", t0)
+    ctx.sync()
+    words = ctx.download(bad.ptr, 4 * K * (D + 1)).view("<u4")
+    assert (words == 0xFFFFFFFF).all(), "a linear row failed: ShareSolvePlan leaves no divisor that can be zero"
+    out = ctx.download(dc.ptr, host.nbytes, host.shape)
+    rt._stage("download", t0)
+    return out if many else out[0]
+
+
+async def prove_inputs(rt, qap, key, x_share, zk=True, check=True):
+    """`prove` from shares of the inputs alone (the demo's whole flow): calculate_witness_shares on key.ctx, then prove
+    on the shares of the witness -> prove's (proof, c_client).  n_rounds + prove's exchanges in all."""
+    if not isinstance(key, pn.PreparedKey):
+        raise TypeError("trinocchio.prove_inputs: key must be a pynocchio.PreparedKey")
+    if isinstance(x_share, np.ndarray) and x_share.ndim == 3:
+        raise ValueError("trinocchio.prove_inputs: one input vector per proof")
+    c_share = await calculate_witness_shares(rt, qap, x_share, ctx=key.ctx)
+    return await prove(rt, qap, key, c_share, zk=zk, check=check)
 
 
 async def prove(rt, qap, key, c_share, zk=True, check=True):
