@@ -539,6 +539,12 @@ int vmpc_bn256_qap_h_combine_dev(vmpc_ctx *ctx, const void *A, const void *B, co
 /* first_bad[w] (n_wit device words) = witness w's smallest bad row, 0xffffffff if none; a, b, y share the stride */
 int vmpc_bn256_qap_check_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t stride, size_t d,
                                    uint32_t *first_bad, size_t n_wit);
+/* out[w] (n_wit consecutive device scalars) = sum_{j<d} rho^j (a_w[j] b_w[j] - y_w[j]) mod n: vmpc_bn256_qap_residual_dev
+ * for n_wit share vectors under ONE rho (a canonical residue in HOST memory, VMPC_E_NONCANON otherwise); a, b, y share
+ * the stride.  A batch with a violated row passes for at most n_wit d of the rho.  Arena:
+ * n_wit x at most 64 partials. */
+int vmpc_bn256_qap_residual_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t stride, size_t d,
+                                      const uint8_t rho[32], void *out, size_t n_wit);
 /* the scan of the factorial prefix products and the inversion ONCE, then one launch for the n_wit rows of ua (and ub) */
 int vmpc_bn256_qap_h_weights_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t d, void *ua,
                                        void *ub, size_t u_stride, size_t n_wit);
@@ -700,6 +706,20 @@ int vmpc_bn256_fr_share_mul_deal_dev(vmpc_ctx *ctx, const void *a, const void *b
  * VMPC_E_INVAL. */
 int vmpc_bn256_fr_share_combine_dev(vmpc_ctx *ctx, const void *parts, size_t parties, size_t n, size_t part_stride,
                                     const uint8_t *weights, const uint32_t *dst, const void *addend, void *out);
+
+/* out[e] = sum_{p < parties} weights[p] parts[p][e] for e < n, a sum of group elements: the recombination of the proof
+ * shares in the exponent (demos/demo_zkp_trinocchio.py:86-93; csrc/bn256_recombine.hip).  group 1
+ * (64-byte affine points) or 2 (128-byte); parts: `parties` rows of points in device memory, row p at
+ * parts + width p part_stride (part_stride in POINTS); all-zero bytes are the point at infinity, in and out; out: n
+ * canonical affine points, so the bytes do not depend on how the sum is organised.  weights: parties x 32 bytes in HOST
+ * memory, canonical residues mod n, passed to the kernel as arguments (a weight above n / 2 as its negative and a
+ * negated point).  Points are not validated (vmpc_bn256_validate_dev).  parties > VMPC_SHARE_MAX_PARTIES, n or
+ * part_stride above 2^31: VMPC_E_RANGE before any pointer is looked at; a weight >= n: VMPC_E_NONCANON at once;
+ * part_stride < n, another group, parties = 0 with n > 0, a null pointer where there is work: VMPC_E_INVAL; n = 0:
+ * VMPC_OK, no launch.  One lane per (party, element), the partial sums of a workgroup's wavefronts added through LDS in
+ * a fixed order; asynchronous on the context's stream, no arena, no atomics. */
+int vmpc_bn256_recombine_dev(vmpc_ctx *ctx, int group, const void *parts, size_t parties, size_t n, size_t part_stride,
+                             const uint8_t *weights /* HOST */, void *out);
 
 /* ---- The R1CS solve on shares mod n (demos/demo_zkp_trinocchio.py:70: qap.calculate_witness on secure values, one
  * MPyC multiplication per `*` line of the flat code, tools/code_to_r1cs.py:253-274; csrc/bn256_r1cs_share.hip, DESIGN.md

@@ -60,6 +60,7 @@ SYMBOLS = [
     "vmpc_fr_cs_triples_batch_dev", "vmpc_fr_cs_extend_batch_dev", "vmpc_fr_cs_extend_batch_bytes",
     "vmpc_bn256_r1cs_solve_batch_dev", "vmpc_bn256_r1cs_solve_launches",
     "vmpc_bn256_r1cs_share_mul_deal_dev", "vmpc_bn256_r1cs_share_finish_dev",
+    "vmpc_bn256_qap_residual_batch_dev", "vmpc_bn256_recombine_dev",
 ]
 
 
@@ -220,6 +221,8 @@ def load_library():
         "vmpc_bn256_fr_share_mul_deal_dev": (i32, [vp, vp, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_bn256_fr_share_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp, vp]),
         "vmpc_bn256_qap_residual_dev": (i32, [vp, vp, vp, vp, sz, vp, vp]),
+        "vmpc_bn256_qap_residual_batch_dev": (i32, [vp, vp, vp, vp, sz, sz, vp, vp, sz]),
+        "vmpc_bn256_recombine_dev": (i32, [vp, i32, vp, sz, sz, sz, vp, vp]),
         "vmpc_fr_cs_lagrange_dev": (i32, [vp, vp, sz, vp, vp]),
         "vmpc_fr_cs_colsum_dev": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_fr_cs_first_diff_dev": (i32, [vp, vp, vp, sz, vp]),
@@ -1128,6 +1131,21 @@ class Context:
         _check(self.lib.vmpc_bn256_qap_residual_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr),
                                                     ctypes.c_void_p(y_ptr), d, rb, ctypes.c_void_p(out_ptr)),
                "vmpc_bn256_qap_residual_dev")
+
+    def bn256_qap_residual_batch(self, a_ptr, b_ptr, y_ptr, stride, d, rho, out_ptr, n_wit):
+        """n_wit device scalars at out_ptr: bn256_qap_residual of n_wit rows `stride` scalars apart, under one rho"""
+        p = ctypes.c_void_p
+        rb = ctypes.create_string_buffer(scalar_to_bytes(rho), 32)
+        _check(self.lib.vmpc_bn256_qap_residual_batch_dev(self.handle, p(a_ptr), p(b_ptr), p(y_ptr), stride, d, rb,
+                                                          p(out_ptr), n_wit), "vmpc_bn256_qap_residual_batch_dev")
+
+    def bn256_recombine(self, group, parts_ptr, parties, n, part_stride, weights, out_ptr):
+        """out[e] = sum_p weights[p] parts[p][e] for n points of G1 (group 1) or the twist (2); parts: `parties` rows
+        of affine points, part_stride points apart; weights: ints below n; out: n affine points"""
+        wb = ctypes.create_string_buffer(b"".join(scalar_to_bytes(w) for w in weights), 32 * max(len(weights), 1))
+        _check(self.lib.vmpc_bn256_recombine_dev(self.handle, group, ctypes.c_void_p(parts_ptr), parties, n,
+                                                 part_stride, wb, ctypes.c_void_p(out_ptr)),
+               "vmpc_bn256_recombine_dev")
 
     def bn256_qap_t_coeffs(self, d, scratch_ptr, out_ptr):
         """out[0..d] = coefficients of prod_{j=1..d} (x - j); scratch: 2 (d + ceil(d / 128)) scalars"""

@@ -23,17 +23,19 @@
 //                                  inversion, as vmpc_bn256_qap_lagrange_dev does for its Q_j.
 //   vmpc_bn256_qap_check_dev       the smallest j with a_j b_j != y_j
 //   vmpc_bn256_qap_residual_dev    sum_j rho^j (a_j b_j - y_j): what a party holding SHARES of the witness computes in
-//                                  place of the check (its own rows never satisfy a_j b_j = y_j)
+//                                  place of the check (its own rows never satisfy a_j b_j = y_j);
+//                                  vmpc_bn256_qap_residual_batch_dev: K share vectors under ONE rho (section 24)
 //   vmpc_bn256_qap_t_coeffs_dev    the d + 1 coefficients of t = prod (x - j): leaves of QH_LEAF factors multiplied out
 //                                  in LDS, then a product tree over vmpc_bn256_fr_poly_mul_dev
 //   vmpc_bn256_qap_horner_dev      P(1), .., P(d) of coefficient vectors (the dense QAP form), one lane per point
 //   vmpc_bn256_qap_h_combine_dev   moments, t, deltas -> h (the halves that it reads of two products, through
 //                                  vmpc_bn256_fr_poly_mul_batch_dev)
 //
-// For K witnesses of one QAP the moments, the weights, the check and the combination have a
-// *_batch_dev entry with rows a stride apart.  Each of these stages is ONE kernel with the witness on the grid's last
-// dimension and ONE static host function (qh_moments, qh_weights, qh_check, qh_combine) that plans, reserves and
-// launches; the single entry and the batch entry check their own arguments and call it, the single one with K = 1.
+// For K witnesses of one QAP the moments, the weights, the check, the residual (section 24) and
+// the combination have a *_batch_dev entry with rows a stride apart.  Each of these stages is ONE kernel with the
+// witness on the grid's last dimension and ONE static host function (qh_moments, qh_weights, qh_check, qh_residual,
+// qh_combine) that plans, reserves and launches; the single entry and the batch entry check their own arguments and
+// call it, the single one with K = 1.
 // The check writes one word per witness, the weights run their scan and inversion ONCE, the moments count K when they
 // cut j into ranges (a large batch: one range, one partial per k), and the combination asks
 // vmpc_bn256_fr_poly_mul_batch_dev only for P[0 .. d-2] and Q[d-1 .. 2d-2] of its two products.
@@ -379,15 +381,18 @@ struct qh_scalar {
     uint32_t v[8];
 };
 
-// part[g] = sum over workgroup g's rows i of rho^i (a_i b_i - y_i) mod n, the row at the point j = i + 1 carrying rho^i.
-// Lane L of the grid owns the rows L, L + S, L + 2S, .. (S = all lanes): it starts its power at rho^L (square and
-// multiply) and advances it by rho^S (`step`, from the host), adding the unreduced products into its own f256_acc
-// (at most 2^20 / S of them), reduced once.  The workgroup's 256 residues are added through LDS in a fixed tree.
+// grid (workgroups, witnesses).  part[w groups + g] = sum over workgroup g's rows i of witness w of rho^i (a_i b_i - y_i)
+// mod n, the row at the point j = i + 1 carrying rho^i (rows `stride` scalars apart; ONE rho for every witness).
+// Lane L of a witness's lanes owns the rows L, L + S, L + 2S, .. (S = all lanes of one witness): it starts its power at
+// rho^L (square and multiply) and advances it by rho^S (`step`, from the host), adding the unreduced products into its
+// own f256_acc (at most 2^20 / S of them), reduced once.  The workgroup's 256 residues are added through LDS in a fixed
+// tree.
 __global__ void __launch_bounds__(QH_WG)
 k_qh_residual(uint32_t d, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ y,
-              qh_scalar rho, qh_scalar step, uint32_t *__restrict__ part) {
+              size_t stride, qh_scalar rho, qh_scalar step, uint32_t *__restrict__ part) {
     __shared__ frbn sR[QH_WG];
     const uint32_t t = threadIdx.x, first = blockIdx.x * QH_WG + t, S = gridDim.x * QH_WG;
+    const size_t w = blockIdx.y, off = 8 * w * stride;
     frbn r = frbn_zero();
     if (first < d) {
         const frbn rh = f256_copy<frbn>(rho.v), st = f256_copy<frbn>(step.v);
@@ -400,7 +405,8 @@ k_qh_residual(uint32_t d, const uint32_t *__restrict__ a, const uint32_t *__rest
         }
         frbn_acc acc = frbn_acc_zero();
         for (uint32_t i = first; i < d; i += S) {
-            const frbn e = frbn_sub(frbn_mul(f256_ld<frbn>(a, i), f256_ld<frbn>(b, i)), f256_ld<frbn>(y, i));
+            const frbn e = frbn_sub(frbn_mul(f256_ld<frbn>(a + off, i), f256_ld<frbn>(b + off, i)),
+                                    f256_ld<frbn>(y + off, i));
             frbn_acc_mac(acc, pw.v, e.v);
             pw = frbn_mul(pw, st);
         }
@@ -412,19 +418,18 @@ k_qh_residual(uint32_t d, const uint32_t *__restrict__ a, const uint32_t *__rest
         if (t < h) sR[t] = frbn_add(sR[t], sR[t + h]);
         __syncthreads();
     }
-    if (t == 0) f256_st(part, blockIdx.x, sR[0]);
+    if (t == 0) f256_st(part, w * gridDim.x + blockIdx.x, sR[0]);
 }
 
-extern "C" int vmpc_bn256_qap_residual_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t d,
-                                           const uint8_t rho[32], void *out) {
-    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
-    if (!ctx || !a || !b || !y || !rho || !out || d == 0) return VMPC_E_INVAL;
+// n_wit >= 1 witnesses, checked by the entries; one witness may come with stride 0.  out: n_wit consecutive scalars.
+static int qh_residual(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t stride, size_t d,
+                       const uint8_t rho[32], void *out, size_t n_wit) {
     qh_scalar r, step;
     memcpy(r.v, rho, 32);
     if (f256_geq_m<frbn>(r.v)) return VMPC_E_NONCANON;
     size_t groups = (d + QH_WG - 1) / QH_WG;
     if (groups > QH_RES_MAX_WGS) groups = QH_RES_MAX_WGS;
-    // rho^S for the S = groups x 256 lanes, on the host (S has one or two bits set above the eighth)
+    // rho^S for the S = groups x 256 lanes of a witness, on the host (S has one or two bits set above the eighth)
     frbn pw = frbn_one();
     const frbn rh = f256_copy<frbn>(r.v);
     for (int bit = 31; bit >= 0; bit--) {
@@ -433,20 +438,39 @@ extern "C" int vmpc_bn256_qap_residual_dev(vmpc_ctx *ctx, const void *a, const v
     }
     memcpy(step.v, pw.v, 32);
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
-    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(groups * 32) + 256));
-    uint32_t *part = (uint32_t *)vmpc_ws_take(ctx, groups * 32);
+    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align(n_wit * groups * 32) + 256));
+    uint32_t *part = (uint32_t *)vmpc_ws_take(ctx, n_wit * groups * 32);
     {
         vmpc_stage_scope sc(ctx, "bn_qap_residual");
-        k_qh_residual<<<(unsigned)groups, QH_WG, 0, ctx->stream>>>((uint32_t)d, (const uint32_t *)a, (const uint32_t *)b,
-                                                                  (const uint32_t *)y, r, step, part);
+        k_qh_residual<<<dim3((unsigned)groups, (unsigned)n_wit), QH_WG, 0, ctx->stream>>>(
+            (uint32_t)d, (const uint32_t *)a, (const uint32_t *)b, (const uint32_t *)y, stride, r, step, part);
         VMPC_KERNEL_CHECK();
     }
     {
         vmpc_stage_scope sc(ctx, "bn_qap_residual_sum");
-        k_qh_partsum<<<1, 256, 0, ctx->stream>>>(part, nullptr, 1, (uint32_t)groups, (uint32_t *)out, nullptr, 0);
+        k_qh_partsum<<<dim3(1, (unsigned)n_wit), 256, 0, ctx->stream>>>(part, nullptr, 1, (uint32_t)groups,
+                                                                        (uint32_t *)out, nullptr, 1);
         VMPC_KERNEL_CHECK();
     }
     return VMPC_OK;
+}
+
+extern "C" int vmpc_bn256_qap_residual_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y, size_t d,
+                                           const uint8_t rho[32], void *out) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !y || !rho || !out || d == 0) return VMPC_E_INVAL;
+    return qh_residual(ctx, a, b, y, 0, d, rho, out, 1);
+}
+
+extern "C" int vmpc_bn256_qap_residual_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, const void *y,
+                                                 size_t stride, size_t d, const uint8_t rho[32], void *out,
+                                                 size_t n_wit) {
+    if (d + 1 > VMPC_BN256_FR_POLY_MAX || n_wit > VMPC_BN256_QAP_MAX_WIT || stride > QH_MAX_STRIDE ||
+        (n_wit && stride < d))
+        return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !y || !rho || !out || d == 0) return VMPC_E_INVAL;
+    if (n_wit == 0) return VMPC_OK;
+    return qh_residual(ctx, a, b, y, stride, d, rho, out, n_wit);
 }
 
 // ---- t's coefficients -----------------------------------------------------------------------------------------------

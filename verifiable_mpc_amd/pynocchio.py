@@ -1509,6 +1509,98 @@ def _h_batch_chunk(ctx, qap, arr, deltas, first, plan, top, t, out_ptr, out_stri
     del dc, aby, coef, bad, dd
 
 
+# ---- h for K SHARE vectors of one QAP (trinocchio.prove_batch) ---------------------------------
+
+def _share_batch_args(qap, c_shares, delta_shares, who):
+    """the host half of compute_h_share_batch, which needs no device: -> ((K, n_wires, 32) array, deltas) with deltas
+    None, a device buffer of 3 K scalars, or a list of K objects; ValueError for a wrong width or a wrong count"""
+    d = int(qap.d)
+    if d + 1 > _native.BN256_FR_POLY_MAX:
+        raise ValueError(f"{who}: d + 1 = {d + 1} exceeds the polynomial product's cap {_native.BN256_FR_POLY_MAX}")
+    arr = witness_batch_array(len(qap.indices), c_shares, qap.indices)
+    K = len(arr)
+    if delta_shares is not None:
+        if hasattr(delta_shares, "ptr"):       # a device buffer (its bytes) or a device vector (its scalars)
+            have = delta_shares.nbytes // 32 if hasattr(delta_shares, "nbytes") else len(delta_shares)
+        else:
+            delta_shares = list(delta_shares)
+            have = 3 * len(delta_shares)
+        if have != 3 * K:
+            raise ValueError(f"{who}: one set of three deltas per witness ({have} scalars for {K} witnesses)")
+    return arr, delta_shares
+
+
+def _upload_row_values_batch(ctx, qap, arr):
+    """K share vectors (a (K, n_wires, 32) array, K >= 1) on the device in ONE upload and their row values, K rows
+    a || b || y of 3 d scalars, by K queued runs of the single path's plan -> (buffer, what must outlive the stream's work
+    on it).  _upload_row_values for K vectors: trinocchio.prove_batch reads the rows for the residual and for h."""
+    K, n_wires, d = len(arr), arr.shape[1], int(qap.d)
+    dc = ctx.upload(arr) if n_wires else ctx.alloc(32)
+    aby = ctx.alloc(32 * 3 * d * K)
+    if isinstance(qap, R1CSQAP):
+        plan = _per_ctx(qap, "rows", ctx, lambda: _row_plan(ctx, qap))
+        for w in range(K):
+            plan.run(dc.ptr + 32 * n_wires * w, n_wires, aby.ptr + 32 * 3 * d * w)
+        return aby, (dc,)
+    plan, top = _per_ctx(qap, "coeffs", ctx, lambda: _coeff_plan(ctx, qap))
+    coef = ctx.alloc(32 * 3 * top * K)
+    for w in range(K):
+        plan.run(dc.ptr + 32 * n_wires * w, n_wires, coef.ptr + 32 * 3 * top * w)
+        ctx.bn256_qap_horner(coef.ptr + 32 * 3 * top * w, top, 3, d, aby.ptr + 32 * 3 * d * w)
+    return aby, (dc, coef)
+
+
+def batch_ranges(qap, K):
+    """[(start, stop), ..]: the K witnesses of a batch as compute_h_batch cuts them - plan_chunks under
+    BATCH_BUDGET_BYTES, each chunk in pieces of at most BN256_QAP_MAX_WIT (the witness is a grid dimension).  Pure."""
+    d, n_wires = int(qap.d), len(qap.indices)
+    top = 0
+    if not isinstance(qap, R1CSQAP):
+        top = max([len(p.coeffs if hasattr(p, "coeffs") else p) for polys in (qap.v, qap.w, qap.y) for p in polys] + [1])
+    out = []
+    for lo, hi in plan_chunks(K, BATCH_BUDGET_BYTES, lambda n: h_batch_bytes(d, n_wires, top, n)):
+        n = min(hi - lo, _native.BN256_QAP_MAX_WIT)
+        out += [(a, min(a + n, hi)) for a in range(lo, hi, n)]
+    return out
+
+
+def _h_from_row_values_batch(ctx, qap, aby, keep, dd, K):
+    """K rows of row values -> K HPoly views into one buffer; dd: device buffer of the rows' three deltas each, or None.
+    The weights, moments and combination run once per range of batch_ranges; a boundary changes no value."""
+    d = int(qap.d)
+    t = _t_coeffs(ctx, qap)
+    stride = d + 1
+    out = ctx.alloc(32 * stride * K)
+    for lo, hi in batch_ranges(qap, K):
+        _h_rows(ctx, d, t, aby.ptr + 32 * 3 * d * lo, hi - lo,
+                _BufferView(dd, 96 * lo, 96 * (hi - lo)) if dd is not None else None, out.ptr + 32 * stride * lo, stride)
+    del keep
+    n_h = d + 1 if dd is not None else max(d - 1, 0)
+    return [HPoly(ctx, _BufferView(out, 32 * stride * w, 32 * stride), n_h) for w in range(K)]
+
+
+def compute_h_share_batch(qap, c_shares, delta_shares=None, ctx=None):
+    """[compute_h_share(qap, c_shares[w], delta_shares[w]) for w in range(K)], coefficient for coefficient and length
+    included, with every stage run once for all K: ONE upload, K queued runs of the row-value plan, then the weights, the
+    moments and the combination of compute_h_batch (csrc/bn256_qap_h.hip's *_batch_dev entries) - no constraint check (a
+    share vector never satisfies a_j b_j = y_j) and no host read-back before the result.  c_shares: one party's K share
+    vectors as a (K, n_wires, 32) uint8 array, or K vectors as compute_h_share takes them; delta_shares: None, a device
+    buffer of 3 K scalars (witness w's delta_v, delta_w, delta_y at 3 w .. 3 w + 2), or K objects with .v .w .y.  -> a list
+    of K HPoly, each a view into ONE device buffer of K rows of d + 1 scalars.
+    K is cut as compute_h_batch cuts it (batch_ranges: plan_chunks over h_batch_bytes under BATCH_BUDGET_BYTES); the
+    share vectors and their row values, n_wires + 3 d scalars per witness, stay on the device for the whole batch."""
+    arr, deltas = _share_batch_args(qap, c_shares, delta_shares, "compute_h_share_batch")
+    K = len(arr)
+    if K == 0:
+        return []
+    ctx = ctx or get_context()
+    dd = deltas
+    if deltas is not None and not hasattr(deltas, "ptr"):
+        dd = _scalar_buf(ctx, [getattr(dl, name) for dl in deltas for name in _DELTAS])
+    aby, keep = _upload_row_values_batch(ctx, qap, arr)
+    return _h_from_row_values_batch(ctx, qap, aby, keep, dd, K)
+
+
 # ---- the witness from the inputs (code_to_qap.QAP.calculate_witness; csrc/bn256_r1cs_solve.hip, DESIGN.md section 22) ----
 
 KIND_CHECK, KIND_Y, KIND_A, KIND_B = 0, 1, 2, 3

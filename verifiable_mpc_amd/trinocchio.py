@@ -31,6 +31,12 @@ need no communication run locally, every multiplicative depth of the circuit cos
 section 23), and `prove_inputs` is the two in a row.  In the clear the witness comes from pynocchio.calculate_witness /
 calculate_witness_batch.
 
+    K witnesses of one QAP        prove_batch, prove_inputs_batch
+
+`prove_batch` is `prove` for K witnesses in the SAME exchanges: one deal round, rho opened once, the K masked residuals
+opened together, one exchange of the 8 K proof-share points.  The recombination in the exponent - of one proof or of K -
+is one vmpc_bn256_recombine_dev launch per group (`Runtime.recombine_points`, csrc/bn256_recombine.hip).
+
 Out of scope:
   * a division by a shared value in the witness computation on shares (it needs an inversion protocol with two more
     exchanges; pynocchio.ShareSolvePlan refuses such a circuit), inputs that are partly public, and parties that
@@ -206,6 +212,36 @@ class Runtime(PartyRuntime):
         n = len(scalars)
         return pts, (self._recombined([part[1] for part in every], n, self._context()) if n else [])
 
+    def recombine_points(self, every, ctx=None):
+        """The M parties' lists of n points each (exchange_points' result: element e of every list in one group) ->
+        the n sums  sum_p weights[p] every[p][e]  in the exponent, as points.  The G1 and the twist elements are packed
+        into one (M, n_g, width) table each: one upload, one validation (a point off its curve raises VmpcError with
+        E_NOTONCURVE, as pynocchio.msm does), one vmpc_bn256_recombine_dev launch per group, ONE synchronisation and
+        one download each."""
+        ctx, M = ctx or self._context(), self.parties
+        if len(every) != M:
+            raise ValueError(f"recombine_points: {len(every)} lists of points for {M} parties")
+        groups = [p.group for p in every[0]]
+        if any([p.group for p in part] != groups for part in every[1:]):
+            raise ValueError("recombine_points: the parties' lists differ in length or in their points' groups")
+        out, pending = [None] * len(groups), []
+        for cls in (pn.BN256Point, pn.BN256TwistPoint):
+            ix = [i for i, g in enumerate(groups) if g == cls.group]
+            if not ix:
+                continue
+            table = np.frombuffer(b"".join(part[i].to_bytes() for part in every for i in ix), np.uint8)
+            parts, res = ctx.upload(table), ctx.alloc(cls.width * len(ix))
+            if ctx.bn256_validate(cls.group, parts.ptr, M * len(ix)):
+                raise _native.VmpcError(_native.E_NOTONCURVE, "trinocchio.recombine_points")
+            ctx.bn256_recombine(cls.group, parts.ptr, M, len(ix), len(ix), self.weights, res.ptr)
+            pending.append((cls, ix, parts, res))
+        ctx.sync()
+        for cls, ix, _, res in pending:
+            raw = ctx.download(res.ptr, cls.width * len(ix)).tobytes()
+            for k, i in enumerate(ix):
+                out[i] = cls.from_bytes(raw[cls.width * k:cls.width * (k + 1)])
+        return out
+
 
 class _Zeros:
     """the zero sharings a party received in one deal round: M rows of `n` scalars at column `offset` of `parts`"""
@@ -374,7 +410,105 @@ async def prove(rt, qap, key, c_share, zk=True, check=True):
     out_ix = int(qap.out_ix)
     every, opened = await rt.exchange_points([share[k] for k in names], np.ascontiguousarray(c_arr[1:out_ix + 1]))
     t0 = time.perf_counter()
-    proof = {k: pn.msm(rt.weights, [part[i] for part in every], ctx) for i, k in enumerate(names)}
-    rt._stage("exchange", t0)
+    proof = dict(zip(names, rt.recombine_points(every, ctx)))
+    rt._stage("recombine", t0)
     return proof, [1] + opened
+
+
+async def prove_batch(rt, qap, key, c_shares, zk=True, check=True):
+    """`prove` for K witnesses of one QAP in the exchanges of ONE: 4 with the check, 2 without, 1 when there is nothing to
+    deal, whatever K is.  c_shares: this party's degree-t shares of the K witnesses, a (K, n_wires, 32) uint8 array or K
+    vectors as `prove` takes them.  -> a list of K (proof, c_client) pairs, proof w with the keys and point types of
+    pynocchio.compute_proof's result; every party returns the same list (K = 0: [] and no exchange).
+
+    One deal round carries 3 K deltas (witness w's at the random shares 3 w .. 3 w + 2) and rho with degree t, and
+    K residual masks and K n_h masks of h with degree 2t - with K = 1 `prove`'s layout.  rho is opened once, after every
+    share it tests is fixed; the K residuals of one vmpc_bn256_qap_residual_batch_dev launch are masked in one
+    combination and opened in ONE exchange.  If any is not zero every party raises
+    ValueError("inconsistent shares: witness w"), w the lowest such witness, before a proof share leaves.  One rho for K
+    witnesses: a batch with a wrong witness passes with probability at most K d / n (each witness's residual is a
+    nonzero polynomial of degree below d in rho, the union bound over the witnesses).  Then compute_h_share_batch's
+    stages on the row values that the residual read, one combination for the masks where h's rows are contiguous
+    (zk: d + 1 of d + 1 scalars), pynocchio.compute_proof_batch, ONE exchange of the 8 K points with the K out_ix shares
+    of the I/O wires, and one recombination launch per group (Runtime.recombine_points)."""
+    if not isinstance(key, pn.PreparedKey):
+        raise TypeError("trinocchio.prove_batch: key must be a pynocchio.PreparedKey")
+    arr, _ = pn._share_batch_args(qap, c_shares, None, "trinocchio.prove_batch")
+    K, d = len(arr), int(qap.d)
+    if K == 0:
+        return []
+    ctx, M = key.ctx, rt.parties
+    assert rt._context() is ctx, "the runtime and the prepared key share one context"
+    n_h = d + 1 if zk else max(d - 1, 0)
+    n_delta, n_check = (3 * K if zk else 0), (1 if check else 0)
+    # 1. all dealt randomness in one exchange: deltas and rho with degree t, zeros (K residuals, K h) with degree 2t
+    rand, zeros = await rt._deal_round(n_delta + n_check, K * (n_check + n_h))
+    t0 = time.perf_counter()
+    aby, keep = pn._upload_row_values_batch(ctx, qap, arr)
+    t0 = rt._stage("h_share", t0)
+    if check:
+        # 2. rho is opened only now: the shares it tests were fixed before anybody knew it
+        rho = (await rt.output(rand[n_delta:]))[0]
+        t0 = time.perf_counter()
+        res = ScalarVector.empty(K, ctx)
+        for lo in range(0, K, _native.BN256_QAP_MAX_WIT):
+            n = min(K - lo, _native.BN256_QAP_MAX_WIT)
+            row = aby.ptr + 32 * 3 * d * lo
+            ctx.bn256_qap_residual_batch(row, row + 32 * d, row + 64 * d, 3 * d, d, rho, res.ptr + 32 * lo, n)
+        # 3. K degree-2t shares of 0 for satisfying witnesses, opened together under K zero sharings
+        masked = rt.masked(zeros, 0, res.ptr, K)
+        rt._stage("residual", t0)
+        opened = await rt.output(masked)
+        bad = [w for w, v in enumerate(opened) if v != 0]
+        if bad:
+            raise ValueError(f"inconsistent shares: witness {bad[0]}")
+        t0 = time.perf_counter()
+    deltas = None
+    if zk:
+        dv = rand[:n_delta].to_ints()            # this party's own shares: compute_proof_batch takes them from the host
+        deltas = [types.SimpleNamespace(v=dv[3 * w], w=dv[3 * w + 1], y=dv[3 * w + 2]) for w in range(K)]
+    hs = pn._h_from_row_values_batch(ctx, qap, aby, keep, rand[:n_delta] if zk else None, K)
+    t0 = rt._stage("h_share", t0)
+    if n_h:
+        # h's K rows lie d + 1 scalars apart: with the deltas they are contiguous and one combination masks them all
+        stride, ones = d + 1, [1] * M
+        first = zeros.parts.ptr + 32 * (zeros.offset + K * n_check)
+        hm = ctx.alloc(32 * stride * K)
+        if n_h == stride:
+            ctx.bn256_share_combine(first, M, K * n_h, zeros.stride, ones, None, hs[0].buf.ptr, hm.ptr)
+        else:
+            for w in range(K):
+                ctx.bn256_share_combine(first + 32 * n_h * w, M, n_h, zeros.stride, ones, None, hs[w].buf.ptr,
+                                        hm.ptr + 32 * stride * w)
+        hs = [pn.HPoly(ctx, pn._BufferView(hm, 32 * stride * w, 32 * stride), n_h) for w in range(K)]
+    t0 = rt._stage("masks", t0)
+    shares = pn.compute_proof_batch(qap, arr, hs, key, deltas)
+    rt._stage("proof_share", t0)
+    # 4. the 8 K points and this party's shares of the K witnesses' I/O wires, one exchange
+    names = list(shares[0])
+    out_ix = int(qap.out_ix)
+    io = np.ascontiguousarray(arr[:, 1:out_ix + 1]).reshape(K * out_ix, 32)
+    every, opened = await rt.exchange_points([share[k] for share in shares for k in names], io)
+    t0 = time.perf_counter()
+    flat = rt.recombine_points(every, ctx)
+    rt._stage("recombine", t0)
+    e = len(names)
+    return [(dict(zip(names, flat[e * w:e * (w + 1)])), [1] + opened[out_ix * w:out_ix * (w + 1)]) for w in range(K)]
+
+
+async def prove_inputs_batch(rt, qap, key, x_shares, zk=True, check=True):
+    """`prove_batch` from shares of the inputs alone: calculate_witness_shares on key.ctx for the K input vectors (a
+    (K, n_in, 32) uint8 array, or K vectors of ints), then prove_batch on the shares of the K witnesses -> prove_batch's
+    list.  n_rounds + prove_batch's exchanges for all K."""
+    if not isinstance(key, pn.PreparedKey):
+        raise TypeError("trinocchio.prove_inputs_batch: key must be a pynocchio.PreparedKey")
+    if not (isinstance(x_shares, np.ndarray) and x_shares.ndim == 3):
+        rows = [pn.scalars_to_array(x if isinstance(x, np.ndarray) else [int(v) for v in x]) for x in x_shares]
+        if len({r.shape for r in rows}) > 1:
+            raise ValueError("trinocchio.prove_inputs_batch: the input vectors differ in length")
+        x_shares = np.stack(rows) if rows else np.zeros((0, 0, 32), np.uint8)
+    if len(x_shares) == 0:
+        return []
+    c_shares = await calculate_witness_shares(rt, qap, x_shares, ctx=key.ctx)
+    return await prove_batch(rt, qap, key, c_shares, zk=zk, check=check)
 
