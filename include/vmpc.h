@@ -71,6 +71,16 @@ int vmpc_ctx_get_short_path(vmpc_ctx *ctx, int *on);       /* the current settin
  * every call that would have to grow the workspace or the pinned block must then fail with VMPC_E_INVAL instead of
  * synchronising a stream that waits on the calling thread */
 int vmpc_ctx_debug_hold_wait(vmpc_ctx *ctx, int on);
+/* test hooks: enqueue a kernel that keeps a stream busy for about `microseconds` and touches no memory (one 64-lane
+ * workgroup, one lane polling the 100-MHz constant-rate counter with s_sleep between polls, and a bound on the number
+ * of polls - 4 per requested microsecond + 64, each under 2048 shader clocks - that ends it even if the counter
+ * stands still).  Work enqueued behind it stays pending while the host enqueues its consumer on another stream: the
+ * cross-stream ordering tests (tests/stream_order_cases.py) delay a producer or a consumer with it.  The first form
+ * delays the context's stream, the second any stream of `device` (a vmpc_stream_create bucket stream).
+ * microseconds > 20000: VMPC_E_RANGE, nothing is launched; 0: VMPC_OK, nothing is launched.  Not for production
+ * paths: nothing in the library calls them. */
+int vmpc_ctx_debug_delay(vmpc_ctx *ctx, unsigned microseconds);
+int vmpc_stream_debug_delay(void *hip_stream, int device, unsigned microseconds);
 /* non-blocking: *done = 1 when everything enqueued on the context's stream has completed (a driver that keeps
  * several commitments in flight refills whichever context finishes first) */
 int vmpc_ctx_query(vmpc_ctx *ctx, int *done);

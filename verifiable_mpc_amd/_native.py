@@ -26,7 +26,7 @@ SCALAR_BYTES, AFFINE_BYTES, PROJ_BYTES, EXT_BYTES = 32, 64, 96, 128
 # against the header and against the built library)
 SYMBOLS = [
     "vmpc_backend_info", "vmpc_last_error", "vmpc_ctx_create", "vmpc_ctx_destroy",
-    "vmpc_ctx_set_stream", "vmpc_ctx_sync", "vmpc_ctx_set_short_path", "vmpc_ctx_get_short_path", "vmpc_ctx_debug_hold_wait", "vmpc_ctx_query", "vmpc_ctx_wait_for", "vmpc_malloc", "vmpc_free", "vmpc_memcpy_h2d",
+    "vmpc_ctx_set_stream", "vmpc_ctx_sync", "vmpc_ctx_set_short_path", "vmpc_ctx_get_short_path", "vmpc_ctx_debug_hold_wait", "vmpc_ctx_debug_delay", "vmpc_stream_debug_delay", "vmpc_ctx_query", "vmpc_ctx_wait_for", "vmpc_malloc", "vmpc_free", "vmpc_memcpy_h2d",
     "vmpc_memcpy_d2h", "vmpc_memcpy_d2d", "vmpc_ctx_profile", "vmpc_ctx_profile_read",
     "vmpc_ctx_set_window", "vmpc_ed25519_msm_plan", "vmpc_msm_sort_view", "vmpc_ed25519_madd_rate", "vmpc_ed25519_msm", "vmpc_ed25519_fold",
     "vmpc_ed25519_fixed_base_batch", "vmpc_fr_axpy", "vmpc_fr_dot", "vmpc_points_validate_dev",
@@ -116,6 +116,8 @@ def load_library():
         "vmpc_ctx_set_short_path": (i32, [vp, i32]),
         "vmpc_ctx_get_short_path": (i32, [vp, ctypes.POINTER(ctypes.c_int)]),
         "vmpc_ctx_debug_hold_wait": (i32, [vp, i32]),
+        "vmpc_ctx_debug_delay": (i32, [vp, ctypes.c_uint]),
+        "vmpc_stream_debug_delay": (i32, [vp, i32, ctypes.c_uint]),
         "vmpc_ctx_query": (i32, [vp, ctypes.POINTER(i32)]),
         "vmpc_ctx_wait_for": (i32, [vp, vp]),
         "vmpc_malloc": (i32, [vp, sz, ctypes.POINTER(vp)]),
@@ -627,6 +629,10 @@ class Context:
     def wait_for(self, other):
         """device-side ordering: this context's stream waits for `other`'s work so far"""
         _check(self.lib.vmpc_ctx_wait_for(self.handle, other.handle), "vmpc_ctx_wait_for")
+
+    def debug_delay(self, usec):
+        """test hook: keep this context's stream busy for about `usec` microseconds (at most 20000; touches no memory)"""
+        _check(self.lib.vmpc_ctx_debug_delay(self.handle, int(usec)), "vmpc_ctx_debug_delay")
 
     def set_stream(self, stream_ptr):
         _check(self.lib.vmpc_ctx_set_stream(self.handle, ctypes.c_void_p(stream_ptr)),
@@ -1304,7 +1310,11 @@ class SharedStream:
         self.lib = load_library()
         h = ctypes.c_void_p()
         _check(self.lib.vmpc_stream_create(int(device), int(priority), ctypes.byref(h)), "vmpc_stream_create")
-        self.handle = h
+        self.handle, self.device = h, int(device)
+
+    def debug_delay(self, usec):
+        """test hook: keep this stream busy for about `usec` microseconds (Context.debug_delay for a shared stream)"""
+        _check(self.lib.vmpc_stream_debug_delay(self.handle, self.device, int(usec)), "vmpc_stream_debug_delay")
 
     def close(self):
         if self.handle:

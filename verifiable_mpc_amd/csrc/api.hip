@@ -187,6 +187,51 @@ extern "C" int vmpc_ctx_debug_hold_wait(vmpc_ctx *ctx, int on) {
     return VMPC_OK;
 }
 
+// Test hook for cross-stream ordering (tests/stream_order_cases.py): a kernel that keeps a stream busy for a requested
+// time, so that whatever is enqueued behind it is still pending while the host goes on to enqueue the consumer on
+// another stream - a missing wait between the two then shows as a wrong result instead of passing by luck.
+// One 64-lane workgroup; lane 0 polls the constant-rate counter (s_memrealtime, 100 MHz) with an s_sleep between two
+// polls, the other lanes leave at once; no memory traffic.  Two independent bounds end it: the counter, and the number
+// of polls.  A poll is s_sleep 16 (64 x 16 = 1024 clocks) + the counter's round trip + the loop, under 2048 clocks:
+//   at the 2.4-GHz peak clock a poll takes >= 1024 / 2400 us = 0.43 us, so VMPC_DEBUG_DELAY_POLLS_PER_US = 4 polls per
+//     requested microsecond (+ 64) never end a delay before the counter does;
+//   at the lowest shader clock of the part's power states (500 MHz) a poll takes < 2048 / 500 us = 4.1 us, so a kernel
+//     whose counter never advances still ends within (4 * microseconds + 64) * 4.1 us: 33 ms for 2000 us, 0.33 s at
+//     the cap.
+#define VMPC_DEBUG_DELAY_MAX_US 20000u
+#define VMPC_DEBUG_DELAY_POLLS_PER_US 4u
+__global__ __launch_bounds__(64) void k_debug_delay(uint32_t ticks, uint32_t max_polls) {
+    if (threadIdx.x != 0) return;
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    for (uint32_t i = 0; i < max_polls; i++) {
+        if (__builtin_amdgcn_s_memrealtime() - t0 >= (uint64_t)ticks) break;
+        __builtin_amdgcn_s_sleep(16);
+    }
+}
+
+extern "C" int vmpc_stream_debug_delay(void *hip_stream, int device, unsigned microseconds) {
+    if (!hip_stream) return VMPC_E_INVAL;
+    if (microseconds > VMPC_DEBUG_DELAY_MAX_US) {
+        snprintf(vmpc_err_buf, sizeof vmpc_err_buf, "debug delay of %u us: the cap is %u us", microseconds,
+                 VMPC_DEBUG_DELAY_MAX_US);
+        return VMPC_E_RANGE;
+    }
+    if (microseconds == 0) return VMPC_OK;
+    VMPC_HIP_CHECK(hipSetDevice(device));
+    k_debug_delay<<<1, 64, 0, (hipStream_t)hip_stream>>>(microseconds * 100u,
+                                                          microseconds * VMPC_DEBUG_DELAY_POLLS_PER_US + 64u);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_ctx_debug_delay(vmpc_ctx *ctx, unsigned microseconds) {
+    if (!ctx) return VMPC_E_INVAL;
+    if (microseconds == 0 || microseconds > VMPC_DEBUG_DELAY_MAX_US)       // nothing to launch: OK or VMPC_E_RANGE
+        return vmpc_stream_debug_delay((void *)ctx->stream, ctx->device, microseconds);
+    vmpc_stage_scope s(ctx, "debug_delay");    // (vmpc_ctx_profile times it: how the tests check the delay's length)
+    return vmpc_stream_debug_delay((void *)ctx->stream, ctx->device, microseconds);
+}
+
 extern "C" int vmpc_ctx_set_short_path(vmpc_ctx *ctx, int on) {
     if (!ctx) return VMPC_E_INVAL;
     ctx->short_path = on ? 1 : 0;
