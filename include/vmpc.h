@@ -464,6 +464,32 @@ int vmpc_bn256_fr_poly_mul_batch_dev(vmpc_ctx *ctx, const void *a, size_t a_stri
                                      size_t b_stride, size_t nb, size_t k_lo, size_t k_cnt, void *out, size_t out_stride,
                                      size_t n_wit);
 size_t vmpc_bn256_fr_poly_mul_batch_bytes(size_t na, size_t nb, size_t k_lo, size_t k_cnt, size_t n_wit);
+/* The same products in O(d log d), by an NTT over the INTEGERS (csrc/bn256_ntt.hip; GF(n) itself has none): the
+ * coefficients - any 32-byte values, not reduced first - are convolved modulo 18 primes c 2^22 + 1 < 2^31, the exact
+ * integer coefficient (< 2^20 2^512 < the primes' product) is rebuilt by Garner's digits and reduced mod n.  The three
+ * entries take the arguments, caps and answers of the three above and write the same canonical residues, bit for bit;
+ * only the window's scalars of a row are written, the transforms are whole (length: the power of two >= na + nb - 1).
+ * Arena: the residues of b and of a group of a rows; n_wit is cut into groups so that it stays below 1 GiB
+ * (vmpc_ctx_set_ntt_arena_cap lowers the cap: what the tests of the group boundary do; 0 restores it). */
+int vmpc_bn256_fr_poly_mul_ntt_dev(vmpc_ctx *ctx, const void *a, size_t na, const void *b, size_t nb, void *out);
+int vmpc_bn256_fr_poly_mul_ntt_batch_dev(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b,
+                                         size_t b_stride, size_t nb, size_t k_lo, size_t k_cnt, void *out,
+                                         size_t out_stride, size_t n_wit);
+size_t vmpc_bn256_fr_poly_mul_ntt_batch_bytes(size_t na, size_t nb, size_t k_lo, size_t k_cnt, size_t n_wit);
+int vmpc_ctx_set_ntt_arena_cap(vmpc_ctx *ctx, size_t bytes);
+/* Which product vmpc_bn256_fr_poly_mul_dev / _batch_dev - and with them every caller: h, t's coefficients, the
+ * knowledge-of-exponent prover - compute with.  SCHOOLBOOK: a new context starts here.  AUTO: the NTT when
+ * min(na, nb) >= VMPC_BN256_FR_NTT_MIN.  NTT: always.  Any other mode: VMPC_E_INVAL, the mode stays. */
+#define VMPC_POLY_PRODUCT_SCHOOLBOOK 0
+#define VMPC_POLY_PRODUCT_AUTO 1
+#define VMPC_POLY_PRODUCT_NTT 2
+/* the smallest power of two at which the NTT's median was below the schoolbook's for a square product (DESIGN.md
+ * section 25) */
+#define VMPC_BN256_FR_NTT_MIN ((size_t)2)
+/* transforms of up to this many points run in one workgroup's LDS; longer ones in two or three passes */
+#define VMPC_BN256_FR_NTT_LDS_LEN 2048
+int vmpc_ctx_set_poly_product(vmpc_ctx *ctx, int mode);
+int vmpc_ctx_get_poly_product(vmpc_ctx *ctx, int *mode);
 /* out[i] = scale * z^(i+1) mod n for i < count (z, scale: one 32-byte device scalar each): the exponents of the
  * trusted setup, which knowledge_of_exponent.py:52-66 reaches by 2n sequential `g1_base ** z` / `g2_base ** z` on the
  * points themselves; here the 2n points are vmpc_bn256_fixed_base_dev of these exponents. */

@@ -52,6 +52,8 @@ SYMBOLS = [
     "vmpc_bn256_qap_check_batch_dev", "vmpc_bn256_qap_h_weights_batch_dev", "vmpc_bn256_qap_moments_batch_dev",
     "vmpc_bn256_qap_moments_batch_bytes", "vmpc_bn256_qap_h_combine_batch_dev", "vmpc_bn256_fr_poly_mul_batch_dev",
     "vmpc_bn256_fr_poly_mul_batch_bytes",
+    "vmpc_bn256_fr_poly_mul_ntt_dev", "vmpc_bn256_fr_poly_mul_ntt_batch_dev", "vmpc_bn256_fr_poly_mul_ntt_batch_bytes",
+    "vmpc_ctx_set_ntt_arena_cap", "vmpc_ctx_set_poly_product", "vmpc_ctx_get_poly_product",
     "vmpc_fr_cs_triples_dev", "vmpc_fr_cs_tables_dev", "vmpc_fr_cs_extend_dev", "vmpc_fr_cs_lagrange_dev",
     "vmpc_fr_cs_colsum_dev", "vmpc_fr_cs_first_diff_dev",
     "vmpc_fr_rows_combine_dev", "vmpc_fr_rows_dot_dev", "vmpc_fr_batch_products_dev",
@@ -206,6 +208,12 @@ def load_library():
         "vmpc_bn256_qap_h_combine_batch_dev": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, sz]),
         "vmpc_bn256_fr_poly_mul_batch_dev": (i32, [vp, vp, sz, sz, vp, sz, sz, sz, sz, vp, sz, sz]),
         "vmpc_bn256_fr_poly_mul_batch_bytes": (sz, [sz, sz, sz, sz, sz]),
+        "vmpc_bn256_fr_poly_mul_ntt_dev": (i32, [vp, vp, sz, vp, sz, vp]),
+        "vmpc_bn256_fr_poly_mul_ntt_batch_dev": (i32, [vp, vp, sz, sz, vp, sz, sz, sz, sz, vp, sz, sz]),
+        "vmpc_bn256_fr_poly_mul_ntt_batch_bytes": (sz, [sz, sz, sz, sz, sz]),
+        "vmpc_ctx_set_ntt_arena_cap": (i32, [vp, sz]),
+        "vmpc_ctx_set_poly_product": (i32, [vp, i32]),
+        "vmpc_ctx_get_poly_product": (i32, [vp, ctypes.POINTER(ctypes.c_int)]),
         "vmpc_fr_cs_triples_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, i32, vp]),
         "vmpc_fr_cs_tables_dev": (i32, [vp, sz, vp, vp]),
         "vmpc_fr_cs_triples_batch_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, sz, sz, i32,
@@ -605,6 +613,22 @@ class Context:
         on = ctypes.c_int(0)
         _check(self.lib.vmpc_ctx_get_short_path(self.handle, ctypes.byref(on)), "vmpc_ctx_get_short_path")
         return bool(on.value)
+
+    def set_poly_product(self, mode):
+        """which product bn256_fr_poly_mul / _batch - and every caller of theirs inside the library - compute with:
+        POLY_PRODUCT_SCHOOLBOOK (0, a new context's), POLY_PRODUCT_AUTO (1: the NTT over the integers of
+        csrc/bn256_ntt.hip from BN256_FR_NTT_MIN coefficients in the shorter operand), POLY_PRODUCT_NTT (2: always).
+        Same bits either way.  VmpcError E_INVAL for any other mode, which leaves the mode as it was."""
+        _check(self.lib.vmpc_ctx_set_poly_product(self.handle, int(mode)), "vmpc_ctx_set_poly_product")
+
+    def get_poly_product(self):
+        mode = ctypes.c_int(0)
+        _check(self.lib.vmpc_ctx_get_poly_product(self.handle, ctypes.byref(mode)), "vmpc_ctx_get_poly_product")
+        return int(mode.value)
+
+    def set_ntt_arena_cap(self, nbytes):
+        """the most arena bytes an NTT product may take before it cuts its batch into groups (0: the library's 1 GiB)"""
+        _check(self.lib.vmpc_ctx_set_ntt_arena_cap(self.handle, int(nbytes)), "vmpc_ctx_set_ntt_arena_cap")
 
     def on_general_path(self, fn):
         """fn() with the short path off, the PREVIOUS setting restored afterwards (a user who switched the path off
@@ -1090,6 +1114,11 @@ class Context:
         _check(self.lib.vmpc_bn256_fr_poly_mul_dev(self.handle, ctypes.c_void_p(a_ptr), na, ctypes.c_void_p(b_ptr), nb,
                                                    ctypes.c_void_p(out_ptr)), "vmpc_bn256_fr_poly_mul_dev")
 
+    def bn256_fr_poly_mul_ntt(self, a_ptr, na, b_ptr, nb, out_ptr):
+        """bn256_fr_poly_mul by the NTT over the integers (csrc/bn256_ntt.hip): same arguments, caps and bits"""
+        _check(self.lib.vmpc_bn256_fr_poly_mul_ntt_dev(self.handle, ctypes.c_void_p(a_ptr), na, ctypes.c_void_p(b_ptr),
+                                                       nb, ctypes.c_void_p(out_ptr)), "vmpc_bn256_fr_poly_mul_ntt_dev")
+
     def bn256_fr_powers(self, z_ptr, scale_ptr, count, out_ptr):
         """out[i] = scale * z^(i+1) mod the BN-256 group order"""
         _check(self.lib.vmpc_bn256_fr_powers_dev(self.handle, ctypes.c_void_p(z_ptr), ctypes.c_void_p(scale_ptr),
@@ -1207,6 +1236,14 @@ class Context:
         _check(self.lib.vmpc_bn256_fr_poly_mul_batch_dev(self.handle, p(a_ptr), a_stride, na, p(b_ptr), b_stride, nb,
                                                          k_lo, k_cnt, p(out_ptr), out_stride, n_wit),
                "vmpc_bn256_fr_poly_mul_batch_dev")
+
+    def bn256_fr_poly_mul_ntt_batch(self, a_ptr, a_stride, na, b_ptr, b_stride, nb, k_lo, k_cnt, out_ptr, out_stride,
+                                    n_wit):
+        """bn256_fr_poly_mul_batch by the NTT over the integers (csrc/bn256_ntt.hip): same arguments, caps and bits"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_bn256_fr_poly_mul_ntt_batch_dev(self.handle, p(a_ptr), a_stride, na, p(b_ptr), b_stride,
+                                                             nb, k_lo, k_cnt, p(out_ptr), out_stride, n_wit),
+               "vmpc_bn256_fr_poly_mul_ntt_batch_dev")
 
     def bn256_r1cs_solve_batch(self, plan_ptrs, level_ptr, n_in, m, c_ptr, c_stride, n_wit, wide_rows, first_bad_ptr):
         """n_wit witnesses of one R1CS from their inputs (include/vmpc.h).  plan_ptrs: the 13 device addresses V, W, Y
@@ -1584,6 +1621,9 @@ def bn256_msm(group, scalars, points):
 
 
 BN256_FR_POLY_MAX = 1 << 20      # VMPC_BN256_FR_POLY_MAX of include/vmpc.h
+BN256_FR_NTT_MIN = 2             # VMPC_BN256_FR_NTT_MIN: POLY_PRODUCT_AUTO takes the NTT from this many coefficients
+BN256_FR_NTT_LDS_LEN = 2048      # VMPC_BN256_FR_NTT_LDS_LEN: the longest transform one workgroup runs in LDS
+POLY_PRODUCT_SCHOOLBOOK, POLY_PRODUCT_AUTO, POLY_PRODUCT_NTT = 0, 1, 2      # VMPC_POLY_PRODUCT_*
 BN256_QAP_MAX_WIT = 65535        # VMPC_BN256_QAP_MAX_WIT
 BN256_R1CS_MAX_WIT = 65535       # VMPC_BN256_R1CS_MAX_WIT
 R1CS_WIDE_ALL = ctypes.c_size_t(-1).value      # wide_rows = SIZE_MAX: every level in one launch
@@ -1603,6 +1643,11 @@ def bn256_qap_moments_batch_bytes(d, n_out, n_wit):
 def bn256_fr_poly_mul_batch_bytes(na, nb, k_lo, k_cnt, n_wit):
     """the arena bytes Context.bn256_fr_poly_mul_batch reserves (0: none)"""
     return int(load_library().vmpc_bn256_fr_poly_mul_batch_bytes(na, nb, k_lo, k_cnt, n_wit))
+
+
+def bn256_fr_poly_mul_ntt_batch_bytes(na, nb, k_lo, k_cnt, n_wit):
+    """the arena bytes Context.bn256_fr_poly_mul_ntt_batch reserves at most (0: arguments out of range, or no work)"""
+    return int(load_library().vmpc_bn256_fr_poly_mul_ntt_batch_bytes(na, nb, k_lo, k_cnt, n_wit))
 
 
 def bn256_fr_poly_mul(a, b):

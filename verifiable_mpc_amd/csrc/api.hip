@@ -124,6 +124,7 @@ extern "C" int vmpc_ctx_destroy(vmpc_ctx *ctx) {
     if (ctx->p4_kblock) VMPC_IGNORE(hipFree(ctx->p4_kblock));
     if (ctx->d_status) VMPC_IGNORE(hipFree(ctx->d_status));
     if (ctx->short_cursors) VMPC_IGNORE(hipFree(ctx->short_cursors));
+    if (ctx->ntt_twiddles) VMPC_IGNORE(hipFree(ctx->ntt_twiddles));
     if (ctx->own_stream) VMPC_IGNORE(hipStreamDestroy(ctx->stream));
     delete ctx;
     return VMPC_OK;

@@ -3,7 +3,10 @@
 //
 //   k_frbn_polymul   c = a * b for two coefficient vectors: the prover's c_poly_lhs * c_poly_rhs
 //                    (knowledge_of_exponent.py:121-123; qap_creator.Poly.__mul__ is O(n^2) Python).  n - 1 = 2^5 * odd, so
-//                    there is no NTT of useful length in this field; the product is the schoolbook one.
+//                    there is no NTT of useful length in this field; the product is the schoolbook one.  (The INTEGERS
+//                    have one: csrc/bn256_ntt.hip convolves modulo 18 NTT-friendly primes and rebuilds the same
+//                    canonical residues; koe_poly_mul hands a product over when the context's mode asks for it,
+//                    vmpc_ctx_set_poly_product - off by default.)
 //   k_frbn_powers    scale * z^(i+1): the exponents of the trusted setup (knowledge_of_exponent.py:52-66 reaches them by
 //                    2n sequential scalar multiplications of a point).
 //
@@ -129,6 +132,9 @@ static koe_batch_plan koe_batch_plan_of(size_t na, size_t nb, size_t k_lo, size_
 // n_wit >= 1 products of a non-empty window, checked by the entries
 static int koe_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b, size_t b_stride, size_t nb,
                         size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit) {
+    if (ctx->poly_product == VMPC_POLY_PRODUCT_NTT ||
+        (ctx->poly_product == VMPC_POLY_PRODUCT_AUTO && (na < nb ? na : nb) >= VMPC_BN256_FR_NTT_MIN))
+        return vmpc_ntt_poly_mul(ctx, a, a_stride, na, b, b_stride, nb, k_lo, k_cnt, out, out_stride, n_wit);
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const koe_batch_plan p = koe_batch_plan_of(na, nb, k_lo, k_cnt, n_wit);
     const long long lo = (long long)k_lo, hi = (long long)(k_lo + k_cnt);

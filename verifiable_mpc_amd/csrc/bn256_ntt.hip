@@ -1,0 +1,336 @@
+// Polynomial products over GF(n) of BN-256 in O(d log d): an NTT over the INTEGERS.  GF(n) itself has no NTT of useful
+// length (csrc/bn256_koe.hip); the coefficients - any 32-byte values, not reduced first - are taken modulo NTT31_NP = 18
+// primes c 2^22 + 1 < 2^31 (csrc/ntt31.h, csrc/ntt31_consts.h), convolved in each prime field, and the exact integer
+// coefficient (< 2^532 < the primes' product) is rebuilt by Garner's digits and reduced mod n: the canonical residue the
+// schoolbook kernel writes, bit for bit.  Same contract as vmpc_bn256_fr_poly_mul_batch_dev: K products of one shape, a
+// window of the outputs, one b for all products when b_stride is 0.
+//
+//   layout         residues are uint32 in Montgomery form, prime-major: res[prime][row][L], L the power of two
+//                  >= na + nb - 1 (at least 2), a row one operand of one product.
+//   k_ntt_split    grid (L / 256, rows): a lane loads one scalar and stores its 18 residues (zeros past the operand).
+//   k_ntt_lds      grid (L / B, prime, rows), B = min(L, NTT_LDS_LEN): the log B LOW stages of a transform on a
+//                  contiguous block in LDS.  A transform of up to NTT_LDS_LEN points is this kernel alone.
+//   k_ntt_cols     grid (L / (64 2^m), prime, rows): m <= 6 HIGH stages on a tile of 2^m rows x 64 consecutive
+//                  columns (256-byte runs).  A longer transform is one or two of these passes plus k_ntt_lds: at the
+//                  cap, L = 2^21, 5 + 5 + 11 stages.
+//                  Forward is decimation in frequency (high stages first, output bit-reversed), inverse decimation in
+//                  time from that order (low stages first): no permutation pass.  The pointwise product is fused into
+//                  the load of the inverse's first pass (always k_ntt_lds).
+//   twiddles       w^e for the 2^21-th root w and e < 2^20 is hi[e >> 10] lo[e & 1023]: two tables of 1024 entries per
+//                  prime and direction (288 KiB in all), independent of L, built on the device once per context.  The
+//                  stages of k_ntt_lds only meet e = 0 mod 1024: one table entry, staged in LDS, no product.
+//   k_ntt_crt      grid (window outputs / 256, products): a lane gathers the 18 residues of one output of the window,
+//                  multiplies by L^-1 (the inverse transform's scale is folded in here), runs Garner and Horner fully
+//                  unrolled and stores the canonical residue.  Only the window is rebuilt; the transforms are whole.
+//
+// Arena: the residues of the shared b (or of a group's b rows) and of a group of a rows; n_wit is cut into groups so that
+// the arena stays below NTT_ARENA_MAX (one row at the cap is 18 x 2^21 x 4 B = 151 MB).  A group boundary changes no
+// value: every row is transformed on its own.  Integer sums in a fixed order, no atomics.
+#include "common.h"
+#include "fr_bn.h"
+#include "ntt31.h"
+
+#define NTT_WG 256
+#define NTT_LDS_LOG 11
+#define NTT_LDS_LEN (1 << NTT_LDS_LOG)
+#define NTT_COL_W_LOG 6                   // a column tile is 64 consecutive values wide
+#define NTT_COL_MAX_STAGES 6              // and at most 2^6 rows high: 4096 values, 16 KiB of LDS
+#define NTT_TW_HALF 1024                  // entries of the lo and of the hi twiddle table
+#define NTT_TW_PER_PRIME (2 * NTT_TW_HALF)
+#define NTT_ARENA_MAX ((size_t)1 << 30)
+
+static_assert(NTT_LDS_LEN == VMPC_BN256_FR_NTT_LDS_LEN, "the header's constant is this kernel's block length");
+
+struct ntt_scale {
+    uint32_t linv[NTT31_NP];
+};
+
+// table[dir][prime][0 .. 1023] = w^j, [1024 .. 2047] = w^(1024 j); w the 2^21-th root (dir 1: its inverse); canonical
+__global__ void __launch_bounds__(NTT_WG) k_ntt_twiddles(uint32_t *__restrict__ table) {
+    const uint32_t W[NTT31_NP] = NTT31_ROOT, WI[NTT31_NP] = NTT31_ROOT_INV;
+    const int pr = blockIdx.x, dir = blockIdx.y;
+    const ntt31_prime q = ntt31_prime_of(pr);
+    const uint32_t w = ntt31_pow(dir ? WI[pr] : W[pr], 1u << (NTT31_TWO_ADICITY - 21), q);
+    uint32_t *t = table + ((size_t)dir * NTT31_NP + pr) * NTT_TW_PER_PRIME;
+    for (uint32_t j = threadIdx.x; j < NTT_TW_PER_PRIME; j += NTT_WG)
+        t[j] = ntt31_pow(w, j < NTT_TW_HALF ? j : (j - NTT_TW_HALF) * NTT_TW_HALF, q);
+}
+
+// dst[prime][row][i] = src_row[i] mod prime for i < n, 0 for n <= i < L
+__global__ void __launch_bounds__(NTT_WG)
+k_ntt_split(const uint32_t *__restrict__ src, size_t stride, uint32_t n, uint32_t L, uint32_t rows,
+            uint32_t *__restrict__ dst) {
+    const uint32_t i = blockIdx.x * NTT_WG + threadIdx.x;
+    if (i >= L) return;
+    const size_t row = blockIdx.y;
+    uint32_t x[8];
+    if (i < n) {
+        const uint32_t *s = src + 8 * (row * stride + i);
+#pragma unroll
+        for (int l = 0; l < 8; l++) x[l] = s[l];
+    }
+#pragma unroll
+    for (int pr = 0; pr < NTT31_NP; pr++)
+        dst[((size_t)pr * rows + row) * L + i] = i < n ? ntt31_reduce256(x, ntt31_prime_of(pr)) : 0u;
+}
+
+// The low stages (halves 1 .. B / 2) of a transform of x's rows, in place, on the block blockIdx.x of B = 2^log_b values.
+// INV: decimation in time with the inverse twiddles, after x[i] *= y[i] (y: y_rows rows, 1 = one row for all).
+template <bool INV>
+__global__ void __launch_bounds__(NTT_WG)
+k_ntt_lds(uint32_t *__restrict__ x, uint32_t rows, const uint32_t *__restrict__ y, uint32_t y_rows, uint32_t L,
+          int log_b, const uint32_t *__restrict__ table) {
+    __shared__ uint32_t sx[NTT_LDS_LEN];
+    __shared__ uint32_t sw[NTT_TW_HALF];
+    const int pr = blockIdx.y;
+    const ntt31_prime q = ntt31_prime_of(pr);
+    const uint32_t B = 1u << log_b, row = blockIdx.z;
+    const size_t off = ((size_t)pr * rows + row) * L + (size_t)blockIdx.x * B;
+    const uint32_t *tw = table + ((size_t)(INV ? 1 : 0) * NTT31_NP + pr) * NTT_TW_PER_PRIME + NTT_TW_HALF;
+    for (uint32_t i = threadIdx.x; i < NTT_TW_HALF; i += NTT_WG) sw[i] = tw[i];
+    if (INV) {
+        const size_t yoff = ((size_t)pr * y_rows + (y_rows == 1 ? 0 : row)) * L + (size_t)blockIdx.x * B;
+        for (uint32_t i = threadIdx.x; i < B; i += NTT_WG)
+            sx[i] = ntt31_mul(x[off + i], ntt31_csub(y[yoff + i], q.p), q);
+    } else {
+        for (uint32_t i = threadIdx.x; i < B; i += NTT_WG) sx[i] = x[off + i];
+    }
+    __syncthreads();
+    for (int s = 0; s < log_b; s++) {
+        const int lh = INV ? s : log_b - 1 - s;        // half-distance 2^lh
+        const uint32_t h = 1u << lh;
+        for (uint32_t t = threadIdx.x; t < B / 2; t += NTT_WG) {
+            const uint32_t r = t & (h - 1), i = ((t >> lh) << (lh + 1)) | r;
+            uint32_t a = sx[i], b = sx[i + h];
+            const uint32_t w = sw[r << (10 - lh)];      // w^(r 2^(20 - lh)): a multiple of 1024 (lh <= 10)
+            if (INV) ntt31_dit(a, b, w, q);
+            else ntt31_dif(a, b, w, q);
+            sx[i] = a;
+            sx[i + h] = b;
+        }
+        __syncthreads();
+    }
+    for (uint32_t i = threadIdx.x; i < B; i += NTT_WG) x[off + i] = sx[i];
+}
+
+// m high stages, on the index bits [hb - m, hb), of a transform of x's rows, in place.  A tile: the 2^m values of those
+// bits x 64 consecutive values of the bits [0, 6); blockIdx.x counts the other bits, [6, hb - m) and [hb, log L).
+template <bool INV>
+__global__ void __launch_bounds__(NTT_WG)
+k_ntt_cols(uint32_t *__restrict__ x, uint32_t rows, uint32_t L, int hb, int m, const uint32_t *__restrict__ table) {
+    __shared__ uint32_t sx[1 << (NTT_COL_MAX_STAGES + NTT_COL_W_LOG)];
+    const int pr = blockIdx.y;
+    const ntt31_prime q = ntt31_prime_of(pr);
+    const int low_bits = hb - m - NTT_COL_W_LOG;
+    const uint32_t ql = blockIdx.x & ((1u << low_bits) - 1), qh = blockIdx.x >> low_bits;
+    const uint32_t base = (qh << hb) | (ql << NTT_COL_W_LOG);
+    const int rs = hb - m;                               // a tile row is 2^rs values from the next
+    uint32_t *xr = x + ((size_t)pr * rows + blockIdx.z) * L;
+    const uint32_t *lo = table + ((size_t)(INV ? 1 : 0) * NTT31_NP + pr) * NTT_TW_PER_PRIME, *hi = lo + NTT_TW_HALF;
+    const uint32_t count = 1u << (m + NTT_COL_W_LOG);
+    for (uint32_t e = threadIdx.x; e < count; e += NTT_WG)
+        sx[e] = xr[base + ((e >> NTT_COL_W_LOG) << rs) + (e & 63)];
+    __syncthreads();
+    for (int k = 0; k < m; k++) {
+        const int s = INV ? k : m - 1 - k;               // tile-row bit s is index bit rs + s
+        const int t = rs + s;
+        for (uint32_t u = threadIdx.x; u < count / 2; u += NTT_WG) {
+            const uint32_t c = u & 63, rr = u >> NTT_COL_W_LOG;
+            const uint32_t r0 = ((rr >> s) << (s + 1)) | (rr & ((1u << s) - 1));
+            const uint32_t e0 = (r0 << NTT_COL_W_LOG) | c, e1 = e0 + (64u << s);
+            const uint32_t pos = (base + (r0 << rs) + c) & ((1u << t) - 1);      // the index mod the half-distance
+            const uint32_t ex = pos << (20 - t);                                  // < 2^20
+            const uint32_t w = ntt31_csub(ntt31_mul(hi[ex >> 10], lo[ex & 1023], q), q.p);
+            uint32_t a = sx[e0], b = sx[e1];
+            if (INV) ntt31_dit(a, b, w, q);
+            else ntt31_dif(a, b, w, q);
+            sx[e0] = a;
+            sx[e1] = b;
+        }
+        __syncthreads();
+    }
+    for (uint32_t e = threadIdx.x; e < count; e += NTT_WG)
+        xr[base + ((e >> NTT_COL_W_LOG) << rs) + (e & 63)] = sx[e];
+}
+
+// out_row[k - k_lo] = the integer coefficient k of row's product, mod n, for k in [k_lo, k_lo + k_cnt)
+__global__ void __launch_bounds__(NTT_WG)
+k_ntt_crt(const uint32_t *__restrict__ res, uint32_t rows, uint32_t L, uint32_t k_lo, uint32_t k_cnt, ntt_scale sc,
+          uint32_t *__restrict__ out, size_t out_stride) {
+    const uint32_t j = blockIdx.x * NTT_WG + threadIdx.x;
+    if (j >= k_cnt) return;
+    const size_t row = blockIdx.y;
+    uint32_t r[NTT31_NP];
+#pragma unroll
+    for (int pr = 0; pr < NTT31_NP; pr++) r[pr] = res[((size_t)pr * rows + row) * L + k_lo + j];
+    frbn_store(out + 8 * (row * out_stride + j), ntt31_crt(r, sc.linv));
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------
+struct ntt_plan {
+    int log_l;
+    size_t L, row_bytes;       // residues of one row
+    size_t group, b_rows;      // a rows per group; b rows held (1: the shared b)
+    size_t bytes;              // arena
+};
+
+static ntt_plan ntt_plan_of(size_t na, size_t nb, bool shared_b, size_t n_wit, size_t cap) {
+    ntt_plan p;
+    p.log_l = 1;
+    while (((size_t)1 << p.log_l) < na + nb - 1) p.log_l++;
+    p.L = (size_t)1 << p.log_l;
+    p.row_bytes = (size_t)NTT31_NP * p.L * 4;
+    const size_t fit = cap / p.row_bytes;                  // rows the cap holds
+    size_t g = shared_b ? (fit > 1 ? fit - 1 : 1) : (fit > 2 ? fit / 2 : 1);
+    p.group = g < n_wit ? g : n_wit;
+    p.b_rows = shared_b ? 1 : p.group;
+    p.bytes = vmpc_align(p.row_bytes * p.b_rows) + vmpc_align(p.row_bytes * p.group) + 512;
+    return p;
+}
+
+static int ntt_tables(vmpc_ctx *ctx) {
+    if (ctx->ntt_twiddles) return VMPC_OK;
+    VMPC_HIP_CHECK(hipMalloc(&ctx->ntt_twiddles, (size_t)2 * NTT31_NP * NTT_TW_PER_PRIME * 4));
+    k_ntt_twiddles<<<dim3(NTT31_NP, 2), NTT_WG, 0, ctx->stream>>>((uint32_t *)ctx->ntt_twiddles);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+// the high stages of a transform longer than NTT_LDS_LEN: one pass of up to 6 stages, or two of about half each
+template <bool INV>
+static int ntt_high_stages(vmpc_ctx *ctx, uint32_t *x, size_t rows, const ntt_plan &p) {
+    const int high = p.log_l - NTT_LDS_LOG;
+    if (high <= 0) return VMPC_OK;
+    const uint32_t *tw = (const uint32_t *)ctx->ntt_twiddles;
+    int m[2] = {high, 0};
+    if (high > NTT_COL_MAX_STAGES) {
+        m[0] = (high + 1) / 2;
+        m[1] = high - m[0];
+    }
+    // forward: from the top bit down; inverse: from bit NTT_LDS_LOG up
+    int hb = INV ? NTT_LDS_LOG : p.log_l;
+    for (int i = 0; i < 2 && m[i]; i++) {
+        if (INV) hb += m[i];
+        k_ntt_cols<INV><<<dim3((unsigned)(p.L >> (m[i] + NTT_COL_W_LOG)), NTT31_NP, (unsigned)rows), NTT_WG, 0,
+                          ctx->stream>>>(x, (uint32_t)rows, (uint32_t)p.L, hb, m[i], tw);
+        VMPC_KERNEL_CHECK();
+        if (!INV) hb -= m[i];
+    }
+    return VMPC_OK;
+}
+
+static int ntt_split(vmpc_ctx *ctx, const void *src, size_t stride, size_t n, size_t rows, const ntt_plan &p,
+                     uint32_t *dst) {
+    vmpc_stage_scope s(ctx, "bn_fr_ntt_split");
+    k_ntt_split<<<dim3((unsigned)((p.L + NTT_WG - 1) / NTT_WG), (unsigned)rows), NTT_WG, 0, ctx->stream>>>(
+        (const uint32_t *)src, stride, (uint32_t)n, (uint32_t)p.L, (uint32_t)rows, dst);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+static int ntt_forward(vmpc_ctx *ctx, uint32_t *x, size_t rows, const ntt_plan &p) {
+    vmpc_stage_scope s(ctx, "bn_fr_ntt_fwd");
+    VMPC_CHECK(ntt_high_stages<false>(ctx, x, rows, p));
+    const int log_b = p.log_l < NTT_LDS_LOG ? p.log_l : NTT_LDS_LOG;
+    k_ntt_lds<false><<<dim3((unsigned)(p.L >> log_b), NTT31_NP, (unsigned)rows), NTT_WG, 0, ctx->stream>>>(
+        x, (uint32_t)rows, nullptr, 0, (uint32_t)p.L, log_b, (const uint32_t *)ctx->ntt_twiddles);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+// x *= y pointwise, then the inverse transform of x (not yet scaled by 1 / L: k_ntt_crt does that)
+static int ntt_inverse(vmpc_ctx *ctx, uint32_t *x, size_t rows, const uint32_t *y, size_t y_rows, const ntt_plan &p) {
+    vmpc_stage_scope s(ctx, "bn_fr_ntt_inv");
+    const int log_b = p.log_l < NTT_LDS_LOG ? p.log_l : NTT_LDS_LOG;
+    k_ntt_lds<true><<<dim3((unsigned)(p.L >> log_b), NTT31_NP, (unsigned)rows), NTT_WG, 0, ctx->stream>>>(
+        x, (uint32_t)rows, y, (uint32_t)y_rows, (uint32_t)p.L, log_b, (const uint32_t *)ctx->ntt_twiddles);
+    VMPC_KERNEL_CHECK();
+    return ntt_high_stages<true>(ctx, x, rows, p);
+}
+
+// n_wit >= 1 products of a non-empty window, checked by the entries (csrc/bn256_koe.hip's koe_poly_mul hands over here)
+int vmpc_ntt_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b, size_t b_stride,
+                      size_t nb, size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit) {
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const bool shared_b = b_stride == 0;
+    const ntt_plan p = ntt_plan_of(na, nb, shared_b, n_wit, ctx->ntt_arena_cap ? ctx->ntt_arena_cap : NTT_ARENA_MAX);
+    VMPC_CHECK(vmpc_ws_reserve(ctx, p.bytes));      // before any launch
+    uint32_t *rb = (uint32_t *)vmpc_ws_take(ctx, p.row_bytes * p.b_rows);
+    uint32_t *ra = (uint32_t *)vmpc_ws_take(ctx, p.row_bytes * p.group);
+    VMPC_CHECK(ntt_tables(ctx));
+    ntt_scale sc;
+    const uint32_t P[NTT31_NP] = NTT31_PRIMES;
+    for (int i = 0; i < NTT31_NP; i++) sc.linv[i] = ntt31_inv_pow2(p.log_l, P[i]);
+    for (size_t w0 = 0; w0 < n_wit; w0 += p.group) {
+        const size_t g = n_wit - w0 < p.group ? n_wit - w0 : p.group;
+        if (!shared_b || w0 == 0) {
+            const size_t rows = shared_b ? 1 : g;
+            VMPC_CHECK(ntt_split(ctx, (const char *)b + 32 * w0 * b_stride, b_stride, nb, rows, p, rb));
+            VMPC_CHECK(ntt_forward(ctx, rb, rows, p));
+        }
+        VMPC_CHECK(ntt_split(ctx, (const char *)a + 32 * w0 * a_stride, a_stride, na, g, p, ra));
+        VMPC_CHECK(ntt_forward(ctx, ra, g, p));
+        VMPC_CHECK(ntt_inverse(ctx, ra, g, rb, shared_b ? 1 : g, p));
+        {
+            vmpc_stage_scope s(ctx, "bn_fr_ntt_crt");
+            k_ntt_crt<<<dim3((unsigned)((k_cnt + NTT_WG - 1) / NTT_WG), (unsigned)g), NTT_WG, 0, ctx->stream>>>(
+                ra, (uint32_t)g, (uint32_t)p.L, (uint32_t)k_lo, (uint32_t)k_cnt, sc,
+                (uint32_t *)out + 8 * w0 * out_stride, out_stride);
+            VMPC_KERNEL_CHECK();
+        }
+    }
+    return VMPC_OK;
+}
+
+static bool ntt_batch_in_range(size_t na, size_t nb, size_t k_lo, size_t k_cnt, size_t n_wit) {
+    return n_wit <= VMPC_BN256_QAP_MAX_WIT && na <= VMPC_BN256_FR_POLY_MAX && nb <= VMPC_BN256_FR_POLY_MAX &&
+           k_lo <= 2 * VMPC_BN256_FR_POLY_MAX && k_cnt <= 2 * VMPC_BN256_FR_POLY_MAX &&
+           (k_cnt == 0 || k_lo + k_cnt + 1 <= na + nb);
+}
+
+extern "C" size_t vmpc_bn256_fr_poly_mul_ntt_batch_bytes(size_t na, size_t nb, size_t k_lo, size_t k_cnt,
+                                                         size_t n_wit) {
+    if (!ntt_batch_in_range(na, nb, k_lo, k_cnt, n_wit) || na == 0 || nb == 0 || k_cnt == 0 || n_wit == 0) return 0;
+    // (the larger of the two layouts: the entry does not know the stride of b here)
+    const size_t s = ntt_plan_of(na, nb, true, n_wit, NTT_ARENA_MAX).bytes;
+    const size_t d = ntt_plan_of(na, nb, false, n_wit, NTT_ARENA_MAX).bytes;
+    return s > d ? s : d;
+}
+
+extern "C" int vmpc_bn256_fr_poly_mul_ntt_batch_dev(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na,
+                                                    const void *b, size_t b_stride, size_t nb, size_t k_lo, size_t k_cnt,
+                                                    void *out, size_t out_stride, size_t n_wit) {
+    const size_t cap = (size_t)1 << 31;
+    if (!ntt_batch_in_range(na, nb, k_lo, k_cnt, n_wit) || a_stride > cap || b_stride > cap || out_stride > cap ||
+        (n_wit && (a_stride < na || (b_stride && b_stride < nb) || out_stride < k_cnt)))
+        return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !out || na == 0 || nb == 0) return VMPC_E_INVAL;
+    if (n_wit == 0 || k_cnt == 0) return VMPC_OK;
+    return vmpc_ntt_poly_mul(ctx, a, a_stride, na, b, b_stride, nb, k_lo, k_cnt, out, out_stride, n_wit);
+}
+
+// the whole product: the window [0, na + nb - 1) of one pair
+extern "C" int vmpc_bn256_fr_poly_mul_ntt_dev(vmpc_ctx *ctx, const void *a, size_t na, const void *b, size_t nb,
+                                              void *out) {
+    if (na > VMPC_BN256_FR_POLY_MAX || nb > VMPC_BN256_FR_POLY_MAX) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !out || na == 0 || nb == 0) return VMPC_E_INVAL;
+    return vmpc_ntt_poly_mul(ctx, a, na, na, b, nb, nb, 0, na + nb - 1, out, na + nb - 1, 1);
+}
+
+extern "C" int vmpc_ctx_set_poly_product(vmpc_ctx *ctx, int mode) {
+    if (!ctx || mode < VMPC_POLY_PRODUCT_SCHOOLBOOK || mode > VMPC_POLY_PRODUCT_NTT) return VMPC_E_INVAL;
+    ctx->poly_product = mode;
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_ctx_get_poly_product(vmpc_ctx *ctx, int *mode) {
+    if (!ctx || !mode) return VMPC_E_INVAL;
+    *mode = ctx->poly_product;
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_ctx_set_ntt_arena_cap(vmpc_ctx *ctx, size_t bytes) {
+    if (!ctx) return VMPC_E_INVAL;
+    ctx->ntt_arena_cap = bytes;
+    return VMPC_OK;
+}

@@ -101,6 +101,10 @@ struct vmpc_ctx {
     void *p4_kblock = nullptr;         // the columns of k in a folded vector's table (a single-lane chain of 240
     int p4_kblock_rows = 0;            // doublings, 0.7 ms): k belongs to the CRS, so they are made once
     uint8_t p4_kblock_key[64] = {0};
+    // polynomial products over GF(n) of BN-256 (csrc/bn256_koe.hip, csrc/bn256_ntt.hip)
+    int poly_product = 0;              // VMPC_POLY_PRODUCT_*: which products koe_poly_mul hands to the NTT (0: none)
+    void *ntt_twiddles = nullptr;      // the NTT's twiddle tables, built on first use, independent of the length
+    size_t ntt_arena_cap = 0;          // > 0: the NTT's arena cap in bytes (vmpc_ctx_set_ntt_arena_cap; 0: NTT_ARENA_MAX)
     // profiling
     bool profile = false;
     std::vector<vmpc_stage> stages;
@@ -122,6 +126,11 @@ int vmpc_stage_h2d(vmpc_ctx *ctx, void *dst, const void *src, size_t bytes);
 // fault on the first kernel write after it).
 int vmpc_pinned_reserve(vmpc_ctx *ctx, size_t bytes);
 inline size_t vmpc_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the product of vmpc_bn256_fr_poly_mul_batch_dev by the NTT over the integers (csrc/bn256_ntt.hip); arguments checked
+// by the caller: n_wit >= 1 products of a non-empty window
+int vmpc_ntt_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b, size_t b_stride,
+                      size_t nb, size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit);
 
 // profiling helpers: bracket a kernel launch with events when ctx->profile is on
 int vmpc_stage_begin(vmpc_ctx *ctx, const char *name);

@@ -8,6 +8,7 @@ Layout in HBM:
 Slices are zero-copy views (pointer + offset), which is what the halving rounds of
 Protocol 4 use (verifiable_mpc/ac20/compressed_pivot.py:35-38).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -48,6 +49,28 @@ def reset_context():
             c.close()
     _AUX.clear()
     _CTX = None
+
+
+POLY_PRODUCT_MODES = {"schoolbook": _native.POLY_PRODUCT_SCHOOLBOOK, "auto": _native.POLY_PRODUCT_AUTO,
+                      "ntt": _native.POLY_PRODUCT_NTT}
+
+
+@contextlib.contextmanager
+def poly_product(mode, ctx=None):
+    """with poly_product("ntt"): every polynomial product over the BN-256 scalar field that `ctx` (default: the
+    process's context) computes inside the block - fr_poly_mul, compute_h and its batch and share forms, t's coefficients,
+    the knowledge-of-exponent prover - goes through the NTT over the integers (csrc/bn256_ntt.hip); "auto": from
+    _native.BN256_FR_NTT_MIN coefficients in the shorter operand; "schoolbook": none (a new context's mode).  The bits
+    are the same in every mode.  The mode found on entry is restored on exit, also when the block raises."""
+    if mode not in POLY_PRODUCT_MODES:
+        raise ValueError(f"poly_product mode {mode!r}: one of {sorted(POLY_PRODUCT_MODES)}")
+    ctx = ctx or get_context()
+    prev = ctx.get_poly_product()
+    ctx.set_poly_product(POLY_PRODUCT_MODES[mode])
+    try:
+        yield ctx
+    finally:
+        ctx.set_poly_product(prev)
 
 
 def reduce_scalar(v):

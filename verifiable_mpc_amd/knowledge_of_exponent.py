@@ -117,14 +117,28 @@ def fr_powers(z, scale, count, ctx=None):
     return out
 
 
-def fr_poly_mul(a, b, ctx=None):
+def fr_poly_mul(a, b, ctx=None, method=None):
     """coefficients (lists of ints / field elements, or (len, 32) uint8 arrays of any 32-byte values) of two polynomials
-    over GF(ORDER) -> (len(a) + len(b) - 1, 32) uint8 canonical coefficients of their product (csrc/bn256_koe.hip)"""
+    over GF(ORDER) -> (len(a) + len(b) - 1, 32) uint8 canonical coefficients of their product (csrc/bn256_koe.hip).
+    method None: what the context's mode says (device.poly_product; schoolbook unless set); "ntt": the NTT over the
+    integers (csrc/bn256_ntt.hip); "schoolbook": that kernel, whatever the mode.  Same bits."""
+    if method not in (None, "ntt", "schoolbook"):
+        raise ValueError(f"fr_poly_mul method {method!r}: None, 'ntt' or 'schoolbook'")
     ctx = ctx or get_context()
     a, b = scalars_to_array(a), scalars_to_array(b)
     da, db = ctx.upload(a), ctx.upload(b)
     out = ctx.alloc(32 * (len(a) + len(b) - 1))
-    ctx.bn256_fr_poly_mul(da.ptr, len(a), db.ptr, len(b), out.ptr)
+    if method == "ntt":
+        ctx.bn256_fr_poly_mul_ntt(da.ptr, len(a), db.ptr, len(b), out.ptr)
+    elif method == "schoolbook":
+        prev = ctx.get_poly_product()
+        ctx.set_poly_product(_native.POLY_PRODUCT_SCHOOLBOOK)
+        try:
+            ctx.bn256_fr_poly_mul(da.ptr, len(a), db.ptr, len(b), out.ptr)
+        finally:
+            ctx.set_poly_product(prev)
+    else:
+        ctx.bn256_fr_poly_mul(da.ptr, len(a), db.ptr, len(b), out.ptr)
     ctx.sync()
     return ctx.download(out.ptr, 32 * (len(a) + len(b) - 1)).reshape(-1, 32)
 
