@@ -24,6 +24,11 @@
 // difference of reduced values (< 2^27.6), and `lazy +- reduced` against a reduced partner all
 // satisfy it; the call sites in ge25519.h state their bounds.  fe_sqr(f): limbs < 2^27.6.
 // tests/native/host_math_test.cpp drives both at these bounds (command `rawmul`).
+// Carry-in (fe_mul_cols): term by term, with an odd limb one bit below an even one, a column sum is largest in
+// column 0: 1 * 2^55.2 + 4 * 19 * 2^55.2 (even x even, wrapped) + 5 * 38 * 2^53.2 (odd x odd, wrapped) < 2^62.2.
+// The carry out of a column is therefore below 2^62.2 / 2^25 < 2^38, and a column sum that starts from the previous
+// column's carry stays below 2^62.2 + 2^38 < 2^64.  It is the integer fe_carry64 forms with `h[i + 1] += c`.
+// tests/native/fe_cols_host_test.cpp compares the two limb for limb at these bounds.
 //
 // Memory format (`fe8`): 32 bytes little-endian = 8 LE uint32 words, canonical residue < p on
 // every public buffer (include/vmpc.h).  fe_unpack / fe_pack convert; internal workspaces keep
@@ -192,6 +197,118 @@ VMPC_HD fe fe_mul(const fe &f, const fe &g) {
         }
     }
     return fe_carry64(h);
+}
+
+// ---- N independent products, column by column, each column sum started from the previous column's carry ----
+// r[p] = f[p] * g[p] under fe_mul's operand contract, and the same ten limbs as fe_mul returns: fe_carry64's
+// `h[k+1] += c` adds the carry of column k to the finished sum of column k+1; here the sum of column k+1 STARTS from
+// that carry, which is the same 64-bit integer (the bound at the top of the file covers it).  On the device the start
+// value rides in v_mad_u64_u32's 64-bit addend, so the 9 carry additions per product (v_lshl_add_u64) are not issued
+// at all.  The compiler does not keep a carry inside a sum of products (it reassociates it to the outside), hence the
+// multiply-adds are written out.  A column is a serial chain through one accumulator; the chains of two products are
+// issued alternately (product 0 term i, product 1 term i, product 0 term i + 1, ...), so that no multiply-add
+// directly follows the one it waits for; an odd product out runs its chain alone.
+// Five terms of a column (of both products of a pair) make ONE asm statement: hipcc puts a wait state (s_nop 0)
+// between any two adjacent asm statements that write registers, dependent or not - about 490 per mixed addition with
+// one multiply-add per statement - and none between the dependent v_mad_u64_u32 it emits itself.
+// Products that share an operand (ge_hwcd_tail_cols: E, G, F, H twice each) share its 19 x and 2 x multiples: those
+// are plain C here and the compiler merges the equal expressions.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(VMPC_NO_DEVICE_ASM)
+// (%1 / %2: the instruction's scalar carry-out operand; never set under the contract, never read)
+__device__ __forceinline__ void fe_mad64_x5(uint64_t &acc, const uint32_t (&a)[5], const uint32_t (&b)[5]) {
+    uint64_t carry_out;
+    asm("v_mad_u64_u32 %0, %1, %2, %7, %0\n\t"
+        "v_mad_u64_u32 %0, %1, %3, %8, %0\n\t"
+        "v_mad_u64_u32 %0, %1, %4, %9, %0\n\t"
+        "v_mad_u64_u32 %0, %1, %5, %10, %0\n\t"
+        "v_mad_u64_u32 %0, %1, %6, %11, %0"
+        : "+v"(acc), "=s"(carry_out)
+        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]));
+}
+__device__ __forceinline__ void fe_mad64_x5(uint64_t &acc0, const uint32_t (&a0)[5], const uint32_t (&b0)[5],
+                                            uint64_t &acc1, const uint32_t (&a1)[5], const uint32_t (&b1)[5]) {
+    uint64_t carry_out;
+    asm("v_mad_u64_u32 %0, %2, %3, %8, %0\n\t"
+        "v_mad_u64_u32 %1, %2, %13, %18, %1\n\t"
+        "v_mad_u64_u32 %0, %2, %4, %9, %0\n\t"
+        "v_mad_u64_u32 %1, %2, %14, %19, %1\n\t"
+        "v_mad_u64_u32 %0, %2, %5, %10, %0\n\t"
+        "v_mad_u64_u32 %1, %2, %15, %20, %1\n\t"
+        "v_mad_u64_u32 %0, %2, %6, %11, %0\n\t"
+        "v_mad_u64_u32 %1, %2, %16, %21, %1\n\t"
+        "v_mad_u64_u32 %0, %2, %7, %12, %0\n\t"
+        "v_mad_u64_u32 %1, %2, %17, %22, %1"
+        : "+v"(acc0), "+v"(acc1), "=s"(carry_out)
+        : "v"(a0[0]), "v"(a0[1]), "v"(a0[2]), "v"(a0[3]), "v"(a0[4]), "v"(b0[0]), "v"(b0[1]), "v"(b0[2]), "v"(b0[3]),
+          "v"(b0[4]), "v"(a1[0]), "v"(a1[1]), "v"(a1[2]), "v"(a1[3]), "v"(a1[4]), "v"(b1[0]), "v"(b1[1]), "v"(b1[2]),
+          "v"(b1[3]), "v"(b1[4]));
+}
+#else
+// the plain C statement of the same column order
+VMPC_HD void fe_mad64_x5(uint64_t &acc, const uint32_t (&a)[5], const uint32_t (&b)[5]) {
+#pragma unroll
+    for (int t = 0; t < 5; t++) acc += (uint64_t)a[t] * b[t];
+}
+VMPC_HD void fe_mad64_x5(uint64_t &acc0, const uint32_t (&a0)[5], const uint32_t (&b0)[5], uint64_t &acc1,
+                         const uint32_t (&a1)[5], const uint32_t (&b1)[5]) {
+#pragma unroll
+    for (int t = 0; t < 5; t++) {
+        acc0 += (uint64_t)a0[t] * b0[t];
+        acc1 += (uint64_t)a1[t] * b1[t];
+    }
+}
+#endif
+
+template <int N>
+VMPC_HD void fe_mul_cols(fe (&r)[N], const fe (&f)[N], const fe (&g)[N]) {
+    uint32_t g19[N][FE_LIMBS], f2[N][FE_LIMBS];
+#pragma unroll
+    for (int p = 0; p < N; p++) {
+#pragma unroll
+        for (int j = 0; j < FE_LIMBS; j++) {
+            g19[p][j] = 19u * g[p].v[j];
+            f2[p][j] = 2u * f[p].v[j];
+        }
+    }
+    uint64_t acc[N];            // column k of every product; enters a column holding the carry of column k - 1
+    uint64_t h0[N];
+#pragma unroll
+    for (int p = 0; p < N; p++) acc[p] = 0;
+#pragma unroll
+    for (int k = 0; k < FE_LIMBS; k++) {
+#pragma unroll
+        for (int i0 = 0; i0 < FE_LIMBS; i0 += 5) {
+            uint32_t a[N][5], b[N][5];      // terms i0 .. i0 + 4 of column k: f_i * g_(k - i), wrapped ones times 19
+#pragma unroll
+            for (int t = 0; t < 5; t++) {
+                const int i = i0 + t, j = (k - i + FE_LIMBS) % FE_LIMBS;
+                const bool wrap = i + j >= FE_LIMBS;
+                const bool odd2 = (i & 1) && (j & 1);
+#pragma unroll
+                for (int p = 0; p < N; p++) {
+                    a[p][t] = odd2 ? f2[p][i] : f[p].v[i];
+                    b[p][t] = wrap ? g19[p][j] : g[p].v[j];
+                }
+            }
+#pragma unroll
+            for (int p = 0; p + 1 < N; p += 2) fe_mad64_x5(acc[p], a[p], b[p], acc[p + 1], a[p + 1], b[p + 1]);
+            if (N & 1) fe_mad64_x5(acc[N - 1], a[N - 1], b[N - 1]);
+        }
+#pragma unroll
+        for (int p = 0; p < N; p++) {
+            const uint64_t s = acc[p];
+            acc[p] = s >> ((k & 1) ? 25 : 26);
+            if (k == 0) h0[p] = s & FE_MASK26;
+            else r[p].v[k] = (uint32_t)s & ((k & 1) ? FE_MASK25 : FE_MASK26);
+        }
+    }
+    // the wrap of limb 9's carry and the last carry into limb 1, as in fe_carry64
+#pragma unroll
+    for (int p = 0; p < N; p++) {
+        h0[p] += 19u * acc[p];
+        r[p].v[0] = (uint32_t)h0[p] & FE_MASK26;
+        r[p].v[1] += (uint32_t)(h0[p] >> 26);
+    }
 }
 
 // r = a^2: 55 products

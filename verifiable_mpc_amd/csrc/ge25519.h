@@ -100,6 +100,68 @@ VMPC_HD ge_ext ge_madd(const ge_ext &p, const ge_niels &q) {
     return ge_hwcd_tail(A, B, C, D);
 }
 
+// The bucket loop's mixed addition (msm.hip k_msm_bucket, k_madd_rate): the same formulas, operands and limbs as
+// ge_madd, on fe_mul_cols (carry-in column sums; bounds as in ge_madd / ge_hwcd_tail).  The chains run in pairs:
+// A with B, C alone, then X with T (after which E is dead) and Y with Z.  Three and four products side by side keep
+// every operand of a level live at once and spill in k_msm_bucket (48 bytes of scratch at 128 VGPRs); pairs fit.
+VMPC_HD ge_ext ge_hwcd_tail_cols(const fe &A, const fe &B, const fe &C, const fe &D) {
+    const fe E = fe_sub_lazy(B, A);
+    const fe H = fe_add_lazy(B, A);
+    const fe F = fe_sub(D, C);
+    const fe G = fe_add_lazy(D, C);
+    ge_ext o;
+    {
+        const fe f[2] = {E, E}, g[2] = {F, H};      // the doubled odd limbs of E: one computation
+        fe r[2];
+        fe_mul_cols<2>(r, f, g);
+        o.X = r[0];
+        o.T = r[1];
+    }
+    {
+        const fe f[2] = {G, G}, g[2] = {H, F};      // 19 H and 19 F are the first pair's
+        fe r[2];
+        fe_mul_cols<2>(r, f, g);
+        o.Y = r[0];
+        o.Z = r[1];
+    }
+    return o;
+}
+
+VMPC_HD ge_ext ge_madd_cols(const ge_ext &p, const ge_niels &q) {
+    fe A, B, C;
+    {
+        const fe f[2] = {fe_sub_lazy(p.Y, p.X), fe_add_lazy(p.Y, p.X)}, g[2] = {q.ymx, q.ypx};
+        fe r[2];
+        fe_mul_cols<2>(r, f, g);
+        A = r[0];
+        B = r[1];
+    }
+    {
+        const fe f[1] = {p.T}, g[1] = {q.t2d};
+        fe r[1];
+        fe_mul_cols<1>(r, f, g);
+        C = r[0];
+    }
+    return ge_hwcd_tail_cols(A, B, C, fe_add_lazy(p.Z, p.Z));
+}
+
+// identity + (neg ? -q : q) without the mixed addition: with p = (0 : 1 : 1 : 0), ge_madd has A = ymx, B = ypx,
+// C = 0, D = 2, hence E = ypx - ymx, H = ypx + ymx, F = G = 2 and (X : Y : Z : T) = (2E : 2H : 4 : E H), one
+// product.  -q swaps ymx and ypx (E changes sign, H does not); t2d is not needed.  The residues are ge_madd's, the
+// coordinates reduced.  q reduced (a table entry).
+VMPC_HD ge_ext ge_ext_from_niels_neg(const ge_niels &q, bool neg) {
+    const fe a = fe_select(q.ymx, q.ypx, neg);
+    const fe b = fe_select(q.ypx, q.ymx, neg);
+    const fe E = fe_sub_lazy(b, a);      // < 2^27.6
+    const fe H = fe_add_lazy(b, a);      // < 2^27.1
+    ge_ext r;
+    r.X = fe_add(E, E);                  // 2^28.6 into the carry pass
+    r.Y = fe_add(H, H);
+    r.Z = fe_from_u32(4);
+    r.T = fe_mul(E, H);                  // 2^54.7
+    return r;
+}
+
 // full addition ext + ext (add-2008-hwcd-3): 9M.  Complete on Ed25519 (a = -1 square... d non-square).
 VMPC_HD ge_ext ge_add(const ge_ext &p, const ge_ext &q) {
     fe A = fe_mul(fe_sub_lazy(p.Y, p.X), fe_sub_lazy(q.Y, q.X));   // 2^27.6 * 2^27.6 = 2^55.2

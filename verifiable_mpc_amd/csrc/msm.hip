@@ -98,29 +98,42 @@ k_msm_bucket(const uint32_t *__restrict__ niels, const uint32_t *__restrict__ so
     // (tasks are numbered by length, so the lanes of a wave agree on the short burst almost always)
     if (len <= 8) msm_idx_fill<8>(col, run, len);
     else msm_idx_fill<MSM_IDX_WIN>(col, run, len);
-    ge_ext acc = ge_ext_identity();
     // The next table entry is requested one addition ahead, but the compiler hoists its sign selection to right
     // behind the load, so in effect the gather latency is hidden by the 4 waves per SIMD, not by this
     // "prefetch".  A hand-scheduled version (inline-asm loads + manual s_waitcnt after the 7 multiplications,
     // 140 VGPRs, 3 waves) measured the same 0.61 ms for this kernel and 0.76 instead of 0.85 ms on the 2 GiB
     // fixed-base table: not worth carrying loads the compiler cannot see.  Staging the gather through LDS with
     // LDS-DMA (global_load_lds_dwordx4 into a [piece][lane] stage, no VGPR cost) measured 1.07 ms.
-    // Initialising the accumulator from the first term (1M instead of 7M) lost to register pressure.
+    // Initialising the accumulator from the first term (1M instead of 7M) lost to register pressure while the mixed
+    // addition kept ten 64-bit column sums live; with one accumulator per product (ge_madd_cols) it fits: 128 VGPRs,
+    // no scratch.  The loop body is 1166 VALU instructions per mixed addition against 1189 with ge_madd (707
+    // v_mad_u64_u32 either way; the 63 carry additions v_lshl_add_u64 are gone, 30 v_mov_b32 that hand the next
+    // entry over at the loop's end came in), and a run of n entries costs n - 1 mixed additions and one product
+    // (EXPERIMENTS.md "Bucket pass: carry-in column products").  Every task has at least one entry (k_msm_plan2).
     // Round 4 settled what the kernel is bound by (profiles/r04_probes/bucket_prefetch_and_occupancy.txt): a variant with
     // the next entry REALLY prefetched (the eight loads as inline assembly between sched_barriers right after the third
     // multiplication, awaited after the seventh: 157 VGPRs, three waves) and a variant that touches the next line
     // early both take the same 660 us as this kernel; confined to 3 / 2 / 1 workgroups per CU all of them take 735 /
     // 760-770 / 880 us, with or without prefetch.  It is bound by vector-ALU issue, not by the gather's latency:
-    // one wave per SIMD already issues 75 % of what four do.
-    for (uint32_t left = len;;) {
+    // one wave per SIMD already issues 75 % of what four do.  (Nor by its instruction count alone: EXPERIMENTS C.2.)
+    uint32_t e = col[0];
+    ge_niels q = niels_ld(niels, e);
+    ge_ext acc;
+    {
+        // the run's first entry IS the accumulator (one product, ge_ext_from_niels_neg), the second is on its way
+        const uint32_t en = col[(len > 1 ? 1 : 0) * MSM_BLOCK];
+        ge_niels qn = niels_ld(niels, en);
+        acc = ge_ext_from_niels_neg(q, (e >> 31) != 0);
+        e = en;
+        q = qn;
+    }
+    for (uint32_t left = len, k = 1;;) {
         const uint32_t n = left < MSM_IDX_WIN ? left : MSM_IDX_WIN;
-        uint32_t e = col[0];
-        ge_niels q = niels_ld(niels, e);
-        for (uint32_t k = 0; k < n; k++) {
+        for (; k < n; k++) {
             // (the window's last addition asks for its own line once more: a hit)
             const uint32_t en = col[(k + 1 < n ? k + 1 : k) * MSM_BLOCK];
             ge_niels qn = niels_ld(niels, en);
-            acc = ge_madd(acc, ge_niels_select_neg(q, (e >> 31) != 0));
+            acc = ge_madd_cols(acc, ge_niels_select_neg(q, (e >> 31) != 0));
             e = en;
             q = qn;
         }
@@ -130,6 +143,9 @@ k_msm_bucket(const uint32_t *__restrict__ niels, const uint32_t *__restrict__ so
         run += MSM_IDX_WIN;
         for (uint32_t k0 = 0; k0 < MSM_IDX_WIN && k0 < left; k0 += 8)
             msm_idx_fill<8>(col + k0 * MSM_BLOCK, run + k0, left - k0);
+        k = 0;
+        e = col[0];
+        q = niels_ld(niels, e);
     }
     ext_st(((tk.w & MSM_TASK_SPLIT) ? partial : buckets) + EXT_WORDS * (size_t)tk.z, acc);
     }
@@ -344,7 +360,7 @@ k_madd_rate(const uint32_t *__restrict__ seed, int iters, uint32_t *__restrict__
     ge_niels q = ge_niels_from_affine(a);
     ge_ext p = ge_ext_identity();
     for (int k = 0; k < iters; k++) {
-        p = ge_madd(p, q);
+        p = ge_madd_cols(p, q);       // the bucket loop's form of the mixed addition
         q.t2d.v[0] ^= (uint32_t)k & 1u;
     }
     fe s = fe_add(fe_add(p.X, p.Y), fe_add(p.Z, p.T));
