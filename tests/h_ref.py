@@ -1,6 +1,7 @@
 """A big-int restatement of the Pinocchio prover's h (verifiable_mpc/trinocchio/pynocchio.py:203-225), deliberately by
 the NAIVE route - interpolate V, W, Y, multiply, divide by t with remainder, add the zero-knowledge terms - so that it
-shares nothing with the moment formula of csrc/bn256_qap_h.hip; that formula restated (moment_h); and a builder of
+shares nothing with the moment formula of csrc/bn256_qap_h.hip; that formula restated (moment_h); an O(d) test of a
+claimed h at one random point, for degrees at which the restatements are too slow (h_identity_holds); and a builder of
 random satisfiable sparse R1CS with their witnesses.  The independent side of tests/test_h_ref.py and
 tests/test_gpu_pinocchio_h.py."""
 import math
@@ -101,6 +102,30 @@ def moment_h(a, b, deltas=None):
     h = [(sum(t[i] * C[i - e] for i in range(e + 1, d + 1)) + dv * dw * t[e] - (dy if e == 0 else 0)) % N
          for e in range(d + 1)]
     return h if deltas is not None else h[:max(d - 1, 0)]
+
+
+def h_identity_holds(a, b, y, h, deltas=None, seed=0):
+    """An O(d) test of a claimed h (ints, lowest coefficient first, any length) against the row values, for degrees at
+    which moment_h is too slow: at one seeded random point r outside the nodes,
+        h(r) t(r) == (V(r) + dv t(r)) (W(r) + dw t(r)) - (Y(r) + dy t(r)),     t(r) = prod_j (r - j),
+    with V(r), W(r), Y(r) by barycentric evaluation of a, b, y at the nodes 1 .. d: P(r) = t(r) sum_j P(j) / (w_j (r - j)),
+    w_j = prod_{k != j} (j - k) = (-1)^(d-j) (j-1)! (d-j)!.  Without deltas dv = dw = dy = 0.  Both sides are polynomials
+    in r of degree at most 2 d, so a wrong h passes with probability at most 2 d / N.  The length of h is not tested."""
+    d = len(a)
+    dv, dw, dy = deltas if deltas is not None else (0, 0, 0)
+    r = random.Random(seed).randrange(d + 1, N)
+    fact = [1] * (d + 1)
+    for j in range(1, d + 1):
+        fact[j] = fact[j - 1] * j % N
+    t = 1
+    for j in range(1, d + 1):
+        t = t * (r - j) % N
+    inv = [pow((-1) ** (d - j) * fact[j - 1] * fact[d - j] * (r - j) % N, -1, N) for j in range(1, d + 1)]
+    V, W, Y = (t * sum(int(v) * i for v, i in zip(vals, inv)) % N for vals in (a, b, y))
+    hr = 0
+    for x in reversed(h):
+        hr = (hr * r + int(x)) % N
+    return hr * t % N == ((V + dv * t) * (W + dw * t) - (Y + dy * t)) % N
 
 
 def satisfiable_r1cs(d, seed, n_io=2, extra=3, zero_a=False, zero_b=False):

@@ -808,8 +808,8 @@ def chunked_format(env, name):
 
 
 def pinocchio_war(env, name):
-    """pynocchio.py compute_proof over a PreparedKey with compute_h's HPoly, and the batch form: aux20 (twist sum) and
-    aux21 (h sum) <- main.  Their inputs reach the device through blocking uploads on the main stream, which drain a
+    """pynocchio.py compute_proof over a PreparedKey with compute_h's HPoly (twice) and the batch form on two witnesses:
+    aux20 (twist sum) and aux21 (h sum) <- main.  Their inputs reach the device through blocking uploads on the main stream, which drain a
     stall there before the waits are issued (no read-after-write case: EXPERIMENTS.md O.3); here the consumers run late
     and the caller proves again with the same key.  Against the reference-made proofs of tests/golden/pinocchio_keygen.json."""
     from tests import test_gpu_pinocchio_h as TH
@@ -821,21 +821,24 @@ def pinocchio_war(env, name):
     gen = TH._gen(pn, td)
     c, deltas = TH._case_inputs(case)
     key = pn.PreparedKey.generate(td, qap, gen)
-    d = delay_of(name)
-    sites = {"pynocchio.py:_compute_proof_prepared": d, "pynocchio.py:_compute_proof_batch_prepared": d}
-    with Recorder(env, delay_waiter=sites) as rec:
-        proofs = []
+    site = "pynocchio.py:_compute_proof_batch_prepared"       # the one proof assembly: compute_proof is its batch of one
+    with Recorder(env, delay_waiter={site: delay_of(name)}) as rec:
+        proofs, ends = [], []
         for _ in range(2):
             h = pn.compute_h(qap, c, deltas)
             proofs.append(pn.compute_proof(qap, c, h, key, deltas))
+            ends.append(len(rec.calls))
         hs = pn.compute_h_batch(qap, [c, c], [deltas, deltas])
         proofs += pn.compute_proof_batch(qap, [c, c], hs, key, [deltas, deltas])
+        ends.append(len(rec.calls))
     for proof in proofs:
         for k, enc in case["proof"].items():
             assert TH._enc(proof[k]) == enc, k
-    assert len(rec.at("pynocchio.py:_compute_proof_prepared", "aux20", "main")) == 2
-    assert len(rec.at("pynocchio.py:_compute_proof_prepared", "aux21")) == 2
-    assert len(rec.at("pynocchio.py:_compute_proof_batch_prepared")) >= 2
+    # per call, whatever K is: aux20 <- main; aux21 <- main (the result buffer) and aux21 <- the context that made h (main)
+    for lo, hi in zip([0] + ends, ends):
+        waits = [(w["waiter"], w["other"]) for w in rec.calls[lo:hi] if w["site"] == site]
+        assert sorted(waits) == [("aux20", "main"), ("aux21", "main"), ("aux21", "main")], waits
+    assert len(rec.at(site, "aux20", "main")) == 3 and len(rec.at(site, "aux21")) == 6 and len(rec.at(site)) == 9
     return {"waits": rec.calls}
 
 

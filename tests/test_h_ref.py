@@ -64,6 +64,27 @@ def test_moment_formula_agrees_with_the_naive_route(d):
         assert got == want and len(got) == (d + 1 if dl is not None else max(d - 1, 0))
 
 
+@pytest.mark.parametrize("d", [1, 2, 65])
+def test_evaluation_identity_agrees_with_the_moment_formula(d):
+    """h_identity_holds accepts moment_h's h, with and without deltas, and rejects it with any one coefficient spoiled
+    (sampled: the lowest, a middle and the top one)"""
+    V, W, Y, out_ix, m, c = H.satisfiable_r1cs(d, seed=100 + d)
+    a, b, y = (H.csr_row_values(M, c) for M in (V, W, Y))
+    for dl in (None, (d * 7919 % N, N - d, pow(3, d, N)), (0, 0, 0)):
+        h = H.moment_h(a, b, dl)
+        assert H.h_identity_holds(a, b, y, h, dl, seed=d)
+        assert H.h_identity_holds(a, b, y, h + [0], dl, seed=d)          # (a top zero is the same polynomial)
+        for k in sorted({0, len(h) // 2, len(h) - 1} & set(range(len(h)))):
+            spoiled = list(h)
+            spoiled[k] = (spoiled[k] + 1) % N
+            assert not H.h_identity_holds(a, b, y, spoiled, dl, seed=d), (dl, k)
+    if d > 1:
+        assert not H.h_identity_holds(a, b, y, H.moment_h(a, b), (1, 2, 3), seed=d)      # h without its deltas' terms
+    # the row values decide, not the witness: a violated row fails whatever h is offered
+    y[0] = (y[0] + 1) % N
+    assert not H.h_identity_holds(a, b, y, H.moment_h(a, b), seed=d)
+
+
 def test_builder_degenerate_forms():
     for kw in ({"zero_a": True}, {"zero_b": True}):
         V, W, Y, out_ix, m, c = H.satisfiable_r1cs(9, seed=3, **kw)

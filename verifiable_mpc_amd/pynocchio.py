@@ -23,7 +23,8 @@ coefficients with the low half of the two series' product.  The result stays on 
 
 K witnesses of ONE QAP: exactly the results of K compute_h / compute_proof calls, with every stage of h run once for all
 K - the witness on the grid, the launch plans chosen with K counted - and the K proofs' uploads, synchronisations,
-downloads and inversions shared.  What verify_batch takes.
+downloads and inversions shared.  What verify_batch takes.  There is one implementation per stage:
+compute_h, compute_h_share and compute_proof over a PreparedKey are these functions' code on a batch of one.
 
     calculate_witness, calculate_witness_batch, prove_batch_inputs, SolvePlan    (tools/code_to_qap.py QAP.calculate_witness)
 
@@ -258,30 +259,6 @@ class _KeyVector:
         self.table = ctx.bn256_table_build(group, dp.ptr, n)
         ctx.sync()
 
-    def launch(self, ctx, head, head_n, tail=()):
-        """enqueue sum over the first head_n + len(tail) points: `head` is a device buffer of head_n
-        scalars shared by several sums, `tail` a few host ints that follow them.  -> pending handle"""
-        m = head_n + len(tail)
-        assert m <= self.n
-        jw = 3 * self.width // 2
-        ds, out = ctx.alloc(max(32, 32 * m)), ctx.alloc(jw)
-        if head_n:
-            ctx.copy(ds.ptr, head.ptr, 32 * head_n)
-        if tail:
-            ctx.upload_into(ds.ptr + 32 * head_n, _native.ints_to_array([int(s) % ORDER for s in tail], 32))
-        ctx.bn256_table_msm(self.group, self.table.ptr, self.n, ds.ptr, m, None, out.ptr)
-        return ctx, out, jw, ds
-
-    def result(self, pending):
-        ctx, out, jw, _ = pending
-        ctx.sync()
-        # the sum comes back in Jacobian coordinates; the one inversion is O(1) host glue
-        return _from_jacobian(self.group, ctx.download(out.ptr, jw).tobytes())
-
-    def msm(self, ctx, scalars):
-        head = ctx.upload(_native.ints_to_array([int(s) % ORDER for s in scalars], 32)) if scalars else None
-        return self.result(self.launch(ctx, head, len(scalars)))
-
 
 class PreparedKey:
     """The evaluation key of one circuit, prepared for many proofs: the eight point vectors that
@@ -400,76 +377,6 @@ def scalars_to_array(values):
     return arr
 
 
-def _compute_proof_prepared(key, c, h, deltas):
-    """The eight sums over a prepared key.  The shared `c_mid` scalars are converted and uploaded once; the SIX G1 sums
-    over them are one multi-key pass (one recoding, sort and plan; six bucket launches over the one sorted index
-    list; one reduction and one finishing launch), the twist sum over them runs beside it on a second stream; ONLY
-    THEN are h's coefficients converted - on the host, while the GPU works through those seven - and the last sum
-    enqueued.  The sums come back in Jacobian coordinates; their inversions are shared on the host (one modular
-    inversion for all seven G1 results).
-    c: indexable by qap.indices_mid (the reference's list of ints / field elements), or an (n_wires, 32) uint8
-    array of canonical residues (rows taken by index); h: the reference's polynomial (.coeffs), a list, or an
-    (len, 32) uint8 array, or compute_h's HPoly (read where it lies on the device)."""
-    from .device import get_aux_context
-    ctx = key.ctx
-    n_mid = len(key.mid)
-    if deltas is not None and key.zk_missing:
-        # the dict path fails with KeyError on the first absent name (pynocchio.py:229-246)
-        raise KeyError("zero-knowledge deltas given but the prepared key lacks "
-                       + ", ".join(sorted(n for names in key.zk_missing.values() for n in names)))
-    if isinstance(c, np.ndarray):
-        c_all = _native.as_bytes_array(c, 32)
-        # (a key whose mid wires are ALL the wires, in order, needs no gather: 8 MB less to copy at 2^18 terms)
-        c_mid = c_all if _mid_is_identity(key, len(c_all)) else np.ascontiguousarray(c_all[key.mid_index])
-    else:
-        c_mid = scalars_to_array([c[i] for i in key.mid])
-    dvals = [int(getattr(deltas, d)) % ORDER for d in _DELTAS] if deltas is not None else []
-    # c_mid || (delta_v, delta_w, delta_y): the scalar vector of the six G1 sums (and, through its own tail, the twist's)
-    n_shared = n_mid + len(dvals)
-    head = ctx.alloc(max(32, 32 * n_shared))
-    if n_mid:
-        ctx.upload_into(head.ptr, c_mid)
-    if dvals:
-        ctx.upload_into(head.ptr + 32 * n_mid, _native.ints_to_array(dvals, 32))
-    hv = key.vectors["h*g1"]
-    h_ctx = get_aux_context(21)
-    h_dev = h if isinstance(h, HPoly) else None
-    h_coeffs = None if h_dev is not None else h if isinstance(h, (np.ndarray, list)) else h.coeffs
-    g1 = [key.vectors[name] for name in _SHARED_G1]
-    out_g1 = ctx.alloc(96 * len(g1))
-    # three streams: the twist sum (the longest single one) first, the six-sum pass beside it, h's sum on a third -
-    # the bucket kernels take turns on the chip, the reductions and recombinations (latency chains) overlap them
-    twist_ctx = get_aux_context(20)
-    twist_ctx.wait_for(ctx)               # `head` was filled on the main stream
-    pending_twist = None
-    for name, (_, zk) in _ELEMENTS.items():
-        if name not in _SHARED_G1:
-            tail = [int(getattr(deltas, attr)) for attr, _ in zk] if deltas is not None else []
-            pending_twist = (name, key.vectors[name].launch(twist_ctx, head, n_mid, tail))
-    ctx.bn256_table_msm_multi(1, [v.table.ptr for v in g1], g1[0].n, head.ptr, n_shared, out_g1.ptr)
-    # h's coefficients: converted (the reference's ints) and uploaded on the third stream while the GPU works through
-    # the seven sums over c (an upload only synchronises the stream it is issued on)
-    if h_dev is not None:
-        # compute_h's coefficients are on the device already: the h stream waits for the stream that made them
-        h_ctx.wait_for(h_dev.ctx)
-        pending_h = hv.launch(h_ctx, h_dev.buf if len(h_dev) else None, len(h_dev))
-    else:
-        if isinstance(h_coeffs, np.ndarray):
-            h_arr = scalars_to_array(h_coeffs)
-        else:
-            h_arr = scalars_to_array([h_coeffs[i] for i in range(len(h))])
-        h_head = h_ctx.upload(h_arr) if len(h_arr) else None
-        pending_h = hv.launch(h_ctx, h_head, len(h_arr))
-    ctx.sync()
-    h_ctx.sync()
-    raw = ctx.download(out_g1.ptr, 96 * len(g1)).tobytes() + h_ctx.download(pending_h[1].ptr, 96).tobytes()
-    points = _from_jacobian_many_g1([raw[96 * i:96 * i + 96] for i in range(len(g1) + 1)])
-    out = dict(zip(_SHARED_G1, points[:-1]))
-    out[pending_twist[0]] = key.vectors[pending_twist[0]].result(pending_twist[1])
-    out["h*g1"] = points[-1]
-    return {name: out[name] for name in list(_ELEMENTS) + ["h*g1"]}
-
-
 def _mid_is_identity(key, n_wires):
     flag = getattr(key, "_mid_identity", None)
     if flag is None:
@@ -480,9 +387,10 @@ def _mid_is_identity(key, n_wires):
 
 def compute_proof(qap, c, h, evalkey, deltas=None):
     """Pinocchio proof elements (pynocchio.py:228-273), one MSM per element.  `evalkey` is the
-    reference's dict of points, or a PreparedKey made from it (device-resident, tabulated)."""
+    reference's dict of points, or a PreparedKey made from it (device-resident, tabulated): then this is
+    _compute_proof_batch_prepared's batch of one, which also says what c and h may be."""
     if isinstance(evalkey, PreparedKey):
-        return _compute_proof_prepared(evalkey, c, h, deltas)
+        return _compute_proof_batch_prepared(evalkey, [c], [h], None if deltas is None else [deltas])[0]
     mid = list(qap.indices_mid)
     cm = [int(c[i]) for i in mid]
 
@@ -510,12 +418,19 @@ def compute_proof(qap, c, h, evalkey, deltas=None):
 
 
 def _compute_proof_batch_prepared(key, cs, hs, deltas):
-    """K proofs over a prepared key, stage-major: ONE upload of the K scalar vectors c_mid || (delta_v, delta_w, delta_y),
-    then K six-key passes on the main stream, K twist sums on aux 20 (with deltas each over c_mid || delta_w, put together
-    by two device copies on that stream) and K h sums on aux 21, queued without a host wait in between (the table sums
-    do not synchronise), one synchronisation per stream, one download of all 8 K Jacobian results and two shared
-    inversions (7 K G1 results, K twist results).  The MSM kernels are the single path's; what the batch saves is the
-    per-proof conversion, upload, synchronisation, download and inversion."""
+    """The eight sums of K proofs over a prepared key, stage-major; compute_proof is the K = 1 call.  ONE upload of the K
+    scalar vectors c_mid || (delta_v, delta_w, delta_y) (K = 1: c_mid straight from the caller's array, the deltas behind
+    it), then on three streams: K twist sums on aux 20 (the longest single sum, first; without deltas read from the shared
+    vector in place, with deltas each over c_mid || delta_w, put together by two device copies on that stream), K
+    six-key passes on the main stream (the SIX G1 sums over c_mid are one multi-key pass: one recoding, sort and plan,
+    six bucket launches over the one sorted index list, one reduction and one finishing launch) and K h sums on aux 21 -
+    the bucket kernels take turns on the chip, the reductions and recombinations (latency chains) overlap them.  All
+    are queued without a host wait in between (the table sums do not synchronise); ONLY THEN are host-side h
+    coefficients converted, while the GPU works through the sums over c.  One synchronisation per stream, one download
+    of all 8 K Jacobian results and two shared inversions (7 K G1 results, K twist results).
+    cs[w]: indexable by qap.indices_mid (the reference's list of ints / field elements), or an (n_wires, 32) uint8 array
+    of canonical residues (rows taken by index); hs[w]: the reference's polynomial (.coeffs), a list, an (len, 32) uint8
+    array, or an HPoly - K HPoly are read where they lie on the device."""
     from .device import get_aux_context
     ctx, K = key.ctx, len(cs)
     if deltas is not None and key.zk_missing:
@@ -526,18 +441,33 @@ def _compute_proof_batch_prepared(key, cs, hs, deltas):
     n_shared = n_mid + (3 if zk else 0)
     n_twist = n_mid + (1 if zk else 0)
     rows = max(n_shared, 1)
-    host = np.zeros((K * rows, 32), np.uint8)
-    for w, c in enumerate(cs):
+
+    def scalars(w):
+        """witness w's c_mid as an (n_mid, 32) array - the caller's own memory where no gather is needed - and its deltas"""
+        c = cs[w]
         if isinstance(c, np.ndarray):
             c_all = _native.as_bytes_array(c, 32)
+            # (a key whose mid wires are ALL the wires, in order, needs no gather: 8 MB less to copy at 2^18 terms)
             c_mid = c_all if _mid_is_identity(key, len(c_all)) else c_all[key.mid_index]
         else:
             c_mid = scalars_to_array([c[i] for i in key.mid])
-        host[w * rows:w * rows + n_mid] = c_mid
+        return c_mid, _native.ints_to_array([int(getattr(deltas[w], d)) % ORDER for d in _DELTAS], 32) if zk else None
+
+    if K == 1:
+        # one proof: c_mid goes up from where it lies and the deltas in a second small upload behind it - staging the
+        # row on the host first would copy 8 MB more at 2^18 terms, of the order of the whole proof
+        head = ctx.alloc(32 * rows)
+        c_mid, dv = scalars(0)
+        ctx.upload_into(head.ptr, c_mid)
         if zk:
-            dv = _native.ints_to_array([int(getattr(deltas[w], d)) % ORDER for d in _DELTAS], 32)
-            host[w * rows + n_mid:w * rows + n_shared] = dv
-    head = ctx.upload(host)
+            ctx.upload_into(head.ptr + 32 * n_mid, dv)
+    else:
+        host = np.zeros((K * rows, 32), np.uint8)
+        for w in range(K):
+            host[w * rows:w * rows + n_mid], dv = scalars(w)
+            if zk:
+                host[w * rows + n_mid:w * rows + n_shared] = dv
+        head = ctx.upload(host)
     twist_sc = ctx.alloc(32 * K * n_twist) if zk else head
     twist_stride = 32 * (n_twist if zk else rows)
     g1 = [key.vectors[name] for name in _SHARED_G1]
@@ -574,7 +504,7 @@ def _compute_proof_batch_prepared(key, cs, hs, deltas):
                 hc = h if isinstance(h, (np.ndarray, list)) else h.coeffs
                 arrs.append(scalars_to_array(hc if isinstance(hc, np.ndarray) else [hc[i] for i in range(len(h))]))
         offs = np.concatenate([[0], np.cumsum([len(a) for a in arrs])]).astype(np.int64)
-        hb = h_ctx.upload(np.concatenate(arrs) if offs[-1] else np.zeros((1, 32), np.uint8))
+        hb = h_ctx.upload((arrs[0] if K == 1 else np.concatenate(arrs)) if offs[-1] else np.zeros((1, 32), np.uint8))
         keep.append(hb)
         h_ptrs = [(hb.ptr + 32 * int(offs[w]), len(arrs[w])) for w in range(K)]
     for w, (ptr, n) in enumerate(h_ptrs):
@@ -1277,18 +1207,10 @@ def _t_coeffs(ctx, qap):
     return _per_ctx(qap, "t", ctx, make)
 
 
-def _row_values(ctx, qap, dc, n_wires):
-    """device buffer a || b || y (d scalars each): the R1CS row values V(j), W(j), Y(j) at the witness"""
+def _check_cap(qap, who):
     d = int(qap.d)
-    aby = ctx.alloc(32 * 3 * d)
-    if isinstance(qap, R1CSQAP):
-        _per_ctx(qap, "rows", ctx, lambda: _row_plan(ctx, qap)).run(dc.ptr, n_wires, aby.ptr)
-        return aby, ()
-    plan, top = _per_ctx(qap, "coeffs", ctx, lambda: _coeff_plan(ctx, qap))
-    coef = ctx.alloc(32 * 3 * top)
-    plan.run(dc.ptr, n_wires, coef.ptr)
-    ctx.bn256_qap_horner(coef.ptr, top, 3, d, aby.ptr)
-    return aby, (coef,)
+    if d + 1 > _native.BN256_FR_POLY_MAX:
+        raise ValueError(f"{who}: d + 1 = {d + 1} exceeds the polynomial product's cap {_native.BN256_FR_POLY_MAX}")
 
 
 def compute_h(qap, c, deltas=None, ctx=None):
@@ -1297,30 +1219,11 @@ def compute_h(qap, c, deltas=None, ctx=None):
     zeros kept).  qap: an R1CSQAP or a reference QAP; c: as compute_proof takes it (ints / field elements indexable by
     qap.indices, negative or >= the order reduced, or an (n_wires, 32) uint8 array).  All O(d^2) work runs on the
     device; the result (an HPoly) stays there and compute_proof over a PreparedKey reads it in place.  A witness that
-    violates a constraint raises ValueError naming the first violated constraint (1-based, the point x = j)."""
-    ctx = ctx or get_context()
-    d = int(qap.d)
-    aby, keep = _upload_row_values(ctx, qap, c, "compute_h")
-    bad = ctx.alloc(4)
-    ctx.bn256_qap_check(aby.ptr, aby.ptr + 32 * d, aby.ptr + 64 * d, d, bad.ptr)
-    ctx.sync()
-    first = int(ctx.download(bad.ptr, 4).view("<u4")[0])
-    if first != 0xFFFFFFFF:
-        raise ValueError(f"compute_h: the witness violates constraint {first + 1} (V(j) W(j) != Y(j) at j = {first + 1})")
-    dd = _scalar_buf(ctx, [deltas.v, deltas.w, deltas.y]) if deltas is not None else None
-    return _h_from_row_values(ctx, qap, aby, keep, dd)
-
-
-def _upload_row_values(ctx, qap, c, who):
-    """c on the device and its row values a || b || y -> (buffer, what must outlive the stream's work on it)"""
-    d = int(qap.d)
-    if d + 1 > _native.BN256_FR_POLY_MAX:
-        raise ValueError(f"{who}: d + 1 = {d + 1} exceeds the polynomial product's cap {_native.BN256_FR_POLY_MAX}")
-    c_arr = _witness_array(qap, c)
-    n_wires = len(c_arr)
-    dc = ctx.upload(c_arr) if n_wires else ctx.alloc(32)
-    aby, keep = _row_values(ctx, qap, dc, n_wires)
-    return aby, (dc,) + tuple(keep)
+    violates a constraint raises ValueError naming the first violated constraint (1-based, the point x = j).
+    compute_h_batch's pipeline (_h_batch) on one row."""
+    _check_cap(qap, "compute_h")
+    return _h_batch(ctx or get_context(), qap, _witness_array(qap, c)[None], None if deltas is None else [deltas],
+                    "compute_h: the witness")[0]
 
 
 def _h_rows(ctx, d, t, aby_ptr, n, dd, out_ptr, out_stride):
@@ -1332,20 +1235,9 @@ def _h_rows(ctx, d, t, aby_ptr, n, dd, out_ptr, out_stride):
     mom = ctx.alloc(32 * 2 * d * n)
     ctx.bn256_qap_moments_batch(u.ptr, u.ptr + 32 * d, 2 * d, d, d, mom.ptr, mom.ptr + 32 * d, 2 * d, n)
     scratch = ctx.alloc(32 * 3 * d * n)
-    ctx.bn256_qap_h_combine_batch(mom.ptr, mom.ptr + 32 * d, 2 * d, t.ptr, d, dd.ptr if dd else None, scratch.ptr,
+    ctx.bn256_qap_h_combine_batch(mom.ptr, mom.ptr + 32 * d, 2 * d, t.ptr, d, None if dd is None else dd.ptr, scratch.ptr,
                                   out_ptr, out_stride, n)
     ctx.sync()      # the temporaries above may be released once the stream has drained
-
-
-def _h_from_row_values(ctx, qap, aby, keep, dd):
-    """one witness's row values -> h; dd: device buffer of the three deltas or None.  Nothing here asks whether the
-    rows satisfy a_j b_j = y_j: the result is the polynomial part of V W / t."""
-    d = int(qap.d)
-    t = _t_coeffs(ctx, qap)
-    out = ctx.alloc(32 * (d + 1))
-    _h_rows(ctx, d, t, aby.ptr, 1, dd, out.ptr, d + 1)
-    del keep
-    return HPoly(ctx, out, d + 1 if dd is not None else max(d - 1, 0))
 
 
 def compute_h_share(qap, c_share, delta_shares=None, ctx=None):
@@ -1357,14 +1249,12 @@ def compute_h_share(qap, c_share, delta_shares=None, ctx=None):
     the h that compute_h(qap, c, deltas) gives, coefficient for coefficient - M >= 2t + 1 parties recombine it with the
     Lagrange weights at 0, no exchange needed.  delta_shares: this party's shares as .v, .w, .y, or a device buffer of
     those three scalars.  Lengths as compute_h: d + 1 with deltas, max(d - 1, 0) without.  (Whether the shared witness
-    satisfies the constraints is trinocchio.prove's residual check, vmpc_bn256_qap_residual_dev.)"""
-    ctx = ctx or get_context()
-    aby, keep = _upload_row_values(ctx, qap, c_share, "compute_h_share")
-    dd = None
-    if delta_shares is not None:
-        dd = delta_shares if hasattr(delta_shares, "ptr") else \
-            _scalar_buf(ctx, [delta_shares.v, delta_shares.w, delta_shares.y])
-    return _h_from_row_values(ctx, qap, aby, keep, dd)
+    satisfies the constraints is trinocchio.prove's residual check, vmpc_bn256_qap_residual_batch_dev.)
+    compute_h_share_batch's pipeline (_h_batch without the check) on one row."""
+    _check_cap(qap, "compute_h_share")
+    if delta_shares is not None and not hasattr(delta_shares, "ptr"):
+        delta_shares = [delta_shares]
+    return _h_batch(ctx or get_context(), qap, _witness_array(qap, c_share)[None], delta_shares, None)[0]
 
 
 # ---- h for K witnesses of one QAP (DESIGN.md section 21) -------------------------------------------------------------
@@ -1448,65 +1338,42 @@ def compute_h_batch(qap, cs, deltas=None, ctx=None):
     weights, moments or products are launched - then weights, moments, combination and one synchronisation.  K is cut
     into consecutive chunks that hold at most BATCH_BUDGET_BYTES of device memory each (plan_chunks, h_batch_bytes); a
     chunk boundary changes no value."""
-    ctx = ctx or get_context()
-    d = int(qap.d)
-    if d + 1 > _native.BN256_FR_POLY_MAX:
-        raise ValueError(f"compute_h_batch: d + 1 = {d + 1} exceeds the polynomial product's cap "
-                         f"{_native.BN256_FR_POLY_MAX}")
-    n_wires = len(qap.indices)
-    arr = witness_batch_array(n_wires, cs, qap.indices)
-    K = len(arr)
+    _check_cap(qap, "compute_h_batch")
+    arr = witness_batch_array(len(qap.indices), cs, qap.indices)
     deltas = None if deltas is None else list(deltas)
-    if deltas is not None and len(deltas) != K:
+    if deltas is not None and len(deltas) != len(arr):
         raise ValueError("compute_h_batch: one set of deltas per witness")
-    if K == 0:
+    if len(arr) == 0:
         return []
-    sparse = isinstance(qap, R1CSQAP)
-    if sparse:
-        plan, top = _per_ctx(qap, "rows", ctx, lambda: _row_plan(ctx, qap)), 0
-    else:
-        plan, top = _per_ctx(qap, "coeffs", ctx, lambda: _coeff_plan(ctx, qap))
-    t = _t_coeffs(ctx, qap)
-    stride = d + 1
-    out = ctx.alloc(32 * stride * K)
-    chunks = plan_chunks(K, BATCH_BUDGET_BYTES, lambda n: h_batch_bytes(d, n_wires, top, n))
-    for lo, hi in chunks:
-        n = min(hi - lo, _native.BN256_QAP_MAX_WIT)
-        for a in range(lo, hi, n):
-            _h_batch_chunk(ctx, qap, arr[a:min(a + n, hi)], None if deltas is None else deltas[a:min(a + n, hi)], a,
-                           plan, top, t, out.ptr + 32 * stride * a, stride)
-    n_h = d + 1 if deltas is not None else max(d - 1, 0)
-    return [HPoly(ctx, _BufferView(out, 32 * stride * w, 32 * stride), n_h) for w in range(K)]
+    return _h_batch(ctx or get_context(), qap, arr, deltas, "compute_h_batch: witness {w}")
 
 
-def _h_batch_chunk(ctx, qap, arr, deltas, first, plan, top, t, out_ptr, out_stride):
-    """one chunk of compute_h_batch: n witnesses (arr) -> n rows of h at out_ptr; `first`: the chunk's first witness"""
-    n, n_wires, d = len(arr), arr.shape[1], int(qap.d)
-    dc = ctx.upload(arr) if n_wires else ctx.alloc(32)
-    aby = ctx.alloc(32 * 3 * d * n)
-    if isinstance(qap, R1CSQAP):
-        coef = None
-        for w in range(n):                       # K queued runs of the single path's plan, no host wait between them
-            plan.run(dc.ptr + 32 * n_wires * w, n_wires, aby.ptr + 32 * 3 * d * w)
-    else:
-        coef = ctx.alloc(32 * 3 * top * n)
-        for w in range(n):
-            plan.run(dc.ptr + 32 * n_wires * w, n_wires, coef.ptr + 32 * 3 * top * w)
-            ctx.bn256_qap_horner(coef.ptr + 32 * 3 * top * w, top, 3, d, aby.ptr + 32 * 3 * d * w)
-    bad = ctx.alloc(4 * n)
-    ctx.bn256_qap_check_batch(aby.ptr, aby.ptr + 32 * d, aby.ptr + 64 * d, 3 * d, d, bad.ptr, n)
-    ctx.sync()
-    words = ctx.download(bad.ptr, 4 * n).view("<u4")
-    viol = np.nonzero(words != 0xFFFFFFFF)[0]
-    if len(viol):
-        w, j = int(viol[0]), int(words[viol[0]]) + 1
-        raise ValueError(f"compute_h_batch: witness {first + w} violates constraint {j} "
-                         f"(V(j) W(j) != Y(j) at j = {j})")
-    dd = None
-    if deltas is not None:
-        dd = _scalar_buf(ctx, [getattr(dl, name) for dl in deltas for name in _DELTAS])
-    _h_rows(ctx, d, t, aby.ptr, n, dd, out_ptr, out_stride)
-    del dc, aby, coef, bad, dd
+def _h_batch(ctx, qap, arr, deltas, check):
+    """The h pipeline behind compute_h, compute_h_share and their batch forms: K >= 1 witnesses (or share vectors) of one
+    QAP, a (K, n_wires, 32) array -> K HPoly views into one device buffer.  One range of batch_ranges at a time: upload
+    and row values (_upload_row_values_batch), the constraint check, then weights, moments and combination
+    (_h_from_rows).  deltas: None, a device buffer of 3 K scalars, or K objects with .v .w .y.  check: None for share
+    vectors, which never satisfy a_j b_j = y_j; else how the ValueError for the lowest bad witness begins, formatted with
+    w = that witness's index - it is raised before the range's weights, moments or products are launched."""
+    d = int(qap.d)
+    if deltas is not None and not hasattr(deltas, "ptr"):
+        deltas = _scalar_buf(ctx, [getattr(dl, name) for dl in deltas for name in _DELTAS])
+
+    def rows(lo, hi):
+        aby, keep = _upload_row_values_batch(ctx, qap, arr[lo:hi])
+        if check is not None:
+            n = hi - lo
+            bad = ctx.alloc(4 * n)
+            ctx.bn256_qap_check_batch(aby.ptr, aby.ptr + 32 * d, aby.ptr + 64 * d, 3 * d, d, bad.ptr, n)
+            ctx.sync()
+            words = ctx.download(bad.ptr, 4 * n).view("<u4")
+            viol = np.nonzero(words != 0xFFFFFFFF)[0]
+            if len(viol):
+                j = int(words[viol[0]]) + 1
+                raise ValueError(f"{check.format(w=lo + int(viol[0]))} violates constraint {j} "
+                                 f"(V(j) W(j) != Y(j) at j = {j})")
+        return aby.ptr, (aby, keep)
+    return _h_from_rows(ctx, qap, len(arr), deltas, rows)
 
 
 # ---- h for K SHARE vectors of one QAP (trinocchio.prove_batch; DESIGN.md section 24) ---------------------------------
@@ -1514,9 +1381,7 @@ def _h_batch_chunk(ctx, qap, arr, deltas, first, plan, top, t, out_ptr, out_stri
 def _share_batch_args(qap, c_shares, delta_shares, who):
     """the host half of compute_h_share_batch, which needs no device: -> ((K, n_wires, 32) array, deltas) with deltas
     None, a device buffer of 3 K scalars, or a list of K objects; ValueError for a wrong width or a wrong count"""
-    d = int(qap.d)
-    if d + 1 > _native.BN256_FR_POLY_MAX:
-        raise ValueError(f"{who}: d + 1 = {d + 1} exceeds the polynomial product's cap {_native.BN256_FR_POLY_MAX}")
+    _check_cap(qap, who)
     arr = witness_batch_array(len(qap.indices), c_shares, qap.indices)
     K = len(arr)
     if delta_shares is not None:
@@ -1531,9 +1396,10 @@ def _share_batch_args(qap, c_shares, delta_shares, who):
 
 
 def _upload_row_values_batch(ctx, qap, arr):
-    """K share vectors (a (K, n_wires, 32) array, K >= 1) on the device in ONE upload and their row values, K rows
-    a || b || y of 3 d scalars, by K queued runs of the single path's plan -> (buffer, what must outlive the stream's work
-    on it).  _upload_row_values for K vectors: trinocchio.prove_batch reads the rows for the residual and for h."""
+    """K witnesses or share vectors (a (K, n_wires, 32) array, K >= 1) on the device in ONE upload and their row values
+    V(j), W(j), Y(j), K rows a || b || y of 3 d scalars, by K queued runs of the QAP's plan with no host wait between them
+    -> (buffer, what must outlive the stream's work on it).  The only code that turns a witness into row values: _h_batch
+    runs it range by range, trinocchio.prove_batch once, and reads the rows for the residual and for h."""
     K, n_wires, d = len(arr), arr.shape[1], int(qap.d)
     dc = ctx.upload(arr) if n_wires else ctx.alloc(32)
     aby = ctx.alloc(32 * 3 * d * K)
@@ -1564,41 +1430,43 @@ def batch_ranges(qap, K):
     return out
 
 
-def _h_from_row_values_batch(ctx, qap, aby, keep, dd, K):
-    """K rows of row values -> K HPoly views into one buffer; dd: device buffer of the rows' three deltas each, or None.
-    The weights, moments and combination run once per range of batch_ranges; a boundary changes no value."""
+def _h_from_rows(ctx, qap, K, dd, rows):
+    """K rows of row values -> K HPoly views into one buffer of K rows of d + 1 scalars; dd: device buffer of the rows'
+    three deltas each, or None.  rows(lo, hi) -> (device pointer to rows lo .. hi - 1, what must stay alive while the
+    stream works on them), asked for once per range of batch_ranges, in order; the weights, moments and combination run
+    once per range and a boundary changes no value.  Nothing here asks whether the rows satisfy a_j b_j = y_j: the
+    result is the polynomial part of V W / t."""
     d = int(qap.d)
     t = _t_coeffs(ctx, qap)
     stride = d + 1
     out = ctx.alloc(32 * stride * K)
     for lo, hi in batch_ranges(qap, K):
-        _h_rows(ctx, d, t, aby.ptr + 32 * 3 * d * lo, hi - lo,
-                _BufferView(dd, 96 * lo, 96 * (hi - lo)) if dd is not None else None, out.ptr + 32 * stride * lo, stride)
-    del keep
+        ptr, keep = rows(lo, hi)
+        _h_rows(ctx, d, t, ptr, hi - lo, _BufferView(dd, 96 * lo, 96 * (hi - lo)) if dd is not None else None,
+                out.ptr + 32 * stride * lo, stride)
+        del keep        # (_h_rows has drained the stream)
     n_h = d + 1 if dd is not None else max(d - 1, 0)
     return [HPoly(ctx, _BufferView(out, 32 * stride * w, 32 * stride), n_h) for w in range(K)]
 
 
+def _h_from_row_values_batch(ctx, qap, aby, dd, K):
+    """_h_from_rows on K rows that are on the device already (_upload_row_values_batch's buffer, which the caller holds):
+    trinocchio.prove_batch's second step, after the residual has read the same rows"""
+    return _h_from_rows(ctx, qap, K, dd, lambda lo, hi: (aby.ptr + 32 * 3 * int(qap.d) * lo, None))
+
+
 def compute_h_share_batch(qap, c_shares, delta_shares=None, ctx=None):
     """[compute_h_share(qap, c_shares[w], delta_shares[w]) for w in range(K)], coefficient for coefficient and length
-    included, with every stage run once for all K: ONE upload, K queued runs of the row-value plan, then the weights, the
-    moments and the combination of compute_h_batch (csrc/bn256_qap_h.hip's *_batch_dev entries) - no constraint check (a
-    share vector never satisfies a_j b_j = y_j) and no host read-back before the result.  c_shares: one party's K share
-    vectors as a (K, n_wires, 32) uint8 array, or K vectors as compute_h_share takes them; delta_shares: None, a device
-    buffer of 3 K scalars (witness w's delta_v, delta_w, delta_y at 3 w .. 3 w + 2), or K objects with .v .w .y.  -> a list
-    of K HPoly, each a view into ONE device buffer of K rows of d + 1 scalars.
-    K is cut as compute_h_batch cuts it (batch_ranges: plan_chunks over h_batch_bytes under BATCH_BUDGET_BYTES); the
-    share vectors and their row values, n_wires + 3 d scalars per witness, stay on the device for the whole batch."""
+    included: compute_h_batch's pipeline (_h_batch: per range of batch_ranges one upload, the queued runs of the row-value
+    plan, then weights, moments and combination) without the constraint check (a share vector never satisfies
+    a_j b_j = y_j) and so without a host read-back before the result.  c_shares: one party's K share vectors as a
+    (K, n_wires, 32) uint8 array, or K vectors as compute_h_share takes them; delta_shares: None, a device buffer of 3 K
+    scalars (witness w's delta_v, delta_w, delta_y at 3 w .. 3 w + 2), or K objects with .v .w .y.  -> a list of K HPoly,
+    each a view into ONE device buffer of K rows of d + 1 scalars."""
     arr, deltas = _share_batch_args(qap, c_shares, delta_shares, "compute_h_share_batch")
-    K = len(arr)
-    if K == 0:
+    if len(arr) == 0:
         return []
-    ctx = ctx or get_context()
-    dd = deltas
-    if deltas is not None and not hasattr(deltas, "ptr"):
-        dd = _scalar_buf(ctx, [getattr(dl, name) for dl in deltas for name in _DELTAS])
-    aby, keep = _upload_row_values_batch(ctx, qap, arr)
-    return _h_from_row_values_batch(ctx, qap, aby, keep, dd, K)
+    return _h_batch(ctx or get_context(), qap, arr, deltas, None)
 
 
 # ---- the witness from the inputs (code_to_qap.QAP.calculate_witness; csrc/bn256_r1cs_solve.hip, DESIGN.md section 22) ----

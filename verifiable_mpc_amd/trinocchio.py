@@ -34,7 +34,8 @@ calculate_witness_batch.
     K witnesses of one QAP        prove_batch, prove_inputs_batch
 
 `prove_batch` is `prove` for K witnesses in the SAME exchanges: one deal round, rho opened once, the K masked residuals
-opened together, one exchange of the 8 K proof-share points.  The recombination in the exponent - of one proof or of K -
+opened together, one exchange of the 8 K proof-share points.  There is one prover body, `_prove`: `prove` runs it on a
+batch of one, and `prove_inputs` / `prove_inputs_batch` are calculate_witness_shares followed by it.  The recombination in the exponent - of one proof or of K -
 is one vmpc_bn256_recombine_dev launch per group (`Runtime.recombine_points`, csrc/bn256_recombine.hip).
 
 Out of scope:
@@ -367,76 +368,43 @@ async def prove(rt, qap, key, c_share, zk=True, check=True):
     check: the parties open a jointly random rho and the masked sum_j rho^j (a_j b_j - y_j) over the shared rows; if it
     is not zero the shares are not of a satisfying witness (or not consistent sharings at all) and every party raises
     ValueError("inconsistent shares") before a proof share is exchanged.  A wrong witness passes with probability at
-    most d / n.  Without the check a wrong witness gives a proof whose H check fails."""
+    most d / n.  Without the check a wrong witness gives a proof whose H check fails.
+
+    `prove_batch`'s body (_prove) on one witness: its exchanges, its random draws and its stages."""
     if not isinstance(key, pn.PreparedKey):
         raise TypeError("trinocchio.prove: key must be a pynocchio.PreparedKey")
-    ctx, d = key.ctx, int(qap.d)
-    assert rt._context() is ctx, "the runtime and the prepared key share one context"
-    c_arr = pn._witness_array(qap, c_share)
-    n_h = d + 1 if zk else max(d - 1, 0)
-    n_delta, n_check = (3 if zk else 0), (1 if check else 0)
-    # 1. all dealt randomness in one exchange: deltas and rho with degree t, zeros (residual, h) with degree 2t
-    rand, zeros = await rt._deal_round(n_delta + n_check, n_check + n_h)
-    t0 = time.perf_counter()
-    aby, keep = pn._upload_row_values(ctx, qap, c_arr, "trinocchio.prove")
-    t0 = rt._stage("h_share", t0)
-    if check:
-        # 2. rho is opened only now: the shares it tests were fixed before anybody knew it
-        rho = (await rt.output(rand[n_delta:]))[0]
-        t0 = time.perf_counter()
-        res = ScalarVector.empty(1, ctx)
-        ctx.bn256_qap_residual(aby.ptr, aby.ptr + 32 * d, aby.ptr + 64 * d, d, rho, res.ptr)
-        # 3. a degree-2t share of 0 for a satisfying witness: opened under a zero sharing, it tells nothing else
-        masked = rt.masked(zeros, 0, res.ptr, 1)
-        rt._stage("residual", t0)
-        if (await rt.output(masked))[0] != 0:
-            raise ValueError("inconsistent shares")
-        t0 = time.perf_counter()
-    deltas = None
-    if zk:
-        dv, dw, dy = rand[:3].to_ints()          # this party's own shares: compute_proof takes them from the host
-        deltas = types.SimpleNamespace(v=dv, w=dw, y=dy)
-    # compute_h_share's two steps (the row values are shared with the check above)
-    h = pn._h_from_row_values(ctx, qap, aby, keep, rand[:3] if zk else None)
-    assert len(h) == n_h
-    t0 = rt._stage("h_share", t0)
-    if n_h:
-        h = pn.HPoly(ctx, rt.masked(zeros, n_check, h.buf.ptr, n_h), n_h)
-    t0 = rt._stage("masks", t0)
-    share = pn.compute_proof(qap, c_arr, h, key, deltas)
-    rt._stage("proof_share", t0)
-    # 4. the eight points and this party's shares of the I/O wires, one exchange
-    names = list(share)
-    out_ix = int(qap.out_ix)
-    every, opened = await rt.exchange_points([share[k] for k in names], np.ascontiguousarray(c_arr[1:out_ix + 1]))
-    t0 = time.perf_counter()
-    proof = dict(zip(names, rt.recombine_points(every, ctx)))
-    rt._stage("recombine", t0)
-    return proof, [1] + opened
+    pn._check_cap(qap, "trinocchio.prove")
+    return (await _prove(rt, qap, key, pn._witness_array(qap, c_share)[None], zk, check, "inconsistent shares"))[0]
 
 
 async def prove_batch(rt, qap, key, c_shares, zk=True, check=True):
     """`prove` for K witnesses of one QAP in the exchanges of ONE: 4 with the check, 2 without, 1 when there is nothing to
     deal, whatever K is.  c_shares: this party's degree-t shares of the K witnesses, a (K, n_wires, 32) uint8 array or K
     vectors as `prove` takes them.  -> a list of K (proof, c_client) pairs, proof w with the keys and point types of
-    pynocchio.compute_proof's result; every party returns the same list (K = 0: [] and no exchange).
-
-    One deal round carries 3 K deltas (witness w's at the random shares 3 w .. 3 w + 2) and rho with degree t, and
-    K residual masks and K n_h masks of h with degree 2t - with K = 1 `prove`'s layout.  rho is opened once, after every
-    share it tests is fixed; the K residuals of one vmpc_bn256_qap_residual_batch_dev launch are masked in one
-    combination and opened in ONE exchange.  If any is not zero every party raises
-    ValueError("inconsistent shares: witness w"), w the lowest such witness, before a proof share leaves.  One rho for K
-    witnesses: a batch with a wrong witness passes with probability at most K d / n (each witness's residual is a
-    nonzero polynomial of degree below d in rho, the union bound over the witnesses).  Then compute_h_share_batch's
-    stages on the row values that the residual read, one combination for the masks where h's rows are contiguous
-    (zk: d + 1 of d + 1 scalars), pynocchio.compute_proof_batch, ONE exchange of the 8 K points with the K out_ix shares
-    of the I/O wires, and one recombination launch per group (Runtime.recombine_points)."""
+    pynocchio.compute_proof's result; every party returns the same list (K = 0: [] and no exchange).  If a masked
+    residual is not zero every party raises ValueError("inconsistent shares: witness w"), w the lowest such witness,
+    before a proof share leaves."""
     if not isinstance(key, pn.PreparedKey):
         raise TypeError("trinocchio.prove_batch: key must be a pynocchio.PreparedKey")
     arr, _ = pn._share_batch_args(qap, c_shares, None, "trinocchio.prove_batch")
-    K, d = len(arr), int(qap.d)
-    if K == 0:
+    if len(arr) == 0:
         return []
+    return await _prove(rt, qap, key, arr, zk, check, "inconsistent shares: witness {w}")
+
+
+async def _prove(rt, qap, key, arr, zk, check, bad):
+    """The prover behind `prove` (K = 1) and `prove_batch`: arr holds this party's shares of K >= 1 witnesses,
+    (K, n_wires, 32); bad: the ValueError's text for a residual that is not zero, formatted with w = the lowest such witness.
+
+    One deal round carries 3 K deltas (witness w's at the random shares 3 w .. 3 w + 2) and rho with degree t, and
+    K residual masks and K n_h masks of h with degree 2t.  rho is opened once, after every share it tests is fixed; the
+    K residuals of one vmpc_bn256_qap_residual_batch_dev launch are masked in one combination and opened in ONE
+    exchange.  One rho for K witnesses: a batch with a wrong witness passes with probability at most K d / n (each
+    witness's residual is a nonzero polynomial of degree below d in rho, the union bound over the witnesses).  Then
+    compute_h_share_batch's stages on the row values that the residual read, one combination for the masks where h's rows
+    are contiguous (zk: d + 1 of d + 1 scalars), pynocchio.compute_proof_batch, ONE exchange of the 8 K points with the K
+    out_ix shares of the I/O wires, and one recombination launch per group (Runtime.recombine_points)."""
+    K, d = len(arr), int(qap.d)
     ctx, M = key.ctx, rt.parties
     assert rt._context() is ctx, "the runtime and the prepared key share one context"
     n_h = d + 1 if zk else max(d - 1, 0)
@@ -459,15 +427,16 @@ async def prove_batch(rt, qap, key, c_shares, zk=True, check=True):
         masked = rt.masked(zeros, 0, res.ptr, K)
         rt._stage("residual", t0)
         opened = await rt.output(masked)
-        bad = [w for w, v in enumerate(opened) if v != 0]
-        if bad:
-            raise ValueError(f"inconsistent shares: witness {bad[0]}")
+        wrong = [w for w, v in enumerate(opened) if v != 0]
+        if wrong:
+            raise ValueError(bad.format(w=wrong[0]))
         t0 = time.perf_counter()
     deltas = None
     if zk:
         dv = rand[:n_delta].to_ints()            # this party's own shares: compute_proof_batch takes them from the host
         deltas = [types.SimpleNamespace(v=dv[3 * w], w=dv[3 * w + 1], y=dv[3 * w + 2]) for w in range(K)]
-    hs = pn._h_from_row_values_batch(ctx, qap, aby, keep, rand[:n_delta] if zk else None, K)
+    hs = pn._h_from_row_values_batch(ctx, qap, aby, rand[:n_delta] if zk else None, K)
+    del aby, keep        # (the stream has drained)
     t0 = rt._stage("h_share", t0)
     if n_h:
         # h's K rows lie d + 1 scalars apart: with the deltas they are contiguous and one combination masks them all
