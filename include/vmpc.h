@@ -591,6 +591,43 @@ int vmpc_bn256_qap_h_weights_batch_dev(vmpc_ctx *ctx, const void *a, const void 
 int vmpc_bn256_qap_moments_batch_dev(vmpc_ctx *ctx, const void *u0, const void *u1, size_t u_stride, size_t d,
                                      size_t n_out, void *out0, void *out1, size_t out_stride, size_t n_wit);
 size_t vmpc_bn256_qap_moments_batch_bytes(size_t d, size_t n_out, size_t n_wit);
+
+/* ---- The same moments in O(d log^2 d): a subproduct tree over the points 1 .. d with its products through the NTT over
+ * the integers, whatever the context's product mode (csrc/bn256_qap_mtree.hip).  With
+ * N(x) = sum_j u_j prod_{i != j} (x - i), T(x) = prod_j (x - j), R and D their coefficients reversed (D(0) = 1),
+ *     sum_{k>=0} A_(k+1) z^k = sum_j u_j / (1 - j z) = R(z) / D(z):   out[k] = (R D^-1 mod z^n_out)[k],
+ * the canonical residues vmpc_bn256_qap_moments_batch_dev writes, bit for bit.
+ * Geometry (csrc/qap_mtree_plan.h): L is the smallest number of levels with s = ceil(d / 2^L) <= 128 and the tree is the
+ * full binary tree of 2^L leaves of s points over 1 .. d' = s 2^L; the points beyond d carry u_j = 0 and change N and T
+ * by the same factor.  At the cap d <= 2^20 - 1: L <= 13 (ceil((2^20 - 1) / 2^13) = 128), so d' <= 128 x 2^13 = 2^20; a
+ * level's products have at most d' + 1 <= 2^20 + 1 coefficients, a Newton step's and the final product's operands at
+ * most n_max <= 2^20 each: every transform length is at most 2^21.
+ * The PLAN depends on (d, n_max) alone - the T of every node, level by level, and D^-1 mod z^n_max (Newton doubling) -
+ * and is built once: vmpc_bn256_qap_mtree_bytes(d, n_max) device bytes, (L + 1) d' + 2^(L+1) - 1 + 3 n_max scalars (2 n_max
+ * of them the build's own; 0 where the build would answer VMPC_E_RANGE or d = 0).  126 MB at d = n_max = 2^18, 570 MB
+ * at the cap.
+ * A call: u1 NULL means one vector; rows as in the batch entries above (strides at least the row's length and at most
+ * 2^31, scalars of a row beyond its length never written); u holds any 32-byte values; 1 <= d, n_out <= n_max with the
+ * (d, n_max) the plan was built for.  VMPC_E_RANGE before any pointer is looked at when d + 1 or n_max exceeds
+ * VMPC_BN256_FR_POLY_MAX, n_out > n_max (so n_out > VMPC_BN256_FR_POLY_MAX too), n_wit > VMPC_BN256_QAP_MAX_WIT or a
+ * stride is out of range; n_out = 0 or n_wit = 0: VMPC_OK, no launch.  scratch: the caller's device memory of
+ * vmpc_bn256_qap_moments_tree_scratch_bytes(d, n_wit) (4 d' scalars a witness).  Arena:
+ * vmpc_bn256_qap_moments_tree_batch_bytes(d, n_out, n_wit), reserved before the first launch; the witnesses are cut
+ * into groups that keep a level's residues within the NTT's arena cap (vmpc_ctx_set_ntt_arena_cap), which changes no
+ * value.  The launches of a call depend on L and on the number of groups, not on d / s or n_wit.  Deterministic. */
+size_t vmpc_bn256_qap_mtree_bytes(size_t d, size_t n_max);
+int vmpc_bn256_qap_mtree_build_dev(vmpc_ctx *ctx, size_t d, size_t n_max, void *plan);
+size_t vmpc_bn256_qap_moments_tree_batch_bytes(size_t d, size_t n_out, size_t n_wit);
+size_t vmpc_bn256_qap_moments_tree_scratch_bytes(size_t d, size_t n_wit);
+int vmpc_bn256_qap_moments_tree_batch_dev(vmpc_ctx *ctx, const void *plan, size_t d, size_t n_max, const void *u0,
+                                          const void *u1, size_t u_stride, size_t n_out, void *out0, void *out1,
+                                          size_t out_stride, void *scratch, size_t n_wit);
+/* compute_h's threshold under device.moment_transform("auto"): the tree from this d on.  The smallest power of two at
+ * which the tree's median (plan cached, two vectors, one witness) is below the direct kernel's in the same run and stays
+ * below at every larger power of two measured: 0.594 ms against 1.637 ms at d = 2^10, the smallest size of the grid
+ * 2^10, 2^12 .. 2^18 of profiles/moments_tree_probe.jsonl (8.57 against 673.8 at 2^18); below 2^10 nothing was
+ * measured. */
+#define VMPC_BN256_QAP_MTREE_MIN ((size_t)1 << 10)
 /* out rows (d + 1 scalars, out_stride apart) from the moments' rows A, B (ab_stride apart), t's d + 1 coefficients (the
  * QAP's, shared) and deltas = n_wit x 3 consecutive scalars (NULL: all zero).  scratch: 3 d scalars per witness.  The two
  * products go through vmpc_bn256_fr_poly_mul_batch_dev and are asked only for what is read: P[0 .. d-2] of A * B and

@@ -54,6 +54,8 @@ SYMBOLS = [
     "vmpc_bn256_fr_poly_mul_batch_bytes",
     "vmpc_bn256_fr_poly_mul_ntt_dev", "vmpc_bn256_fr_poly_mul_ntt_batch_dev", "vmpc_bn256_fr_poly_mul_ntt_batch_bytes",
     "vmpc_ctx_set_ntt_arena_cap", "vmpc_ctx_set_poly_product", "vmpc_ctx_get_poly_product",
+    "vmpc_bn256_qap_mtree_bytes", "vmpc_bn256_qap_mtree_build_dev", "vmpc_bn256_qap_moments_tree_batch_bytes",
+    "vmpc_bn256_qap_moments_tree_scratch_bytes", "vmpc_bn256_qap_moments_tree_batch_dev",
     "vmpc_fr_cs_triples_dev", "vmpc_fr_cs_tables_dev", "vmpc_fr_cs_extend_dev", "vmpc_fr_cs_lagrange_dev",
     "vmpc_fr_cs_colsum_dev", "vmpc_fr_cs_first_diff_dev",
     "vmpc_fr_rows_combine_dev", "vmpc_fr_rows_dot_dev", "vmpc_fr_batch_products_dev",
@@ -205,6 +207,11 @@ def load_library():
         "vmpc_bn256_qap_h_weights_batch_dev": (i32, [vp, vp, vp, sz, sz, vp, vp, sz, sz]),
         "vmpc_bn256_qap_moments_batch_dev": (i32, [vp, vp, vp, sz, sz, sz, vp, vp, sz, sz]),
         "vmpc_bn256_qap_moments_batch_bytes": (sz, [sz, sz, sz]),
+        "vmpc_bn256_qap_mtree_bytes": (sz, [sz, sz]),
+        "vmpc_bn256_qap_mtree_build_dev": (i32, [vp, sz, sz, vp]),
+        "vmpc_bn256_qap_moments_tree_batch_bytes": (sz, [sz, sz, sz]),
+        "vmpc_bn256_qap_moments_tree_scratch_bytes": (sz, [sz, sz]),
+        "vmpc_bn256_qap_moments_tree_batch_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, sz, vp, vp, sz, vp, sz]),
         "vmpc_bn256_qap_h_combine_batch_dev": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, sz]),
         "vmpc_bn256_fr_poly_mul_batch_dev": (i32, [vp, vp, sz, sz, vp, sz, sz, sz, sz, vp, sz, sz]),
         "vmpc_bn256_fr_poly_mul_batch_bytes": (sz, [sz, sz, sz, sz, sz]),
@@ -480,6 +487,7 @@ class Context:
         self._cached_bytes = 0
         self.cache_limit = 16 << 30
         self._pinned = {}         # size class -> [PinnedBuffer]
+        self.moment_transform = "direct"      # how compute_h makes its moments (device.moment_transform)
 
     def _take_pinned(self, nbytes):
         cap = _size_class(nbytes)
@@ -1221,6 +1229,22 @@ class Context:
                                                          p(out0_ptr), p(out1_ptr), out_stride, n_wit),
                "vmpc_bn256_qap_moments_batch_dev")
 
+    def bn256_qap_mtree_build(self, d, n_max, plan_ptr):
+        """the moment transform's subproduct tree over the points 1..d and D^-1 mod z^n_max (csrc/bn256_qap_mtree.hip)
+        into bn256_qap_mtree_bytes(d, n_max) device bytes at plan_ptr; once per (d, n_max)"""
+        _check(self.lib.vmpc_bn256_qap_mtree_build_dev(self.handle, d, n_max, ctypes.c_void_p(plan_ptr)),
+               "vmpc_bn256_qap_mtree_build_dev")
+
+    def bn256_qap_moments_tree_batch(self, plan_ptr, d, n_max, u0_ptr, u1_ptr, u_stride, n_out, out0_ptr, out1_ptr,
+                                     out_stride, scratch_ptr, n_wit):
+        """bn256_qap_moments_batch's bytes in O(d log^2 d) from the plan of (d, n_max), n_out <= n_max; scratch_ptr:
+        bn256_qap_moments_tree_scratch_bytes(d, n_wit) device bytes"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_bn256_qap_moments_tree_batch_dev(self.handle, p(plan_ptr), d, n_max, p(u0_ptr), p(u1_ptr),
+                                                              u_stride, n_out, p(out0_ptr), p(out1_ptr), out_stride,
+                                                              p(scratch_ptr), n_wit),
+               "vmpc_bn256_qap_moments_tree_batch_dev")
+
     def bn256_qap_h_combine_batch(self, a_ptr, b_ptr, ab_stride, t_ptr, d, deltas_ptr, scratch_ptr, out_ptr, out_stride,
                                   n_wit):
         """n_wit rows of h (d + 1 scalars each) from the moments' rows, t and n_wit x 3 deltas (0 / None: none);
@@ -1638,6 +1662,25 @@ def bn256_r1cs_solve_launches(level_ptr, n_wit, wide_rows=0):
 def bn256_qap_moments_batch_bytes(d, n_out, n_wit):
     """the arena bytes Context.bn256_qap_moments_batch reserves (host arithmetic: no GPU, no context)"""
     return int(load_library().vmpc_bn256_qap_moments_batch_bytes(d, n_out, n_wit))
+
+
+BN256_QAP_MTREE_MIN = 1 << 10    # VMPC_BN256_QAP_MTREE_MIN: moment_transform("auto") takes the tree from this d on
+BN256_QAP_MTREE_S_MAX = 128      # QAP_MTREE_S_MAX of csrc/qap_mtree_plan.h: points per leaf at most
+
+
+def bn256_qap_mtree_bytes(d, n_max):
+    """device bytes of the moment transform's plan: (L + 1) d' + 2^(L+1) - 1 + 3 n_max scalars (0: out of range)"""
+    return int(load_library().vmpc_bn256_qap_mtree_bytes(d, n_max))
+
+
+def bn256_qap_moments_tree_batch_bytes(d, n_out, n_wit):
+    """the arena bytes Context.bn256_qap_moments_tree_batch reserves at most (two vectors, the library's arena cap)"""
+    return int(load_library().vmpc_bn256_qap_moments_tree_batch_bytes(d, n_out, n_wit))
+
+
+def bn256_qap_moments_tree_scratch_bytes(d, n_wit):
+    """the caller's device scratch of Context.bn256_qap_moments_tree_batch: 4 d' scalars a witness"""
+    return int(load_library().vmpc_bn256_qap_moments_tree_scratch_bytes(d, n_wit))
 
 
 def bn256_fr_poly_mul_batch_bytes(na, nb, k_lo, k_cnt, n_wit):

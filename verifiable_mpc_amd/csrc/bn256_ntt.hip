@@ -26,6 +26,11 @@
 // Arena: the residues of the shared b (or of a group's b rows) and of a group of a rows; n_wit is cut into groups so that
 // the arena stays below NTT_ARENA_MAX (one row at the cap is 18 x 2^21 x 4 B = 151 MB).  A group boundary changes no
 // value: every row is transformed on its own.  Integer sums in a fixed order, no atomics.
+//
+// vmpc_ntt_tree_level (internal; csrc/bn256_qap_mtree.hip): one level of a subproduct tree,
+// N_parent = N_left T_right + N_right T_left for all nodes and rows in one launch sequence - k_ntt_split_nodes,
+// k_ntt_lds_pair and k_ntt_crt_nodes around the transform kernels above, which take the level's many short transforms
+// as one flat row.
 #include "common.h"
 #include "fr_bn.h"
 #include "ntt31.h"
@@ -74,6 +79,26 @@ k_ntt_split(const uint32_t *__restrict__ src, size_t stride, uint32_t n, uint32_
         dst[((size_t)pr * rows + row) * L + i] = i < n ? ntt31_reduce256(x, ntt31_prime_of(pr)) : 0u;
 }
 
+// the log_b stages of a block of B = 2^log_b values staged in sx, sw the hi twiddle table (k_ntt_lds, k_ntt_lds_pair)
+template <bool INV>
+__device__ __forceinline__ void ntt_lds_stages(uint32_t *sx, const uint32_t *sw, uint32_t B, int log_b,
+                                               const ntt31_prime &q) {
+    for (int s = 0; s < log_b; s++) {
+        const int lh = INV ? s : log_b - 1 - s;        // half-distance 2^lh
+        const uint32_t h = 1u << lh;
+        for (uint32_t t = threadIdx.x; t < B / 2; t += NTT_WG) {
+            const uint32_t r = t & (h - 1), i = ((t >> lh) << (lh + 1)) | r;
+            uint32_t a = sx[i], b = sx[i + h];
+            const uint32_t w = sw[r << (10 - lh)];      // w^(r 2^(20 - lh)): a multiple of 1024 (lh <= 10)
+            if (INV) ntt31_dit(a, b, w, q);
+            else ntt31_dif(a, b, w, q);
+            sx[i] = a;
+            sx[i + h] = b;
+        }
+        __syncthreads();
+    }
+}
+
 // The low stages (halves 1 .. B / 2) of a transform of x's rows, in place, on the block blockIdx.x of B = 2^log_b values.
 // INV: decimation in time with the inverse twiddles, after x[i] *= y[i] (y: y_rows rows, 1 = one row for all).
 template <bool INV>
@@ -96,21 +121,62 @@ k_ntt_lds(uint32_t *__restrict__ x, uint32_t rows, const uint32_t *__restrict__ 
         for (uint32_t i = threadIdx.x; i < B; i += NTT_WG) sx[i] = x[off + i];
     }
     __syncthreads();
-    for (int s = 0; s < log_b; s++) {
-        const int lh = INV ? s : log_b - 1 - s;        // half-distance 2^lh
-        const uint32_t h = 1u << lh;
-        for (uint32_t t = threadIdx.x; t < B / 2; t += NTT_WG) {
-            const uint32_t r = t & (h - 1), i = ((t >> lh) << (lh + 1)) | r;
-            uint32_t a = sx[i], b = sx[i + h];
-            const uint32_t w = sw[r << (10 - lh)];      // w^(r 2^(20 - lh)): a multiple of 1024 (lh <= 10)
-            if (INV) ntt31_dit(a, b, w, q);
-            else ntt31_dif(a, b, w, q);
-            sx[i] = a;
-            sx[i + h] = b;
-        }
-        __syncthreads();
-    }
+    ntt_lds_stages<INV>(sx, sw, B, log_b, q);
     for (uint32_t i = threadIdx.x; i < B; i += NTT_WG) x[off + i] = sx[i];
+}
+
+// ---- a level of a subproduct tree (csrc/bn256_qap_mtree.hip): many short transforms, flat --------------------------
+// A level has `rows` rows of `nodes` children each, every child one transform of L = 2^log_l points: too many for a
+// grid dimension, so the transforms lie one after the other (res[prime][row nodes + node][L]) and the kernels above
+// take them as ONE row of rows x nodes x L values - their stages never look beyond the 2^log_l block they are given.
+
+// dst[prime][row nodes + node][i] = src[row row_stride + node node_stride + i] mod prime for i < n, 0 for n <= i < L;
+// grid (nodes L / 256, rows' y, rows' z), row = z gridDim.y + y
+__global__ void __launch_bounds__(NTT_WG)
+k_ntt_split_nodes(const uint32_t *__restrict__ src, size_t row_stride, size_t node_stride, uint32_t n, int log_l,
+                  uint32_t nodes, uint32_t *__restrict__ dst) {
+    const size_t e = (size_t)blockIdx.x * NTT_WG + threadIdx.x, per_row = (size_t)nodes << log_l;
+    if (e >= per_row) return;
+    const size_t row = (size_t)blockIdx.z * gridDim.y + blockIdx.y, rows = (size_t)gridDim.y * gridDim.z;
+    const uint32_t node = (uint32_t)(e >> log_l), i = (uint32_t)e & ((1u << log_l) - 1);
+    uint32_t x[8];
+    if (i < n) {
+        const uint32_t *s = src + 8 * (row * row_stride + node * node_stride + i);
+#pragma unroll
+        for (int l = 0; l < 8; l++) x[l] = s[l];
+    }
+#pragma unroll
+    for (int pr = 0; pr < NTT31_NP; pr++)
+        dst[((size_t)pr * rows + row) * per_row + e] = i < n ? ntt31_reduce256(x, ntt31_prime_of(pr)) : 0u;
+}
+
+// The inverse's first pass for the parents of a level: parent p of row r starts from x[2p] y[2p+1] + x[2p+1] y[2p]
+// (x: the rows' child transforms, y: the level's T transforms, ONE set for all rows), the two products added in the
+// residue domain (csrc/qap_mtree_plan.h has the bound), and goes to z[prime][r nodes / 2 + p][L].
+// grid (rows (nodes / 2) (L / B), prime); nodes = 2^log_nodes >= 2
+__global__ void __launch_bounds__(NTT_WG)
+k_ntt_lds_pair(const uint32_t *__restrict__ x, const uint32_t *__restrict__ y, uint32_t *__restrict__ z, uint32_t rows,
+               int log_nodes, int log_l, int log_b, const uint32_t *__restrict__ table) {
+    __shared__ uint32_t sx[NTT_LDS_LEN];
+    __shared__ uint32_t sw[NTT_TW_HALF];
+    const int pr = blockIdx.y;
+    const ntt31_prime q = ntt31_prime_of(pr);
+    const uint32_t B = 1u << log_b;
+    const size_t L = (size_t)1 << log_l, nodes = (size_t)1 << log_nodes;
+    const size_t tp = blockIdx.x >> (log_l - log_b);                       // row (nodes / 2) + p
+    const size_t inb = (size_t)(blockIdx.x & ((1u << (log_l - log_b)) - 1)) * B;
+    const size_t row = tp >> (log_nodes - 1), p = tp & ((nodes >> 1) - 1);
+    const size_t x0 = (((size_t)pr * rows + row) * nodes + 2 * p) * L + inb, x1 = x0 + L;
+    const size_t y0 = ((size_t)pr * nodes + 2 * p) * L + inb, y1 = y0 + L;
+    const size_t z0 = ((size_t)pr * rows * (nodes >> 1) + tp) * L + inb;
+    const uint32_t *tw = table + ((size_t)NTT31_NP + pr) * NTT_TW_PER_PRIME + NTT_TW_HALF;
+    for (uint32_t i = threadIdx.x; i < NTT_TW_HALF; i += NTT_WG) sw[i] = tw[i];
+    for (uint32_t i = threadIdx.x; i < B; i += NTT_WG)
+        sx[i] = ntt31_add(ntt31_mul(x[x0 + i], ntt31_csub(y[y1 + i], q.p), q),
+                          ntt31_mul(x[x1 + i], ntt31_csub(y[y0 + i], q.p), q), q.p);
+    __syncthreads();
+    ntt_lds_stages<true>(sx, sw, B, log_b, q);
+    for (uint32_t i = threadIdx.x; i < B; i += NTT_WG) z[z0 + i] = sx[i];
 }
 
 // m high stages, on the index bits [hb - m, hb), of a transform of x's rows, in place.  A tile: the 2^m values of those
@@ -164,6 +230,20 @@ k_ntt_crt(const uint32_t *__restrict__ res, uint32_t rows, uint32_t L, uint32_t 
 #pragma unroll
     for (int pr = 0; pr < NTT31_NP; pr++) r[pr] = res[((size_t)pr * rows + row) * L + k_lo + j];
     frbn_store(out + 8 * (row * out_stride + j), ntt31_crt(r, sc.linv));
+}
+
+// a tree level's parents: out[tr k_cnt + j] = coefficient j < k_cnt of the flat transform tr, mod n (the parents of a
+// row tile it: k_cnt = two children's coefficients); grid (transforms k_cnt / 256)
+__global__ void __launch_bounds__(NTT_WG)
+k_ntt_crt_nodes(const uint32_t *__restrict__ res, size_t transforms, int log_l, uint32_t k_cnt, ntt_scale sc,
+                uint32_t *__restrict__ out) {
+    const size_t e = (size_t)blockIdx.x * NTT_WG + threadIdx.x;
+    if (e >= transforms * k_cnt) return;
+    const size_t tr = e / k_cnt, at = (tr << log_l) + (e - tr * k_cnt);
+    uint32_t r[NTT31_NP];
+#pragma unroll
+    for (int pr = 0; pr < NTT31_NP; pr++) r[pr] = res[((size_t)pr * transforms << log_l) + at];
+    frbn_store(out + 8 * e, ntt31_crt(r, sc.linv));
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
@@ -228,14 +308,18 @@ static int ntt_split(vmpc_ctx *ctx, const void *src, size_t stride, size_t n, si
     return VMPC_OK;
 }
 
-static int ntt_forward(vmpc_ctx *ctx, uint32_t *x, size_t rows, const ntt_plan &p) {
-    vmpc_stage_scope s(ctx, "bn_fr_ntt_fwd");
+static int ntt_forward_launch(vmpc_ctx *ctx, uint32_t *x, size_t rows, const ntt_plan &p) {
     VMPC_CHECK(ntt_high_stages<false>(ctx, x, rows, p));
     const int log_b = p.log_l < NTT_LDS_LOG ? p.log_l : NTT_LDS_LOG;
     k_ntt_lds<false><<<dim3((unsigned)(p.L >> log_b), NTT31_NP, (unsigned)rows), NTT_WG, 0, ctx->stream>>>(
         x, (uint32_t)rows, nullptr, 0, (uint32_t)p.L, log_b, (const uint32_t *)ctx->ntt_twiddles);
     VMPC_KERNEL_CHECK();
     return VMPC_OK;
+}
+
+static int ntt_forward(vmpc_ctx *ctx, uint32_t *x, size_t rows, const ntt_plan &p) {
+    vmpc_stage_scope s(ctx, "bn_fr_ntt_fwd");
+    return ntt_forward_launch(ctx, x, rows, p);
 }
 
 // x *= y pointwise, then the inverse transform of x (not yet scaled by 1 / L: k_ntt_crt does that)
@@ -253,7 +337,7 @@ int vmpc_ntt_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, 
                       size_t nb, size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit) {
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const bool shared_b = b_stride == 0;
-    const ntt_plan p = ntt_plan_of(na, nb, shared_b, n_wit, ctx->ntt_arena_cap ? ctx->ntt_arena_cap : NTT_ARENA_MAX);
+    const ntt_plan p = ntt_plan_of(na, nb, shared_b, n_wit, vmpc_ntt_arena_cap(ctx));
     VMPC_CHECK(vmpc_ws_reserve(ctx, p.bytes));      // before any launch
     uint32_t *rb = (uint32_t *)vmpc_ws_take(ctx, p.row_bytes * p.b_rows);
     uint32_t *ra = (uint32_t *)vmpc_ws_take(ctx, p.row_bytes * p.group);
@@ -279,6 +363,72 @@ int vmpc_ntt_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, 
             VMPC_KERNEL_CHECK();
         }
     }
+    return VMPC_OK;
+}
+
+size_t vmpc_ntt_arena_cap(const vmpc_ctx *ctx) {
+    return ctx ? (ctx->ntt_arena_cap ? ctx->ntt_arena_cap : NTT_ARENA_MAX) : NTT_ARENA_MAX;
+}
+
+size_t vmpc_ntt_poly_mul_bytes(size_t na, size_t nb, bool shared_b, size_t n_wit, size_t cap) {
+    return ntt_plan_of(na, nb, shared_b, n_wit, cap).bytes;
+}
+
+static int ntt_tree_log_l(size_t m) {
+    int log_l = 1;
+    while (((size_t)1 << log_l) < 2 * m) log_l++;
+    return log_l;
+}
+
+// the residues of the level's T (one set), of the rows' children and of their parents
+size_t vmpc_ntt_tree_level_bytes(size_t m, size_t nodes, size_t rows) {
+    const size_t t = (size_t)NTT31_NP * 4 * (nodes << ntt_tree_log_l(m));
+    return vmpc_align(t) + vmpc_align(t * rows) + vmpc_align(t * rows / 2) + 768;
+}
+
+// One level of a subproduct tree (csrc/bn256_qap_mtree.hip), ONE launch sequence for all nodes and rows:
+//     nout[row][p] = nin[row][2p] T[2p+1] + nin[row][2p+1] T[2p]     for the 2^(log_nodes - 1) parents p of every row
+// T: 2^log_nodes nodes of m + 1 coefficients each, one after the other; nin: rows of 2^log_nodes children of m
+// coefficients, a row nodes x m scalars from the next; nout: the parents of 2 m coefficients in the same rows.
+// rows = rows_y x rows_z (two grid dimensions), at least 1; log_nodes >= 1; everything checked by the caller, who has
+// also kept rows x nodes x L within vmpc_ntt_arena_cap (below 2^32 values per prime).
+int vmpc_ntt_tree_level(vmpc_ctx *ctx, const void *T, size_t m, int log_nodes, const void *nin, void *nout,
+                        size_t rows_y, size_t rows_z) {
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const int log_l = ntt_tree_log_l(m), log_b = log_l < NTT_LDS_LOG ? log_l : NTT_LDS_LOG;
+    const size_t nodes = (size_t)1 << log_nodes, rows = rows_y * rows_z, per_row = nodes << log_l;
+    const size_t t_b = (size_t)NTT31_NP * 4 * per_row;
+    VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_ntt_tree_level_bytes(m, nodes, rows)));      // before any launch
+    uint32_t *rb = (uint32_t *)vmpc_ws_take(ctx, t_b);
+    uint32_t *ra = (uint32_t *)vmpc_ws_take(ctx, t_b * rows);
+    uint32_t *rp = (uint32_t *)vmpc_ws_take(ctx, t_b * rows / 2);
+    VMPC_CHECK(ntt_tables(ctx));
+    ntt_scale sc;
+    const uint32_t P[NTT31_NP] = NTT31_PRIMES;
+    for (int i = 0; i < NTT31_NP; i++) sc.linv[i] = ntt31_inv_pow2(log_l, P[i]);
+    ntt_plan flat;      // the transforms one after the other: the stages of log_l, the grid of all values
+    flat.log_l = log_l;
+    const unsigned split_x = (unsigned)((per_row + NTT_WG - 1) / NTT_WG);
+    vmpc_stage_scope s(ctx, "bn_qap_mtree_level");
+    k_ntt_split_nodes<<<dim3(split_x, 1, 1), NTT_WG, 0, ctx->stream>>>((const uint32_t *)T, 0, m + 1, (uint32_t)(m + 1),
+                                                                      log_l, (uint32_t)nodes, rb);
+    VMPC_KERNEL_CHECK();
+    flat.L = per_row;
+    VMPC_CHECK(ntt_forward_launch(ctx, rb, 1, flat));
+    k_ntt_split_nodes<<<dim3(split_x, (unsigned)rows_y, (unsigned)rows_z), NTT_WG, 0, ctx->stream>>>(
+        (const uint32_t *)nin, nodes * m, m, (uint32_t)m, log_l, (uint32_t)nodes, ra);
+    VMPC_KERNEL_CHECK();
+    flat.L = rows * per_row;
+    VMPC_CHECK(ntt_forward_launch(ctx, ra, 1, flat));
+    k_ntt_lds_pair<<<dim3((unsigned)((rows * (nodes / 2)) << (log_l - log_b)), NTT31_NP), NTT_WG, 0, ctx->stream>>>(
+        ra, rb, rp, (uint32_t)rows, log_nodes, log_l, log_b, (const uint32_t *)ctx->ntt_twiddles);
+    VMPC_KERNEL_CHECK();
+    flat.L = rows * per_row / 2;
+    VMPC_CHECK(ntt_high_stages<true>(ctx, rp, 1, flat));
+    const size_t outs = rows * nodes * m;
+    k_ntt_crt_nodes<<<(unsigned)((outs + NTT_WG - 1) / NTT_WG), NTT_WG, 0, ctx->stream>>>(
+        rp, rows * (nodes / 2), log_l, (uint32_t)(2 * m), sc, (uint32_t *)nout);
+    VMPC_KERNEL_CHECK();
     return VMPC_OK;
 }
 

@@ -45,6 +45,7 @@
 #include "fr_bn.h"
 #include "fr_conv.h"
 #include "fr_scan.h"
+#include "qap_tleaf.h"
 #include "share_combine.h"
 
 #define QH_WG 256
@@ -55,7 +56,6 @@
 #define QH_MAX_GROUPS 32            // j ranges (partials per k) at most
 #define QH_TARGET_WGS 2048
 #define QH_RUN 64                   // sequence elements per lane in the weights' scan
-#define QH_LEAF 128                 // factors (x - j) per leaf of t's product tree
 #define QH_MAX_STRIDE ((size_t)1 << 31)  // row strides of the batch entries, in scalars, at most
 #define QH_RES_MAX_WGS 64           // workgroups (partials) of the residual at most: rows beyond 64 x 256 share lanes
 
@@ -475,22 +475,12 @@ extern "C" int vmpc_bn256_qap_residual_batch_dev(vmpc_ctx *ctx, const void *a, c
 
 // ---- t's coefficients -----------------------------------------------------------------------------------------------
 // leaf l: prod (x - j) over j = l QH_LEAF + 1 .. min((l+1) QH_LEAF, d), its deg + 1 coefficients at dst + 32 (l QH_LEAF + l)
-// (leaves packed one after the other).  Thread i owns coefficient i: new_i = old_(i-1) - j old_i.
+// (leaves packed one after the other).  The product itself: csrc/qap_tleaf.h.
 __global__ void __launch_bounds__(QH_WG) k_qh_tleaf(uint32_t d, uint32_t *__restrict__ dst) {
     __shared__ frbn sP[2][QH_LEAF + 1];
     const uint32_t t = threadIdx.x, l = blockIdx.x;
     const uint32_t j0 = l * QH_LEAF + 1, j1 = j0 + QH_LEAF - 1 < d ? j0 + QH_LEAF - 1 : d;
-    int cur = 0;
-    if (t <= QH_LEAF) sP[0][t] = t == 0 ? frbn_one() : frbn_zero();
-    __syncthreads();
-    for (uint32_t j = j0; j <= j1; j++) {
-        if (t <= QH_LEAF) {
-            const frbn left = t ? sP[cur][t - 1] : frbn_zero();
-            sP[cur ^ 1][t] = frbn_sub(left, frbn_mul_small(sP[cur][t], j));
-        }
-        cur ^= 1;
-        __syncthreads();
-    }
+    const int cur = qh_tleaf_product(t, j0, j1, sP);
     const uint32_t deg = j1 - j0 + 1;
     if (t <= deg) f256_st(dst, (long long)l * (QH_LEAF + 1) + t, sP[cur][t]);
 }

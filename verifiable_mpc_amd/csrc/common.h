@@ -132,6 +132,14 @@ inline size_t vmpc_align(size_t b) { return (b + 255) & ~(size_t)255; }
 int vmpc_ntt_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b, size_t b_stride,
                       size_t nb, size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit);
 
+// what csrc/bn256_qap_mtree.hip needs of it besides: the arena cap in force, the arena of vmpc_ntt_poly_mul under a cap,
+// and one level of a subproduct tree (all its nodes and rows in one launch sequence) with its arena
+size_t vmpc_ntt_arena_cap(const vmpc_ctx *ctx);
+size_t vmpc_ntt_poly_mul_bytes(size_t na, size_t nb, bool shared_b, size_t n_wit, size_t cap);
+size_t vmpc_ntt_tree_level_bytes(size_t m, size_t nodes, size_t rows);
+int vmpc_ntt_tree_level(vmpc_ctx *ctx, const void *T, size_t m, int log_nodes, const void *nin, void *nout,
+                        size_t rows_y, size_t rows_z);
+
 // profiling helpers: bracket a kernel launch with events when ctx->profile is on
 int vmpc_stage_begin(vmpc_ctx *ctx, const char *name);
 void vmpc_stage_end(vmpc_ctx *ctx, int handle);

@@ -73,6 +73,29 @@ def poly_product(mode, ctx=None):
         ctx.set_poly_product(prev)
 
 
+MOMENT_TRANSFORM_MODES = ("direct", "auto", "tree")
+
+
+@contextlib.contextmanager
+def moment_transform(mode, ctx=None):
+    """with moment_transform("tree"): compute_h, its batch and share forms and every prover above them (pynocchio's
+    _h_rows) make the moments of the weighted rows on `ctx` (default: the process's context) by the subproduct tree of
+    csrc/bn256_qap_mtree.hip, O(d log^2 d), instead of the direct kernel's d^2 steps; "auto": from
+    _native.BN256_QAP_MTREE_MIN constraints on; "direct": never (a new context's mode).  The bits are the same in every
+    mode.  The tree's plan - (L + 1) d' + 2^(L+1) - 1 + 3 n_max scalars with n_max = d, 126 MB at d = 2^18 and 570 MB
+    at 2^20 - is built once per QAP and context and kept on the QAP.  The mode found on entry is restored on exit,
+    also when the block raises."""
+    if mode not in MOMENT_TRANSFORM_MODES:
+        raise ValueError(f"moment_transform mode {mode!r}: one of {sorted(MOMENT_TRANSFORM_MODES)}")
+    ctx = ctx or get_context()
+    prev = ctx.moment_transform
+    ctx.moment_transform = mode
+    try:
+        yield ctx
+    finally:
+        ctx.moment_transform = prev
+
+
 def reduce_scalar(v):
     """Canonical residue of an int / field element (negative and oversized ints allowed:
     every base has order l, SURVEY.md hard part 5)."""

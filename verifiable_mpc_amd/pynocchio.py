@@ -1226,14 +1226,38 @@ def compute_h(qap, c, deltas=None, ctx=None):
                     "compute_h: the witness")[0]
 
 
-def _h_rows(ctx, d, t, aby_ptr, n, dd, out_ptr, out_stride):
+def _moments_by_tree(ctx, d):
+    """whether the context's mode (device.moment_transform) sends d constraints to the subproduct tree"""
+    mode = getattr(ctx, "moment_transform", "direct")
+    return mode == "tree" or (mode == "auto" and d >= _native.BN256_QAP_MTREE_MIN)
+
+
+def _mtree_plan(ctx, qap, d):
+    """device buffer of the moment transform's plan for d points and n_max = d (csrc/bn256_qap_mtree.hip), made once
+    per (context, QAP): (L + 1) d' + 2^(L+1) - 1 + 3 d scalars, 126 MB at d = 2^18 and 570 MB at 2^20"""
+    def make():
+        plan = ctx.alloc(_native.bn256_qap_mtree_bytes(d, d))
+        ctx.bn256_qap_mtree_build(d, d, plan.ptr)
+        return plan
+    return _per_ctx(qap, "mtree", ctx, make)
+
+
+def _h_rows(ctx, d, t, aby_ptr, n, dd, out_ptr, out_stride, qap=None):
     """weights -> moments -> combination for n rows a || b || y, 3 d scalars apart, at aby_ptr ->
-    n rows of h at out_ptr; dd: device buffer of the rows' three deltas each, or None.  Ends with the stream drained,
-    so the caller may release what the rows were made from."""
+    n rows of h at out_ptr; dd: device buffer of the rows' three deltas each, or None.  The moments come from the
+    subproduct tree where the context's device.moment_transform mode says so and `qap`, which
+    keeps the plan, is given; the bits are the same.  Ends with the stream drained, so the caller may release what the
+    rows were made from."""
     u = ctx.alloc(32 * 2 * d * n)                # rows ua || ub, stride 2 d; the moments alike
     ctx.bn256_qap_h_weights_batch(aby_ptr, aby_ptr + 32 * d, 3 * d, d, u.ptr, u.ptr + 32 * d, 2 * d, n)
     mom = ctx.alloc(32 * 2 * d * n)
-    ctx.bn256_qap_moments_batch(u.ptr, u.ptr + 32 * d, 2 * d, d, d, mom.ptr, mom.ptr + 32 * d, 2 * d, n)
+    if qap is not None and _moments_by_tree(ctx, d):
+        plan = _mtree_plan(ctx, qap, d)
+        tree_scratch = ctx.alloc(_native.bn256_qap_moments_tree_scratch_bytes(d, n))
+        ctx.bn256_qap_moments_tree_batch(plan.ptr, d, d, u.ptr, u.ptr + 32 * d, 2 * d, d, mom.ptr, mom.ptr + 32 * d,
+                                         2 * d, tree_scratch.ptr, n)
+    else:
+        ctx.bn256_qap_moments_batch(u.ptr, u.ptr + 32 * d, 2 * d, d, d, mom.ptr, mom.ptr + 32 * d, 2 * d, n)
     scratch = ctx.alloc(32 * 3 * d * n)
     ctx.bn256_qap_h_combine_batch(mom.ptr, mom.ptr + 32 * d, 2 * d, t.ptr, d, None if dd is None else dd.ptr, scratch.ptr,
                                   out_ptr, out_stride, n)
@@ -1314,17 +1338,24 @@ def plan_chunks(k, budget, cost):
     return chunks
 
 
-def h_batch_bytes(d, n_wires, n_coef, n):
+def h_batch_bytes(d, n_wires, n_coef, n, tree=False):
     """device bytes compute_h_batch holds for a chunk of n witnesses: per witness the witness itself, the row values
     (3 d), the weighted rows (2 d), the moments (2 d), the combination's scratch (3 d) and, for a dense QAP, 3 n_coef
-    coefficients; plus the arenas of the moments and of the two half products"""
+    coefficients; plus the arenas of the moments and of the two half products.  tree: the moments by the subproduct
+    tree (device.moment_transform) - its scratch (4 d' scalars a witness) and its arena in place of the direct
+    kernel's; the plan, which is the QAP's and not the chunk's, is not counted."""
     if n == 0:
         return 0
     per = 32 * (n_wires + 10 * d + 3 * n_coef)
-    arena = max(_native.bn256_qap_moments_batch_bytes(d, d, n),
+    if tree:
+        moments = _native.bn256_qap_moments_tree_batch_bytes(d, d, n)
+        scratch = _native.bn256_qap_moments_tree_scratch_bytes(d, n)
+    else:
+        moments, scratch = _native.bn256_qap_moments_batch_bytes(d, d, n), 0
+    arena = max(moments,
                 _native.bn256_fr_poly_mul_batch_bytes(d, d, 0, d - 1, n),
                 _native.bn256_fr_poly_mul_batch_bytes(d, d, d - 1, d, n))
-    return per * n + arena
+    return per * n + scratch + arena
 
 
 def compute_h_batch(qap, cs, deltas=None, ctx=None):
@@ -1416,15 +1447,16 @@ def _upload_row_values_batch(ctx, qap, arr):
     return aby, (dc, coef)
 
 
-def batch_ranges(qap, K):
+def batch_ranges(qap, K, tree=False):
     """[(start, stop), ..]: the K witnesses of a batch as compute_h_batch cuts them - plan_chunks under
-    BATCH_BUDGET_BYTES, each chunk in pieces of at most BN256_QAP_MAX_WIT (the witness is a grid dimension).  Pure."""
+    BATCH_BUDGET_BYTES, each chunk in pieces of at most BN256_QAP_MAX_WIT (the witness is a grid dimension); tree: as
+    h_batch_bytes takes it.  Pure."""
     d, n_wires = int(qap.d), len(qap.indices)
     top = 0
     if not isinstance(qap, R1CSQAP):
         top = max([len(p.coeffs if hasattr(p, "coeffs") else p) for polys in (qap.v, qap.w, qap.y) for p in polys] + [1])
     out = []
-    for lo, hi in plan_chunks(K, BATCH_BUDGET_BYTES, lambda n: h_batch_bytes(d, n_wires, top, n)):
+    for lo, hi in plan_chunks(K, BATCH_BUDGET_BYTES, lambda n: h_batch_bytes(d, n_wires, top, n, tree)):
         n = min(hi - lo, _native.BN256_QAP_MAX_WIT)
         out += [(a, min(a + n, hi)) for a in range(lo, hi, n)]
     return out
@@ -1440,10 +1472,10 @@ def _h_from_rows(ctx, qap, K, dd, rows):
     t = _t_coeffs(ctx, qap)
     stride = d + 1
     out = ctx.alloc(32 * stride * K)
-    for lo, hi in batch_ranges(qap, K):
+    for lo, hi in batch_ranges(qap, K, _moments_by_tree(ctx, d)):
         ptr, keep = rows(lo, hi)
         _h_rows(ctx, d, t, ptr, hi - lo, _BufferView(dd, 96 * lo, 96 * (hi - lo)) if dd is not None else None,
-                out.ptr + 32 * stride * lo, stride)
+                out.ptr + 32 * stride * lo, stride, qap)
         del keep        # (_h_rows has drained the stream)
     n_h = d + 1 if dd is not None else max(d - 1, 0)
     return [HPoly(ctx, _BufferView(out, 32 * stride * w, 32 * stride), n_h) for w in range(K)]
