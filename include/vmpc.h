@@ -81,6 +81,21 @@ int vmpc_ctx_debug_hold_wait(vmpc_ctx *ctx, int on);
  * paths: nothing in the library calls them. */
 int vmpc_ctx_debug_delay(vmpc_ctx *ctx, unsigned microseconds);
 int vmpc_stream_debug_delay(void *hip_stream, int device, unsigned microseconds);
+/* test hooks for the rule that a call's result is a function of its arguments, never of what the scratch arena held
+ * (tests/arena_cases.py, DESIGN.md "Arena independence").  Not for production paths: nothing in the library calls them.
+ * vmpc_ctx_debug_arena_fill: enqueue a fill of the whole arena with the 32-bit `word` on the context's stream, and of the
+ *   prover's pool kept between proofs when no vmpc_p4 holds it.  No arena yet: VMPC_OK, nothing enqueued.  word > 0xFFFF:
+ *   VMPC_E_RANGE, nothing enqueued - the values are small on purpose, so that a kernel which trusts a stale count or
+ *   index computes a wrong answer and not an address far outside its buffers.  While the context holds a queued stream
+ *   wait (vmpc_ctx_debug_hold_wait, a prover round between begin and end): VMPC_E_INVAL, nothing enqueued.
+ * vmpc_ctx_debug_arena_info: the arena's size, the bytes the last call that reserved it took from it (0: it reserved and
+ *   took nothing), and how many times the arena has been (re)allocated so far (any of the three may be NULL).
+ * vmpc_ctx_debug_rearmed: synchronises the stream; *ok = 1 when every cursor word of the fused short path is zero (what
+ *   the path's last kernel leaves, csrc/common.h) or when the path was never set up on this context, else 0. */
+#define VMPC_DEBUG_ARENA_FILL_MAX 0xFFFFu
+int vmpc_ctx_debug_arena_fill(vmpc_ctx *ctx, uint32_t word);
+int vmpc_ctx_debug_arena_info(vmpc_ctx *ctx, size_t *bytes, size_t *used, uint64_t *generation);
+int vmpc_ctx_debug_rearmed(vmpc_ctx *ctx, int *ok);
 /* non-blocking: *done = 1 when everything enqueued on the context's stream has completed (a driver that keeps
  * several commitments in flight refills whichever context finishes first) */
 int vmpc_ctx_query(vmpc_ctx *ctx, int *done);

@@ -26,7 +26,7 @@ SCALAR_BYTES, AFFINE_BYTES, PROJ_BYTES, EXT_BYTES = 32, 64, 96, 128
 # against the header and against the built library)
 SYMBOLS = [
     "vmpc_backend_info", "vmpc_last_error", "vmpc_ctx_create", "vmpc_ctx_destroy",
-    "vmpc_ctx_set_stream", "vmpc_ctx_sync", "vmpc_ctx_set_short_path", "vmpc_ctx_get_short_path", "vmpc_ctx_debug_hold_wait", "vmpc_ctx_debug_delay", "vmpc_stream_debug_delay", "vmpc_ctx_query", "vmpc_ctx_wait_for", "vmpc_malloc", "vmpc_free", "vmpc_memcpy_h2d",
+    "vmpc_ctx_set_stream", "vmpc_ctx_sync", "vmpc_ctx_set_short_path", "vmpc_ctx_get_short_path", "vmpc_ctx_debug_hold_wait", "vmpc_ctx_debug_delay", "vmpc_stream_debug_delay", "vmpc_ctx_debug_arena_fill", "vmpc_ctx_debug_arena_info", "vmpc_ctx_debug_rearmed", "vmpc_ctx_query", "vmpc_ctx_wait_for", "vmpc_malloc", "vmpc_free", "vmpc_memcpy_h2d",
     "vmpc_memcpy_d2h", "vmpc_memcpy_d2d", "vmpc_ctx_profile", "vmpc_ctx_profile_read",
     "vmpc_ctx_set_window", "vmpc_ed25519_msm_plan", "vmpc_msm_sort_view", "vmpc_ed25519_madd_rate", "vmpc_ed25519_msm", "vmpc_ed25519_fold",
     "vmpc_ed25519_fixed_base_batch", "vmpc_fr_axpy", "vmpc_fr_dot", "vmpc_points_validate_dev",
@@ -122,6 +122,9 @@ def load_library():
         "vmpc_ctx_debug_hold_wait": (i32, [vp, i32]),
         "vmpc_ctx_debug_delay": (i32, [vp, ctypes.c_uint]),
         "vmpc_stream_debug_delay": (i32, [vp, i32, ctypes.c_uint]),
+        "vmpc_ctx_debug_arena_fill": (i32, [vp, ctypes.c_uint32]),
+        "vmpc_ctx_debug_arena_info": (i32, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), u64p]),
+        "vmpc_ctx_debug_rearmed": (i32, [vp, ctypes.POINTER(i32)]),
         "vmpc_ctx_query": (i32, [vp, ctypes.POINTER(i32)]),
         "vmpc_ctx_wait_for": (i32, [vp, vp]),
         "vmpc_malloc": (i32, [vp, sz, ctypes.POINTER(vp)]),
@@ -665,6 +668,24 @@ class Context:
     def debug_delay(self, usec):
         """test hook: keep this context's stream busy for about `usec` microseconds (at most 20000; touches no memory)"""
         _check(self.lib.vmpc_ctx_debug_delay(self.handle, int(usec)), "vmpc_ctx_debug_delay")
+
+    def debug_arena_fill(self, word):
+        """test hook: fill the whole scratch arena (and the prover's idle pool) with the 32-bit `word` (at most 0xFFFF)
+        on this context's stream; nothing happens when there is no arena yet"""
+        _check(self.lib.vmpc_ctx_debug_arena_fill(self.handle, int(word)), "vmpc_ctx_debug_arena_fill")
+
+    def debug_arena_info(self):
+        """test hook: (arena bytes, bytes the last call took, allocations of the arena so far)"""
+        b, u, g = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
+        _check(self.lib.vmpc_ctx_debug_arena_info(self.handle, ctypes.byref(b), ctypes.byref(u), ctypes.byref(g)),
+               "vmpc_ctx_debug_arena_info")
+        return int(b.value), int(u.value), int(g.value)
+
+    def debug_rearmed(self):
+        """test hook: synchronises; True when the short path's cursor words are all zero (or it was never set up)"""
+        ok = ctypes.c_int(0)
+        _check(self.lib.vmpc_ctx_debug_rearmed(self.handle, ctypes.byref(ok)), "vmpc_ctx_debug_rearmed")
+        return bool(ok.value)
 
     def set_stream(self, stream_ptr):
         _check(self.lib.vmpc_ctx_set_stream(self.handle, ctypes.c_void_p(stream_ptr)),

@@ -233,6 +233,45 @@ extern "C" int vmpc_ctx_debug_delay(vmpc_ctx *ctx, unsigned microseconds) {
     return vmpc_stream_debug_delay((void *)ctx->stream, ctx->device, microseconds);
 }
 
+// Test hooks for arena independence (tests/arena_cases.py): a call's result is a function of its arguments, never of
+// what the arena held before it.  The fill values stay small (VMPC_DEBUG_ARENA_FILL_MAX): a kernel that trusts a stale
+// count or index then computes a wrong value instead of addressing far outside its buffers.
+extern "C" int vmpc_ctx_debug_arena_fill(vmpc_ctx *ctx, uint32_t word) {
+    if (!ctx || ctx->stream_waits) return VMPC_E_INVAL;     // (a fill would land between a held round's kernels)
+    if (word > VMPC_DEBUG_ARENA_FILL_MAX) {
+        snprintf(vmpc_err_buf, sizeof vmpc_err_buf, "arena fill word 0x%x: the cap is 0x%x", (unsigned)word,
+                 (unsigned)VMPC_DEBUG_ARENA_FILL_MAX);
+        return VMPC_E_RANGE;
+    }
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    if (ctx->ws && ctx->ws_bytes >= 4)
+        VMPC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ctx->ws, (int)word, ctx->ws_bytes / 4, ctx->stream));
+    if (ctx->p4_pool && !ctx->p4_pool_busy && ctx->p4_pool_bytes >= 4)
+        VMPC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ctx->p4_pool, (int)word, ctx->p4_pool_bytes / 4, ctx->stream));
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_ctx_debug_arena_info(vmpc_ctx *ctx, size_t *bytes, size_t *used, uint64_t *generation) {
+    if (!ctx) return VMPC_E_INVAL;
+    if (bytes) *bytes = ctx->ws_bytes;
+    if (used) *used = ctx->ws_used;
+    if (generation) *generation = ctx->ws_generation;
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_ctx_debug_rearmed(vmpc_ctx *ctx, int *ok) {
+    if (!ctx || !ok || ctx->stream_waits) return VMPC_E_INVAL;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    VMPC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *ok = 1;
+    if (!ctx->short_cursors) return VMPC_OK;
+    std::vector<uint32_t> words(VMPC_SHORT_CURSOR_WORDS);
+    VMPC_HIP_CHECK(hipMemcpy(words.data(), ctx->short_cursors, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint32_t w : words)
+        if (w) *ok = 0;
+    return VMPC_OK;
+}
+
 extern "C" int vmpc_ctx_set_short_path(vmpc_ctx *ctx, int on) {
     if (!ctx) return VMPC_E_INVAL;
     ctx->short_path = on ? 1 : 0;
@@ -376,6 +415,7 @@ int vmpc_ws_reserve(vmpc_ctx *ctx, size_t total_bytes) {
         return VMPC_E_NOMEM;
     }
     ctx->ws_bytes = want;
+    ctx->ws_generation++;
     return VMPC_OK;
 }
 

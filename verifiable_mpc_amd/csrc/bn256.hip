@@ -52,6 +52,7 @@ static int bn_msm_dev(vmpc_ctx *ctx, const void *scalars, const void *points, si
     msm_layout(p, w, nullptr, C::ENTRY_WORDS * 4, C::ACC_WORDS * 4);
     VMPC_CHECK(vmpc_ws_reserve(ctx, w.total));
     msm_layout(p, w, (char *)ctx->ws, C::ENTRY_WORDS * 4, C::ACC_WORDS * 4);
+    ctx->ws_used = w.total;      // (laid out by hand, not by vmpc_ws_take: the mark vmpc_ctx_debug_arena_info reports)
     {
         vmpc_stage_scope s(ctx, "bn_prep");
         VMPC_CHECK((bn_kernels<C, F>::prep(ctx, points, n, w.entries)));
@@ -108,6 +109,7 @@ static int bn_table_msm_dev(vmpc_ctx *ctx, const void *table, size_t table_n, co
     msm_layout(p, w, nullptr, 0, C::ACC_WORDS * 4);
     VMPC_CHECK(vmpc_ws_reserve(ctx, w.total));
     msm_layout(p, w, (char *)ctx->ws, 0, C::ACC_WORDS * 4);
+    ctx->ws_used = w.total;
     VMPC_CHECK(msm_recode_rows(ctx, scalars, m, nullptr, 0, 0, stride, w.digits, BN_TABLE_C, BN_TABLE_W, BN_TABLE_W,
                                BN_ORDER));
     VMPC_CHECK(msm_sort_digits(ctx, p, w));
@@ -160,6 +162,7 @@ static int bn_table_msm_multi_dev(vmpc_ctx *ctx, const void *const *tables, int 
     const size_t base = vmpc_align(w.total);
     VMPC_CHECK(vmpc_ws_reserve(ctx, base + b_bytes + c_bytes + r_bytes));
     msm_layout(p, w, (char *)ctx->ws, 0, C::ACC_WORDS * 4);
+    ctx->ws_used = base + b_bytes + c_bytes + r_bytes;
     char *extra = (char *)ctx->ws + base;
     uint32_t *buckets = (uint32_t *)extra;
     uint32_t *counts = (uint32_t *)(extra + b_bytes);

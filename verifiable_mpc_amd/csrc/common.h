@@ -34,6 +34,7 @@ extern thread_local char vmpc_err_buf[512];
 #define VMPC_ST_SHORT_OVERFLOW 1  // the fused short-commitment path (msm_short.hip) met a bin or bucket beyond its fixed
                                   // capacities: the call's result is void, vmpc_ctx_sync returns VMPC_E_AGAIN
 #define VMPC_ST_WORDS 4
+#define VMPC_SHORT_CURSOR_WORDS 256  // ctx->short_cursors: [2][128] words (msm_short.hip checks it against its bin count)
 
 struct vmpc_stage {
     const char *name;
@@ -50,6 +51,7 @@ struct vmpc_ctx {
     void *ws = nullptr;
     size_t ws_bytes = 0;
     size_t ws_used = 0;
+    uint64_t ws_generation = 0;    // allocations of the arena so far (vmpc_ctx_debug_arena_info)
     uint32_t *d_status = nullptr;
     int window_override = 0;
     int bucket_wgs_per_cu = 0;     // > 0: persistent bucket kernel with this many 256-thread workgroups per CU

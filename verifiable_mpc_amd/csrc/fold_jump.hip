@@ -220,6 +220,7 @@ static int table_fold(vmpc_ctx *ctx, const void *table, size_t table_n, size_t t
     const size_t proj_bytes = (m_out * 96 + 255) & ~(size_t)255;
     VMPC_CHECK(vmpc_ws_reserve(ctx, sched_bytes + partial_bytes + proj_bytes));
     char *ws = (char *)ctx->ws;
+    ctx->ws_used = sched_bytes + partial_bytes + proj_bytes;      // (laid out by hand, not by vmpc_ws_take: the mark vmpc_ctx_debug_arena_info reports)
     uint32_t *d_sched = (uint32_t *)ws, *d_proj = (uint32_t *)(ws + sched_bytes);
     uint32_t *d_partial = (uint32_t *)(ws + sched_bytes + proj_bytes);
     vmpc_stage_scope s(ctx, "table_fold");

@@ -514,6 +514,7 @@ extern "C" int vmpc_msm_dev(vmpc_ctx *ctx, const void *scalars, const void *affi
     msm_layout(p, w, nullptr, NIELS_WORDS * 4, EXT_WORDS * 4);
     VMPC_CHECK(vmpc_ws_reserve(ctx, w.total));
     msm_layout(p, w, (char *)ctx->ws, NIELS_WORDS * 4, EXT_WORDS * 4);
+    ctx->ws_used = w.total;      // (laid out by hand, not by vmpc_ws_take: the mark vmpc_ctx_debug_arena_info reports)
 
     {
         vmpc_stage_scope s(ctx, "msm_prep");
@@ -669,6 +670,7 @@ static int msm_table_batch_wide(vmpc_ctx *ctx, const void *table, size_t table_n
     msm_layout(p, w, nullptr, 0, EXT_WORDS * 4);
     VMPC_CHECK(vmpc_ws_reserve(ctx, w.total));
     msm_layout(p, w, (char *)ctx->ws, 0, EXT_WORDS * 4);
+    ctx->ws_used = w.total;
     VMPC_CHECK(msm_recode_wide_batch(ctx, scalars, m, extra_scalars, K, table_n, table_extra, stride, (int32_t *)w.digits,
                                      p.n_pad, ED25519_L));
     VMPC_CHECK(msm_sort_digits(ctx, p, w));
@@ -721,6 +723,7 @@ static int msm_table_batch(vmpc_ctx *ctx, const void *table, size_t table_n, siz
     msm_layout(p, w, nullptr, 0, EXT_WORDS * 4);
     VMPC_CHECK(vmpc_ws_reserve(ctx, w.total));
     msm_layout(p, w, (char *)ctx->ws, 0, EXT_WORDS * 4);
+    ctx->ws_used = w.total;
     for (int k = 0; k < K; k++)
         if (m && !scalars[k]) return VMPC_E_INVAL;
     VMPC_CHECK(msm_recode_rows_batch(ctx, scalars, m, extra_scalars, K, table_n, table_extra, stride, w.digits,

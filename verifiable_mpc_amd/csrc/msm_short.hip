@@ -35,6 +35,7 @@
 #include "rt_tree.h"
 
 #define SH_BINS 128
+static_assert(2 * SH_BINS == VMPC_SHORT_CURSOR_WORDS, "ctx->short_cursors: vmpc_ctx_debug_rearmed reads this many words");
 #define SH_FINE 256
 #define SH_T 12288             // entries per workgroup: 48 KB of LDS sorted + staging shared with the tree's 80 KB
 #define SH_THREADS 512
