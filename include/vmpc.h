@@ -737,8 +737,31 @@ int vmpc_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m,
  * launched. */
 int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m, const void *fact,
                                 const void *ifact, void *z_tail, size_t z_stride, size_t n_wit);
-/* the arena bytes vmpc_fr_cs_extend_batch_dev reserves (0 where the call would answer VMPC_E_RANGE or do nothing) */
+/* the arena bytes vmpc_fr_cs_extend_batch_dev reserves (0 where the call would answer VMPC_E_RANGE or do nothing) on a
+ * context in the DIRECT mode below; _ctx: on THIS context, by the route its mode gives this m and under its NTT arena
+ * cap (ctx NULL: the direct figure) */
 size_t vmpc_fr_cs_extend_batch_bytes(size_t m, size_t n_wit);
+size_t vmpc_fr_cs_extend_batch_bytes_ctx(const vmpc_ctx *ctx, size_t m, size_t n_wit);
+/* How the three extension entries - and with them circuit_sat_prover, its batch and the M-party prover - compute the
+ * sums over j for x = m+2 .. 2m.  DIRECT: the correlation kernel, 2 m^2 multiply-accumulates; a new context starts
+ * here.  NTT: the cyclic product of the 2 n_wit rows u_f, u_g with the table 1 / k by the multi-prime NTT over the
+ * integers (csrc/bn256_ntt.hip) at L = vmpc_fr_cs_extend_ntt_len(m) points, the window's exact integer coefficients
+ * (< 2^20 l^2) reduced mod l: the same canonical residues, so z is the direct kernel's bit for bit.  AUTO: the NTT from
+ * VMPC_FR_CS_EXT_NTT_MIN gates on.  Any other mode: VMPC_E_INVAL, the mode stays.  A mode of its own:
+ * vmpc_ctx_set_poly_product does not touch it.  The arena then also holds the residues of the table and of a group of the
+ * rows (vmpc_ctx_set_ntt_arena_cap applies), still ONE reservation before the first launch.
+ * vmpc_fr_cs_extend_ntt_len: L, the smallest power of two >= 2m + 2 (alias-free for the window m+1 .. 2m-1 although
+ * the whole product has 3m + 2 coefficients), or 0 where the direct kernel is taken WHATEVER the mode: m < 2 (no
+ * correlation) and m = 2^20 = VMPC_FR_CS_MAX_M, where 2m + 2 exceeds the longest transform, 2^21 points. */
+#define VMPC_CS_EXTENSION_DIRECT 0
+#define VMPC_CS_EXTENSION_AUTO 1
+#define VMPC_CS_EXTENSION_NTT 2
+/* the smallest power of two on the grid of scripts/cs_extension_probe.py at which the NTT's median was below the direct
+ * kernel's and stayed below at every larger grid size (the table of DESIGN.md section 28) */
+#define VMPC_FR_CS_EXT_NTT_MIN ((size_t)64)
+int vmpc_ctx_set_cs_extension(vmpc_ctx *ctx, int mode);
+int vmpc_ctx_get_cs_extension(vmpc_ctx *ctx, int *mode);
+size_t vmpc_fr_cs_extend_ntt_len(size_t m);
 /* The same extension with f and g kept apart, nothing multiplied and no z: f_out[0] = f(0), f_out[1 + o] = f(m + 2 + o)
  * for o < m - 1, g_out alike; max(m, 1) scalars each.  Linear in a and b, so on Shamir shares of them it gives shares
  * of f and g at those points (mpc_ac20_cb.py:66-85 interpolates and evaluates share polynomials).  Arena as above. */

@@ -62,6 +62,8 @@ SYMBOLS = [
     "vmpc_fr_cs_extend_fg_dev", "vmpc_fr_share_mul_deal_dev", "vmpc_fr_share_combine_dev",
     "vmpc_bn256_fr_share_mul_deal_dev", "vmpc_bn256_fr_share_combine_dev", "vmpc_bn256_qap_residual_dev",
     "vmpc_fr_cs_triples_batch_dev", "vmpc_fr_cs_extend_batch_dev", "vmpc_fr_cs_extend_batch_bytes",
+    "vmpc_fr_cs_extend_batch_bytes_ctx", "vmpc_ctx_set_cs_extension", "vmpc_ctx_get_cs_extension",
+    "vmpc_fr_cs_extend_ntt_len",
     "vmpc_bn256_r1cs_solve_batch_dev", "vmpc_bn256_r1cs_solve_launches",
     "vmpc_bn256_r1cs_share_mul_deal_dev", "vmpc_bn256_r1cs_share_finish_dev",
     "vmpc_bn256_qap_residual_batch_dev", "vmpc_bn256_recombine_dev",
@@ -230,6 +232,10 @@ def load_library():
                                                vp]),
         "vmpc_fr_cs_extend_batch_dev": (i32, [vp, vp, vp, sz, sz, vp, vp, vp, sz, sz]),
         "vmpc_fr_cs_extend_batch_bytes": (sz, [sz, sz]),
+        "vmpc_fr_cs_extend_batch_bytes_ctx": (sz, [vp, sz, sz]),
+        "vmpc_ctx_set_cs_extension": (i32, [vp, i32]),
+        "vmpc_ctx_get_cs_extension": (i32, [vp, ctypes.POINTER(ctypes.c_int)]),
+        "vmpc_fr_cs_extend_ntt_len": (sz, [sz]),
         "vmpc_fr_cs_extend_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
         "vmpc_bn256_r1cs_solve_batch_dev": (i32, [vp] * 15 + [sz, sz, sz, vp, sz, sz, sz, vp]),
         "vmpc_bn256_r1cs_solve_launches": (sz, [vp, sz, sz, sz]),
@@ -995,8 +1001,25 @@ class Context:
                "vmpc_fr_cs_extend_batch_dev")
 
     def cs_extend_batch_bytes(self, m, n_wit):
-        """the arena bytes cs_extend_batch reserves for n_wit witnesses"""
-        return int(self.lib.vmpc_fr_cs_extend_batch_bytes(m, n_wit))
+        """the arena bytes cs_extend_batch reserves for n_wit witnesses on THIS context: by the route its extension
+        mode gives m (set_cs_extension) and under its NTT arena cap"""
+        return int(self.lib.vmpc_fr_cs_extend_batch_bytes_ctx(self.handle, m, n_wit))
+
+    def set_cs_extension(self, mode):
+        """how cs_extend / cs_extend_fg / cs_extend_batch of this context compute the sums for x = m+2 .. 2m:
+        CS_EXTENSION_DIRECT (0, a new context's: the correlation kernel), CS_EXTENSION_AUTO (1: the NTT over the
+        integers from FR_CS_EXT_NTT_MIN gates), CS_EXTENSION_NTT (2: wherever cs_extend_ntt_len(m) > 0).  The same
+        bytes either way.  Another value: VMPC_E_INVAL, the mode stays"""
+        _check(self.lib.vmpc_ctx_set_cs_extension(self.handle, int(mode)), "vmpc_ctx_set_cs_extension")
+
+    def get_cs_extension(self):
+        mode = ctypes.c_int(-1)
+        _check(self.lib.vmpc_ctx_get_cs_extension(self.handle, ctypes.byref(mode)), "vmpc_ctx_get_cs_extension")
+        return mode.value
+
+    def cs_extend_ntt_len(self, m):
+        """the NTT route's transform length for m gates; 0: the direct kernel whatever the mode (m < 2, m = 2^20)"""
+        return int(self.lib.vmpc_fr_cs_extend_ntt_len(m))
 
     # ---- Shamir sharings of vectors (csrc/mpc_share.hip) -------------------------------------------------------------
     def share_mul_deal(self, a_ptr, b_ptr, n, coeffs_ptr, t, parties, out_ptr, out_stride):
@@ -1669,6 +1692,8 @@ BN256_FR_POLY_MAX = 1 << 20      # VMPC_BN256_FR_POLY_MAX of include/vmpc.h
 BN256_FR_NTT_MIN = 2             # VMPC_BN256_FR_NTT_MIN: POLY_PRODUCT_AUTO takes the NTT from this many coefficients
 BN256_FR_NTT_LDS_LEN = 2048      # VMPC_BN256_FR_NTT_LDS_LEN: the longest transform one workgroup runs in LDS
 POLY_PRODUCT_SCHOOLBOOK, POLY_PRODUCT_AUTO, POLY_PRODUCT_NTT = 0, 1, 2      # VMPC_POLY_PRODUCT_*
+CS_EXTENSION_DIRECT, CS_EXTENSION_AUTO, CS_EXTENSION_NTT = 0, 1, 2          # VMPC_CS_EXTENSION_*
+FR_CS_EXT_NTT_MIN = 64           # VMPC_FR_CS_EXT_NTT_MIN: CS_EXTENSION_AUTO takes the NTT from this many gates
 BN256_QAP_MAX_WIT = 65535        # VMPC_BN256_QAP_MAX_WIT
 BN256_R1CS_MAX_WIT = 65535       # VMPC_BN256_R1CS_MAX_WIT
 R1CS_WIDE_ALL = ctypes.c_size_t(-1).value      # wide_rows = SIZE_MAX: every level in one launch

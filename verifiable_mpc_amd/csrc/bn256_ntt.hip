@@ -27,6 +27,11 @@
 // the arena stays below NTT_ARENA_MAX (one row at the cap is 18 x 2^21 x 4 B = 151 MB).  A group boundary changes no
 // value: every row is transformed on its own.  Integer sums in a fixed order, no atomics.
 //
+// Nothing but the last Horner reduction belongs to GF(n): k_ntt_crt and the loop over the groups (ntt_poly_mul_in, which
+// works in residue buffers its caller took from the arena and reserves nothing) are templates over the field, and
+// vmpc_ntt_fr_rows_mul is their GF(l) instantiation for Protocol 8's extension (csrc/circuit_sat.hip, DESIGN.md section
+// 28), which plans a WRAPPED transform (vmpc_ntt_plan_at: L shorter than the whole product, its window alias-free).
+//
 // vmpc_ntt_tree_level (internal; csrc/bn256_qap_mtree.hip): one level of a subproduct tree,
 // N_parent = N_left T_right + N_right T_left for all nodes and rows in one launch sequence - k_ntt_split_nodes,
 // k_ntt_lds_pair and k_ntt_crt_nodes around the transform kernels above, which take the level's many short transforms
@@ -43,6 +48,7 @@
 #define NTT_TW_HALF 1024                  // entries of the lo and of the hi twiddle table
 #define NTT_TW_PER_PRIME (2 * NTT_TW_HALF)
 #define NTT_ARENA_MAX ((size_t)1 << 30)
+#define NTT_MAX_GROUP ((size_t)65535)    // rows of one launch: a grid's y and z dimensions hold no more
 
 static_assert(NTT_LDS_LEN == VMPC_BN256_FR_NTT_LDS_LEN, "the header's constant is this kernel's block length");
 
@@ -219,7 +225,10 @@ k_ntt_cols(uint32_t *__restrict__ x, uint32_t rows, uint32_t L, int hb, int m, c
         xr[base + ((e >> NTT_COL_W_LOG) << rs) + (e & 63)] = sx[e];
 }
 
-// out_row[k - k_lo] = the integer coefficient k of row's product, mod n, for k in [k_lo, k_lo + k_cnt)
+// out_row[k - k_lo] = the integer coefficient k of row's product, mod the modulus of F (frbn: n; fr: l, the Protocol 8
+// extension of csrc/circuit_sat.hip), for k in [k_lo, k_lo + k_cnt).  The coefficient is the CYCLIC product's: the
+// caller has chosen L so that nothing aliases into the window.
+template <class F>
 __global__ void __launch_bounds__(NTT_WG)
 k_ntt_crt(const uint32_t *__restrict__ res, uint32_t rows, uint32_t L, uint32_t k_lo, uint32_t k_cnt, ntt_scale sc,
           uint32_t *__restrict__ out, size_t out_stride) {
@@ -229,7 +238,7 @@ k_ntt_crt(const uint32_t *__restrict__ res, uint32_t rows, uint32_t L, uint32_t 
     uint32_t r[NTT31_NP];
 #pragma unroll
     for (int pr = 0; pr < NTT31_NP; pr++) r[pr] = res[((size_t)pr * rows + row) * L + k_lo + j];
-    frbn_store(out + 8 * (row * out_stride + j), ntt31_crt(r, sc.linv));
+    f256_store(out + 8 * (row * out_stride + j), ntt31_crt_in<F>(r, sc.linv));
 }
 
 // a tree level's parents: out[tr k_cnt + j] = coefficient j < k_cnt of the flat transform tr, mod n (the parents of a
@@ -247,25 +256,29 @@ k_ntt_crt_nodes(const uint32_t *__restrict__ res, size_t transforms, int log_l, 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-struct ntt_plan {
-    int log_l;
-    size_t L, row_bytes;       // residues of one row
-    size_t group, b_rows;      // a rows per group; b rows held (1: the shared b)
-    size_t bytes;              // arena
-};
+typedef vmpc_ntt_plan ntt_plan;      // csrc/common.h: log_l, L, row_bytes, group, b_rows, bytes
 
-static ntt_plan ntt_plan_of(size_t na, size_t nb, bool shared_b, size_t n_wit, size_t cap) {
+// the plan of n_wit products by transforms of 2^log_l points.  A group's rows lie on a grid's y (k_ntt_split,
+// k_ntt_crt) or z (the transforms): at most 65535 of them, whatever the cap holds.
+ntt_plan vmpc_ntt_plan_at(int log_l, bool shared_b, size_t n_wit, size_t cap) {
     ntt_plan p;
-    p.log_l = 1;
-    while (((size_t)1 << p.log_l) < na + nb - 1) p.log_l++;
+    p.log_l = log_l;
     p.L = (size_t)1 << p.log_l;
     p.row_bytes = (size_t)NTT31_NP * p.L * 4;
     const size_t fit = cap / p.row_bytes;                  // rows the cap holds
     size_t g = shared_b ? (fit > 1 ? fit - 1 : 1) : (fit > 2 ? fit / 2 : 1);
+    if (g > NTT_MAX_GROUP) g = NTT_MAX_GROUP;
     p.group = g < n_wit ? g : n_wit;
     p.b_rows = shared_b ? 1 : p.group;
     p.bytes = vmpc_align(p.row_bytes * p.b_rows) + vmpc_align(p.row_bytes * p.group) + 512;
     return p;
+}
+
+// the whole product: L the power of two >= na + nb - 1
+static ntt_plan ntt_plan_of(size_t na, size_t nb, bool shared_b, size_t n_wit, size_t cap) {
+    int log_l = 1;
+    while (((size_t)1 << log_l) < na + nb - 1) log_l++;
+    return vmpc_ntt_plan_at(log_l, shared_b, n_wit, cap);
 }
 
 static int ntt_tables(vmpc_ctx *ctx) {
@@ -299,9 +312,9 @@ static int ntt_high_stages(vmpc_ctx *ctx, uint32_t *x, size_t rows, const ntt_pl
     return VMPC_OK;
 }
 
-static int ntt_split(vmpc_ctx *ctx, const void *src, size_t stride, size_t n, size_t rows, const ntt_plan &p,
-                     uint32_t *dst) {
-    vmpc_stage_scope s(ctx, "bn_fr_ntt_split");
+static int ntt_split(vmpc_ctx *ctx, const char *stage, const void *src, size_t stride, size_t n, size_t rows,
+                     const ntt_plan &p, uint32_t *dst) {
+    vmpc_stage_scope s(ctx, stage);
     k_ntt_split<<<dim3((unsigned)((p.L + NTT_WG - 1) / NTT_WG), (unsigned)rows), NTT_WG, 0, ctx->stream>>>(
         (const uint32_t *)src, stride, (uint32_t)n, (uint32_t)p.L, (uint32_t)rows, dst);
     VMPC_KERNEL_CHECK();
@@ -317,14 +330,15 @@ static int ntt_forward_launch(vmpc_ctx *ctx, uint32_t *x, size_t rows, const ntt
     return VMPC_OK;
 }
 
-static int ntt_forward(vmpc_ctx *ctx, uint32_t *x, size_t rows, const ntt_plan &p) {
-    vmpc_stage_scope s(ctx, "bn_fr_ntt_fwd");
+static int ntt_forward(vmpc_ctx *ctx, const char *stage, uint32_t *x, size_t rows, const ntt_plan &p) {
+    vmpc_stage_scope s(ctx, stage);
     return ntt_forward_launch(ctx, x, rows, p);
 }
 
 // x *= y pointwise, then the inverse transform of x (not yet scaled by 1 / L: k_ntt_crt does that)
-static int ntt_inverse(vmpc_ctx *ctx, uint32_t *x, size_t rows, const uint32_t *y, size_t y_rows, const ntt_plan &p) {
-    vmpc_stage_scope s(ctx, "bn_fr_ntt_inv");
+static int ntt_inverse(vmpc_ctx *ctx, const char *stage, uint32_t *x, size_t rows, const uint32_t *y, size_t y_rows,
+                       const ntt_plan &p) {
+    vmpc_stage_scope s(ctx, stage);
     const int log_b = p.log_l < NTT_LDS_LOG ? p.log_l : NTT_LDS_LOG;
     k_ntt_lds<true><<<dim3((unsigned)(p.L >> log_b), NTT31_NP, (unsigned)rows), NTT_WG, 0, ctx->stream>>>(
         x, (uint32_t)rows, y, (uint32_t)y_rows, (uint32_t)p.L, log_b, (const uint32_t *)ctx->ntt_twiddles);
@@ -332,15 +346,17 @@ static int ntt_inverse(vmpc_ctx *ctx, uint32_t *x, size_t rows, const uint32_t *
     return ntt_high_stages<true>(ctx, x, rows, p);
 }
 
-// n_wit >= 1 products of a non-empty window, checked by the entries (csrc/bn256_koe.hip's koe_poly_mul hands over here)
-int vmpc_ntt_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b, size_t b_stride,
-                      size_t nb, size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit) {
-    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+// The product in residue buffers the CALLER has taken from the arena (no reservation here): rb holds
+// p.row_bytes x p.b_rows bytes, ra p.row_bytes x p.group.  n_wit >= 1 rows of a in groups of p.group, b one row for all
+// (b_stride 0) or a row per product; the transforms have 2^p.log_l points whatever na + nb is, and out_w[k - k_lo] is
+// coefficient k of the CYCLIC product of that length, mod the modulus of F - the caller knows that nothing aliases
+// into [k_lo, k_lo + k_cnt) (vmpc_ntt_poly_mul: L >= na + nb - 1; cs_extend of csrc/circuit_sat.hip: its own argument).
+// The integer bound is the caller's as well: every coefficient a sum of at most 2^20 products of 32-byte values.
+template <class F>
+static int ntt_poly_mul_in(vmpc_ctx *ctx, const ntt_plan &p, const vmpc_ntt_stages &st, uint32_t *rb, uint32_t *ra,
+                           const void *a, size_t a_stride, size_t na, const void *b, size_t b_stride, size_t nb,
+                           size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit) {
     const bool shared_b = b_stride == 0;
-    const ntt_plan p = ntt_plan_of(na, nb, shared_b, n_wit, vmpc_ntt_arena_cap(ctx));
-    VMPC_CHECK(vmpc_ws_reserve(ctx, p.bytes));      // before any launch
-    uint32_t *rb = (uint32_t *)vmpc_ws_take(ctx, p.row_bytes * p.b_rows);
-    uint32_t *ra = (uint32_t *)vmpc_ws_take(ctx, p.row_bytes * p.group);
     VMPC_CHECK(ntt_tables(ctx));
     ntt_scale sc;
     const uint32_t P[NTT31_NP] = NTT31_PRIMES;
@@ -349,21 +365,43 @@ int vmpc_ntt_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, 
         const size_t g = n_wit - w0 < p.group ? n_wit - w0 : p.group;
         if (!shared_b || w0 == 0) {
             const size_t rows = shared_b ? 1 : g;
-            VMPC_CHECK(ntt_split(ctx, (const char *)b + 32 * w0 * b_stride, b_stride, nb, rows, p, rb));
-            VMPC_CHECK(ntt_forward(ctx, rb, rows, p));
+            VMPC_CHECK(ntt_split(ctx, st.split, (const char *)b + 32 * w0 * b_stride, b_stride, nb, rows, p, rb));
+            VMPC_CHECK(ntt_forward(ctx, st.fwd, rb, rows, p));
         }
-        VMPC_CHECK(ntt_split(ctx, (const char *)a + 32 * w0 * a_stride, a_stride, na, g, p, ra));
-        VMPC_CHECK(ntt_forward(ctx, ra, g, p));
-        VMPC_CHECK(ntt_inverse(ctx, ra, g, rb, shared_b ? 1 : g, p));
+        VMPC_CHECK(ntt_split(ctx, st.split, (const char *)a + 32 * w0 * a_stride, a_stride, na, g, p, ra));
+        VMPC_CHECK(ntt_forward(ctx, st.fwd, ra, g, p));
+        VMPC_CHECK(ntt_inverse(ctx, st.inv, ra, g, rb, shared_b ? 1 : g, p));
         {
-            vmpc_stage_scope s(ctx, "bn_fr_ntt_crt");
-            k_ntt_crt<<<dim3((unsigned)((k_cnt + NTT_WG - 1) / NTT_WG), (unsigned)g), NTT_WG, 0, ctx->stream>>>(
+            vmpc_stage_scope s(ctx, st.crt);
+            k_ntt_crt<F><<<dim3((unsigned)((k_cnt + NTT_WG - 1) / NTT_WG), (unsigned)g), NTT_WG, 0, ctx->stream>>>(
                 ra, (uint32_t)g, (uint32_t)p.L, (uint32_t)k_lo, (uint32_t)k_cnt, sc,
                 (uint32_t *)out + 8 * w0 * out_stride, out_stride);
             VMPC_KERNEL_CHECK();
         }
     }
     return VMPC_OK;
+}
+
+// n_wit >= 1 products of a non-empty window, checked by the entries (csrc/bn256_koe.hip's koe_poly_mul hands over here)
+int vmpc_ntt_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b, size_t b_stride,
+                      size_t nb, size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit) {
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    const ntt_plan p = ntt_plan_of(na, nb, b_stride == 0, n_wit, vmpc_ntt_arena_cap(ctx));
+    VMPC_CHECK(vmpc_ws_reserve(ctx, p.bytes));      // before any launch
+    uint32_t *rb = (uint32_t *)vmpc_ws_take(ctx, p.row_bytes * p.b_rows);
+    uint32_t *ra = (uint32_t *)vmpc_ws_take(ctx, p.row_bytes * p.group);
+    const vmpc_ntt_stages st = {"bn_fr_ntt_split", "bn_fr_ntt_fwd", "bn_fr_ntt_inv", "bn_fr_ntt_crt"};
+    return ntt_poly_mul_in<frbn>(ctx, p, st, rb, ra, a, a_stride, na, b, b_stride, nb, k_lo, k_cnt, out, out_stride,
+                                 n_wit);
+}
+
+// The window [k_lo, k_lo + k_cnt) of the cyclic products, of 2^p.log_l points, of `rows` rows of a with ONE b, over
+// GF(l) of Ed25519, in the caller's residue buffers (p = vmpc_ntt_plan_at(log_l, true, rows, cap); rb one row, ra
+// p.group rows): the correlation of Protocol 8's extension (cs_extend, csrc/circuit_sat.hip), which has reserved.
+int vmpc_ntt_fr_rows_mul(vmpc_ctx *ctx, const vmpc_ntt_plan &p, const vmpc_ntt_stages &st, uint32_t *rb, uint32_t *ra,
+                         const void *a, size_t a_stride, size_t na, size_t rows, const void *b, size_t nb, size_t k_lo,
+                         size_t k_cnt, void *out, size_t out_stride) {
+    return ntt_poly_mul_in<fr>(ctx, p, st, rb, ra, a, a_stride, na, b, 0, nb, k_lo, k_cnt, out, out_stride, rows);
 }
 
 size_t vmpc_ntt_arena_cap(const vmpc_ctx *ctx) {

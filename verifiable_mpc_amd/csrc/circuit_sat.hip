@@ -1,5 +1,7 @@
 // Protocol 8 (circuit satisfiability, verifiable_mpc/ac20/circuit_sat_cb.py:59-252) from a sparse circuit, over the
-// Ed25519 scalar field GF(l) (csrc/fr.h).  l - 1 = 2^2 * odd: no NTT, and f, g, h are never interpolated.
+// Ed25519 scalar field GF(l) (csrc/fr.h).  l - 1 = 2^2 * odd: GF(l) itself has no NTT, and f, g, h are never
+// interpolated; the one long convolution, the extension's, can go through the multi-prime NTT over the INTEGERS instead
+// (csrc/bn256_ntt.hip, vmpc_ctx_set_cs_extension; "the NTT route" below).
 //
 // With m multiplication gates, z = (x, f(0), g(0), h(0), h(1), .., h(2m)) and M = m + 1 nodes 1..M that carry
 // v = a || r_a (f) and b || r_b (g):
@@ -23,6 +25,10 @@
 //                             k_frbn_polymul (csrc/bn256_koe.hip); f and g share the staged T.  Every x meets every j,
 //                             so the work per tile is uniform; the range of j is cut into segments for occupancy, their
 //                             partial sums added in a fixed order.  Integer sums only: deterministic.
+//                             Under VMPC_CS_EXTENSION_NTT (and _AUTO from VMPC_FR_CS_EXT_NTT_MIN gates) k_cs_corr is
+//                             replaced by the cyclic product of the 2K rows u_f, u_g with T modulo 18 primes and the
+//                             GF(l) reconstruction of its window, written where k_cs_corr's ONE segment would be: same
+//                             canonical residues, every other kernel unchanged.
 //   vmpc_fr_cs_extend_fg_dev  the same f(x), g(x) left apart and unmultiplied, for a witness that is a vector of Shamir
 //                             shares: the extension is linear in v, the product is the parties' (csrc/mpc_share.hip)
 //   vmpc_fr_cs_extend_batch_dev  vmpc_fr_cs_extend_dev for K witnesses: T and the weights once, the correlation on a grid
@@ -348,25 +354,71 @@ k_cs_finish_fg(uint32_t m, uint32_t n_out, uint32_t n_seg, const uint32_t *__res
     }
 }
 
+// ---- the NTT route ------------------------------------------------------------------------------------------------------
+// The sums k_cs_corr computes are the coefficients k = m+1 .. 2m-1 of u (M = m + 1 terms) x T (n_t = 2m + 2 terms).  In a
+// CYCLIC product of length L, coefficient k also collects the full product's coefficients k + L, k + 2L, ..  The full
+// product ends at index (M - 1) + (n_t - 1) = 3m + 1 and the smallest k wanted is m + 1: with L >= 2m + 2 the first
+// alias, k + L >= 3m + 3, is past the end, so the window is alias-free for EVERY L >= 2m + 2 - not only for
+// L >= 3m + 2, the whole product's length - and L is the smallest power of two >= 2m + 2 (m = 3: L = 8 = 2m + 2, met
+// with equality).  A window coefficient is still a sum of at most M <= 2^20 products of residues < l:
+// below 2^20 l^2 < 2^526, within the 551 bits of the 18 primes (csrc/ntt31.h).
+// m < 2 has no correlation; at m = 2^20 (VMPC_FR_CS_MAX_M) 2m + 2 exceeds the longest transform, 2^21 points: 0, and
+// the direct kernel is taken whatever the mode.
+extern "C" size_t vmpc_fr_cs_extend_ntt_len(size_t m) {
+    if (m < 2 || m > VMPC_FR_CS_MAX_M || 2 * m + 2 > ((size_t)1 << 21)) return 0;
+    size_t L = 2;
+    while (L < 2 * m + 2) L *= 2;
+    return L;
+}
+
+static bool cs_extend_by_ntt(int mode, size_t m) {
+    if (vmpc_fr_cs_extend_ntt_len(m) == 0) return false;
+    return mode == VMPC_CS_EXTENSION_NTT || (mode == VMPC_CS_EXTENSION_AUTO && m >= VMPC_FR_CS_EXT_NTT_MIN);
+}
+
+extern "C" int vmpc_ctx_set_cs_extension(vmpc_ctx *ctx, int mode) {
+    if (!ctx || mode < VMPC_CS_EXTENSION_DIRECT || mode > VMPC_CS_EXTENSION_NTT) return VMPC_E_INVAL;
+    ctx->cs_extension = mode;
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_ctx_get_cs_extension(vmpc_ctx *ctx, int *mode) {
+    if (!ctx || !mode) return VMPC_E_INVAL;
+    *mode = ctx->cs_extension;
+    return VMPC_OK;
+}
+
 // The segment length with the witnesses counted: tiles x segments x K workgroups against CS_TARGET_WGS.  A large batch
 // ends at one segment per witness, so the partial sums never exceed K n_out scalars per polynomial beyond what the grid
-// needs.
+// needs.  On the NTT route (ntt_cap > 0: the NTT's arena cap in force) there is ONE "segment", the reconstructed window,
+// and the arena also holds the residues of T and of a group of the 2K rows u_f, u_g.
 struct cs_batch_plan {
     long long seg;
     unsigned tiles, n_seg;
     size_t part_b, total_b;
+    bool ntt;
+    vmpc_ntt_plan np;
 };
 
-static cs_batch_plan cs_extend_batch_plan(size_t m, size_t n_wit) {
+static cs_batch_plan cs_extend_batch_plan(size_t m, size_t n_wit, size_t ntt_cap = 0) {
     const long long M = (long long)m + 1, n_t = 2 * (long long)m + 2, n_out = m >= 2 ? (long long)m - 1 : 0;
     cs_batch_plan p;
+    p.ntt = ntt_cap != 0;
+    p.np = {};
     p.tiles = (unsigned)((n_out + FR_CONV_TILE - 1) / FR_CONV_TILE);
     p.seg = CS_MIN_SEG;
     while ((long long)p.tiles * ((M + p.seg - 1) / p.seg) * (long long)n_wit > CS_TARGET_WGS && p.seg < M) p.seg *= 2;
     p.n_seg = (unsigned)((M + p.seg - 1) / p.seg);
+    if (p.ntt) p.n_seg = 1;
     p.part_b = vmpc_align(n_wit * (size_t)p.n_seg * (size_t)(n_out ? n_out : 1) * 32);
     p.total_b = 2 * vmpc_align(n_wit * (size_t)M * 32) + vmpc_align((size_t)n_t * 32) + 2 * p.part_b +
                 vmpc_align(n_wit * 64) + 2048;
+    if (p.ntt) {
+        int log_l = 1;
+        while (((size_t)1 << log_l) < vmpc_fr_cs_extend_ntt_len(m)) log_l++;
+        p.np = vmpc_ntt_plan_at(log_l, true, 2 * n_wit, ntt_cap);
+        p.total_b += p.np.bytes;
+    }
     return p;
 }
 
@@ -377,14 +429,29 @@ static int cs_extend(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stri
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     const long long M = (long long)m + 1, n_t = 2 * (long long)m + 2;
     const long long n_out = m >= 2 ? (long long)m - 1 : 0, k_lo = (long long)m + 1;
-    const cs_batch_plan p = cs_extend_batch_plan(m, n_wit);
+    const bool by_ntt = cs_extend_by_ntt(ctx->cs_extension, m);
+    const cs_batch_plan p = cs_extend_batch_plan(m, n_wit, by_ntt ? vmpc_ntt_arena_cap(ctx) : 0);
     VMPC_CHECK(vmpc_ws_reserve(ctx, p.total_b));        // before any launch: a batch too large for the arena does nothing
-    uint32_t *uf = (uint32_t *)vmpc_ws_take(ctx, n_wit * (size_t)M * 32);
-    uint32_t *ug = (uint32_t *)vmpc_ws_take(ctx, n_wit * (size_t)M * 32);
-    uint32_t *T = (uint32_t *)vmpc_ws_take(ctx, (size_t)n_t * 32);
-    uint32_t *pf = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
-    uint32_t *pg = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
+    uint32_t *uf, *ug, *T, *pf, *pg, *rb = nullptr, *ra = nullptr;
+    if (p.ntt) {
+        // u_f and u_g one after the other, the 2K rows of ONE product; their windows alike
+        uf = (uint32_t *)vmpc_ws_take(ctx, 2 * n_wit * (size_t)M * 32);
+        ug = uf + n_wit * (size_t)M * 8;
+        T = (uint32_t *)vmpc_ws_take(ctx, (size_t)n_t * 32);
+        pf = (uint32_t *)vmpc_ws_take(ctx, 2 * n_wit * (size_t)n_out * 32);
+        pg = pf + n_wit * (size_t)n_out * 8;
+    } else {
+        uf = (uint32_t *)vmpc_ws_take(ctx, n_wit * (size_t)M * 32);
+        ug = (uint32_t *)vmpc_ws_take(ctx, n_wit * (size_t)M * 32);
+        T = (uint32_t *)vmpc_ws_take(ctx, (size_t)n_t * 32);
+        pf = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
+        pg = (uint32_t *)vmpc_ws_take(ctx, p.part_b);
+    }
     uint32_t *s0 = (uint32_t *)vmpc_ws_take(ctx, n_wit * 64);
+    if (p.ntt) {
+        rb = (uint32_t *)vmpc_ws_take(ctx, p.np.row_bytes * p.np.b_rows);
+        ra = (uint32_t *)vmpc_ws_take(ctx, p.np.row_bytes * p.np.group);
+    }
     const unsigned K = (unsigned)n_wit;
     {
         vmpc_stage_scope sc(ctx, "cs_extend_prep");
@@ -395,7 +462,12 @@ static int cs_extend(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stri
         k_cs_dot0<<<K, CS_WG, 0, ctx->stream>>>((uint32_t)M, uf, ug, T, s0);
         VMPC_KERNEL_CHECK();
     }
-    if (n_out) {
+    if (p.ntt) {
+        // T is split and transformed once per call, the rows in groups the NTT's arena cap and a grid dimension hold
+        const vmpc_ntt_stages st = {"cs_extend_ntt_split", "cs_extend_ntt_fwd", "cs_extend_ntt_inv", "cs_extend_ntt_crt"};
+        VMPC_CHECK(vmpc_ntt_fr_rows_mul(ctx, p.np, st, rb, ra, uf, (size_t)M, (size_t)M, 2 * n_wit, T, (size_t)n_t,
+                                        (size_t)k_lo, (size_t)n_out, pf, (size_t)n_out));
+    } else if (n_out) {
         vmpc_stage_scope sc(ctx, "cs_extend_corr");
         k_cs_corr<<<dim3(p.tiles, p.n_seg, K), FR_CONV_TILE, 0, ctx->stream>>>(uf, ug, M, T, n_t, k_lo, n_out, p.seg, pf, pg);
         VMPC_KERNEL_CHECK();
@@ -433,6 +505,13 @@ extern "C" int vmpc_fr_cs_extend_fg_dev(vmpc_ctx *ctx, const void *a, const void
 extern "C" size_t vmpc_fr_cs_extend_batch_bytes(size_t m, size_t n_wit) {
     if (m > VMPC_FR_CS_MAX_M || n_wit > VMPC_FR_CS_MAX_WIT || n_wit == 0) return 0;
     return cs_extend_batch_plan(m, n_wit).total_b;
+}
+
+// the same for the route ctx's mode (and its NTT arena cap) gives this m: what a call on ctx reserves
+extern "C" size_t vmpc_fr_cs_extend_batch_bytes_ctx(const vmpc_ctx *ctx, size_t m, size_t n_wit) {
+    if (m > VMPC_FR_CS_MAX_M || n_wit > VMPC_FR_CS_MAX_WIT || n_wit == 0) return 0;
+    const bool ntt = ctx && cs_extend_by_ntt(ctx->cs_extension, m);
+    return cs_extend_batch_plan(m, n_wit, ntt ? vmpc_ntt_arena_cap(ctx) : 0).total_b;
 }
 
 extern "C" int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m,

@@ -107,6 +107,7 @@ struct vmpc_ctx {
     int poly_product = 0;              // VMPC_POLY_PRODUCT_*: which products koe_poly_mul hands to the NTT (0: none)
     void *ntt_twiddles = nullptr;      // the NTT's twiddle tables, built on first use, independent of the length
     size_t ntt_arena_cap = 0;          // > 0: the NTT's arena cap in bytes (vmpc_ctx_set_ntt_arena_cap; 0: NTT_ARENA_MAX)
+    int cs_extension = 0;              // VMPC_CS_EXTENSION_*: which extensions of Protocol 8 cs_extend hands to it (0: none)
     // profiling
     bool profile = false;
     std::vector<vmpc_stage> stages;
@@ -133,6 +134,26 @@ inline size_t vmpc_align(size_t b) { return (b + 255) & ~(size_t)255; }
 // by the caller: n_wit >= 1 products of a non-empty window
 int vmpc_ntt_poly_mul(vmpc_ctx *ctx, const void *a, size_t a_stride, size_t na, const void *b, size_t b_stride,
                       size_t nb, size_t k_lo, size_t k_cnt, void *out, size_t out_stride, size_t n_wit);
+
+// The same machinery for a caller that reserves itself (cs_extend of csrc/circuit_sat.hip: ONE reservation per call).
+// vmpc_ntt_plan_at plans n_wit products by transforms of 2^log_l points under an arena cap: `bytes` is what the two
+// residue buffers need, b_rows rows of row_bytes for b and `group` rows for a (at most 65535: a grid dimension).
+// vmpc_ntt_fr_rows_mul is the product over GF(l) in those buffers, no reservation: `rows` rows of a against ONE b, the
+// window [k_lo, k_lo + k_cnt) of the CYCLIC product of 2^log_l points (the caller's L: nothing may alias into the
+// window), under the caller's stage names.
+struct vmpc_ntt_plan {
+    int log_l;
+    size_t L, row_bytes;       // residues of one row
+    size_t group, b_rows;      // a rows per group; b rows held (1: the shared b)
+    size_t bytes;              // arena
+};
+struct vmpc_ntt_stages {
+    const char *split, *fwd, *inv, *crt;
+};
+vmpc_ntt_plan vmpc_ntt_plan_at(int log_l, bool shared_b, size_t n_wit, size_t cap);
+int vmpc_ntt_fr_rows_mul(vmpc_ctx *ctx, const vmpc_ntt_plan &p, const vmpc_ntt_stages &st, uint32_t *rb, uint32_t *ra,
+                         const void *a, size_t a_stride, size_t na, size_t rows, const void *b, size_t nb, size_t k_lo,
+                         size_t k_cnt, void *out, size_t out_stride);
 
 // what csrc/bn256_qap_mtree.hip needs of it besides: the arena cap in force, the arena of vmpc_ntt_poly_mul under a cap,
 // and one level of a subproduct tree (all its nodes and rows in one launch sequence) with its arena

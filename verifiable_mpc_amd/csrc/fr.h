@@ -51,6 +51,46 @@ VMPC_HD bool fr_geq_l(const uint32_t a[8]) {
 
 VMPC_HD bool fr_is_canonical(const fr &a) { return !fr_geq_l(a.v); }
 
+// ---- multiplication by a small integer: the Horner step of the multi-prime NTT's reconstruction (csrc/ntt31.h) -------
+#define VMPC_FR_SMALL_BITS 31
+#define VMPC_FR_M284 0xffffffffu   // floor(2^284 / l) = 2^32 - 1 (l = 2^252 + d, d < 2^125: 2^284 / l = 2^32 - d 2^-220 + ..)
+
+// a * j mod l for a CANONICAL a (< l) and j < 2^31, canonical: the counterpart of frbn_mul_small (csrc/fr_bn.h).
+// x = a j < 2^31 l < 2^284, so floor(x / l) < 2^31.  With X = floor(x / 2^192) < 2^92 and M = VMPC_FR_M284 the estimate
+// q = floor(X M / 2^92) never exceeds x / l (both factors are rounded down) and
+//     X M / 2^92 > (x / 2^192 - 1) (2^284 / l - 1) / 2^92 > x / l - x / 2^284 - 2^192 / l > x / l - (1/2 + 2^-128) - 2^-60,
+// because x < 2^31 l = 2^284 (l / 2^253) and l / 2^253 < 1/2 + 2^-128.  The estimate loses less than 1: q is
+// floor(x / l) or one less, x - q l < 2 l < 2^254 fits eight limbs and one conditional subtraction finishes.
+// (X M < 2^124: the three partial products below carry into 64 bits without overflow; p2 = floor(X M / 2^64) < 2^60.)
+VMPC_HD fr fr_mul_small(const fr &a, uint32_t j) {
+    const uint32_t L[8] = VMPC_FR_L;
+    uint32_t x[9];
+    uint64_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        c += (uint64_t)a.v[i] * j;
+        x[i] = (uint32_t)c;
+        c >>= 32;
+    }
+    x[8] = (uint32_t)c;
+    const uint64_t p0 = (uint64_t)x[6] * VMPC_FR_M284;
+    const uint64_t p1 = (uint64_t)x[7] * VMPC_FR_M284 + (p0 >> 32);
+    const uint64_t p2 = (uint64_t)x[8] * VMPC_FR_M284 + (p1 >> 32);     // bits 64.. of (x >> 192) M284
+    const uint32_t q = (uint32_t)(p2 >> 28);                            // < 2^31
+    fr r;
+    uint64_t m = 0;
+    int64_t b = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        m += (uint64_t)q * L[i];
+        b += (int64_t)x[i] - (int64_t)(uint32_t)m;
+        r.v[i] = (uint32_t)b;
+        b >>= 32;
+        m >>= 32;
+    }
+    return fr_cond_sub_l(r);      // the ninth limb of x - q l is zero (< 2^254)
+}
+
 // reduce an arbitrary 256-bit value (e.g. a SHA-256 digest read as LE integer)
 VMPC_HD fr fr_from_u256(const uint32_t a[8]) {
     uint32_t t[16];

@@ -17,10 +17,15 @@
 // x = a j < 2^287, the quotient fits 32 bits and the estimate loses less than x / 2^287 + 2^-63 < 1, so it is still the
 // quotient or one less and one conditional subtraction finishes (tests/native/ntt31_host_test.cpp holds it against
 // unsigned __int128 limb arithmetic).
+// Nothing above belongs to GF(n) but that last Horner reduction: ntt31_horner_in / ntt31_crt_in take the field as a
+// template parameter, and GF(l) of Ed25519 (csrc/fr.h, fr_mul_small with its own bound; the Protocol 8 extension of
+// csrc/circuit_sat.hip, coefficients at most 2^20 (l - 1)^2 < 2^526) is the second instantiation
+// (tests/native/ntt31_fr_host_test.cpp).
 // VMPC_HD, plain C++: host-testable (tests/native/ntt31_host_test.cpp).
 #pragma once
 #include <stdint.h>
 
+#include "fr.h"
 #include "fr_bn.h"
 #include "ntt31_consts.h"
 
@@ -114,22 +119,30 @@ VMPC_HD void ntt31_garner(const uint32_t r[NTT31_NP], uint32_t d[NTT31_NP]) {
     }
 }
 
-// the value of the digits mod n, from the top digit: acc = acc p_i + d_i
-VMPC_HD frbn ntt31_horner(const uint32_t d[NTT31_NP]) {
+// acc p mod the field's modulus, canonical, for a 31-bit p: frbn_mul_small (csrc/fr_bn.h) takes ANY 256-bit acc,
+// fr_mul_small (csrc/fr.h) a canonical one - which acc is at every step of ntt31_horner_in: it starts as a digit < 2^31
+// and every step ends in an f256_add of canonical values.
+VMPC_HD frbn ntt31_mul_small(const frbn &a, uint32_t p) { return frbn_mul_small(a, p); }
+VMPC_HD fr ntt31_mul_small(const fr &a, uint32_t p) { return fr_mul_small(a, p); }
+
+// the value of the digits mod the modulus of F (frbn: n, fr: l), from the top digit: acc = acc p_i + d_i
+template <class F>
+VMPC_HD F ntt31_horner_in(const uint32_t d[NTT31_NP]) {
     const uint32_t P[NTT31_NP] = NTT31_PRIMES;
-    frbn acc = frbn_zero();
+    F acc = f256_zero<F>();
     acc.v[0] = d[NTT31_NP - 1];
 #pragma unroll
     for (int i = NTT31_NP - 2; i >= 0; i--) {
-        frbn di = frbn_zero();
+        F di = f256_zero<F>();
         di.v[0] = d[i];
-        acc = frbn_add(frbn_mul_small(acc, P[i]), di);
+        acc = f256_add(ntt31_mul_small(acc, P[i]), di);
     }
     return acc;
 }
 
 // res[i]: the inverse transform's output mod p_i (Montgomery form, lazy, still times L); linv[i] = ntt31_inv_pow2
-VMPC_HD frbn ntt31_crt(const uint32_t res[NTT31_NP], const uint32_t linv[NTT31_NP]) {
+template <class F>
+VMPC_HD F ntt31_crt_in(const uint32_t res[NTT31_NP], const uint32_t linv[NTT31_NP]) {
     uint32_t r[NTT31_NP], d[NTT31_NP];
 #pragma unroll
     for (int i = 0; i < NTT31_NP; i++) {
@@ -137,5 +150,11 @@ VMPC_HD frbn ntt31_crt(const uint32_t res[NTT31_NP], const uint32_t linv[NTT31_N
         r[i] = ntt31_csub(ntt31_mul(res[i], linv[i], q), q.p);
     }
     ntt31_garner(r, d);
-    return ntt31_horner(d);
+    return ntt31_horner_in<F>(d);
+}
+
+// the GF(n) instantiations under the names they have always had
+VMPC_HD frbn ntt31_horner(const uint32_t d[NTT31_NP]) { return ntt31_horner_in<frbn>(d); }
+VMPC_HD frbn ntt31_crt(const uint32_t res[NTT31_NP], const uint32_t linv[NTT31_NP]) {
+    return ntt31_crt_in<frbn>(res, linv);
 }

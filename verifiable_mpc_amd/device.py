@@ -73,6 +73,29 @@ def poly_product(mode, ctx=None):
         ctx.set_poly_product(prev)
 
 
+CS_EXTENSION_MODES = {"direct": _native.CS_EXTENSION_DIRECT, "auto": _native.CS_EXTENSION_AUTO,
+                      "ntt": _native.CS_EXTENSION_NTT}
+
+
+@contextlib.contextmanager
+def cs_extension(mode, ctx=None):
+    """with cs_extension("ntt"): every extension of Protocol 8's f and g that `ctx` (default: the process's context)
+    computes inside the block - cs_extend and its share and batch forms, and with them circuit_sat_prover, its batch and
+    the M-party prover - takes the sums for x = m+2 .. 2m from the NTT over the integers (csrc/bn256_ntt.hip) instead
+    of the quadratic correlation kernel; "auto": from _native.FR_CS_EXT_NTT_MIN gates; "direct": never (a new context's
+    mode).  The bits are the same in every mode.  A mode of its own: poly_product does not touch it.  The mode found on
+    entry is restored on exit, also when the block raises."""
+    if mode not in CS_EXTENSION_MODES:
+        raise ValueError(f"cs_extension mode {mode!r}: one of {sorted(CS_EXTENSION_MODES)}")
+    ctx = ctx or get_context()
+    prev = ctx.get_cs_extension()
+    ctx.set_cs_extension(CS_EXTENSION_MODES[mode])
+    try:
+        yield ctx
+    finally:
+        ctx.set_cs_extension(prev)
+
+
 MOMENT_TRANSFORM_MODES = ("direct", "auto", "tree")
 
 
