@@ -509,6 +509,22 @@ int vmpc_ctx_get_poly_product(vmpc_ctx *ctx, int *mode);
  * trusted setup, which knowledge_of_exponent.py:52-66 reaches by 2n sequential `g1_base ** z` / `g2_base ** z` on the
  * points themselves; here the 2n points are vmpc_bn256_fixed_base_dev of these exponents. */
 int vmpc_bn256_fr_powers_dev(vmpc_ctx *ctx, const void *z, const void *scale, size_t count, void *out);
+/* out = c * x + y (y NULL: c * x) and <a, b> left in device memory, mod n: vmpc_fr_axpy_dev and vmpc_fr_dot_to_dev over
+ * this field, the same kernels (csrc/frvec.hip).  c: a canonical residue, else VMPC_E_NONCANON; the vectors any 32-byte
+ * values.  The dot product's partial sums go to `scratch`, the caller's device memory of
+ * vmpc_bn256_fr_dot_scratch_bytes(n) bytes, not to the arena.  n = 0: out_dev = 0. */
+int vmpc_bn256_fr_axpy_dev(vmpc_ctx *ctx, const uint8_t c[32], const void *x, const void *y, size_t n, void *out);
+size_t vmpc_bn256_fr_dot_scratch_bytes(size_t n);
+int vmpc_bn256_fr_dot_to_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, void *out_dev, void *scratch);
+/* The operands of the opening's product from device memory (knowledge_of_exponent.py:116-123):
+ * lhs = (gamma, x_0, .., x_{n-1}) (n + 1 scalars) and rhs = (L_{n-1}, .., L_0) (n scalars).  lhs or rhs may be NULL
+ * (the verifier reverses L only; gamma and x are then not read).  gamma >= n: VMPC_E_NONCANON.
+ * n < VMPC_BN256_FR_POLY_MAX, else VMPC_E_RANGE.  No arena. */
+int vmpc_bn256_koe_stage_dev(vmpc_ctx *ctx, const void *x, const uint8_t gamma[32], const void *L, size_t n, void *lhs,
+                             void *rhs);
+/* After the product c (2n scalars): u_out (one device scalar) = c[n] = <L, x>, and c[n] = 0, so that c is the scalar
+ * vector of Q's MSM over the 2n generators (knowledge_of_exponent.py:124-130).  n >= 1.  No arena. */
+int vmpc_bn256_koe_split_dev(vmpc_ctx *ctx, void *c, size_t n, void *u_out);
 
 /* ---- Pinocchio key generation (verifiable_mpc/trinocchio/pynocchio.py:101-200): the exponents of the key points,
  * same scalar conventions.  Every key entry is (exponent) * g1 or g2, made by vmpc_bn256_fixed_base_dev. */
@@ -781,6 +797,34 @@ int vmpc_fr_cs_colsum_dev(vmpc_ctx *ctx, const void *weights, size_t n_rows, con
                           size_t n_partial, void *out, size_t n_out);
 /* *first_diff (a device uint32) = the smallest i < n with a[i] != b[i], 0xffffffff if none.  No arena. */
 int vmpc_fr_cs_first_diff_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, uint32_t *first_diff);
+
+/* ---- The same over GF(n), n the BN-256 group order: Protocol 8 for the knowledge-of-exponent pivot (DESIGN.md section
+ * 29).  One template per kernel and host body with the GF(l) entries above (csrc/circuit_sat.hip), instantiated at
+ * csrc/fr_bn.h; arguments, caps (VMPC_FR_CS_MAX_M) and answers are those of the namesake above, VMPC_E_NONCANON for a
+ * scalar ARGUMENT >= n.  Scalars in device memory may be any 32-byte value (reduced mod n when loaded); outputs are
+ * canonical residues.  vmpc_ctx_set_cs_extension governs vmpc_bn256_fr_cs_extend_dev as it governs the GF(l) entry: on
+ * the NTT route a window coefficient is below 2^20 n^2 < 2^532, inside the 551 bits of the 18 primes, and is reduced mod
+ * n - the same canonical residues as the direct kernel's.  Arena: the extension and the column sum reserve as above;
+ * tables and lagrange do NOT use the arena - `scratch` is the caller's device memory of
+ * vmpc_bn256_fr_cs_tables_scratch_bytes(K) / vmpc_bn256_fr_cs_lagrange_scratch_bytes(K) bytes (0: K out of range), not
+ * read, and free again when the stream has passed the call.  The batch, share (_fg) and MPC forms exist over GF(l) only. */
+int vmpc_bn256_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_vals,
+                                 const void *a_const, const uint32_t *b_row_ptr, const uint32_t *b_col,
+                                 const void *b_vals, const void *b_const, const uint32_t *gates, size_t n_gates,
+                                 size_t n_x, size_t gamma_offset, void *z, void *a_out, void *b_out, int check,
+                                 uint32_t *first_bad);
+size_t vmpc_bn256_fr_cs_tables_scratch_bytes(size_t K);
+int vmpc_bn256_fr_cs_tables_dev(vmpc_ctx *ctx, size_t K, void *fact, void *ifact, void *scratch);
+int vmpc_bn256_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
+                                const void *ifact, void *z_tail);
+size_t vmpc_bn256_fr_cs_lagrange_scratch_bytes(size_t K);
+int vmpc_bn256_fr_cs_lagrange_dev(vmpc_ctx *ctx, const uint8_t c[32], size_t K, const void *ifact, void *out,
+                                  void *scratch);
+int vmpc_bn256_fr_cs_colsum_dev(vmpc_ctx *ctx, const void *weights, size_t n_rows, const uint32_t *rows,
+                                const void *vals, size_t nnz, const uint32_t *items, size_t n_items,
+                                const uint32_t *long_cols, size_t n_long, size_t n_partial, void *out, size_t n_out);
+/* two encodings of one residue (v and v + n, where that fits 256 bits) compare equal */
+int vmpc_bn256_fr_cs_first_diff_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, uint32_t *first_diff);
 
 /* ---- Shamir sharings of vectors mod l (csrc/mpc_share.hip; verifiable_mpc/ac20/mpc_ac20_cb.py:39-189 through
  * mpc.schur_prod and mpc._random).  Party q < parties holds the value at node q + 1.  Matrices are row-major in device

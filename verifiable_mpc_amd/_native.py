@@ -67,6 +67,11 @@ SYMBOLS = [
     "vmpc_bn256_r1cs_solve_batch_dev", "vmpc_bn256_r1cs_solve_launches",
     "vmpc_bn256_r1cs_share_mul_deal_dev", "vmpc_bn256_r1cs_share_finish_dev",
     "vmpc_bn256_qap_residual_batch_dev", "vmpc_bn256_recombine_dev",
+    "vmpc_bn256_fr_cs_triples_dev", "vmpc_bn256_fr_cs_tables_scratch_bytes", "vmpc_bn256_fr_cs_tables_dev",
+    "vmpc_bn256_fr_cs_extend_dev", "vmpc_bn256_fr_cs_lagrange_scratch_bytes", "vmpc_bn256_fr_cs_lagrange_dev",
+    "vmpc_bn256_fr_cs_colsum_dev", "vmpc_bn256_fr_cs_first_diff_dev",
+    "vmpc_bn256_fr_axpy_dev", "vmpc_bn256_fr_dot_scratch_bytes", "vmpc_bn256_fr_dot_to_dev",
+    "vmpc_bn256_koe_stage_dev", "vmpc_bn256_koe_split_dev",
 ]
 
 
@@ -252,6 +257,19 @@ def load_library():
         "vmpc_fr_cs_lagrange_dev": (i32, [vp, vp, sz, vp, vp]),
         "vmpc_fr_cs_colsum_dev": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, vp, sz]),
         "vmpc_fr_cs_first_diff_dev": (i32, [vp, vp, vp, sz, vp]),
+        "vmpc_bn256_fr_cs_triples_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, i32, vp]),
+        "vmpc_bn256_fr_cs_tables_scratch_bytes": (sz, [sz]),
+        "vmpc_bn256_fr_cs_tables_dev": (i32, [vp, sz, vp, vp, vp]),
+        "vmpc_bn256_fr_cs_extend_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
+        "vmpc_bn256_fr_cs_lagrange_scratch_bytes": (sz, [sz]),
+        "vmpc_bn256_fr_cs_lagrange_dev": (i32, [vp, vp, sz, vp, vp, vp]),
+        "vmpc_bn256_fr_cs_colsum_dev": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, vp, sz]),
+        "vmpc_bn256_fr_cs_first_diff_dev": (i32, [vp, vp, vp, sz, vp]),
+        "vmpc_bn256_fr_axpy_dev": (i32, [vp, vp, vp, vp, sz, vp]),
+        "vmpc_bn256_fr_dot_scratch_bytes": (sz, [sz]),
+        "vmpc_bn256_fr_dot_to_dev": (i32, [vp, vp, vp, sz, vp, vp]),
+        "vmpc_bn256_koe_stage_dev": (i32, [vp, vp, vp, vp, sz, vp, vp]),
+        "vmpc_bn256_koe_split_dev": (i32, [vp, vp, sz, vp]),
         "vmpc_fr_rows_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp]),
         "vmpc_fr_rows_dot_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
         "vmpc_fr_batch_products_dev": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, sz, vp, vp]),
@@ -896,11 +914,15 @@ class Context:
                                                 ctypes.c_void_p(out_proj_ptr)),
                "vmpc_affine_to_proj_dev")
 
-    def fr_axpy(self, c, x_ptr, y_ptr, n, out_ptr):
+    def _field_entry(self, name, bn):
+        """(function, its name) of the GF(l) entry vmpc_fr_<name> or, bn=True, its GF(n) namesake vmpc_bn256_fr_<name>"""
+        full = ("vmpc_bn256_fr_" if bn else "vmpc_fr_") + name
+        return getattr(self.lib, full), full
+
+    def fr_axpy(self, c, x_ptr, y_ptr, n, out_ptr, bn=False):
         cb = ctypes.create_string_buffer(scalar_to_bytes(c), 32)
-        _check(self.lib.vmpc_fr_axpy_dev(self.handle, cb, ctypes.c_void_p(x_ptr),
-                                         ctypes.c_void_p(y_ptr), n, ctypes.c_void_p(out_ptr)),
-               "vmpc_fr_axpy_dev")
+        fn, name = self._field_entry("axpy_dev", bn)
+        _check(fn(self.handle, cb, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), n, ctypes.c_void_p(out_ptr)), name)
 
     def fr_axpy_tail(self, c, x_ptr, y_ptr, n, tail, out_ptr):
         """out[0..n) = c * x + y (y_ptr None: c * x), out[n] = tail"""
@@ -956,27 +978,47 @@ class Context:
                                            ctypes.c_void_p(out.ptr)), "vmpc_fr_dot_to_dev")
         return out
 
-    def fr_dot_into(self, a_ptr, b_ptr, n, out_ptr):
-        """inner product into a scalar of the caller's device memory, no synchronisation"""
-        _check(self.lib.vmpc_fr_dot_to_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), n,
-                                           ctypes.c_void_p(out_ptr)), "vmpc_fr_dot_to_dev")
+    def fr_dot_into(self, a_ptr, b_ptr, n, out_ptr, bn=False):
+        """inner product into a scalar of the caller's device memory, no synchronisation.  bn: over GF(n); that entry's
+        partial sums are a block of this context's cache, free for reuse once the stream has passed the call"""
+        p = ctypes.c_void_p
+        if bn:
+            scratch = self.alloc(max(32, int(self.lib.vmpc_bn256_fr_dot_scratch_bytes(n))))
+            _check(self.lib.vmpc_bn256_fr_dot_to_dev(self.handle, p(a_ptr), p(b_ptr), n, p(out_ptr), p(scratch.ptr)),
+                   "vmpc_bn256_fr_dot_to_dev")
+        else:
+            _check(self.lib.vmpc_fr_dot_to_dev(self.handle, p(a_ptr), p(b_ptr), n, p(out_ptr)), "vmpc_fr_dot_to_dev")
+
+    def bn256_fr_dot(self, a_ptr, b_ptr, n):
+        """<a, b> mod n, the BN-256 order, as an int"""
+        out = self.alloc(32)
+        self.fr_dot_into(a_ptr, b_ptr, n, out.ptr, bn=True)
+        return int.from_bytes(self.download(out.ptr, 32).tobytes(), "little")
 
     # ---- Protocol 8 from a sparse circuit (csrc/circuit_sat.hip) ------------------------------------------------------
-    def cs_triples(self, A, B, gates_ptr, n_gates, n_x, gamma_offset, z_ptr, a_ptr, b_ptr, check=0, first_bad_ptr=None):
+    # bn=True: the GF(n) namesake of the entry (the knowledge-of-exponent variant over BN-256); scratch that entry asks of
+    # its caller is a block of this context's cache
+    def cs_triples(self, A, B, gates_ptr, n_gates, n_x, gamma_offset, z_ptr, a_ptr, b_ptr, check=0, first_bad_ptr=None,
+                   bn=False):
         """A, B: (row_ptr, col, vals, consts) device pointers"""
         p = ctypes.c_void_p
-        _check(self.lib.vmpc_fr_cs_triples_dev(self.handle, p(A[0]), p(A[1]), p(A[2]), p(A[3]), p(B[0]), p(B[1]), p(B[2]),
-                                               p(B[3]), p(gates_ptr), n_gates, n_x, gamma_offset, p(z_ptr), p(a_ptr),
-                                               p(b_ptr), check, p(first_bad_ptr)), "vmpc_fr_cs_triples_dev")
+        fn, name = self._field_entry("cs_triples_dev", bn)
+        _check(fn(self.handle, p(A[0]), p(A[1]), p(A[2]), p(A[3]), p(B[0]), p(B[1]), p(B[2]), p(B[3]), p(gates_ptr), n_gates,
+                  n_x, gamma_offset, p(z_ptr), p(a_ptr), p(b_ptr), check, p(first_bad_ptr)), name)
 
-    def cs_tables(self, K, fact_ptr, ifact_ptr):
-        _check(self.lib.vmpc_fr_cs_tables_dev(self.handle, K, ctypes.c_void_p(fact_ptr), ctypes.c_void_p(ifact_ptr)),
-               "vmpc_fr_cs_tables_dev")
-
-    def cs_extend(self, a_ptr, b_ptr, m, fact_ptr, ifact_ptr, z_tail_ptr):
+    def cs_tables(self, K, fact_ptr, ifact_ptr, bn=False):
         p = ctypes.c_void_p
-        _check(self.lib.vmpc_fr_cs_extend_dev(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr),
-                                              p(z_tail_ptr)), "vmpc_fr_cs_extend_dev")
+        if bn:
+            scratch = self.alloc(max(32, int(self.lib.vmpc_bn256_fr_cs_tables_scratch_bytes(K))))
+            _check(self.lib.vmpc_bn256_fr_cs_tables_dev(self.handle, K, p(fact_ptr), p(ifact_ptr), p(scratch.ptr)),
+                   "vmpc_bn256_fr_cs_tables_dev")
+        else:
+            _check(self.lib.vmpc_fr_cs_tables_dev(self.handle, K, p(fact_ptr), p(ifact_ptr)), "vmpc_fr_cs_tables_dev")
+
+    def cs_extend(self, a_ptr, b_ptr, m, fact_ptr, ifact_ptr, z_tail_ptr, bn=False):
+        p = ctypes.c_void_p
+        fn, name = self._field_entry("cs_extend_dev", bn)
+        _check(fn(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr), p(z_tail_ptr)), name)
 
     def cs_extend_fg(self, a_ptr, b_ptr, m, fact_ptr, ifact_ptr, f_out_ptr, g_out_ptr):
         """f(0), f(m+2..2m) and g alike, unmultiplied (max(m, 1) scalars each)"""
@@ -1049,10 +1091,15 @@ class Context:
                                                         p(dst_ptr), p(addend_ptr), p(out_ptr)),
                "vmpc_bn256_fr_share_combine_dev")
 
-    def cs_lagrange(self, c, K, ifact_ptr, out_ptr):
+    def cs_lagrange(self, c, K, ifact_ptr, out_ptr, bn=False):
         cb = ctypes.create_string_buffer(scalar_to_bytes(c), 32)
-        _check(self.lib.vmpc_fr_cs_lagrange_dev(self.handle, cb, K, ctypes.c_void_p(ifact_ptr), ctypes.c_void_p(out_ptr)),
-               "vmpc_fr_cs_lagrange_dev")
+        p = ctypes.c_void_p
+        if bn:
+            scratch = self.alloc(max(32, int(self.lib.vmpc_bn256_fr_cs_lagrange_scratch_bytes(K))))
+            _check(self.lib.vmpc_bn256_fr_cs_lagrange_dev(self.handle, cb, K, p(ifact_ptr), p(out_ptr), p(scratch.ptr)),
+                   "vmpc_bn256_fr_cs_lagrange_dev")
+        else:
+            _check(self.lib.vmpc_fr_cs_lagrange_dev(self.handle, cb, K, p(ifact_ptr), p(out_ptr)), "vmpc_fr_cs_lagrange_dev")
 
     def _colsum(self, entry, weights_ptr, n_rows, rows_ptr, vals_ptr, nnz, items_ptr, n_items, long_ptr, n_long, n_partial,
                 out_ptr, n_out):
@@ -1066,13 +1113,30 @@ class Context:
         plan: the arguments of _colsum after `entry`"""
         self._colsum("vmpc_fr_cs_colsum_dev", *plan)
 
-    def cs_first_diff(self, a_ptr, b_ptr, n):
+    def bn256_cs_colsum(self, *plan):
+        """cs_colsum mod n, the BN-256 order"""
+        self._colsum("vmpc_bn256_fr_cs_colsum_dev", *plan)
+
+    def cs_first_diff(self, a_ptr, b_ptr, n, bn=False):
         """the smallest i with a[i] != b[i], or None"""
         out = self.alloc(4)
-        _check(self.lib.vmpc_fr_cs_first_diff_dev(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), n,
-                                                  ctypes.c_void_p(out.ptr)), "vmpc_fr_cs_first_diff_dev")
+        fn, name = self._field_entry("cs_first_diff_dev", bn)
+        _check(fn(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), n, ctypes.c_void_p(out.ptr)), name)
         v = int(self.download(out.ptr, 4).view(np.uint32)[0])
         return None if v == 0xFFFFFFFF else v
+
+    # ---- the knowledge-of-exponent opening from device operands (csrc/bn256_koe.hip) -----------------------------------
+    def bn256_koe_stage(self, x_ptr, gamma, L_ptr, n, lhs_ptr, rhs_ptr):
+        """lhs = (gamma, x_0..x_{n-1}), rhs = (L_{n-1}..L_0); lhs_ptr or rhs_ptr None: that side is not written"""
+        p = ctypes.c_void_p
+        gb = ctypes.create_string_buffer(scalar_to_bytes(gamma if gamma is not None else 0), 32)
+        _check(self.lib.vmpc_bn256_koe_stage_dev(self.handle, p(x_ptr), gb, p(L_ptr), n, p(lhs_ptr), p(rhs_ptr)),
+               "vmpc_bn256_koe_stage_dev")
+
+    def bn256_koe_split(self, c_ptr, n, u_ptr):
+        """u = c[n], c[n] = 0, on the device"""
+        _check(self.lib.vmpc_bn256_koe_split_dev(self.handle, ctypes.c_void_p(c_ptr), n, ctypes.c_void_p(u_ptr)),
+               "vmpc_bn256_koe_split_dev")
 
     # ---- Pi_Nullity over a dense form matrix (csrc/nullity.hip) ------------------------------------------------------
     def fr_rows_combine(self, rows_ptr, s, n, row_stride, rho, out_ptr):

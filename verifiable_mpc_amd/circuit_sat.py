@@ -46,11 +46,19 @@ WIDE_TABLE_MIN = (1 << 19) - 1
 def create_generators(g_length, pivot_choice, group=None, progress_bar=False):
     """Create generators g, h, k with g_i = h ** r_i on the GPU (one lane per generator,
     csrc/exact.hip k_repeat).  Exponents are drawn from `prng` in the reference's order:
-    r_0 .. r_{g_length-1}, then k's exponent (circuit_sat_r1cs.py:64,81)."""
+    r_0 .. r_{g_length-1}, then k's exponent (circuit_sat_r1cs.py:64,81).
+
+    PivotChoice.koe with `group` a list of two (circuit_sat_r1cs.py:83-89) - two groups with a .generator, or the two
+    generator points themselves, of BN-256 and of its twist: the pp of knowledge_of_exponent.trusted_setup for vectors
+    of g_length scalars (2 g_length points a side), over the BN-256 group order."""
     choice = choice_name(pivot_choice)
+    if choice == "koe" and isinstance(group, list) and len(group) == 2:
+        from . import knowledge_of_exponent as koe
+        g1, g2 = (getattr(g, "generator", g) for g in group)
+        return koe.trusted_setup(g1, g2, g_length, koe.ORDER, progress_bar)
     if choice not in ("pivot", "compressed"):
-        # the KoE pivot lives on BN256 with pairings: not part of the accelerated path (an installed reference
-        # keeps its own create_generators for it, dropin.py)
+        # one group, or none: the KoE pivot lives on BN-256 and its twist (an installed reference keeps its own
+        # create_generators for it, dropin.py)
         raise NotImplementedError
     assert group is not None
     if not is_ed25519_group(group):

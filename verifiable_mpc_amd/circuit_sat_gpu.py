@@ -16,6 +16,14 @@ pivot.
 Transcripts, selected by `transcript=` (default: TRANSCRIPT below): "compact" (DESIGN.md section 15 states the bytes;
 tests/p8_ref.py restates them) - the path that scales, z and L device-resident - and "reference": the reference's two
 str(input_list) hashes with its element types, list mode, O((n_out + 3) N) text, for parity on small circuits.
+
+Two fields and two commitment schemes, ONE statement of the protocol.  A SparseCircuit carries its
+order: the Ed25519 order (the default) or the BN-256 order, and with it the device vector class and the kernels' field
+(_Field).  The generators select the scheme as in the reference (circuit_sat_cb.py:65-72, :183): {"g", "h", ..} commit
+to z by an Ed25519 vector commitment and open L with the compressed or the plain pivot; a pp {"pp_lhs", "pp_rhs"}
+(knowledge_of_exponent.trusted_setup) commits by the restriction argument (P, pi) and opens L with the
+knowledge-of-exponent pivot - three group elements whatever N is, no power-of-two padding of z, compact transcript
+only.  A verifier recognises the variant by a z_commitment that is a dict.
 """
 import hashlib
 from random import SystemRandom
@@ -23,12 +31,33 @@ from random import SystemRandom
 import numpy as np
 
 from . import compressed_pivot, pivot, sparse, wire
-from .device import ScalarVector, get_context
+from . import knowledge_of_exponent as koe
+from .device import BN256_ORDER, BnScalarVector, ScalarVector, get_context
+from .fields import FiniteFieldElement
 from .groups import ORDER
 
 prng = SystemRandom()
 
 TRANSCRIPT = "compact"
+
+
+class _Field:
+    """what Protocol 8 knows of its scalar field: the order, the device vector class (ScalarVector / BnScalarVector;
+    its BN is the `bn=` of the Context's cs_* methods) and the tag of a circuit's digest"""
+
+    def __init__(self, order, vector, circuit_tag):
+        self.order, self.vector, self.bn, self.circuit_tag = order, vector, vector.BN, circuit_tag
+
+    def residue(self, v):
+        """int, own or foreign field element -> canonical residue (pivot._residue, with this field's order)"""
+        return int(v.value if pivot._duck_field(v) and not isinstance(v, FiniteFieldElement) else v) % self.order
+
+    def residues(self, vals):
+        return sparse.residue_array([self.residue(v) for v in vals], self.order)
+
+
+_FIELDS = {ORDER: _Field(ORDER, ScalarVector, b"vmpc-ac20/p8/circuit/v1"),
+           BN256_ORDER: _Field(BN256_ORDER, BnScalarVector, b"vmpc-ac20/p8/circuit/bn256/v1")}
 
 
 class SparseCircuit:
@@ -39,16 +68,24 @@ class SparseCircuit:
     for str(circuit) (default: the hex SHA-256 of the canonical CSR bytes).
 
     m = 0 is allowed: f and g are then the constants r_a, r_b (the reference's lagrange_interp_ff of a one-point
-    vector) and z = x + [r_a, r_b, r_a r_b]."""
+    vector) and z = x + [r_a, r_b, r_a r_b].
 
-    def __init__(self, n_x, A, B, O=None, text=None):
+    order: the field the forms are canonicalised in and the device tables and kernels run over - the Ed25519 order
+    (default: today's object and digest) or the BN-256 order (the knowledge-of-exponent variant; the digest's tag then
+    says so)."""
+
+    def __init__(self, n_x, A, B, O=None, text=None, order=ORDER):
         self.n_x = int(n_x)
+        if int(order) not in _FIELDS:
+            raise ValueError("SparseCircuit: order is neither the Ed25519 nor the BN-256 group order")
+        self.order, self.field = int(order), _FIELDS[int(order)]
+        order = self.order
         m = len(A[0]) - 1
-        self.A = sparse.CanonicalCSR(A, self.n_x + m, ORDER, "SparseCircuit: A")
-        self.B = sparse.CanonicalCSR(B, self.n_x + m, ORDER, "SparseCircuit: B")
+        self.A = sparse.CanonicalCSR(A, self.n_x + m, order, "SparseCircuit: A")
+        self.B = sparse.CanonicalCSR(B, self.n_x + m, order, "SparseCircuit: B")
         if self.B.n_rows != m:
             raise ValueError("SparseCircuit: A and B must have one row per multiplication gate each")
-        self.O = sparse.CanonicalCSR(O if O is not None else ([0], [], [], []), self.n_x + m, ORDER, "SparseCircuit: O")
+        self.O = sparse.CanonicalCSR(O if O is not None else ([0], [], [], []), self.n_x + m, order, "SparseCircuit: O")
         self.m, self.n_out = m, self.O.n_rows
         for M, what in ((self.A, "A"), (self.B, "B")):
             bad = np.nonzero(M.col >= self.n_x + M.rows)[0]
@@ -56,8 +93,8 @@ class SparseCircuit:
                 e = bad[np.argmin(M.rows[bad])]
                 raise ValueError(f"SparseCircuit: row {int(M.rows[e])} of {what} reads gamma_{int(M.col[e]) - self.n_x}, "
                                  f"which is not an earlier gate")
-        self.digest = hashlib.sha256(b"vmpc-ac20/p8/circuit/v1" + b"".join(v.to_bytes(8, "little") for v in
-                                                                             (self.n_x, self.m, self.n_out)) +
+        self.digest = hashlib.sha256(self.field.circuit_tag + b"".join(v.to_bytes(8, "little") for v in
+                                                                       (self.n_x, self.m, self.n_out)) +
                                      b"".join(M.canonical_bytes() for M in (self.A, self.B, self.O))).digest()
         self.text = text if text is not None else self.digest.hex()
         # depth of each multiplication gate and the gates grouped by depth: dependencies point backwards, so one pass
@@ -102,7 +139,7 @@ class SparseCircuit:
         return list(x) + [0] * self.padding(len(x))
 
     @classmethod
-    def from_circuit(cls, circuit):
+    def from_circuit(cls, circuit, order=ORDER):
         """From a circuit_builder.Circuit (duck-typed), by the rules of construct_affine_form
         (circuit_builder.py:417-498), each add / scalar-mul gate expanded once."""
         n = circuit.input_ct
@@ -162,7 +199,7 @@ class SparseCircuit:
         muls = circuit.mul_gates()
         raw = {"A": [var_form(g.inputs[0]) for g in muls], "B": [var_form(g.inputs[1]) for g in muls],
                "O": [forms[id(circuit.gates[ix])] for ix in circuit.output_gates]}
-        sc = cls(n, csr(raw["A"]), csr(raw["B"]), csr(raw["O"]), text=str(circuit))
+        sc = cls(n, csr(raw["A"]), csr(raw["B"]), csr(raw["O"]), text=str(circuit), order=order)
         sc._raw = raw
         return sc
 
@@ -182,18 +219,18 @@ class SparseCircuit:
     # ---- device state, made once ------------------------------------------------------------------------------------
     def device(self):
         if self._dev is None:
-            ctx = get_context()
-            d = {"ctx": ctx, "A": sparse.DeviceMatrix(ctx, self.A), "B": sparse.DeviceMatrix(ctx, self.B),
-                 "O": sparse.DeviceMatrix(ctx, self.O), "order": ctx.upload(self.level_order) if self.m else ctx.alloc(4)}
+            ctx, V = get_context(), self.field.vector
+            d = {"ctx": ctx, "A": sparse.DeviceMatrix(ctx, self.A, V), "B": sparse.DeviceMatrix(ctx, self.B, V),
+                 "O": sparse.DeviceMatrix(ctx, self.O, V), "order": ctx.upload(self.level_order) if self.m else ctx.alloc(4)}
             K = 2 * self.m + 1
-            d["fact"], d["ifact"] = ScalarVector.empty(K + 1, ctx), ScalarVector.empty(K + 1, ctx)
-            ctx.cs_tables(K, d["fact"].ptr, d["ifact"].ptr)
+            d["fact"], d["ifact"] = V.empty(K + 1, ctx), V.empty(K + 1, ctx)
+            ctx.cs_tables(K, d["fact"].ptr, d["ifact"].ptr, bn=self.field.bn)
             self._dev = d
         return self._dev
 
 
-def as_sparse(circuit):
-    return circuit if isinstance(circuit, SparseCircuit) else SparseCircuit.from_circuit(circuit)
+def as_sparse(circuit, order=ORDER):
+    return circuit if isinstance(circuit, SparseCircuit) else SparseCircuit.from_circuit(circuit, order)
 
 
 # ---- transcript ------------------------------------------------------------------------------------------------------------
@@ -201,8 +238,79 @@ def _mode(transcript):
     return compressed_pivot.transcript_mode(transcript, TRANSCRIPT)
 
 
+class _Pedersen:
+    """z is committed to by an Ed25519 vector commitment [z] = gamma h + sum_i z_i g_i; L is opened by the compressed
+    or the plain pivot"""
+    order = ORDER
+    first_tag, second_tag = b"vmpc-ac20/p8/first/v1", b"vmpc-ac20/p8/second/v1"
+
+    @staticmethod
+    def commit(generators, z, gamma):
+        return pivot.vector_commitment(z, gamma, generators["g"], generators["h"])
+
+    @staticmethod
+    def commitment_bytes(z_commitment):
+        return wire.compress_point(z_commitment)
+
+
+class _Koe:
+    """z is committed to by the restriction argument over a pp: (P, pi), one G1 and one G2 MSM
+    (knowledge_of_exponent.restriction_argument_prover); L is opened by the knowledge-of-exponent pivot.  N = len(z)
+    needs 2N points on either side of the pp, the reference's assertion (knowledge_of_exponent.py:109,128)."""
+    order = BN256_ORDER
+    first_tag, second_tag = b"vmpc-ac20/p8-koe/first/v1", b"vmpc-ac20/p8-koe/second/v1"
+
+    @staticmethod
+    def commit(generators, z, gamma):
+        N = len(z)
+        assert 2 * N - 1 <= len(generators["pp_lhs"]), \
+            "Requirement does not hold: 2*len(x)-1 <= number of generators in first group."
+        assert len(generators["pp_lhs"]) == 2 * N
+        P, pi = koe.restriction_argument_prover(range(N), z, gamma, generators)
+        return {"P": P, "pi": pi}
+
+    @staticmethod
+    def commitment_bytes(z_commitment):
+        return z_commitment["P"].to_bytes() + z_commitment["pi"].to_bytes()
+
+
+_KOE_REFERENCE_TRANSCRIPT = (
+    "Protocol 8 with a knowledge-of-exponent pp: only the compact transcript is built.  The reference's own prover "
+    "hashes the dict z_commitment where its verifier hashes the list [P, pi, ..] (circuit_sat_cb.py:107 against "
+    ":189-194), so its two sides do not agree on the first challenge, and MPyC's repr of a BN-256 point - the text both "
+    "would hash - is not pinned anywhere in this package")
+
+
+def _scheme_of_commitment(z_commitment):
+    return _Koe if isinstance(z_commitment, dict) else _Pedersen
+
+
+def _scheme_of_generators(generators, circuit, gf):
+    """the reference's dispatch (circuit_sat_cb.py:65-72): a pp selects the knowledge-of-exponent variant.  The field
+    of gf and of the circuit must be the scheme's."""
+    if "pp_lhs" in generators:
+        scheme = _Koe
+    elif "g" in generators:
+        scheme = _Pedersen
+    else:
+        raise NotImplementedError("Protocol 8 over a SparseCircuit: generators are neither {'g', 'h', ..} nor a "
+                                  "knowledge-of-exponent pp over BN-256")
+    _check_field(scheme, circuit, gf)
+    return scheme
+
+
+def _check_field(scheme, circuit, gf):
+    what = "the knowledge-of-exponent pp (BN-256)" if scheme is _Koe else "Ed25519 generators"
+    if gf.order != scheme.order:
+        raise ValueError(f"Protocol 8: gf.order is not the group order of {what}")
+    if circuit.order != scheme.order:
+        raise ValueError(f"Protocol 8: the circuit's order is not the group order of {what}: build the SparseCircuit "
+                         f"with order=")
+
+
 def _first_digest(z_commitment, circuit, n_in):
-    return hashlib.sha256(b"vmpc-ac20/p8/first/v1" + wire.compress_point(z_commitment) + circuit.digest +
+    scheme = _scheme_of_commitment(z_commitment)
+    return hashlib.sha256(scheme.first_tag + scheme.commitment_bytes(z_commitment) + circuit.digest +
                           n_in.to_bytes(8, "little")).digest()
 
 
@@ -211,8 +319,8 @@ def first_challenge(digest, order):
     return int.from_bytes(digest, "little") % order
 
 
-def _second_challenge(digest, ys, outputs, order):
-    h = hashlib.sha256(b"vmpc-ac20/p8/second/v1" + digest)
+def _second_challenge(digest, ys, outputs, order, tag=_Pedersen.second_tag):
+    h = hashlib.sha256(tag + digest)
     h.update(b"".join((int(v) % order).to_bytes(32, "little") for v in ys))
     h.update(len(outputs).to_bytes(4, "little") + b"".join((int(v) % order).to_bytes(32, "little") for v in outputs))
     return int.from_bytes(h.digest(), "little") % order
@@ -237,24 +345,25 @@ class _Forms:
         waits here; the caller sets self.k once it has read them (the batch prover reads all witnesses' at once)"""
         d = circuit.device()
         ctx, m = d["ctx"], circuit.m
+        assert order == circuit.order
         self.circuit, self.n_in, self.N, self.order, self.ctx = circuit, n_in, n_in + 3 + 2 * m, order, ctx
-        N = self.N
-        self.lam = ScalarVector.empty(m + 1, ctx)               # nodes 0..m
-        ctx.cs_lagrange(c, m, d["ifact"].ptr, self.lam.ptr)
-        self.H = ScalarVector.empty(N, ctx)                      # zeros, then the vector of the nodes 0..2m
+        N, Vec, bn = self.N, circuit.field.vector, circuit.field.bn
+        self.lam = Vec.empty(m + 1, ctx)                         # nodes 0..m
+        ctx.cs_lagrange(c, m, d["ifact"].ptr, self.lam.ptr, bn=bn)
+        self.H = Vec.empty(N, ctx)                               # zeros, then the vector of the nodes 0..2m
         ctx.upload_into(self.H.ptr, np.zeros((n_in + 2, 32), np.uint8))
-        ctx.cs_lagrange(c, 2 * m, d["ifact"].ptr, self.H.ptr + 32 * (n_in + 2))
-        self.F, self.G = ScalarVector.empty(N, ctx), ScalarVector.empty(N, ctx)
+        ctx.cs_lagrange(c, 2 * m, d["ifact"].ptr, self.H.ptr + 32 * (n_in + 2), bn=bn)
+        self.F, self.G = Vec.empty(N, ctx), Vec.empty(N, ctx)
         self.k = []
         for wire_ix, (M, V) in enumerate(((d["A"], self.F), (d["B"], self.G))):
             M.weighted_columns(self.lam.ptr + 32, circuit.n_x, n_in, V.ptr, N)
             ctx.copy(V.ptr + 32 * (n_in + wire_ix), self.lam.ptr, 32)
             if k_out is None:
-                self.k.append(ctx.fr_dot(self.lam.ptr + 32, M.consts.ptr, m) if m else 0)
+                self.k.append(self.lam[1:].dot(M.consts) if m else 0)
             else:
                 self.k.append(None)
                 if m:
-                    ctx.fr_dot_into(self.lam.ptr + 32, M.consts.ptr, m, k_out + 32 * wire_ix)
+                    ctx.fr_dot_into(self.lam.ptr + 32, M.consts.ptr, m, k_out + 32 * wire_ix, bn=bn)
         self.k.append(0)
 
     def values(self, z):
@@ -265,8 +374,9 @@ class _Forms:
         circuit, order = self.circuit, self.order
         n_out = circuit.n_out
         pw = [pow(rho, k, order) for k in range(n_out + 3)]
-        co = ScalarVector.empty(self.N, self.ctx)
-        wts = ScalarVector.from_ints(pw[:n_out], self.ctx)
+        Vec = circuit.field.vector
+        co = Vec.empty(self.N, self.ctx)
+        wts = Vec.from_ints(pw[:n_out], self.ctx)
         circuit.device()["O"].weighted_columns(wts.ptr, circuit.n_x, self.n_in, co.ptr, self.N)
         const = sum(p * (k - int(o)) for p, k, o in zip(pw, circuit.O.const_ints(), outputs))
         for V, k, y, p in zip((self.F, self.G, self.H), self.k, ys, pw[n_out:]):
@@ -279,31 +389,33 @@ def _witness_on_device(circuit, x, order, gamma_witness=None):
     """z = (x, f(0), g(0), h(0), h(1..2m)) as a device vector; draws r_a, r_b from `prng`"""
     n_in, m, n_x = len(x), circuit.m, circuit.n_x
     d = circuit.device()
-    ctx = d["ctx"]
+    ctx, F = d["ctx"], circuit.field
+    assert order == F.order
     N = n_in + 3 + 2 * m
-    z = ScalarVector.empty(N, ctx)
-    ctx.upload_into(z.ptr, sparse.residue_array([pivot._residue(v) for v in x], ORDER))
+    z = F.vector.empty(N, ctx)
+    ctx.upload_into(z.ptr, F.residues(x))
     r_a = prng.randrange(1, order)
     r_b = prng.randrange(1, order)
-    a, b = ScalarVector.empty(m + 1, ctx), ScalarVector.empty(m + 1, ctx)
-    ctx.upload_into(a.ptr + 32 * m, sparse.residue_array([r_a], ORDER))
-    ctx.upload_into(b.ptr + 32 * m, sparse.residue_array([r_b], ORDER))
+    a, b = F.vector.empty(m + 1, ctx), F.vector.empty(m + 1, ctx)
+    ctx.upload_into(a.ptr + 32 * m, F.residues([r_a]))
+    ctx.upload_into(b.ptr + 32 * m, F.residues([r_b]))
     g_off = n_in + 3
     if gamma_witness is not None:
         if len(gamma_witness) != m:
             raise ValueError(f"gamma_witness: {m} gate outputs expected")
         if m:
-            ctx.upload_into(z.ptr + 32 * g_off, sparse.residue_array([pivot._residue(v) for v in gamma_witness], ORDER))
+            ctx.upload_into(z.ptr + 32 * g_off, F.residues(gamma_witness))
             bad = ctx.alloc(4)
-            ctx.cs_triples(d["A"].csr(), d["B"].csr(), None, m, n_x, g_off, z.ptr, a.ptr, b.ptr, 1, bad.ptr)
+            ctx.cs_triples(d["A"].csr(), d["B"].csr(), None, m, n_x, g_off, z.ptr, a.ptr, b.ptr, 1, bad.ptr, bn=F.bn)
             first = int(ctx.download(bad.ptr, 4).view(np.uint32)[0])
             if first != 0xFFFFFFFF:
                 raise ValueError(f"gamma_witness: multiplication gate {first} is not the product of its wires")
     else:
         for lv in range(len(circuit.level_ptr) - 1):
             lo, hi = int(circuit.level_ptr[lv]), int(circuit.level_ptr[lv + 1])
-            ctx.cs_triples(d["A"].csr(), d["B"].csr(), d["order"].ptr + 4 * lo, hi - lo, n_x, g_off, z.ptr, a.ptr, b.ptr)
-    ctx.cs_extend(a.ptr, b.ptr, m, d["fact"].ptr, d["ifact"].ptr, z.ptr + 32 * n_in)
+            ctx.cs_triples(d["A"].csr(), d["B"].csr(), d["order"].ptr + 4 * lo, hi - lo, n_x, g_off, z.ptr, a.ptr, b.ptr,
+                           bn=F.bn)
+    ctx.cs_extend(a.ptr, b.ptr, m, d["fact"].ptr, d["ifact"].ptr, z.ptr + 32 * n_in, bn=F.bn)
     return z
 
 
@@ -417,13 +529,14 @@ def protocol_8_excl_pivot_prover(generators, circuit, x, gf, use_koe=False, gamm
     order: r_a, r_b, then gamma.  gamma_witness: the gate outputs, if the caller has them - they are checked (one
     launch) instead of computed (one launch per depth level)."""
     mode = _mode(transcript)
-    if use_koe or "g" not in generators:
+    if use_koe and "pp_lhs" not in generators:
         raise NotImplementedError("Protocol 8 over a SparseCircuit: the knowledge-of-exponent variant lives in another "
-                                  "field (BN-256) and is not built")
-    circuit = as_sparse(circuit)
-    g, h = generators["g"], generators["h"]
-    order = gf.order
-    assert order == ORDER
+                                  "field (BN-256) and takes a pp (knowledge_of_exponent.trusted_setup) as generators")
+    circuit = as_sparse(circuit, _Koe.order if "pp_lhs" in generators else ORDER)
+    scheme = _scheme_of_generators(generators, circuit, gf)
+    if scheme is _Koe and mode == "reference":
+        raise NotImplementedError(_KOE_REFERENCE_TRANSCRIPT)
+    order, F = gf.order, circuit.field
     n_in, m, n_x = len(x), circuit.m, circuit.n_x
     if n_in < n_x:
         raise ValueError(f"the circuit has {n_x} inputs, {n_in} given")
@@ -434,7 +547,7 @@ def protocol_8_excl_pivot_prover(generators, circuit, x, gf, use_koe=False, gamm
         return _reference_prover(generators, circuit, x, z, gf)
 
     gamma = prng.randrange(1, order)
-    z_commitment = pivot.vector_commitment(z, gamma, g, h)
+    z_commitment = scheme.commit(generators, z, gamma)
     proof = {"z_commitment": z_commitment}
     digest = _first_digest(z_commitment, circuit, n_in)
     c = first_challenge(digest, order)
@@ -446,11 +559,11 @@ def protocol_8_excl_pivot_prover(generators, circuit, x, gf, use_koe=False, gamm
     proof["y1"], proof["y2"], proof["y3"] = y1, y2, y3
     outputs = []
     if circuit.n_out:
-        o1 = ScalarVector.empty(circuit.n_out, ctx)      # the kernel's two row sets are both O: one buffer takes both
-        ctx.cs_triples(d["O"].csr(), d["O"].csr(), None, circuit.n_out, n_x, g_off, z.ptr, o1.ptr, o1.ptr, 2)
+        o1 = F.vector.empty(circuit.n_out, ctx)          # the kernel's two row sets are both O: one buffer takes both
+        ctx.cs_triples(d["O"].csr(), d["O"].csr(), None, circuit.n_out, n_x, g_off, z.ptr, o1.ptr, o1.ptr, 2, bn=F.bn)
         outputs = [gf(v) for v in o1.to_ints()]
     proof["outputs"] = outputs
-    rho = _second_challenge(digest, (y1, y2, y3), outputs, order)
+    rho = _second_challenge(digest, (y1, y2, y3), outputs, order, scheme.second_tag)
     L = forms.combine(rho, (y1, y2, y3), outputs, gf)
     proof["L"] = L
     return proof, z_commitment, L, z, gamma
@@ -459,9 +572,14 @@ def protocol_8_excl_pivot_prover(generators, circuit, x, gf, use_koe=False, gamm
 def protocol_8_excl_pivot_verifier(proof, circuit, gf, use_koe=False, transcript=None):
     """circuit_sat_cb.py:169-252: (verification, L); O(nnz + N), nothing quadratic"""
     mode = _mode(transcript)
-    if use_koe or isinstance(proof.get("z_commitment"), dict):
-        raise NotImplementedError("Protocol 8 over a SparseCircuit: the knowledge-of-exponent variant is not built")
-    circuit = as_sparse(circuit)
+    scheme = _scheme_of_commitment(proof.get("z_commitment"))
+    if use_koe and scheme is not _Koe:
+        raise NotImplementedError("Protocol 8 over a SparseCircuit: a knowledge-of-exponent proof carries "
+                                  "z_commitment = {'P', 'pi'} over BN-256")
+    if scheme is _Koe and mode == "reference":
+        raise NotImplementedError(_KOE_REFERENCE_TRANSCRIPT)
+    circuit = as_sparse(circuit, scheme.order)
+    _check_field(scheme, circuit, gf)
     order = gf.order
     verification = {}
     y1, y2, y3 = (int(proof[k]) % order for k in ("y1", "y2", "y3"))
@@ -483,11 +601,13 @@ def protocol_8_excl_pivot_verifier(proof, circuit, gf, use_koe=False, transcript
         verification["L_wellformed_from_Cfgh_forms"] = False
         return verification, None
     forms = _Forms(circuit, n_in, c, order)
-    rho = _second_challenge(digest, (y1, y2, y3), outputs, order)
+    rho = _second_challenge(digest, (y1, y2, y3), outputs, order, scheme.second_tag)
     L = forms.combine(rho, (y1, y2, y3), outputs, gf)
-    theirs = proof["L"]
+    theirs, F = proof["L"], circuit.field
+    their_coeffs = theirs.coeffs if isinstance(theirs.coeffs, F.vector) else \
+        F.vector.from_ints([F.residue(v) for v in theirs.coeffs], forms.ctx)
     same = int(theirs.constant) % order == int(L.constant) % order and \
-        forms.ctx.cs_first_diff(L.coeffs.ptr, pivot._as_device(theirs.coeffs).ptr, N) is None
+        forms.ctx.cs_first_diff(L.coeffs.ptr, their_coeffs.ptr, N, bn=F.bn) is None
     verification["L_wellformed_from_Cfgh_forms"] = bool(same)
     return verification, L
 
@@ -496,17 +616,30 @@ def _choice(pivot_choice):
     return getattr(pivot_choice, "name", pivot_choice)
 
 
+def _check_choice(choice, has_pp):
+    """the pivot and the generators go together: koe with a pp over BN-256, the other two with Ed25519 generators"""
+    if choice not in ("compressed", "pivot", "koe"):
+        raise NotImplementedError
+    if choice == "koe" and not has_pp:
+        raise NotImplementedError("PivotChoice.koe over a SparseCircuit: the knowledge-of-exponent pivot lives in "
+                                  "another field (BN-256) and takes a pp (knowledge_of_exponent.trusted_setup), a "
+                                  "circuit of that order and GF(that order); these generators are Ed25519's")
+    if choice != "koe" and has_pp:
+        raise ValueError(f"PivotChoice.{choice} with a knowledge-of-exponent pp: a pp goes with PivotChoice.koe")
+
+
 def circuit_sat_prover(generators, circuit, x, gf, pivot_choice="compressed", gamma_witness=None, transcript=None):
     """circuit_sat_cb.py:255-282 for a SparseCircuit, wholly in this package"""
     choice = _choice(pivot_choice)
-    if choice == "koe":
-        raise NotImplementedError("PivotChoice.koe over a SparseCircuit: the knowledge-of-exponent pivot lives in "
-                                  "another field (BN-256); Protocol 8 is built over the Ed25519 scalar field")
-    if choice not in ("compressed", "pivot"):
-        raise NotImplementedError
+    _check_choice(choice, "pp_lhs" in generators)
     mode = _mode(transcript)
     proof, z_commitment, L, z, gamma = protocol_8_excl_pivot_prover(generators, circuit, x, gf,
                                                                     gamma_witness=gamma_witness, transcript=mode)
+    if choice == "koe":
+        # L(z) = 0 is the opening's own coefficient N: nothing is evaluated here, z and L stay on the device
+        proof["pivot_proof"] = koe.opening_linear_form_prover(L, z, gamma, generators, z_commitment["P"],
+                                                              z_commitment["pi"])[0]
+        return proof
     y = L(z)
     if choice == "compressed":
         r = compressed_pivot.masks(len(z), L.coeffs.ctx) if isinstance(z, ScalarVector) and \
@@ -524,13 +657,26 @@ def circuit_sat_prover(generators, circuit, x, gf, pivot_choice="compressed", ga
 def circuit_sat_verifier(proof, generators, circuit, gf, pivot_choice="compressed", transcript=None):
     """circuit_sat_cb.py:285-318 for a SparseCircuit: the verification dict"""
     choice = _choice(pivot_choice)
-    if choice == "koe":
-        raise NotImplementedError("PivotChoice.koe over a SparseCircuit is not built")
-    if choice not in ("compressed", "pivot"):
-        raise NotImplementedError
+    _check_choice(choice, "pp_lhs" in generators)
     mode = _mode(transcript)
+    if (choice == "koe") != isinstance(proof.get("z_commitment"), dict):
+        raise ValueError("circuit_sat_verifier: a knowledge-of-exponent proof (z_commitment = {'P', 'pi'}) goes with "
+                         "PivotChoice.koe and a pp, any other proof with Ed25519 generators")
     verification, L = protocol_8_excl_pivot_verifier(proof, circuit, gf, transcript=mode)
     if L is None:
+        return verification
+    if choice == "koe":
+        # a proof whose L is not the forms' combination is rejected already: the opening (two MSMs, five Miller loops)
+        # is not run against the verifier's own L, and every key that is False names what was wrong
+        if not verification["L_wellformed_from_Cfgh_forms"]:
+            return verification
+        # the opening is checked on the (P, pi) that the first challenge was drawn from: a pivot proof that names
+        # other points than the commitment fails the restriction check
+        zc, pp_proof = proof["z_commitment"], proof["pivot_proof"]
+        bound = all(pp_proof[k].to_bytes() == zc[k].to_bytes() for k in ("P", "pi"))
+        ok = koe.opening_linear_form_verifier(L, generators, {"P": zc["P"], "pi": zc["pi"], "Q": pp_proof["Q"]}, 0)
+        ok["restriction_arg_check"] = bool(ok["restriction_arg_check"] and bound)
+        verification["pivot_verification"] = ok
         return verification
     if choice == "compressed":
         ok = compressed_pivot.protocol_5_verifier(generators, proof["z_commitment"], L, gf(0), proof["pivot_proof"], gf,

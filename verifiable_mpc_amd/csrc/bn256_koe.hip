@@ -9,6 +9,9 @@
 //                    vmpc_ctx_set_poly_product - off by default.)
 //   k_frbn_powers    scale * z^(i+1): the exponents of the trusted setup (knowledge_of_exponent.py:52-66 reaches them by
 //                    2n sequential scalar multiplications of a point).
+//   k_koe_stage      the product's operands (gamma, x) and L reversed from a witness and a form in device memory, and
+//   k_koe_split      c[n] out of the product and zeroed in place: the opening of Protocol 8's L over BN-256 never
+//                    passes z or L through the host.
 //
 // Product kernel: the output-stationary tile of csrc/fr_conv.h over one SEGMENT of the index i of a.  The triangle
 // (tiles near k = n meet the whole of a, tiles at the ends almost nothing) is balanced by the segments: a tile is cut
@@ -190,6 +193,59 @@ extern "C" int vmpc_bn256_fr_poly_mul_batch_dev(vmpc_ctx *ctx, const void *a, si
     if (!ctx || !a || !b || !out || na == 0 || nb == 0) return VMPC_E_INVAL;
     if (n_wit == 0 || k_cnt == 0) return VMPC_OK;
     return koe_poly_mul(ctx, a, a_stride, na, b, b_stride, nb, k_lo, k_cnt, out, out_stride, n_wit);
+}
+
+// ---- the opening's operands and result, device to device ----------------------------------------------------------------
+// lhs = (gamma, x_0, .., x_{n-1}) and rhs = (L_{n-1}, .., L_0): the two polynomials of knowledge_of_exponent.py:116-123
+// from a witness and a form that are already in device memory.  Thread i < n writes lhs[i + 1] and rhs[n - 1 - i], thread
+// n writes lhs[0]; either output may be left out (the verifier wants the reversed form only).
+struct koe_scalar_arg {
+    uint32_t v[8];
+};
+__global__ void __launch_bounds__(256)
+k_koe_stage(const uint32_t *__restrict__ x, koe_scalar_arg gamma, const uint32_t *__restrict__ L, size_t n,
+            uint32_t *__restrict__ lhs, uint32_t *__restrict__ rhs) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        if (lhs) f256_st(lhs, (long long)i + 1, f256_ld<frbn>(x, (long long)i));
+        if (rhs) f256_st(rhs, (long long)(n - 1 - i), f256_ld<frbn>(L, (long long)i));
+    } else if (i == n && lhs) {
+        f256_st(lhs, 0, f256_copy<frbn>(gamma.v));
+    }
+}
+
+// u[0] = c[n], then c[n] = 0: the opened value leaves the product and the MSM over the 2n generators skips its place
+// (knowledge_of_exponent.py:124-130)
+__global__ void k_koe_split(uint32_t *__restrict__ c, size_t n, uint32_t *__restrict__ u) {
+    f256_st(u, 0, f256_ld<frbn>(c, (long long)n));
+    f256_st(c, (long long)n, frbn_zero());
+}
+
+extern "C" int vmpc_bn256_koe_stage_dev(vmpc_ctx *ctx, const void *x, const uint8_t gamma[32], const void *L, size_t n,
+                                        void *lhs, void *rhs) {
+    if (n > VMPC_BN256_FR_POLY_MAX - 1) return VMPC_E_RANGE;
+    if (!ctx || (!lhs && !rhs) || (lhs && (!gamma || (n && !x))) || (rhs && n && !L)) return VMPC_E_INVAL;
+    koe_scalar_arg g = {};
+    if (lhs) {
+        memcpy(g.v, gamma, 32);
+        if (!f256_is_canonical<frbn>(g.v)) return VMPC_E_NONCANON;
+    }
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope s(ctx, "bn_koe_stage");
+    k_koe_stage<<<(unsigned)((n + 1 + 255) / 256), 256, 0, ctx->stream>>>((const uint32_t *)x, g, (const uint32_t *)L, n,
+                                                                         (uint32_t *)lhs, (uint32_t *)rhs);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_bn256_koe_split_dev(vmpc_ctx *ctx, void *c, size_t n, void *u_out) {
+    if (n > VMPC_BN256_FR_POLY_MAX - 1) return VMPC_E_RANGE;
+    if (!ctx || !c || !u_out || n == 0) return VMPC_E_INVAL;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope s(ctx, "bn_koe_split");
+    k_koe_split<<<1, 1, 0, ctx->stream>>>((uint32_t *)c, n, (uint32_t *)u_out);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
 }
 
 extern "C" int vmpc_bn256_fr_powers_dev(vmpc_ctx *ctx, const void *z, const void *scale, size_t count, void *out) {

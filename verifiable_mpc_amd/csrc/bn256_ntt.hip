@@ -404,6 +404,13 @@ int vmpc_ntt_fr_rows_mul(vmpc_ctx *ctx, const vmpc_ntt_plan &p, const vmpc_ntt_s
     return ntt_poly_mul_in<fr>(ctx, p, st, rb, ra, a, a_stride, na, b, 0, nb, k_lo, k_cnt, out, out_stride, rows);
 }
 
+// the same window reduced mod n, the BN-256 order: the extension of Protocol 8 over GF(n) (cs_extend<frbn>)
+int vmpc_ntt_frbn_rows_mul(vmpc_ctx *ctx, const vmpc_ntt_plan &p, const vmpc_ntt_stages &st, uint32_t *rb, uint32_t *ra,
+                           const void *a, size_t a_stride, size_t na, size_t rows, const void *b, size_t nb, size_t k_lo,
+                           size_t k_cnt, void *out, size_t out_stride) {
+    return ntt_poly_mul_in<frbn>(ctx, p, st, rb, ra, a, a_stride, na, b, 0, nb, k_lo, k_cnt, out, out_stride, rows);
+}
+
 size_t vmpc_ntt_arena_cap(const vmpc_ctx *ctx) {
     return ctx ? (ctx->ntt_arena_cap ? ctx->ntt_arena_cap : NTT_ARENA_MAX) : NTT_ARENA_MAX;
 }

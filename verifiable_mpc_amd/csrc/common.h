@@ -154,6 +154,10 @@ vmpc_ntt_plan vmpc_ntt_plan_at(int log_l, bool shared_b, size_t n_wit, size_t ca
 int vmpc_ntt_fr_rows_mul(vmpc_ctx *ctx, const vmpc_ntt_plan &p, const vmpc_ntt_stages &st, uint32_t *rb, uint32_t *ra,
                          const void *a, size_t a_stride, size_t na, size_t rows, const void *b, size_t nb, size_t k_lo,
                          size_t k_cnt, void *out, size_t out_stride);
+// the same window reduced mod n, the BN-256 order (cs_extend<frbn>)
+int vmpc_ntt_frbn_rows_mul(vmpc_ctx *ctx, const vmpc_ntt_plan &p, const vmpc_ntt_stages &st, uint32_t *rb, uint32_t *ra,
+                           const void *a, size_t a_stride, size_t na, size_t rows, const void *b, size_t nb, size_t k_lo,
+                           size_t k_cnt, void *out, size_t out_stride);
 
 // what csrc/bn256_qap_mtree.hip needs of it besides: the arena cap in force, the arena of vmpc_ntt_poly_mul under a cap,
 // and one level of a subproduct tree (all its nodes and rows in one launch sequence) with its arena

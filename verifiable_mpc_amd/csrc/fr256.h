@@ -45,6 +45,17 @@ VMPC_HD bool f256_equal(const F &a, const F &b) {
     return o == 0;
 }
 
+// a < modulus ?  (what an entry asks of a 32-byte scalar ARGUMENT before it answers VMPC_E_NONCANON)
+template <class F>
+VMPC_HD bool f256_is_canonical(const uint32_t a[8]) {
+    const typename F::P p{};
+    for (int i = 7; i >= 0; i--) {
+        if (a[i] > p.m[i]) return false;
+        if (a[i] < p.m[i]) return true;
+    }
+    return false;
+}
+
 // r = a - m if a >= m, for a nine-limb a < 2m (a8: the ninth limb, 0 or 1)
 template <class F>
 VMPC_HD F f256_cond_sub(const F &a, uint32_t a8) {

@@ -7,6 +7,7 @@
 // 2048 workgroups with a grid-stride loop.
 #include "common.h"
 #include "fr.h"
+#include "fr_bn.h"
 
 #define FR_BLOCK 256
 #define FR_MAX_GRID 2048
@@ -29,17 +30,20 @@ __device__ __forceinline__ void frv_st(uint32_t *dst, const fr &a) {
     p[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
 }
 
+// axpy, dot and sum are templates on the field of csrc/fr256.h: fr here, frbn for the vmpc_bn256_fr_* entries at the end
+// (Protocol 8 over GF(n)), where a load reduces any 32-byte value (f256_ld)
+template <class F>
 __global__ void __launch_bounds__(FR_BLOCK)
 k_fr_axpy(fr_arg c, const uint32_t *__restrict__ x, const uint32_t *__restrict__ y, size_t n,
           uint32_t *__restrict__ out) {
-    fr cc;
+    F cc;
 #pragma unroll
     for (int i = 0; i < 8; i++) cc.v[i] = c.v[i];
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (size_t)gridDim.x * blockDim.x) {
-        fr r = fr_mul(cc, frv_ld(x + 8 * i));
-        if (y) r = fr_add(r, frv_ld(y + 8 * i));
-        frv_st(out + 8 * i, r);
+        F r = f256_mul(cc, f256_ld<F>(x, (long long)i));
+        if (y) r = f256_add(r, f256_ld<F>(y, (long long)i));
+        f256_st(out, (long long)i, r);
     }
 }
 
@@ -65,39 +69,39 @@ k_fr_axpy_tail(fr_arg c, const uint32_t *__restrict__ x, const uint32_t *__restr
     }
 }
 
+// the tree over a workgroup's FR_BLOCK partial sums in LDS; the total ends in lds[0..7]
+template <class F>
+__device__ __forceinline__ void frv_block_sum(uint32_t *lds, const F &acc) {
+    f256_st(lds, threadIdx.x, acc);
+    __syncthreads();
+    for (int stride = FR_BLOCK / 2; stride >= 1; stride >>= 1) {
+        if ((int)threadIdx.x < stride)
+            f256_st(lds, threadIdx.x, f256_add(f256_ld<F>(lds, threadIdx.x), f256_ld<F>(lds, threadIdx.x + stride)));
+        __syncthreads();
+    }
+}
+
+template <class F>
 __global__ void __launch_bounds__(FR_BLOCK)
 k_fr_dot(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, size_t n,
          uint32_t *__restrict__ partials) {
     __shared__ uint32_t lds[FR_BLOCK * 8];
-    fr acc = fr_zero();
+    F acc = f256_zero<F>();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (size_t)gridDim.x * blockDim.x)
-        acc = fr_add(acc, fr_mul(frv_ld(a + 8 * i), frv_ld(b + 8 * i)));
-    frv_st(lds + 8 * threadIdx.x, acc);
-    __syncthreads();
-    for (int stride = FR_BLOCK / 2; stride >= 1; stride >>= 1) {
-        if ((int)threadIdx.x < stride)
-            frv_st(lds + 8 * threadIdx.x,
-                   fr_add(frv_ld(lds + 8 * threadIdx.x), frv_ld(lds + 8 * (threadIdx.x + stride))));
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) frv_st(partials + 8 * blockIdx.x, frv_ld(lds));
+        acc = f256_add(acc, f256_mul(f256_ld<F>(a, (long long)i), f256_ld<F>(b, (long long)i)));
+    frv_block_sum<F>(lds, acc);
+    if (threadIdx.x == 0) f256_st(partials, blockIdx.x, f256_ld<F>(lds, 0));
 }
 
+template <class F>
 __global__ void __launch_bounds__(FR_BLOCK)
 k_fr_sum(const uint32_t *__restrict__ v, size_t n, uint32_t *__restrict__ out) {
     __shared__ uint32_t lds[FR_BLOCK * 8];
-    fr acc = fr_zero();
-    for (size_t i = threadIdx.x; i < n; i += blockDim.x) acc = fr_add(acc, frv_ld(v + 8 * i));
-    frv_st(lds + 8 * threadIdx.x, acc);
-    __syncthreads();
-    for (int stride = FR_BLOCK / 2; stride >= 1; stride >>= 1) {
-        if ((int)threadIdx.x < stride)
-            frv_st(lds + 8 * threadIdx.x,
-                   fr_add(frv_ld(lds + 8 * threadIdx.x), frv_ld(lds + 8 * (threadIdx.x + stride))));
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) frv_st(out, frv_ld(lds));
+    F acc = f256_zero<F>();
+    for (size_t i = threadIdx.x; i < n; i += blockDim.x) acc = f256_add(acc, f256_ld<F>(v, (long long)i));
+    frv_block_sum<F>(lds, acc);
+    if (threadIdx.x == 0) f256_st(out, 0, f256_ld<F>(lds, 0));
 }
 
 __global__ void __launch_bounds__(FR_BLOCK)
@@ -211,18 +215,37 @@ static int fr_arg_from(const uint8_t c[32], fr_arg &a) {
     return fr_geq_l(a.v) ? VMPC_E_NONCANON : VMPC_OK;
 }
 
-extern "C" int vmpc_fr_axpy_dev(vmpc_ctx *ctx, const uint8_t c[32], const void *x, const void *y,
-                                size_t n, void *out) {
+// out = c x + y over the field of F; c: a canonical residue of that field, else VMPC_E_NONCANON
+template <class F>
+static int frv_axpy(vmpc_ctx *ctx, const uint8_t c[32], const void *x, const void *y, size_t n, void *out) {
     if (!ctx || !c || (n && (!x || !out))) return VMPC_E_INVAL;
     if (n == 0) return VMPC_OK;
     fr_arg ca;
-    VMPC_CHECK(fr_arg_from(c, ca));
+    memcpy(ca.v, c, 32);
+    if (!f256_is_canonical<F>(ca.v)) return VMPC_E_NONCANON;
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     vmpc_stage_scope s(ctx, "fr_axpy");
-    k_fr_axpy<<<fr_grid(n), FR_BLOCK, 0, ctx->stream>>>(ca, (const uint32_t *)x, (const uint32_t *)y, n,
-                                                        (uint32_t *)out);
+    k_fr_axpy<F><<<fr_grid(n), FR_BLOCK, 0, ctx->stream>>>(ca, (const uint32_t *)x, (const uint32_t *)y, n,
+                                                           (uint32_t *)out);
     VMPC_KERNEL_CHECK();
     return VMPC_OK;
+}
+
+// <a, b> into out_dev (device, 32 bytes) through the caller's `partials` of fr_grid(n) scalars; n >= 1
+template <class F>
+static int frv_dot_launch(vmpc_ctx *ctx, const void *a, const void *b, size_t n, uint32_t *partials, void *out_dev) {
+    const unsigned g = fr_grid(n);
+    vmpc_stage_scope s(ctx, "fr_dot");
+    k_fr_dot<F><<<g, FR_BLOCK, 0, ctx->stream>>>((const uint32_t *)a, (const uint32_t *)b, n, partials);
+    VMPC_KERNEL_CHECK();
+    k_fr_sum<F><<<1, FR_BLOCK, 0, ctx->stream>>>(partials, g, (uint32_t *)out_dev);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_fr_axpy_dev(vmpc_ctx *ctx, const uint8_t c[32], const void *x, const void *y,
+                                size_t n, void *out) {
+    return frv_axpy<fr>(ctx, c, x, y, n, out);
 }
 
 extern "C" int vmpc_fr_axpy_tail_dev(vmpc_ctx *ctx, const uint8_t c[32], const void *x, const void *y, size_t n,
@@ -256,13 +279,7 @@ extern "C" int vmpc_fr_dot_dev(vmpc_ctx *ctx, const void *a, const void *b, size
     VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align((size_t)g * 32) + 256));
     uint32_t *partials = (uint32_t *)vmpc_ws_take(ctx, (size_t)g * 32);
     uint32_t *res = (uint32_t *)vmpc_ws_take(ctx, 32);
-    {
-        vmpc_stage_scope s(ctx, "fr_dot");
-        k_fr_dot<<<g, FR_BLOCK, 0, ctx->stream>>>((const uint32_t *)a, (const uint32_t *)b, n, partials);
-        VMPC_KERNEL_CHECK();
-        k_fr_sum<<<1, FR_BLOCK, 0, ctx->stream>>>(partials, g, res);
-        VMPC_KERNEL_CHECK();
-    }
+    VMPC_CHECK(frv_dot_launch<fr>(ctx, a, b, n, partials, res));
     VMPC_HIP_CHECK(hipMemcpyAsync(out, res, 32, hipMemcpyDeviceToHost, ctx->stream));
     VMPC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return VMPC_OK;
@@ -281,12 +298,27 @@ extern "C" int vmpc_fr_dot_to_dev(vmpc_ctx *ctx, const void *a, const void *b, s
     unsigned g = fr_grid(n);
     VMPC_CHECK(vmpc_ws_reserve(ctx, vmpc_align((size_t)g * 32) + 256));
     uint32_t *partials = (uint32_t *)vmpc_ws_take(ctx, (size_t)g * 32);
-    vmpc_stage_scope s(ctx, "fr_dot");
-    k_fr_dot<<<g, FR_BLOCK, 0, ctx->stream>>>((const uint32_t *)a, (const uint32_t *)b, n, partials);
-    VMPC_KERNEL_CHECK();
-    k_fr_sum<<<1, FR_BLOCK, 0, ctx->stream>>>(partials, g, (uint32_t *)out_dev);
-    VMPC_KERNEL_CHECK();
-    return VMPC_OK;
+    return frv_dot_launch<fr>(ctx, a, b, n, partials, out_dev);
+}
+
+// ---- GF(n), the BN-256 order: what Protocol 8's knowledge-of-exponent variant needs of the above --------------------
+extern "C" int vmpc_bn256_fr_axpy_dev(vmpc_ctx *ctx, const uint8_t c[32], const void *x, const void *y, size_t n,
+                                      void *out) {
+    return frv_axpy<frbn>(ctx, c, x, y, n, out);
+}
+
+// the partial sums of vmpc_bn256_fr_dot_to_dev: the caller's memory, not the arena
+extern "C" size_t vmpc_bn256_fr_dot_scratch_bytes(size_t n) { return n ? (size_t)fr_grid(n) * 32 : 0; }
+
+extern "C" int vmpc_bn256_fr_dot_to_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t n, void *out_dev,
+                                        void *scratch) {
+    if (!ctx || !out_dev || (n && (!a || !b || !scratch))) return VMPC_E_INVAL;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    if (n == 0) {
+        VMPC_HIP_CHECK(hipMemsetAsync(out_dev, 0, 32, ctx->stream));
+        return VMPC_OK;
+    }
+    return frv_dot_launch<frbn>(ctx, a, b, n, (uint32_t *)scratch, out_dev);
 }
 
 extern "C" int vmpc_fr_challenge_products_dev(vmpc_ctx *ctx, const uint8_t *challenges, int rounds,

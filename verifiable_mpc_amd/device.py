@@ -17,6 +17,8 @@ from . import _native, formats
 from .groups import ORDER, Ed25519Point, as_point
 
 _CTX = None
+# the order of the BN-256 groups (pynocchio.ORDER; that module imports this one)
+BN256_ORDER = 65000549695646603732796438742359905742570406053903786389881062969044166799969
 
 
 def get_context():
@@ -162,7 +164,11 @@ class DeviceScalar:
 
 
 class ScalarVector:
-    """n scalars mod l on the device."""
+    """n scalars mod l on the device.  ORDER and BN name the field: BnScalarVector below is the same vector over the
+    BN-256 scalar field, with the part of this interface that Protocol 8 uses."""
+
+    ORDER = ORDER
+    BN = False          # the `bn=` of the Context methods that exist for both fields
 
     def __init__(self, view, ctx=None):
         self.ctx = ctx or get_context()
@@ -171,7 +177,7 @@ class ScalarVector:
     @classmethod
     def from_ints(cls, values, ctx=None):
         ctx = ctx or get_context()
-        arr = _native.ints_to_array([reduce_scalar(v) for v in values], 32)
+        arr = _native.ints_to_array([int(v) % cls.ORDER for v in values], 32)
         return cls(_View(ctx.upload(arr), 0, len(values), 32), ctx)
 
     @classmethod
@@ -196,7 +202,7 @@ class ScalarVector:
     def __getitem__(self, key):
         if isinstance(key, slice):
             a, b = _slice_bounds(key, self.v.n)
-            return ScalarVector(self.v.sub(a, b), self.ctx)
+            return type(self)(self.v.sub(a, b), self.ctx)
         if key < 0:
             key += self.v.n
         raw = self.ctx.download(self.v.ptr + 32 * key, 32)
@@ -220,10 +226,10 @@ class ScalarVector:
 
     # ---- arithmetic (csrc/frvec.hip) ------------------------------------------------------
     def axpy(self, c, y):
-        """c * self + y  (element-wise, mod l)."""
+        """c * self + y  (element-wise, mod the field's order)."""
         assert len(y) == len(self)
-        out = ScalarVector.empty(len(self), self.ctx)
-        self.ctx.fr_axpy(reduce_scalar(c), self.ptr, y.ptr, len(self), out.ptr)
+        out = type(self).empty(len(self), self.ctx)
+        self.ctx.fr_axpy(int(c) % self.ORDER, self.ptr, y.ptr, len(self), out.ptr, bn=self.BN)
         return out
 
     def axpy_concat(self, c, y, tail):
@@ -281,6 +287,28 @@ class ScalarVector:
     def __repr__(self):
         body = self.text().tobytes().decode()
         return "[" + body[:-2] + "]"
+
+
+class BnScalarVector(ScalarVector):
+    """n scalars mod the BN-256 group order on the device: what Protocol 8 uses of ScalarVector (empty, from_ints,
+    from_array, to_ints, slices, axpy, dot, ptr, len) through the GF(n) entries.  Words >= the order are reduced when a
+    kernel loads them.  The Ed25519-only parts of ScalarVector (transcript text, the compressed pivot's tail forms) are
+    not offered."""
+
+    ORDER = BN256_ORDER
+    BN = True
+
+    def dot(self, other):
+        assert len(other) == len(self)
+        return self.ctx.bn256_fr_dot(self.ptr, other.ptr, len(self))
+
+    def _ed25519_only(self, *args, **kwargs):
+        raise NotImplementedError("BnScalarVector: an Ed25519-only operation of ScalarVector")
+
+    concat = __add__ = axpy_concat = scale = dot_dev = text_begin = text = text_chunks = _ed25519_only
+
+    def __repr__(self):
+        return f"<BnScalarVector of {len(self)} scalars>"
 
 
 # Measured at 2^20 generators with the round-context prover (5 rounds + one multi-round fold on this table, the

@@ -18,15 +18,18 @@ Points are written additively here (the reference switches its groups to multipl
 `k * g` here.  The verifier evaluates both checks as "product of pairings == 1" in ONE pairing_product launch; points
 not on their curve raise ValueError; G2 subgroup membership is not checked (as in pynocchio.verify).
 
-Not here: prove_nullity_koe (its challenge hashes repr() of an MPyC point), the circuit front end's koe branch
-(circuit_sat.create_generators keeps raising NotImplementedError for PivotChoice.koe) and the MPC setup.
+x and L's coefficients may be device vectors (device.BnScalarVector): the prover's operands, the split of the product
+and the verifier's reversed form are then made on the device (csrc/bn256_koe.hip), which is how Protocol 8 over a
+SparseCircuit of this order opens its L (circuit_sat_gpu.py).  Lists take the host path.
+
+Not here: prove_nullity_koe (its challenge hashes repr() of an MPyC point) and the MPC setup.
 """
 from random import SystemRandom
 
 import numpy as np
 
 from . import _native
-from .device import get_context
+from .device import BnScalarVector, get_context
 from .pynocchio import (ORDER, BN256Point, BN256TwistPoint, _as_bytes, _neg_g1_rows, _pairing_product_arrays,
                         scalars_to_array)
 
@@ -181,13 +184,35 @@ def _restriction_scalars(S, x, gamma):
     return scalars_to_array(sc)
 
 
+def _on_device(v):
+    """is v a device vector of scalars of this order (device.BnScalarVector)?"""
+    return isinstance(v, BnScalarVector)
+
+
+def _staged(ctx, x, gamma, L_coeffs):
+    """(lhs, rhs) device buffers: lhs = (gamma, x_0, .., x_{n-1}) from a device x (None: no lhs), rhs = (L_{n-1}, ..,
+    L_0) from device coefficients (None: no rhs) - csrc/bn256_koe.hip, nothing passes through the host"""
+    n = len(x) if x is not None else len(L_coeffs)
+    lhs = ctx.alloc(32 * (n + 1)) if x is not None else None
+    rhs = ctx.alloc(max(32, 32 * n)) if L_coeffs is not None else None
+    ptr = lambda v: v.ptr if v is not None else None      # noqa: E731
+    ctx.bn256_koe_stage(ptr(x), int(gamma) % ORDER if x is not None else None, ptr(L_coeffs), n, ptr(lhs), ptr(rhs))
+    return lhs, rhs
+
+
 def restriction_argument_prover(S, x, gamma, pp):
     """(P, pi): the commitment gamma pp_lhs[0] + sum_{i in S} x[i] pp_lhs[i+1] to the S-indices of x and the same sum
-    over pp_rhs (knowledge_of_exponent.py:75-95).  One G1 MSM and one G2 MSM."""
+    over pp_rhs (knowledge_of_exponent.py:75-95).  One G1 MSM and one G2 MSM.  x may be a device BnScalarVector when S
+    is all of it: the scalars (gamma, x) are then put together on the device."""
     ctx = get_context()
-    sc = _restriction_scalars(S, x, gamma)
-    ds = (ctx.upload(sc), len(sc))
-    return _side(ctx, pp, "pp_lhs", len(sc)).msm(ds), _side(ctx, pp, "pp_rhs", len(sc)).msm(ds)
+    if _on_device(x):
+        if not (isinstance(S, range) and S == range(len(x))):
+            raise ValueError("restriction_argument_prover: a device vector x is committed to as a whole, S = range(len(x))")
+        ds = (_staged(ctx, x, gamma, None)[0], len(x) + 1)
+    else:
+        sc = _restriction_scalars(S, x, gamma)
+        ds = (ctx.upload(sc), len(sc))
+    return _side(ctx, pp, "pp_lhs", ds[1]).msm(ds), _side(ctx, pp, "pp_rhs", ds[1]).msm(ds)
 
 
 def _proof_point(ctx, pt, group, name):
@@ -243,21 +268,37 @@ def opening_linear_form_prover(L, x, gamma, pp, P=None, pi=None):
     proof["P"] = P
     proof["pi"] = pi
 
-    coeffs, constant = _form_parts(L)
-    assert len(coeffs) == n, "Length of inputs to be equal to coefficients of linear form."
-    lhs = scalars_to_array([gamma] + list(x))
-    rhs = _reversed_coeffs(coeffs, n)
-    d_lhs, d_rhs, c_bar = ctx.upload(lhs), ctx.upload(rhs), ctx.alloc(32 * 2 * n)
-    ctx.bn256_fr_poly_mul(d_lhs.ptr, n + 1, d_rhs.ptr, n, c_bar.ptr)
-    ctx.sync()
-    u_linear = int.from_bytes(ctx.download(c_bar.ptr + 32 * n, 32).tobytes(), "little")
-    ctx.upload_into(c_bar.ptr + 32 * n, np.zeros(32, np.uint8))
+    on_device = _on_device(x) and _on_device(L.coeffs)
+    if on_device:
+        # z and L never pass through the host: the operands are put together, the product split and Q's scalars
+        # left where the MSM reads them (csrc/bn256_koe.hip); only u's 32 bytes come back, after the MSM has synchronised
+        coeffs, constant = L.coeffs, getattr(L, "constant", 0)
+        assert len(coeffs) == n, "Length of inputs to be equal to coefficients of linear form."
+        (d_lhs, d_rhs), c_bar, d_u = _staged(ctx, x, gamma, coeffs), ctx.alloc(32 * 2 * n), ctx.alloc(32)
+        ctx.bn256_fr_poly_mul(d_lhs.ptr, n + 1, d_rhs.ptr, n, c_bar.ptr)
+        ctx.bn256_koe_split(c_bar.ptr, n, d_u.ptr)
+    else:
+        if _on_device(x):
+            x = x.to_ints()
+        coeffs, constant = _form_parts(L)
+        assert len(coeffs) == n, "Length of inputs to be equal to coefficients of linear form."
+        lhs = scalars_to_array([gamma] + list(x))
+        rhs = _reversed_coeffs(coeffs, n)
+        d_lhs, d_rhs, c_bar = ctx.upload(lhs), ctx.upload(rhs), ctx.alloc(32 * 2 * n)
+        ctx.bn256_fr_poly_mul(d_lhs.ptr, n + 1, d_rhs.ptr, n, c_bar.ptr)
+        ctx.sync()
+        u_linear = int.from_bytes(ctx.download(c_bar.ptr + 32 * n, 32).tobytes(), "little")
+        ctx.upload_into(c_bar.ptr + 32 * n, np.zeros(32, np.uint8))
     assert n_lhs == 2 * n
     Q = _side(ctx, pp, "pp_lhs").msm((c_bar, 2 * n))
     if Q.coords is not None:
         Q = BN256Point((Q.coords[0], -Q.coords[1]))
     proof["Q"] = Q
-    sample = constant if hasattr(constant, "value") else (coeffs[0] if n else 0)
+    if on_device:
+        u_linear = int.from_bytes(ctx.download(d_u.ptr, 32).tobytes(), "little")
+        sample = constant
+    else:
+        sample = constant if hasattr(constant, "value") else (coeffs[0] if n else 0)
     u = _like(sample, (u_linear + int(constant)) % ORDER)
     return proof, u
 
@@ -267,14 +308,17 @@ def opening_linear_form_verifier(L, pp, proof, u):
     is one G2 MSM; then both checks in one pairing_product launch, five Miller loops and two final exponentiations:
         e(P, g2) e(-g1, pi) == 1      and      e(P, R) e(Q, g2) e(-g1, u pp_rhs[n]) == 1"""
     ctx = get_context()
-    coeffs, constant = _form_parts(L)
+    on_device = _on_device(L.coeffs)
+    coeffs, constant = (L.coeffs, getattr(L, "constant", 0)) if on_device else _form_parts(L)
     n = len(coeffs)
     lhs, rhs = _side(ctx, pp, "pp_lhs", 1), _side(ctx, pp, "pp_rhs", n + 1)
     if len(rhs) <= n:
         raise ValueError("pp_rhs holds fewer than len(L) + 1 points")
     u_linear = (int(u) - int(constant)) % ORDER
     rP, rpi, rQ = (_proof_point(ctx, proof[k], g, k) for k, g in (("P", 1), ("pi", 2), ("Q", 1)))
-    R = np.frombuffer(rhs.msm(_reversed_coeffs(coeffs, n)).to_bytes(), np.uint8)
+    # R's scalars: L's coefficients reversed - on the device when that is where they are
+    r_scalars = (_staged(ctx, None, None, coeffs)[1], n) if on_device else _reversed_coeffs(coeffs, n)
+    R = np.frombuffer(rhs.msm(r_scalars).to_bytes(), np.uint8)
     # u * pp_rhs[n]: the one-base case of the verifier's small linear combinations (csrc/bn256_pairing.hip)
     uT = ctx.alloc(128)
     ctx.bn256_lincomb_batch(2, rhs.buf.ptr + 128 * n, 1, ctx.upload(_scalar_bytes(u_linear)).ptr, None, 0, 1, False,

@@ -16,7 +16,8 @@ from .device import ScalarVector
 
 SEG = 64                    # entries per lane of the column sums (csrc/fr_colsum.h); longer columns are cut
 PARTIAL = 1 << 31           # an item's dst with this bit set is a partial sum of a long column (FR_COLSUM_PARTIAL)
-_COLSUM = {"bn256": "bn256_qap_colsum", "ed25519": "cs_colsum"}      # field -> the Context method of its entry point
+# field -> the Context method of its entry point ("bn256_cs": Protocol 8's forms over GF(n): out zeroed first, as "ed25519")
+_COLSUM = {"bn256": "bn256_qap_colsum", "ed25519": "cs_colsum", "bn256_cs": "bn256_cs_colsum"}
 
 
 def residue_array(vals, order):
@@ -167,17 +168,18 @@ class CanonicalCSR:
 
 
 class DeviceMatrix:
-    """a CanonicalCSR over GF(l) in HBM: CSR for the row evaluation, a ColumnPlan over its non-empty columns for the
-    transposed product"""
+    """a CanonicalCSR over GF(l) - or, vector=BnScalarVector, over GF(n) - in HBM: CSR for the row evaluation, a
+    ColumnPlan over its non-empty columns for the transposed product"""
 
-    def __init__(self, ctx, M):
+    def __init__(self, ctx, M, vector=ScalarVector):
         self.ctx, self.n_rows, self.nnz = ctx, M.n_rows, len(M.col)
         self.row_ptr = ctx.upload(M.row_ptr.astype(np.uint32))
         self.col = ctx.upload(M.col.astype(np.uint32)) if self.nnz else ctx.alloc(4)
         self.vals = ctx.upload(M.vals) if self.nnz else ctx.alloc(32)
-        self.consts = ScalarVector.from_array(M.consts, ctx) if M.n_rows else ScalarVector.empty(0, ctx)
+        self.consts = vector.from_array(M.consts, ctx) if M.n_rows else vector.empty(0, ctx)
         self.listed, compact = np.unique(M.col, return_inverse=True)
-        self.plan = ColumnPlan(ctx, compact, M.rows, M.vals, len(self.listed), field="ed25519", place=False)
+        self.plan = ColumnPlan(ctx, compact, M.rows, M.vals, len(self.listed), field="bn256_cs" if vector.BN else "ed25519",
+                               place=False)
         self._placed = None             # the (n_x, n_in) of the plan's items: weighted_columns places them
 
     def csr(self):
