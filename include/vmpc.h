@@ -807,7 +807,9 @@ int vmpc_fr_cs_first_diff_dev(vmpc_ctx *ctx, const void *a, const void *b, size_
  * n - the same canonical residues as the direct kernel's.  Arena: the extension and the column sum reserve as above;
  * tables and lagrange do NOT use the arena - `scratch` is the caller's device memory of
  * vmpc_bn256_fr_cs_tables_scratch_bytes(K) / vmpc_bn256_fr_cs_lagrange_scratch_bytes(K) bytes (0: K out of range), not
- * read, and free again when the stream has passed the call.  The batch, share (_fg) and MPC forms exist over GF(l) only. */
+ * read, and free again when the stream has passed the call.  The share form (_fg) exists over both fields
+ * (vmpc_bn256_fr_cs_extend_fg_dev below: the M-party KoE prover); the batch form exists over GF(l)
+ * only. */
 int vmpc_bn256_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_vals,
                                  const void *a_const, const uint32_t *b_row_ptr, const uint32_t *b_col,
                                  const void *b_vals, const void *b_const, const uint32_t *gates, size_t n_gates,
@@ -817,6 +819,11 @@ size_t vmpc_bn256_fr_cs_tables_scratch_bytes(size_t K);
 int vmpc_bn256_fr_cs_tables_dev(vmpc_ctx *ctx, size_t K, void *fact, void *ifact, void *scratch);
 int vmpc_bn256_fr_cs_extend_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
                                 const void *ifact, void *z_tail);
+/* vmpc_fr_cs_extend_fg_dev over GF(n): f and g kept apart for a witness of Shamir shares mod n (mpc_ac20_cb.py:66-85),
+ * max(m, 1) canonical residues each; arguments, caps, answers and arena as there, the route by
+ * vmpc_ctx_set_cs_extension. */
+int vmpc_bn256_fr_cs_extend_fg_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
+                                   const void *ifact, void *f_out, void *g_out);
 size_t vmpc_bn256_fr_cs_lagrange_scratch_bytes(size_t K);
 int vmpc_bn256_fr_cs_lagrange_dev(vmpc_ctx *ctx, const uint8_t c[32], size_t K, const void *ifact, void *out,
                                   void *scratch);
@@ -875,6 +882,17 @@ int vmpc_bn256_fr_share_combine_dev(vmpc_ctx *ctx, const void *parts, size_t par
  * a fixed order; asynchronous on the context's stream, no arena, no atomics. */
 int vmpc_bn256_recombine_dev(vmpc_ctx *ctx, int group, const void *parts, size_t parties, size_t n, size_t part_stride,
                              const uint8_t *weights /* HOST */, void *out);
+
+/* out[i] = scalars[i] * points[i] for i < n, every point with a scalar of its own: one party's pass over a jointly made
+ * pp of the knowledge-of-exponent pivot (csrc/bn256_scale.hip; the role of the loop of
+ * verifiable_mpc/ac20/mpc_ac20.py:54-84).  group 1 (64-byte affine points) or 2 (128-byte); points, scalars and out in
+ * device memory; all-zero bytes are the point at infinity, in and out; out: n canonical affine points, so the bytes do
+ * not depend on how the chain is organised.  A scalar is the 256-bit little-endian integer as it stands, NOT reduced
+ * mod n (for a point of order n the result is the same either way); 0 gives infinity.  Points are not validated
+ * (vmpc_bn256_validate_dev).  n above 2^31: VMPC_E_RANGE before any pointer is looked at; another group, a null pointer
+ * with n > 0: VMPC_E_INVAL; n = 0: VMPC_OK, no launch.  One lane per element, a branch-free 256-bit double-and-add
+ * (csrc/scale_chain.h) and one inversion; asynchronous on the context's stream, no arena, no atomics. */
+int vmpc_bn256_scale_points_dev(vmpc_ctx *ctx, int group, const void *points, const void *scalars, size_t n, void *out);
 
 /* ---- The R1CS solve on shares mod n (demos/demo_zkp_trinocchio.py:70: qap.calculate_witness on secure values, one
  * MPyC multiplication per `*` line of the flat code, tools/code_to_r1cs.py:253-274; csrc/bn256_r1cs_share.hip, DESIGN.md

@@ -72,6 +72,7 @@ SYMBOLS = [
     "vmpc_bn256_fr_cs_colsum_dev", "vmpc_bn256_fr_cs_first_diff_dev",
     "vmpc_bn256_fr_axpy_dev", "vmpc_bn256_fr_dot_scratch_bytes", "vmpc_bn256_fr_dot_to_dev",
     "vmpc_bn256_koe_stage_dev", "vmpc_bn256_koe_split_dev",
+    "vmpc_bn256_fr_cs_extend_fg_dev", "vmpc_bn256_scale_points_dev",
 ]
 
 
@@ -270,6 +271,8 @@ def load_library():
         "vmpc_bn256_fr_dot_to_dev": (i32, [vp, vp, vp, sz, vp, vp]),
         "vmpc_bn256_koe_stage_dev": (i32, [vp, vp, vp, vp, sz, vp, vp]),
         "vmpc_bn256_koe_split_dev": (i32, [vp, vp, sz, vp]),
+        "vmpc_bn256_fr_cs_extend_fg_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
+        "vmpc_bn256_scale_points_dev": (i32, [vp, i32, vp, vp, sz, vp]),
         "vmpc_fr_rows_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp]),
         "vmpc_fr_rows_dot_dev": (i32, [vp, vp, sz, sz, sz, vp, vp, vp]),
         "vmpc_fr_batch_products_dev": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, sz, vp, vp]),
@@ -1020,11 +1023,11 @@ class Context:
         fn, name = self._field_entry("cs_extend_dev", bn)
         _check(fn(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr), p(z_tail_ptr)), name)
 
-    def cs_extend_fg(self, a_ptr, b_ptr, m, fact_ptr, ifact_ptr, f_out_ptr, g_out_ptr):
+    def cs_extend_fg(self, a_ptr, b_ptr, m, fact_ptr, ifact_ptr, f_out_ptr, g_out_ptr, bn=False):
         """f(0), f(m+2..2m) and g alike, unmultiplied (max(m, 1) scalars each)"""
         p = ctypes.c_void_p
-        _check(self.lib.vmpc_fr_cs_extend_fg_dev(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr),
-                                                 p(f_out_ptr), p(g_out_ptr)), "vmpc_fr_cs_extend_fg_dev")
+        fn, name = self._field_entry("cs_extend_fg_dev", bn)
+        _check(fn(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr), p(f_out_ptr), p(g_out_ptr)), name)
 
     def cs_triples_batch(self, A, B, gates_ptr, n_gates, n_x, gamma_offset, z_ptr, z_stride, a_ptr, b_ptr, ab_stride, n_wit,
                          check=0, first_bad_ptr=None):
@@ -1297,6 +1300,13 @@ class Context:
         _check(self.lib.vmpc_bn256_recombine_dev(self.handle, group, ctypes.c_void_p(parts_ptr), parties, n,
                                                  part_stride, wb, ctypes.c_void_p(out_ptr)),
                "vmpc_bn256_recombine_dev")
+
+    def bn256_scale_points(self, group, points_ptr, scalars_ptr, n, out_ptr):
+        """out[i] = scalars[i] * points[i] for n affine points of G1 (group 1) or the twist (2), every point with its
+        own 32-byte scalar (used as it stands, not reduced); all in device memory"""
+        _check(self.lib.vmpc_bn256_scale_points_dev(self.handle, group, ctypes.c_void_p(points_ptr),
+                                                    ctypes.c_void_p(scalars_ptr), n, ctypes.c_void_p(out_ptr)),
+               "vmpc_bn256_scale_points_dev")
 
     def bn256_qap_t_coeffs(self, d, scratch_ptr, out_ptr):
         """out[0..d] = coefficients of prod_{j=1..d} (x - j); scratch: 2 (d + ceil(d / 128)) scalars"""

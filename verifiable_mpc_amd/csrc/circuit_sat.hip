@@ -51,7 +51,8 @@
 // The GF(n) entries take the arguments of their GF(l) namesakes.  The two that need scratch besides their outputs
 // (tables, lagrange) take it from the CALLER - a vmpc_bn256_fr_cs_*_scratch_bytes() query and a pointer - where the GF(l)
 // entries take it from the context arena and hand the taken pointers to the same body; the extension and the column sum
-// reserve inside cs_extend<F> / fr_colsum<F> for either field.  The batch, share (_fg) and MPC forms stay GF(l) only.
+// reserve inside cs_extend<F> / fr_colsum<F> for either field.  The share form (_fg) exists over both fields (the M-party
+// provers: DESIGN.md sections 18 and 30); the batch form stays GF(l) only.
 #include "common.h"
 #include "fr.h"
 #include "fr_bn.h"
@@ -624,6 +625,13 @@ extern "C" int vmpc_fr_cs_extend_fg_dev(vmpc_ctx *ctx, const void *a, const void
     if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
     if (!ctx || !a || !b || !fact || !ifact || !f_out || !g_out) return VMPC_E_INVAL;
     return cs_extend<fr>(ctx, a, b, 0, m, fact, ifact, nullptr, 0, f_out, g_out, 1);
+}
+
+extern "C" int vmpc_bn256_fr_cs_extend_fg_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t m, const void *fact,
+                                              const void *ifact, void *f_out, void *g_out) {
+    if (m > VMPC_FR_CS_MAX_M) return VMPC_E_RANGE;
+    if (!ctx || !a || !b || !fact || !ifact || !f_out || !g_out) return VMPC_E_INVAL;
+    return cs_extend<frbn>(ctx, a, b, 0, m, fact, ifact, nullptr, 0, f_out, g_out, 1);
 }
 
 extern "C" size_t vmpc_fr_cs_extend_batch_bytes(size_t m, size_t n_wit) {

@@ -22,7 +22,10 @@ x and L's coefficients may be device vectors (device.BnScalarVector): the prover
 and the verifier's reversed form are then made on the device (csrc/bn256_koe.hip), which is how Protocol 8 over a
 SparseCircuit of this order opens its L (circuit_sat_gpu.py).  Lists take the host path.
 
-Not here: prove_nullity_koe (its challenge hashes repr() of an MPyC point) and the MPC setup.
+`update_setup` is one party's pass over a pp - every point times that party's own g_exp z^(i+1) - and what the joint
+setup of mpc_koe.koe_trusted_setup is made of.
+
+Not here: prove_nullity_koe (its challenge hashes repr() of an MPyC point).
 """
 from random import SystemRandom
 
@@ -155,6 +158,12 @@ def trusted_setup(_g1, _g2, n, order, progress_bar=False):
     g_exp = prng.randrange(1, order)
     alpha = prng.randrange(order)
     z = prng.randrange(order)
+    return setup_under(_g1, _g2, n, g_exp, alpha, z)
+
+
+def setup_under(_g1, _g2, n, g_exp, alpha, z):
+    """trusted_setup's pp under a GIVEN trapdoor (g_exp, alpha, z): the first party's contribution to a jointly made pp
+    (mpc_koe.koe_trusted_setup), which the later parties' update_setup passes then multiply into"""
     ctx = get_context()
     pp = {}
     for name, group, base, scale in (("pp_lhs", 1, _g1, g_exp), ("pp_rhs", 2, _g2, g_exp * alpha % ORDER)):
@@ -170,6 +179,33 @@ def trusted_setup(_g1, _g2, n, order, progress_bar=False):
         ctx.sync()
         pp[name] = PPVector(ctx, group, pts, 2 * n)
     return pp
+
+
+def update_setup(pp, g_exp, alpha, z):
+    """One party's pass over a pp: a new pp with
+        lhs'[i] = (g_exp z^(i+1)) * lhs[i]          rhs'[i] = (g_exp alpha z^(i+1)) * rhs[i]
+    so that update_setup(trusted_setup under (a, b, c), a', b', c') IS trusted_setup under (a a', b b', c c'), byte for
+    byte - the trapdoors multiply, and a pp that went through M parties has a trapdoor nobody knows unless all M
+    collude.  The exponents are one fr_powers launch per side, the points one vmpc_bn256_scale_points_dev launch
+    (csrc/bn256_scale.hip: every point with a scalar of its own).  The sides may be PPVectors or lists of points; lists
+    are uploaded and validated (a point off its curve: ValueError naming the side).  A factor that is 0 mod the order
+    would send the whole pp to infinity: ValueError."""
+    factors = {"g_exp": int(g_exp) % ORDER, "alpha": int(alpha) % ORDER, "z": int(z) % ORDER}
+    for name, v in factors.items():
+        if v == 0:
+            raise ValueError(f"update_setup: {name} is 0 mod the group order")
+    ctx = get_context()
+    out = {}
+    for name, group, scale in (("pp_lhs", 1, factors["g_exp"]),
+                               ("pp_rhs", 2, factors["g_exp"] * factors["alpha"] % ORDER)):
+        side = _side(ctx, pp, name)
+        n = len(side)
+        exps = fr_powers(factors["z"], scale, n, ctx)
+        pts = ctx.alloc(max(1, side.width * n))
+        ctx.bn256_scale_points(group, side.buf.ptr, exps.ptr, n, pts.ptr)
+        ctx.sync()
+        out[name] = PPVector(ctx, group, pts, n)
+    return out
 
 
 def _restriction_scalars(S, x, gamma):
