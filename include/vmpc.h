@@ -418,6 +418,20 @@ int vmpc_bn256_table_msm_dev(vmpc_ctx *ctx, int group, const void *table, size_t
  * sums that differ in a few trailing terms (the zero-knowledge deltas) still share every scalar. */
 int vmpc_bn256_table_msm_multi_dev(vmpc_ctx *ctx, int group, const void *const *tables, int n_tables, size_t table_n,
                                    const void *scalars, size_t m, void *out_jacobian);
+/* ONE prepared key, `rows` scalar vectors: out_affine[r] (64 / 128 B each, consecutive; all-zero bytes = infinity) =
+ * sum_{i<m} scalars[r * row_stride + i] * P_i.  The shape of a batch of knowledge-of-exponent verifications
+ * (ac20/knowledge_of_exponent.py:136-153: R = sum_j L[n-1-j] pp_rhs[j], one linear form per proof over one pp).
+ * Scalars are read as vmpc_bn256_table_msm_dev reads them; row_stride is counted in scalars and is >= m.  Rows go in
+ * groups of at most 16: each row has its own recoding and sort, a group shares one launch of the bucket stage (the row on
+ * the grid's y axis), one bucket reduction and one recombination launch.  No arena: `scratch` is the caller's device
+ * memory of at least vmpc_bn256_table_msm_rows_scratch_bytes(group, table_n, rows) bytes (sized for one group, so the
+ * same for every rows >= 16; 0: an argument out of range), not read, and free again when the stream has passed the
+ * call.  m == 0: every output is infinity; rows == 0: nothing is written.  m > table_n, row_stride < m, a NULL pointer
+ * or too small a scratch_bytes: VMPC_E_INVAL before any launch.  Asynchronous. */
+size_t vmpc_bn256_table_msm_rows_scratch_bytes(int group, size_t table_n, size_t rows);
+int vmpc_bn256_table_msm_rows_dev(vmpc_ctx *ctx, int group, const void *table, size_t table_n, const void *scalars,
+                                  size_t row_stride, size_t m, size_t rows, void *scratch, size_t scratch_bytes,
+                                  void *out_affine);
 
 /* ---- BN-256 optimal-ate pairing (verifiable_mpc/ac20/pairing.py:614-643; the Pinocchio verifier, trinocchio/
  * pynocchio.py:276-325) -------------------------------------------------------------------------------------------

@@ -39,6 +39,7 @@ SYMBOLS = [
     "vmpc_bn256_g1_msm", "vmpc_bn256_g2_msm", "vmpc_bn256_g1_msm_dev", "vmpc_bn256_g2_msm_dev",
     "vmpc_bn256_validate_dev", "vmpc_bn256_fixed_base_dev",
     "vmpc_msm_table_fold_dev", "vmpc_msm_table_fold_table_dev", "vmpc_msm_table_fold_plan", "vmpc_p4_create", "vmpc_p4_create_opts", "vmpc_p4_prefold", "vmpc_p4_set_commit_table", "vmpc_p4_round", "vmpc_p4_round_begin", "vmpc_p4_round_end", "vmpc_p4_finish", "vmpc_p4_run_compact", "vmpc_p4_destroy", "vmpc_bn256_table_bytes", "vmpc_bn256_table_build_dev", "vmpc_bn256_table_msm_dev", "vmpc_bn256_table_msm_multi_dev",
+    "vmpc_bn256_table_msm_rows_scratch_bytes", "vmpc_bn256_table_msm_rows_dev",
     "vmpc_comm_unique_id", "vmpc_comm_create_rccl", "vmpc_comm_create_callback", "vmpc_comm_destroy", "vmpc_comm_info",
     "vmpc_comm_allgather_dev", "vmpc_comm_points_allsum_dev", "vmpc_p4_create_sharded", "vmpc_gather_probe_dev", "vmpc_bn256_madd_rate",
     "vmpc_stream_create", "vmpc_stream_destroy", "vmpc_ctx_set_bucket_stream",
@@ -293,6 +294,8 @@ def load_library():
         "vmpc_bn256_table_build_dev": (i32, [vp, i32, vp, sz, vp]),
         "vmpc_bn256_table_msm_dev": (i32, [vp, i32, vp, sz, vp, sz, vp, vp]),
         "vmpc_bn256_table_msm_multi_dev": (i32, [vp, i32, vp, i32, sz, vp, sz, vp]),
+        "vmpc_bn256_table_msm_rows_scratch_bytes": (sz, [i32, sz, sz]),
+        "vmpc_bn256_table_msm_rows_dev": (i32, [vp, i32, vp, sz, vp, sz, sz, sz, vp, sz, vp]),
         "vmpc_comm_unique_id": (i32, [vp]),
         "vmpc_comm_create_rccl": (i32, [vp, vp, i32, i32, ctypes.POINTER(vp)]),
         "vmpc_comm_create_callback": (i32, [i32, i32, EXCHANGE_FN, vp, ctypes.POINTER(vp)]),
@@ -1205,6 +1208,17 @@ class Context:
         _check(self.lib.vmpc_bn256_table_msm_multi_dev(self.handle, group, tabs, k, table_n,
                                                        ctypes.c_void_p(scalars_ptr), m, ctypes.c_void_p(out_jac_ptr)),
                "vmpc_bn256_table_msm_multi_dev")
+
+    def bn256_table_msm_rows(self, group, table_ptr, table_n, scalars_ptr, row_stride, m, rows, out_ptr):
+        """one prepared key, `rows` scalar vectors row_stride scalars apart: out[r] = sum_{i<m} scalars[r][i] P_i, affine,
+        consecutive (include/vmpc.h).  The entry's scratch is a block of this context's cache, free for reuse once the
+        stream has passed the call.  Asynchronous"""
+        p = ctypes.c_void_p
+        nbytes = int(self.lib.vmpc_bn256_table_msm_rows_scratch_bytes(group, table_n, rows)) if m and rows else 0
+        scratch = self.alloc(max(32, nbytes))
+        _check(self.lib.vmpc_bn256_table_msm_rows_dev(self.handle, group, p(table_ptr), table_n, p(scalars_ptr), row_stride,
+                                                      m, rows, p(scratch.ptr), nbytes, p(out_ptr)),
+               "vmpc_bn256_table_msm_rows_dev")
 
     def bn256_fixed_base(self, group, base_ptr, scalars_ptr, n, out_ptr):
         _check(self.lib.vmpc_bn256_fixed_base_dev(self.handle, group, ctypes.c_void_p(base_ptr),

@@ -688,10 +688,19 @@ def circuit_sat_verifier(proof, generators, circuit, gf, pivot_choice="compresse
     return verification
 
 
-def circuit_sat_verifier_batch(proofs, generators, circuit, gf, transcript=None):
-    """[circuit_sat_verifier(proof, generators, circuit, gf, "compressed", transcript) for proof in proofs] - many inputs
-    of one circuit: Protocol 8's checks per proof, then the proofs that yielded an L in ONE batched pivot verification
-    (compressed_pivot.protocol_5_verifier_batch)"""
+def circuit_sat_verifier_batch(proofs, generators, circuit, gf, transcript=None, pivot_choice=None):
+    """[circuit_sat_verifier(proof, generators, circuit, gf, pivot_choice, transcript) for proof in proofs] - many inputs
+    of one circuit: Protocol 8's checks per proof, then the proofs that yielded an L in ONE batched pivot verification.
+    pivot_choice None: by the generators - a pp selects the knowledge-of-exponent pivot
+    (knowledge_of_exponent.opening_linear_form_verifier_batch), Ed25519 generators the compressed
+    one (compressed_pivot.protocol_5_verifier_batch); "pivot" has no batch form."""
+    has_pp = "pp_lhs" in generators
+    choice = ("koe" if has_pp else "compressed") if pivot_choice is None else _choice(pivot_choice)
+    _check_choice(choice, has_pp)
+    if choice == "koe":
+        return _koe_verifier_batch(proofs, generators, circuit, gf, _mode(transcript))
+    if choice != "compressed":
+        raise NotImplementedError("circuit_sat_verifier_batch: the compressed and the knowledge-of-exponent pivot")
     mode = _mode(transcript)
     circuit = as_sparse(circuit)
     out, statements, where = [], [], []
@@ -703,6 +712,51 @@ def circuit_sat_verifier_batch(proofs, generators, circuit, gf, transcript=None)
         out.append(verification)
     for i, ok in zip(where, compressed_pivot.protocol_5_verifier_batch(generators, statements, gf, transcript=mode)):
         out[i]["pivot_verification"] = ok
+    return out
+
+
+# bytes of linear forms L (32 N each) that the knowledge-of-exponent route of circuit_sat_verifier_batch keeps alive at a
+# time: the proofs are consumed in chunks of that many, one batched opening per chunk
+KOE_VERIFY_BUDGET_BYTES = 1 << 28
+
+
+def _koe_verifier_batch(proofs, pp, circuit, gf, mode):
+    """circuit_sat_verifier(.., PivotChoice.koe) proof for proof, up to L; then one opening batch per chunk of proofs"""
+    out, chunk, held = [], [], 0
+
+    def flush():
+        # (L, proof points, bound, index) of the chunk's proofs that got as far as the opening; one batch per length of
+        # L (an honest batch of one circuit has one)
+        by_len = {}
+        for item in chunk:
+            by_len.setdefault(len(item[0].coeffs), []).append(item)
+        for items in by_len.values():
+            oks = koe.opening_linear_form_verifier_batch([L for L, _, _, _ in items], pp, [pts for _, pts, _, _ in items],
+                                                         [0] * len(items))
+            for (_, _, bound, i), ok in zip(items, oks):
+                ok["restriction_arg_check"] = bool(ok["restriction_arg_check"] and bound)
+                out[i]["pivot_verification"] = ok
+        chunk.clear()
+
+    for proof in proofs:
+        if not isinstance(proof.get("z_commitment"), dict):
+            raise ValueError("circuit_sat_verifier: a knowledge-of-exponent proof (z_commitment = {'P', 'pi'}) goes with "
+                             "PivotChoice.koe and a pp, any other proof with Ed25519 generators")
+        nbytes = 32 * len(proof["L"].coeffs)
+        if held and held + nbytes > KOE_VERIFY_BUDGET_BYTES:
+            flush()
+            held = 0
+        held += nbytes
+        verification, L = protocol_8_excl_pivot_verifier(proof, circuit, gf, transcript=mode)
+        out.append(verification)
+        if L is None or not verification["L_wellformed_from_Cfgh_forms"]:
+            continue
+        # as in circuit_sat_verifier: the opening is checked on the commitment's (P, pi); a pivot proof that names other
+        # points fails the restriction check
+        zc, pp_proof = proof["z_commitment"], proof["pivot_proof"]
+        bound = all(pp_proof[k].to_bytes() == zc[k].to_bytes() for k in ("P", "pi"))
+        chunk.append((L, {"P": zc["P"], "pi": zc["pi"], "Q": pp_proof["Q"]}, bound, len(out) - 1))
+    flush()
     return out
 
 

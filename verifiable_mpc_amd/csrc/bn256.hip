@@ -203,6 +203,132 @@ extern "C" int vmpc_bn256_table_msm_multi_dev(vmpc_ctx *ctx, int group, const vo
     return VMPC_E_INVAL;
 }
 
+// ---- ONE prepared key, several scalar rows (the sums R_p = sum_j L_p[N-1-j] pp_rhs[j] of a batch of knowledge-of-
+// exponent openings, knowledge_of_exponent.py:136-153: one pp, a linear form per proof) - the transpose of the multi-key
+// pass above.  Rows go in groups of at most BN_ROWS_MAX = 16 (that pass's bound on the windows of one reduction).  In a
+// group every row is recoded and sorted on its own, into its own msm_ws; the bucket stage of the whole group is one
+// launch per kernel with the row on blockIdx.y (bn_kernels::bucket_rows), the G bucket sets are consecutive and are
+// reduced as the G windows of one launch, and G workgroups finish them side by side, each writing its affine point.
+// Memory comes from the caller's scratch only - never the arena - and the plan is made under a new context's tuning
+// values, whatever the caller's context has been set to: the layout is then a function of (group, table_n, rows) alone,
+// which is all the scratch query is given.  The sums are exact group elements in canonical form, so the plan does not
+// show in the output.
+struct bn_rows_layout {
+    msm_plan p;                 // one row: a table pass of one window
+    msm_ws w0;                  // its arrays as offsets from a null base (no entries, no accumulators)
+    size_t ws_stride, sp_stride, sp_off, b_off, c_off, r_off, total;
+};
+
+template <class C>
+static void bn_rows_make_layout(size_t table_n, size_t G, bn_rows_layout &L) {
+    vmpc_ctx defaults;
+    msm_plan &p = L.p;
+    p.n_main = p.n_total = (size_t)BN_TABLE_W * bn_table_stride(table_n);
+    p.n_extra = 0;
+    p.scalar_bits = 256;
+    p.c = BN_TABLE_C;
+    p.W = 1;
+    p.top_row = -1;
+    p.top_max_b = 0;
+    p.period = 0;
+    msm_plan_geometry(&defaults, p);
+    msm_layout(p, L.w0, nullptr, 0, 0);
+    const size_t acc = (size_t)C::ACC_WORDS * 4;
+    L.ws_stride = vmpc_align(L.w0.total);
+    L.sp_stride = vmpc_align(L.w0.t_max * acc);
+    L.sp_off = G * L.ws_stride;
+    L.b_off = L.sp_off + G * L.sp_stride;
+    L.c_off = L.b_off + vmpc_align(G * p.nb * acc);
+    L.r_off = L.c_off + vmpc_align(G * p.nb1 * 4);
+    // (a group's reduction leaves at most 2 * p.red_blocks partial sums per row: fewer chunk-lanes with more rows)
+    L.total = L.r_off + vmpc_align(G * 2 * p.red_blocks * acc);
+}
+
+template <class C, class F>
+static int bn_table_msm_rows_dev(vmpc_ctx *ctx, const void *table, size_t table_n, const void *scalars,
+                                 size_t row_stride, size_t m, size_t rows, void *scratch, size_t scratch_bytes,
+                                 void *out_affine) {
+    if (!ctx || !table || !out_affine || table_n == 0 || table_n > ((size_t)1 << 26) || m > table_n || row_stride < m)
+        return VMPC_E_INVAL;
+    if (rows == 0) return VMPC_OK;
+    const size_t G_max = rows < BN_ROWS_MAX ? rows : BN_ROWS_MAX;
+    bn_rows_layout L;
+    if (m) {
+        if (!scalars || !scratch) return VMPC_E_INVAL;
+        bn_rows_make_layout<C>(table_n, G_max, L);
+        if (scratch_bytes < L.total) return VMPC_E_INVAL;
+    }
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (m == 0) {   // empty sums = points at infinity (all-zero encoding)
+        VMPC_HIP_CHECK(hipMemsetAsync(out_affine, 0, rows * C::AFF_WORDS * 4, st));
+        return VMPC_OK;
+    }
+    const msm_plan &p = L.p;
+    const size_t stride = bn_table_stride(table_n);
+    char *base = (char *)scratch;
+    uint32_t *buckets = (uint32_t *)(base + L.b_off), *counts = (uint32_t *)(base + L.c_off);
+    for (size_t g0 = 0; g0 < rows; g0 += BN_ROWS_MAX) {
+        const int G = (int)(rows - g0 < BN_ROWS_MAX ? rows - g0 : BN_ROWS_MAX);
+        msm_ws ws[BN_ROWS_MAX];
+        for (int r = 0; r < G; r++) {
+            msm_ws &w = ws[r];
+            msm_layout(p, w, base + (size_t)r * L.ws_stride, 0, 0);
+            w.seg_partial = (uint32_t *)(base + L.sp_off + (size_t)r * L.sp_stride);
+            w.buckets = buckets + (size_t)r * p.nb * C::ACC_WORDS;
+            VMPC_CHECK(msm_recode_rows(ctx, (const char *)scalars + (g0 + r) * row_stride * 32, m, nullptr, 0, 0, stride,
+                                       w.digits, BN_TABLE_C, BN_TABLE_W, BN_TABLE_W, BN_ORDER));
+            VMPC_CHECK(msm_sort_digits(ctx, p, w));
+            // the reduction reads window r's bucket counts at counts + r * nb1
+            VMPC_HIP_CHECK(hipMemcpyAsync(counts + (size_t)r * p.nb1, w.counts, (size_t)p.nb1 * 4, hipMemcpyDeviceToDevice, st));
+        }
+        {
+            vmpc_stage_scope s(ctx, "bn_bucket");
+            VMPC_CHECK((bn_kernels<C, F>::bucket_rows(ctx, p, ws, G, (const uint32_t *)table)));
+        }
+        msm_plan pk = p;                      // the G bucket sets as G windows of the reduction: bn_table_msm_multi_dev's rule
+        pk.W = G;
+        while ((size_t)pk.chunks * G > (size_t)MSM_REDUCE_CHUNKS * 16 && pk.chunks > 256) pk.chunks /= 2;
+        pk.chunk_len = pk.nb / pk.chunks;
+        pk.red_blocks = (pk.chunks + MSM_BLOCK - 1) / MSM_BLOCK;
+        msm_ws wm = ws[0];
+        wm.buckets = buckets;
+        wm.counts = counts;
+        wm.partials = (uint32_t *)(base + L.r_off);
+        {
+            vmpc_stage_scope s(ctx, "bn_reduce");
+            VMPC_CHECK((bn_kernels<C, F>::reduce(ctx, pk, wm)));
+        }
+        {
+            vmpc_stage_scope s(ctx, "bn_final");
+            VMPC_CHECK((bn_kernels<C, F>::final_rows(ctx, pk, wm, (char *)out_affine + g0 * C::AFF_WORDS * 4, G)));
+        }
+    }
+    ctx->sort_view_valid = false;      // (the sorts' arrays are the caller's memory, not the arena: no view of them is kept)
+    return VMPC_OK;
+}
+
+extern "C" size_t vmpc_bn256_table_msm_rows_scratch_bytes(int group, size_t table_n, size_t rows) {
+    if ((group != 1 && group != 2) || table_n == 0 || table_n > ((size_t)1 << 26) || rows == 0) return 0;
+    const size_t G = rows < BN_ROWS_MAX ? rows : BN_ROWS_MAX;
+    bn_rows_layout L;
+    if (group == 1) bn_rows_make_layout<G1>(table_n, G, L);
+    else bn_rows_make_layout<G2>(table_n, G, L);
+    return L.total;
+}
+
+extern "C" int vmpc_bn256_table_msm_rows_dev(vmpc_ctx *ctx, int group, const void *table, size_t table_n,
+                                             const void *scalars, size_t row_stride, size_t m, size_t rows, void *scratch,
+                                             size_t scratch_bytes, void *out_affine) {
+    if (group == 1)
+        return bn_table_msm_rows_dev<G1, BnF1>(ctx, table, table_n, scalars, row_stride, m, rows, scratch, scratch_bytes,
+                                               out_affine);
+    if (group == 2)
+        return bn_table_msm_rows_dev<G2, BnF2>(ctx, table, table_n, scalars, row_stride, m, rows, scratch, scratch_bytes,
+                                               out_affine);
+    return VMPC_E_INVAL;
+}
+
 extern "C" int vmpc_bn256_table_bytes(int group, size_t n, size_t *bytes) {
     if (!bytes || (group != 1 && group != 2) || n == 0 || n > ((size_t)1 << 26)) return VMPC_E_INVAL;
     *bytes = (size_t)BN_TABLE_W * bn_table_stride(n) * (group == 1 ? G1::ENTRY_WORDS : G2::ENTRY_WORDS) * 4;

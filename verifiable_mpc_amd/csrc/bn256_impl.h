@@ -97,6 +97,91 @@ gk_finish(const uint32_t *__restrict__ heavy_list, const uint32_t *__restrict__ 
     }
 }
 
+// ---- the bucket stage of up to BN_ROWS_MAX scalar rows over ONE table in one launch (bn_table_msm_rows_dev) -----------
+// Row r = blockIdx.y has its own sort (sorted list, task table, split-bucket lists, partial sums) and its own bucket
+// set; the entries are shared.  The three kernels restate the bodies of gk_bucket / gk_finish_light / gk_finish above
+// with the row's pointers taken from the argument block: those kernels are launched by every other BN-256 sum and are
+// left as they are.  The grid's x extent is the rows' common t_max; a row's lanes beyond its *n_tasks leave at once.
+#define BN_ROWS_MAX 16
+struct bn_rows_args {
+    const uint32_t *sorted[BN_ROWS_MAX];
+    const msm_task *tasks[BN_ROWS_MAX];
+    const uint32_t *ctrl[BN_ROWS_MAX];          // [0] = #split buckets, [1] = #tasks, [4] = #heavily split buckets
+    const uint32_t *heavy_list[BN_ROWS_MAX], *nseg[BN_ROWS_MAX], *seg_starts[BN_ROWS_MAX];
+    uint32_t *buckets[BN_ROWS_MAX], *partial[BN_ROWS_MAX];
+};
+
+template <class C>
+__global__ void __launch_bounds__(MSM_BLOCK)
+gk_bucket_rows(const uint32_t *__restrict__ entries, const bn_rows_args a) {
+    const int r = blockIdx.y;
+    const uint32_t *__restrict__ sorted = a.sorted[r];
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.ctrl[r][1]) return;
+    const msm_task tk = a.tasks[r][t];
+    const uint32_t lo = tk.x, len = tk.y;
+    typename C::acc_t acc = C::identity();
+    for (uint32_t j = 0; j < len; j++) {
+        uint32_t e = sorted[lo + j];
+        typename C::entry_t q = C::entry_ld(entries + (size_t)C::ENTRY_WORDS * (e & 0x7fffffffu));
+        acc = C::madd(acc, q, (e >> 31) != 0);
+    }
+    C::acc_st(((tk.w & MSM_TASK_SPLIT) ? a.partial[r] : a.buckets[r]) + (size_t)C::ACC_WORDS * tk.z, acc);
+}
+
+template <class C, class F>
+__global__ void __launch_bounds__(MSM_BLOCK)
+gk_finish_light_rows(const bn_rows_args a, int nb1) {
+    const int r = blockIdx.y;
+    const uint32_t *__restrict__ heavy_list = a.heavy_list[r], *__restrict__ nseg = a.nseg[r];
+    const uint32_t *__restrict__ seg_starts = a.seg_starts[r], *__restrict__ partial = a.partial[r];
+    uint32_t *__restrict__ buckets = a.buckets[r];
+    const uint32_t n_heavy = a.ctrl[r][0];
+    for (uint32_t h = blockIdx.x * blockDim.x + threadIdx.x; h < n_heavy; h += gridDim.x * blockDim.x) {
+        uint32_t ci = heavy_list[h];
+        uint32_t ns = nseg[ci];
+        if (ns > MSM_FINISH_SERIAL) continue;
+        const uint32_t *src = partial + (size_t)C::ACC_WORDS * seg_starts[ci];
+        typename C::acc_t acc = C::acc_ld(src);
+        for (uint32_t j = 1; j < ns; j++) acc = jac_add<F>(acc, C::acc_ld(src + (size_t)C::ACC_WORDS * j));
+        C::acc_st(buckets + (size_t)C::ACC_WORDS * msm_bucket_slot(ci, nb1), acc);
+    }
+}
+
+template <class C, class F>
+__global__ void __launch_bounds__(MSM_BLOCK)
+gk_finish_rows(const bn_rows_args a, int nb1) {
+    __shared__ uint32_t lds[MSM_BLOCK * C::ACC_WORDS];
+    const int r = blockIdx.y;
+    const uint32_t *__restrict__ ctrl = a.ctrl[r];
+    if (ctrl[4] == 0) return;                      // no heavily split bucket in this row
+    const uint32_t *__restrict__ heavy_list = a.heavy_list[r], *__restrict__ nseg = a.nseg[r];
+    const uint32_t *__restrict__ seg_starts = a.seg_starts[r], *__restrict__ partial = a.partial[r];
+    uint32_t *__restrict__ buckets = a.buckets[r];
+    const uint32_t n_heavy = ctrl[0];
+    for (uint32_t h = blockIdx.x; h < n_heavy; h += gridDim.x) {
+        uint32_t ci = heavy_list[h];
+        uint32_t ns = nseg[ci];
+        if (ns <= MSM_FINISH_SERIAL) continue;
+        const uint32_t *src = partial + (size_t)C::ACC_WORDS * seg_starts[ci];
+        typename C::acc_t acc = jac_identity<F>();
+        for (uint32_t j = threadIdx.x; j < ns; j += blockDim.x)
+            acc = jac_add<F>(acc, C::acc_ld(src + (size_t)C::ACC_WORDS * j));
+        C::acc_st(lds + C::ACC_WORDS * threadIdx.x, acc);
+        __syncthreads();
+        for (uint32_t stride = MSM_BLOCK / 2; stride >= 1; stride >>= 1) {
+            if (threadIdx.x < stride)
+                C::acc_st(lds + C::ACC_WORDS * threadIdx.x,
+                          jac_add<F>(C::acc_ld(lds + C::ACC_WORDS * threadIdx.x),
+                                     C::acc_ld(lds + C::ACC_WORDS * (threadIdx.x + stride))));
+            __syncthreads();
+        }
+        if (threadIdx.x == 0)
+            C::acc_st(buckets + (size_t)C::ACC_WORDS * msm_bucket_slot(ci, nb1), C::acc_ld(lds));
+        __syncthreads();
+    }
+}
+
 // ---- reduce: sum_b b * B_b per window ---------------------------------------------------------
 // SPLIT = 2 (few chunks: a 17-row table's single bucket set is 2^15 one-bucket chunks, 512 waves for 1024 SIMDs):
 // TWO lanes per chunk share the offset ladder - lane kind 0 takes the low `hb` bits of the chunk index, kind 1 the
@@ -281,6 +366,10 @@ struct bn_kernels {
     static int final(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w, void *out_affine, void *out_jac);
     // K one-window sums side by side (w.partials: K x red_blocks), Jacobian out, K x 3 field elements
     static int final_multi(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w, void *out_jac, int K);
+    // G <= BN_ROWS_MAX rows over one table: ws[r] = row r's sort and bucket set (bucket stage in one launch per kernel);
+    // then G one-window sums side by side like final_multi, affine out, G x AFF_WORDS
+    static int bucket_rows(vmpc_ctx *ctx, const msm_plan &p, const msm_ws *ws, int G, const uint32_t *entries);
+    static int final_rows(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w, void *out_affine, int G);
     static int table_build(vmpc_ctx *ctx, const void *points, size_t n, size_t stride, void *table);
     static int validate(vmpc_ctx *ctx, const void *points, size_t n, unsigned long long *d_bad);
     static int fixed_base(vmpc_ctx *ctx, const void *base_affine, const void *scalars, size_t n, void *out_affine);
@@ -336,6 +425,41 @@ template <class C, class F>
 int bn_kernels<C, F>::final_multi(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w, void *out_jac, int K) {
     gk_final<C, F><<<K, 64, 0, ctx->stream>>>(w.partials, 1, bn_reduce_split(p) ? 2 * p.red_blocks : p.red_blocks, p.c,
                                               nullptr, (uint32_t *)out_jac);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+template <class C, class F>
+int bn_kernels<C, F>::bucket_rows(vmpc_ctx *ctx, const msm_plan &p, const msm_ws *ws, int G, const uint32_t *entries) {
+    if (G < 1 || G > BN_ROWS_MAX) return VMPC_E_INVAL;
+    hipStream_t st = ctx->stream;
+    bn_rows_args a;
+    size_t t_max = 0;
+    for (int r = 0; r < BN_ROWS_MAX; r++) {
+        const msm_ws &w = ws[r < G ? r : 0];     // (slots beyond G are never indexed: blockIdx.y < G)
+        a.sorted[r] = w.sorted;
+        a.tasks[r] = w.tasks;
+        a.ctrl[r] = w.ctrl;
+        a.heavy_list[r] = w.heavy_list;
+        a.nseg[r] = w.nseg;
+        a.seg_starts[r] = w.seg_starts;
+        a.buckets[r] = w.buckets;
+        a.partial[r] = w.seg_partial;
+        if (r < G && w.t_max > t_max) t_max = w.t_max;
+    }
+    gk_bucket_rows<C><<<dim3((unsigned)((t_max + MSM_BLOCK - 1) / MSM_BLOCK), G), MSM_BLOCK, 0, st>>>(entries, a);
+    VMPC_KERNEL_CHECK();
+    gk_finish_light_rows<C, F><<<dim3(2 * ctx->cu_count, G), MSM_BLOCK, 0, st>>>(a, p.nb1);
+    VMPC_KERNEL_CHECK();
+    gk_finish_rows<C, F><<<dim3(2 * ctx->cu_count, G), MSM_BLOCK, 0, st>>>(a, p.nb1);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+template <class C, class F>
+int bn_kernels<C, F>::final_rows(vmpc_ctx *ctx, const msm_plan &p, msm_ws &w, void *out_affine, int G) {
+    gk_final<C, F><<<G, 64, 0, ctx->stream>>>(w.partials, 1, bn_reduce_split(p) ? 2 * p.red_blocks : p.red_blocks, p.c,
+                                              (uint32_t *)out_affine, nullptr);
     VMPC_KERNEL_CHECK();
     return VMPC_OK;
 }

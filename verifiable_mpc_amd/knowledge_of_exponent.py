@@ -22,6 +22,10 @@ x and L's coefficients may be device vectors (device.BnScalarVector): the prover
 and the verifier's reversed form are then made on the device (csrc/bn256_koe.hip), which is how Protocol 8 over a
 SparseCircuit of this order opens its L (circuit_sat_gpu.py).  Lists take the host path.
 
+`opening_linear_form_verifier_batch` (not in the reference) verifies K openings under one pp with the answers of K
+single calls: the proofs' 5 K pairings in one pairing_product launch, their sums R as rows of PPVector.msm_rows
+(vmpc_bn256_table_msm_rows_dev); DESIGN.md section 31.
+
 `update_setup` is one party's pass over a pp - every point times that party's own g_exp z^(i+1) - and what the joint
 setup of mpc_koe.koe_trusted_setup is made of.
 
@@ -101,6 +105,27 @@ class PPVector:
             ctx.bn256_msm(self.group, ds.ptr, self.buf.ptr, m, out.ptr)
         ctx.sync()
         return _CLS[self.group].from_bytes(ctx.download(out.ptr, self.width).tobytes())
+
+    def msm_rows(self, matrix, m, rows, row_stride=None):
+        """sum_{i < m} matrix[r][i] * self[i] for r < rows -> (rows, width) uint8 affine points (all zero: infinity).
+        matrix: a device buffer of scalar rows, row_stride (default m) scalars apart.  One call of
+        vmpc_bn256_table_msm_rows_dev over the vector's table and one synchronisation; an untabulated vector (from_points)
+        runs its sums one by one."""
+        ctx = self.ctx
+        stride = m if row_stride is None else row_stride
+        assert 0 < m <= self.n and stride >= m
+        if rows == 0:
+            return np.zeros((0, self.width), np.uint8)
+        out = ctx.alloc(self.width * rows)
+        if self._tabulate:
+            if self._table is None:
+                self._table = ctx.bn256_table_build(self.group, self.buf.ptr, self.n)
+            ctx.bn256_table_msm_rows(self.group, self._table.ptr, self.n, matrix.ptr, stride, m, rows, out.ptr)
+        else:
+            for r in range(rows):
+                ctx.bn256_msm(self.group, matrix.ptr + 32 * stride * r, self.buf.ptr, m, out.ptr + self.width * r)
+        ctx.sync()
+        return ctx.download(out.ptr, self.width * rows).reshape(rows, self.width)
 
 
 def _side(ctx, pp, name, count=None):
@@ -366,3 +391,76 @@ def opening_linear_form_verifier(L, pp, proof, u):
     _, ones = _pairing_product_arrays(ctx, np.stack([rP, neg_g1, rP, rQ, neg_g1]), np.stack([g2, rpi, R, g2, uT]),
                                       [0, 2, 5], validate=False)
     return {"restriction_arg_check": ones[0], "PRQ_check": ones[1]}
+
+
+# bytes of reversed linear forms (32 N each) that opening_linear_form_verifier_batch holds on the device at a time: the
+# proofs' sums R go through msm_rows in chunks of this many bytes' worth of rows (circuit_sat_gpu.BATCH_BUDGET_BYTES)
+BATCH_ROWS_BUDGET_BYTES = 1 << 28
+
+
+def _batch_proof_points(ctx, proofs, name, group):
+    """(K, width) uint8 rows of proofs[i][name], uploaded and validated in one call each; a point off its curve is then
+    found proof by proof: ValueError with the single verifier's message, prefixed with the proof's index"""
+    enc = [_as_bytes(proof[name]) for proof in proofs]
+    for i, (grp, _) in enumerate(enc):
+        if grp != group:
+            raise ValueError(f"proof {i}: {name} is not on the {_CURVE[group]}")
+    rows = np.frombuffer(b"".join(raw for _, raw in enc), np.uint8).reshape(len(proofs), 64 * group)
+    if ctx.bn256_validate(group, ctx.upload(rows).ptr, len(rows)):
+        for i, proof in enumerate(proofs):
+            try:
+                _proof_point(ctx, proof[name], group, name)
+            except ValueError as e:
+                raise ValueError(f"proof {i}: {e}") from None
+    return rows
+
+
+def opening_linear_form_verifier_batch(Ls, pp, proofs, us):
+    """[opening_linear_form_verifier(L, pp, proof, u) for L, proof, u in zip(Ls, proofs, us)] - the same dicts with the
+    same booleans - for K openings under one pp, all forms of one length N.  The K proofs are 5 K
+    pairs and 2 K products of ONE pairing_product launch (a lane runs a whole Miller loop or final exponentiation, so
+    the launch lasts as long as for one proof); the sums R_p = sum_j L_p[N-1-j] pp_rhs[j] are rows of msm_rows, the
+    points u_p pp_rhs[N] one lincomb launch.  No random weights: every proof keeps its own two checks.  Forms of
+    different lengths: ValueError; a point off its curve: ValueError naming the proof and the point."""
+    Ls, proofs, us = list(Ls), list(proofs), list(us)
+    K = len(Ls)
+    if len(proofs) != K or len(us) != K:
+        raise ValueError("opening_linear_form_verifier_batch: Ls, proofs and us differ in length")
+    if K == 0:
+        return []
+    ctx = get_context()
+    forms = [(L.coeffs, getattr(L, "constant", 0)) if _on_device(L.coeffs) else _form_parts(L) for L in Ls]
+    n = len(forms[0][0])
+    if any(len(coeffs) != n for coeffs, _ in forms):
+        raise ValueError("opening_linear_form_verifier_batch: the linear forms differ in length")
+    lhs, rhs = _side(ctx, pp, "pp_lhs", 1), _side(ctx, pp, "pp_rhs", n + 1)
+    if len(rhs) <= n:
+        raise ValueError("pp_rhs holds fewer than len(L) + 1 points")
+    rP, rpi, rQ = (_batch_proof_points(ctx, proofs, k, g) for k, g in (("P", 1), ("pi", 2), ("Q", 1)))
+    # R's scalars: every L reversed, one row of a (G, n) device matrix per proof; G under the byte budget
+    R = np.empty((K, 128), np.uint8)
+    G = max(1, min(K, BATCH_ROWS_BUDGET_BYTES // (32 * n)))
+    matrix = ctx.alloc(32 * n * G)
+    for k0 in range(0, K, G):
+        chunk = forms[k0:k0 + G]
+        for j, (coeffs, _) in enumerate(chunk):
+            row = matrix.ptr + 32 * n * j
+            if _on_device(coeffs):
+                ctx.bn256_koe_stage(None, None, coeffs.ptr, n, None, row)
+            else:
+                ctx.upload_into(row, _reversed_coeffs(coeffs, n))
+        R[k0:k0 + len(chunk)] = rhs.msm_rows(matrix, n, len(chunk))
+    # u_p * pp_rhs[n] for every proof: one launch, one base
+    u_linear = scalars_to_array([(int(u) - int(constant)) % ORDER for u, (_, constant) in zip(us, forms)])
+    uT = ctx.alloc(128 * K)
+    ctx.bn256_lincomb_batch(2, rhs.buf.ptr + 128 * n, 1, ctx.upload(u_linear).ptr, None, 0, K, False, uT.ptr)
+    ctx.sync()
+    uT = ctx.download(uT.ptr, 128 * K).reshape(K, 128)
+    g2 = np.broadcast_to(rhs.rows()[0], (K, 128))
+    neg_g1 = np.broadcast_to(_neg_g1_rows(lhs.rows()[:1])[0], (K, 64))
+    # per proof: e(P, g2) e(-g1, pi)  and  e(P, R) e(Q, g2) e(-g1, u pp_rhs[n])
+    g1_rows = np.stack([rP, neg_g1, rP, rQ, neg_g1], axis=1).reshape(5 * K, 64)
+    g2_rows = np.stack([g2, rpi, R, g2, uT], axis=1).reshape(5 * K, 128)
+    offsets = np.sort(np.concatenate([5 * np.arange(K + 1), 5 * np.arange(K) + 2]))
+    _, ones = _pairing_product_arrays(ctx, g1_rows, g2_rows, offsets, validate=False)
+    return [{"restriction_arg_check": ones[2 * i], "PRQ_check": ones[2 * i + 1]} for i in range(K)]
