@@ -539,6 +539,20 @@ int vmpc_bn256_koe_stage_dev(vmpc_ctx *ctx, const void *x, const uint8_t gamma[3
 /* After the product c (2n scalars): u_out (one device scalar) = c[n] = <L, x>, and c[n] = 0, so that c is the scalar
  * vector of Q's MSM over the 2n generators (knowledge_of_exponent.py:124-130).  n >= 1.  No arena. */
 int vmpc_bn256_koe_split_dev(vmpc_ctx *ctx, void *c, size_t n, void *u_out);
+/* vmpc_bn256_koe_stage_dev for n_wit openings of one length n in ONE launch (the witness on the grid's y): for every p,
+ * lhs_p = (gammas[p], x_p[0..n-1]) and rhs_p = (L_p[n-1], .., L_p[0]), row p of x, L, lhs, rhs being p times its stride
+ * (in scalars) past the pointer.  gammas: n_wit device scalars, uploaded as canonical residues.  x NULL: no lhs is
+ * written (gammas and lhs are not read); L NULL: no rhs; both NULL: VMPC_E_INVAL.  n < VMPC_BN256_FR_POLY_MAX,
+ * n_wit <= VMPC_BN256_QAP_MAX_WIT, every stride <= 2^31 and, for n_wit > 0, lhs_stride >= n + 1 and the others >= n - of
+ * all four, whichever sides are asked for - else VMPC_E_RANGE before any pointer is looked at.  n_wit = 0: VMPC_OK, no
+ * launch.  The bits are those of n_wit single calls.  No arena. */
+int vmpc_bn256_koe_stage_batch_dev(vmpc_ctx *ctx, const void *x, size_t x_stride, const void *gammas, const void *L,
+                                   size_t L_stride, size_t n, size_t n_wit, void *lhs, size_t lhs_stride, void *rhs,
+                                   size_t rhs_stride);
+/* vmpc_bn256_koe_split_dev for n_wit products, rows of 2n scalars c_stride >= 2n scalars apart, in one launch with a
+ * lane per row: u_out[p] = c_p[n] (n_wit device scalars), then c_p[n] = 0; nothing else is written.  n >= 1; caps as
+ * above, else VMPC_E_RANGE; n_wit = 0: VMPC_OK, no launch.  No arena. */
+int vmpc_bn256_koe_split_batch_dev(vmpc_ctx *ctx, void *c, size_t c_stride, size_t n, size_t n_wit, void *u_out);
 
 /* ---- Pinocchio key generation (verifiable_mpc/trinocchio/pynocchio.py:101-200): the exponents of the key points,
  * same scalar conventions.  Every key entry is (exponent) * g1 or g2, made by vmpc_bn256_fixed_base_dev. */
@@ -772,6 +786,19 @@ int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, siz
  * cap (ctx NULL: the direct figure) */
 size_t vmpc_fr_cs_extend_batch_bytes(size_t m, size_t n_wit);
 size_t vmpc_fr_cs_extend_batch_bytes_ctx(const vmpc_ctx *ctx, size_t m, size_t n_wit);
+/* The batch entries over GF(n), the BN-256 order: the same templates at the other field (the batch prover of the
+ * knowledge-of-exponent variant).  Arguments, range checks, caps (VMPC_FR_CS_MAX_WIT, VMPC_FR_CS_MAX_M), return codes and
+ * both extension routes are their GF(l) namesakes'; the arena figures are the same numbers. */
+int vmpc_bn256_fr_cs_triples_batch_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col,
+                                       const void *a_vals, const void *a_const, const uint32_t *b_row_ptr,
+                                       const uint32_t *b_col, const void *b_vals, const void *b_const,
+                                       const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset, void *z,
+                                       size_t z_stride, void *a_out, void *b_out, size_t ab_stride, size_t n_wit, int check,
+                                       uint32_t *first_bad);
+int vmpc_bn256_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m,
+                                      const void *fact, const void *ifact, void *z_tail, size_t z_stride, size_t n_wit);
+size_t vmpc_bn256_fr_cs_extend_batch_bytes(size_t m, size_t n_wit);
+size_t vmpc_bn256_fr_cs_extend_batch_bytes_ctx(const vmpc_ctx *ctx, size_t m, size_t n_wit);
 /* How the three extension entries - and with them circuit_sat_prover, its batch and the M-party prover - compute the
  * sums over j for x = m+2 .. 2m.  DIRECT: the correlation kernel, 2 m^2 multiply-accumulates; a new context starts
  * here.  NTT: the cyclic product of the 2 n_wit rows u_f, u_g with the table 1 / k by the multi-prime NTT over the

@@ -74,6 +74,8 @@ SYMBOLS = [
     "vmpc_bn256_fr_axpy_dev", "vmpc_bn256_fr_dot_scratch_bytes", "vmpc_bn256_fr_dot_to_dev",
     "vmpc_bn256_koe_stage_dev", "vmpc_bn256_koe_split_dev",
     "vmpc_bn256_fr_cs_extend_fg_dev", "vmpc_bn256_scale_points_dev",
+    "vmpc_bn256_fr_cs_triples_batch_dev", "vmpc_bn256_fr_cs_extend_batch_dev", "vmpc_bn256_fr_cs_extend_batch_bytes",
+    "vmpc_bn256_fr_cs_extend_batch_bytes_ctx", "vmpc_bn256_koe_stage_batch_dev", "vmpc_bn256_koe_split_batch_dev",
 ]
 
 
@@ -272,6 +274,13 @@ def load_library():
         "vmpc_bn256_fr_dot_to_dev": (i32, [vp, vp, vp, sz, vp, vp]),
         "vmpc_bn256_koe_stage_dev": (i32, [vp, vp, vp, vp, sz, vp, vp]),
         "vmpc_bn256_koe_split_dev": (i32, [vp, vp, sz, vp]),
+        "vmpc_bn256_koe_stage_batch_dev": (i32, [vp, vp, sz, vp, vp, sz, sz, sz, vp, sz, vp, sz]),
+        "vmpc_bn256_koe_split_batch_dev": (i32, [vp, vp, sz, sz, sz, vp]),
+        "vmpc_bn256_fr_cs_triples_batch_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, sz,
+                                                     sz, i32, vp]),
+        "vmpc_bn256_fr_cs_extend_batch_dev": (i32, [vp, vp, vp, sz, sz, vp, vp, vp, sz, sz]),
+        "vmpc_bn256_fr_cs_extend_batch_bytes": (sz, [sz, sz]),
+        "vmpc_bn256_fr_cs_extend_batch_bytes_ctx": (sz, [vp, sz, sz]),
         "vmpc_bn256_fr_cs_extend_fg_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp]),
         "vmpc_bn256_scale_points_dev": (i32, [vp, i32, vp, vp, sz, vp]),
         "vmpc_fr_rows_combine_dev": (i32, [vp, vp, sz, sz, sz, vp, vp]),
@@ -1033,25 +1042,25 @@ class Context:
         _check(fn(self.handle, p(a_ptr), p(b_ptr), m, p(fact_ptr), p(ifact_ptr), p(f_out_ptr), p(g_out_ptr)), name)
 
     def cs_triples_batch(self, A, B, gates_ptr, n_gates, n_x, gamma_offset, z_ptr, z_stride, a_ptr, b_ptr, ab_stride, n_wit,
-                         check=0, first_bad_ptr=None):
+                         check=0, first_bad_ptr=None, bn=False):
         """cs_triples for n_wit witnesses of one circuit in one launch: rows of z / a / b, strides in scalars;
         first_bad_ptr: n_wit device words"""
         p = ctypes.c_void_p
-        _check(self.lib.vmpc_fr_cs_triples_batch_dev(self.handle, p(A[0]), p(A[1]), p(A[2]), p(A[3]), p(B[0]), p(B[1]),
-                                                     p(B[2]), p(B[3]), p(gates_ptr), n_gates, n_x, gamma_offset, p(z_ptr),
-                                                     z_stride, p(a_ptr), p(b_ptr), ab_stride, n_wit, check,
-                                                     p(first_bad_ptr)), "vmpc_fr_cs_triples_batch_dev")
+        fn, name = self._field_entry("cs_triples_batch_dev", bn)
+        _check(fn(self.handle, p(A[0]), p(A[1]), p(A[2]), p(A[3]), p(B[0]), p(B[1]), p(B[2]), p(B[3]), p(gates_ptr), n_gates,
+                  n_x, gamma_offset, p(z_ptr), z_stride, p(a_ptr), p(b_ptr), ab_stride, n_wit, check, p(first_bad_ptr)),
+               name)
 
-    def cs_extend_batch(self, a_ptr, b_ptr, ab_stride, m, fact_ptr, ifact_ptr, z_tail_ptr, z_stride, n_wit):
+    def cs_extend_batch(self, a_ptr, b_ptr, ab_stride, m, fact_ptr, ifact_ptr, z_tail_ptr, z_stride, n_wit, bn=False):
         p = ctypes.c_void_p
-        _check(self.lib.vmpc_fr_cs_extend_batch_dev(self.handle, p(a_ptr), p(b_ptr), ab_stride, m, p(fact_ptr),
-                                                    p(ifact_ptr), p(z_tail_ptr), z_stride, n_wit),
-               "vmpc_fr_cs_extend_batch_dev")
+        fn, name = self._field_entry("cs_extend_batch_dev", bn)
+        _check(fn(self.handle, p(a_ptr), p(b_ptr), ab_stride, m, p(fact_ptr), p(ifact_ptr), p(z_tail_ptr), z_stride, n_wit),
+               name)
 
-    def cs_extend_batch_bytes(self, m, n_wit):
+    def cs_extend_batch_bytes(self, m, n_wit, bn=False):
         """the arena bytes cs_extend_batch reserves for n_wit witnesses on THIS context: by the route its extension
         mode gives m (set_cs_extension) and under its NTT arena cap"""
-        return int(self.lib.vmpc_fr_cs_extend_batch_bytes_ctx(self.handle, m, n_wit))
+        return int(self._field_entry("cs_extend_batch_bytes_ctx", bn)[0](self.handle, m, n_wit))
 
     def set_cs_extension(self, mode):
         """how cs_extend / cs_extend_fg / cs_extend_batch of this context compute the sums for x = m+2 .. 2m:
@@ -1143,6 +1152,20 @@ class Context:
         """u = c[n], c[n] = 0, on the device"""
         _check(self.lib.vmpc_bn256_koe_split_dev(self.handle, ctypes.c_void_p(c_ptr), n, ctypes.c_void_p(u_ptr)),
                "vmpc_bn256_koe_split_dev")
+
+    def bn256_koe_stage_batch(self, x_ptr, x_stride, gammas_ptr, L_ptr, L_stride, n, n_wit, lhs_ptr, lhs_stride, rhs_ptr,
+                              rhs_stride):
+        """bn256_koe_stage for n_wit rows in one launch: row p of lhs = (gammas[p], x_p), row p of rhs = L_p reversed;
+        strides in scalars; x_ptr None: no lhs, L_ptr None: no rhs"""
+        p = ctypes.c_void_p
+        _check(self.lib.vmpc_bn256_koe_stage_batch_dev(self.handle, p(x_ptr), x_stride, p(gammas_ptr), p(L_ptr), L_stride, n,
+                                                       n_wit, p(lhs_ptr), lhs_stride, p(rhs_ptr), rhs_stride),
+               "vmpc_bn256_koe_stage_batch_dev")
+
+    def bn256_koe_split_batch(self, c_ptr, c_stride, n, n_wit, u_ptr):
+        """u[p] = c_p[n], c_p[n] = 0 for n_wit rows c_stride scalars apart, one launch"""
+        _check(self.lib.vmpc_bn256_koe_split_batch_dev(self.handle, ctypes.c_void_p(c_ptr), c_stride, n, n_wit,
+                                                       ctypes.c_void_p(u_ptr)), "vmpc_bn256_koe_split_batch_dev")
 
     # ---- Pi_Nullity over a dense form matrix (csrc/nullity.hip) ------------------------------------------------------
     def fr_rows_combine(self, rows_ptr, s, n, row_stride, rho, out_ptr):

@@ -24,6 +24,9 @@ to z by an Ed25519 vector commitment and open L with the compressed or the plain
 (knowledge_of_exponent.trusted_setup) commits by the restriction argument (P, pi) and opens L with the
 knowledge-of-exponent pivot - three group elements whatever N is, no power-of-two padding of z, compact transcript
 only.  A verifier recognises the variant by a z_commitment that is a dict.
+
+K witnesses of ONE circuit: protocol_8_excl_pivot_prover_batch / circuit_sat_prover_batch run every stage once for all
+K, over either field and scheme (DESIGN.md sections 20 and 32), and return what K single calls return.
 """
 import hashlib
 from random import SystemRandom
@@ -249,6 +252,15 @@ class _Pedersen:
         return pivot.vector_commitment(z, gamma, generators["g"], generators["h"])
 
     @staticmethod
+    def commit_batch(generators, Z, N, gammas):
+        """([z_commitment], None) for the rows of Z: K queued commitments, read back together"""
+        zs = [Z[p * N:(p + 1) * N] for p in range(len(gammas))]
+        gv, h = pivot._points_on_device(generators["g"]), pivot._as_point(generators["h"])
+        assert len(gv) >= N, "Not enough generators."
+        pending = [pivot._commit_launch(z, gamma, gv, h, gv.ctx) for z, gamma in zip(zs, gammas)]
+        return [pc.result() for pc in pending], None     # the first waits for all K, the others only copy
+
+    @staticmethod
     def commitment_bytes(z_commitment):
         return wire.compress_point(z_commitment)
 
@@ -256,7 +268,10 @@ class _Pedersen:
 class _Koe:
     """z is committed to by the restriction argument over a pp: (P, pi), one G1 and one G2 MSM
     (knowledge_of_exponent.restriction_argument_prover); L is opened by the knowledge-of-exponent pivot.  N = len(z)
-    needs 2N points on either side of the pp, the reference's assertion (knowledge_of_exponent.py:109,128)."""
+    needs 2N points on either side of the pp, the reference's assertion (knowledge_of_exponent.py:109,128).  K
+    witnesses of one circuit (commit_batch) are the K rows of ONE staged matrix (gamma_p, z_p) and two row-MSMs
+    (knowledge_of_exponent.restriction_argument_prover_batch); the matrix goes on to the batched opening, which
+    multiplies the same rows."""
     order = BN256_ORDER
     first_tag, second_tag = b"vmpc-ac20/p8-koe/first/v1", b"vmpc-ac20/p8-koe/second/v1"
 
@@ -268,6 +283,15 @@ class _Koe:
         assert len(generators["pp_lhs"]) == 2 * N
         P, pi = koe.restriction_argument_prover(range(N), z, gamma, generators)
         return {"P": P, "pi": pi}
+
+    @staticmethod
+    def commit_batch(generators, Z, N, gammas):
+        """([{"P", "pi"}], lhs) for the rows of Z; lhs: the staged rows (gamma_p, z_p), for the opening"""
+        assert 2 * N - 1 <= len(generators["pp_lhs"]), \
+            "Requirement does not hold: 2*len(x)-1 <= number of generators in first group."
+        assert len(generators["pp_lhs"]) == 2 * N
+        pairs, lhs = koe.restriction_argument_prover_batch(Z, gammas, generators, stride=N, n=N, return_lhs=True)
+        return [{"P": P, "pi": pi} for P, pi in pairs], lhs
 
     @staticmethod
     def commitment_bytes(z_commitment):
@@ -766,10 +790,13 @@ BATCH_BUDGET_BYTES = 1 << 30
 MAX_BATCH = 65535           # VMPC_FR_CS_MAX_WIT of include/vmpc.h
 
 
-def _batch_inputs(xs, n_in):
-    """(K, n_in, rows): rows a (K, n_in, 32) uint8 array of canonical residues, or the caller's device ScalarVector of
-    K n_in scalars.  Only a sequence of input lists is converted integer by integer."""
+def _batch_inputs(xs, n_in, field=_FIELDS[ORDER]):
+    """(K, n_in, rows): rows a (K, n_in, 32) uint8 array of canonical residues of `field`, or the caller's device vector
+    (the field's: ScalarVector / BnScalarVector) of K n_in scalars.  Only a sequence of input lists is converted integer
+    by integer."""
     if isinstance(xs, ScalarVector):
+        if xs.BN != field.bn:
+            raise ValueError(f"xs on the device: a {field.vector.__name__} goes with this circuit's order")
         if n_in is None:
             raise ValueError("xs on the device: n_in= says where a witness ends")
         if (n_in == 0 and len(xs)) or (n_in and len(xs) % n_in):
@@ -779,11 +806,12 @@ def _batch_inputs(xs, n_in):
         if xs.ndim != 3 or xs.shape[2] != 32:
             raise ValueError("xs as an array: (K, n_in, 32) uint8 little-endian residues")
         rows = np.ascontiguousarray(xs)
-        big = np.argwhere(rows[:, :, 31] >= 0x10)       # l < 2^253: the few values that may not be canonical
+        # only values whose top byte reaches the order's may not be canonical (l < 2^253: 0x10)
+        big = np.argwhere(rows[:, :, 31] >= field.order >> 248)
         if len(big):
             rows = rows.copy()
             for p, i in big.tolist():
-                v = int.from_bytes(rows[p, i].tobytes(), "little") % ORDER
+                v = int.from_bytes(rows[p, i].tobytes(), "little") % field.order
                 rows[p, i] = np.frombuffer(v.to_bytes(32, "little"), np.uint8)
         return rows.shape[0], rows.shape[1], rows
     xs = [list(x) for x in xs]
@@ -791,7 +819,7 @@ def _batch_inputs(xs, n_in):
         return 0, 0, np.zeros((0, 0, 32), np.uint8)
     if any(len(x) != len(xs[0]) for x in xs):
         raise ValueError("xs: every witness takes the same number of inputs")
-    rows = [sparse.residue_array([pivot._residue(v) for v in x], ORDER).reshape(len(xs[0]), 32) for x in xs]
+    rows = [field.residues(x).reshape(len(xs[0]), 32) for x in xs]
     return len(xs), len(xs[0]), np.stack(rows)
 
 
@@ -810,7 +838,7 @@ def _input_lists(xs, n_in):
 def _batch_bytes(circuit, n_in, k):
     """device bytes of k witnesses' Z, row values and extension workspace"""
     m = circuit.m
-    return 32 * k * (n_in + 3 + 2 * m + 2 * (m + 1)) + circuit.device()["ctx"].cs_extend_batch_bytes(m, k)
+    return 32 * k * (n_in + 3 + 2 * m + 2 * (m + 1)) + circuit.device()["ctx"].cs_extend_batch_bytes(m, k, bn=circuit.field.bn)
 
 
 def _chunk_size(circuit, n_in, K):
@@ -826,20 +854,21 @@ def _chunk_size(circuit, n_in, K):
 
 
 def _witnesses_on_device(circuit, rows, n_in, draws, gamma_witnesses=None, first=0):
-    """Z: the K = len(draws) vectors z of _witness_on_device as consecutive rows of ONE device vector (stride N), for
-    the inputs `rows` (host array or device vector from witness 0 on) and draws [(r_a, r_b, ..)].  Every stage runs
-    once for all K; `first` is only what an error calls witness 0."""
+    """Z: the K = len(draws) vectors z of _witness_on_device as consecutive rows of ONE device vector (stride N) of the
+    circuit's field, for the inputs `rows` (host array or device vector from witness 0 on) and draws [(r_a, r_b, ..)].
+    Every stage runs once for all K; `first` is only what an error calls witness 0."""
     K, m, n_x = len(draws), circuit.m, circuit.n_x
     d = circuit.device()
-    ctx = d["ctx"]
+    ctx, F = d["ctx"], circuit.field
+    Vec, bn = F.vector, F.bn
     M, N, g_off = m + 1, n_in + 3 + 2 * m, n_in + 3
-    Z = ScalarVector.empty(K * N, ctx)
-    a, b = ScalarVector.empty(K * M, ctx), ScalarVector.empty(K * M, ctx)
-    X = rows if isinstance(rows, ScalarVector) else ScalarVector.from_array(rows.reshape(K * n_in, 32), ctx)
-    r = ctx.upload(sparse.residue_array([dr[0] for dr in draws] + [dr[1] for dr in draws], ORDER))
+    Z = Vec.empty(K * N, ctx)
+    a, b = Vec.empty(K * M, ctx), Vec.empty(K * M, ctx)
+    X = rows if isinstance(rows, ScalarVector) else Vec.from_array(rows.reshape(K * n_in, 32), ctx)
+    r = ctx.upload(F.residues([dr[0] for dr in draws] + [dr[1] for dr in draws]))
     G = None
     if gamma_witnesses is not None and m:
-        G = ctx.upload(sparse.residue_array([pivot._residue(v) for gw in gamma_witnesses for v in gw], ORDER))
+        G = ctx.upload(F.residues([v for gw in gamma_witnesses for v in gw]))
     for p in range(K):
         ctx.copy(Z.ptr + 32 * p * N, X.ptr + 32 * p * n_in, 32 * n_in)
         ctx.copy(a.ptr + 32 * (p * M + m), r.ptr + 32 * p, 32)
@@ -848,7 +877,8 @@ def _witnesses_on_device(circuit, rows, n_in, draws, gamma_witnesses=None, first
             ctx.copy(Z.ptr + 32 * (p * N + g_off), G.ptr + 32 * p * m, 32 * m)
     if G is not None:
         bad = ctx.alloc(4 * K)
-        ctx.cs_triples_batch(d["A"].csr(), d["B"].csr(), None, m, n_x, g_off, Z.ptr, N, a.ptr, b.ptr, M, K, 1, bad.ptr)
+        ctx.cs_triples_batch(d["A"].csr(), d["B"].csr(), None, m, n_x, g_off, Z.ptr, N, a.ptr, b.ptr, M, K, 1, bad.ptr,
+                             bn=bn)
         firsts = ctx.download(bad.ptr, 4 * K).view(np.uint32)
         for p in np.nonzero(firsts != 0xFFFFFFFF)[0][:1].tolist():
             raise ValueError(f"gamma_witnesses[{first + p}]: multiplication gate {int(firsts[p])} is not the product of "
@@ -857,23 +887,23 @@ def _witnesses_on_device(circuit, rows, n_in, draws, gamma_witnesses=None, first
         for lv in range(len(circuit.level_ptr) - 1):
             lo, hi = int(circuit.level_ptr[lv]), int(circuit.level_ptr[lv + 1])
             ctx.cs_triples_batch(d["A"].csr(), d["B"].csr(), d["order"].ptr + 4 * lo, hi - lo, n_x, g_off, Z.ptr, N, a.ptr,
-                                 b.ptr, M, K)
-    ctx.cs_extend_batch(a.ptr, b.ptr, M, m, d["fact"].ptr, d["ifact"].ptr, Z.ptr + 32 * n_in, N, K)
+                                 b.ptr, M, K, bn=bn)
+    ctx.cs_extend_batch(a.ptr, b.ptr, M, m, d["fact"].ptr, d["ifact"].ptr, Z.ptr + 32 * n_in, N, K, bn=bn)
     return Z
 
 
 def _prove_chunk(generators, circuit, rows, n_in, draws, gamma_witnesses, gf, first):
     """Protocol 8 without the pivot for the witnesses of one chunk, stage by stage; nothing is read back inside a loop
-    over witnesses"""
+    over witnesses.  (results, Z, staged): the chunk's matrix Z and what the scheme's commit_batch staged besides the
+    commitments (the knowledge-of-exponent rows (gamma_p, z_p); None for Ed25519), for the pivot that follows."""
     order, K, m, n_x, n_out = gf.order, len(draws), circuit.m, circuit.n_x, circuit.n_out
     d = circuit.device()
     ctx, N, g_off = d["ctx"], n_in + 3 + 2 * m, n_in + 3
+    Vec, bn = circuit.field.vector, circuit.field.bn
+    scheme = _Koe if "pp_lhs" in generators else _Pedersen
     Z = _witnesses_on_device(circuit, rows, n_in, draws, gamma_witnesses, first)
     zs = [Z[p * N:(p + 1) * N] for p in range(K)]           # views: each keeps the allocation alive
-    gv, h = pivot._points_on_device(generators["g"]), pivot._as_point(generators["h"])
-    assert len(gv) >= N, "Not enough generators."
-    pending = [pivot._commit_launch(z, dr[2], gv, h, gv.ctx) for z, dr in zip(zs, draws)]
-    commitments = [pc.result() for pc in pending]           # the first waits for all K, the others only copy
+    commitments, staged = scheme.commit_batch(generators, Z, N, [dr[2] for dr in draws])
     digests = [_first_digest(zc, circuit, n_in) for zc in commitments]
     cs = [first_challenge(dg, order) for dg in digests]
     for p, c in enumerate(cs):
@@ -881,17 +911,18 @@ def _prove_chunk(generators, circuit, rows, n_in, draws, gamma_witnesses, gf, fi
             raise ChallengeOnNode(f"Protocol 8, witness {first + p}: the first challenge {c} is an interpolation node "
                                   f"(0..{2 * m})")
     # per witness F z, G z, H z and the constants of F and G: five scalars, read back together
-    Y = ScalarVector.empty(5 * K, ctx)
+    Y = Vec.empty(5 * K, ctx)
     forms = []
     for p, (z, c) in enumerate(zip(zs, cs)):
         f = _Forms(circuit, n_in, c, order, Y.ptr + 32 * (5 * p + 3))
         for i, V in enumerate((f.F, f.G, f.H)):
-            ctx.fr_dot_into(V.ptr, z.ptr, N, Y.ptr + 32 * (5 * p + i))
+            ctx.fr_dot_into(V.ptr, z.ptr, N, Y.ptr + 32 * (5 * p + i), bn=bn)
         forms.append(f)
     o1 = None
     if n_out:
-        o1 = ScalarVector.empty(K * n_out, ctx)
-        ctx.cs_triples_batch(d["O"].csr(), d["O"].csr(), None, n_out, n_x, g_off, Z.ptr, N, o1.ptr, o1.ptr, n_out, K, 2)
+        o1 = Vec.empty(K * n_out, ctx)
+        ctx.cs_triples_batch(d["O"].csr(), d["O"].csr(), None, n_out, n_x, g_off, Z.ptr, N, o1.ptr, o1.ptr, n_out, K, 2,
+                             bn=bn)
     ys = Y.to_ints()
     outs = o1.to_ints() if n_out else []
     results = []
@@ -902,37 +933,26 @@ def _prove_chunk(generators, circuit, rows, n_in, draws, gamma_witnesses, gf, fi
         proof = {"z_commitment": zc, "y1": y1, "y2": y2, "y3": y3}
         outputs = [gf(v) for v in outs[p * n_out:(p + 1) * n_out]]
         proof["outputs"] = outputs
-        rho = _second_challenge(dg, (y1, y2, y3), outputs, order)
+        rho = _second_challenge(dg, (y1, y2, y3), outputs, order, scheme.second_tag)
         L = f.combine(rho, (y1, y2, y3), outputs, gf)
         proof["L"] = L
         results.append((proof, zc, L, z, dr[2]))
-    return results
+    return results, Z, staged
 
 
-def protocol_8_excl_pivot_prover_batch(generators, circuit, xs, gf, gamma_witnesses=None, transcript=None, n_in=None):
-    """[protocol_8_excl_pivot_prover(generators, circuit, x, gf, ...) for x in xs] for K inputs of ONE circuit, with the
-    random draws those K calls would make (r_a, r_b, gamma of witness 0, then witness 1, ..: all before the first launch)
-    and so the same proofs - but every stage once for all K: one launch per depth level, one batched extension, K queued
-    commitments read back together, K queued sets of forms whose values are read back together.
-
-    xs: K input lists of one length; a (K, n_in, 32) uint8 array of little-endian residues; or a device ScalarVector of
-    K n_in scalars with n_in=.  gamma_witnesses: K lists of gate outputs, checked in one launch.  Each returned z is a
-    slice of one device vector.  K is cut into chunks of at most BATCH_BUDGET_BYTES of Z, row values and workspace."""
-    mode = _mode(transcript)
-    if "g" not in generators:
-        raise NotImplementedError("Protocol 8 over a SparseCircuit: the knowledge-of-exponent variant lives in another "
-                                  "field (BN-256) and is not built")
-    circuit = as_sparse(circuit)
+def _prove_chunks(generators, circuit, xs, gf, gamma_witnesses, mode, n_in):
+    """protocol_8_excl_pivot_prover_batch's checks and draws, then one _prove_chunk per chunk of witnesses: yields what
+    _prove_chunk returns.  The compact transcript only."""
+    has_pp = "pp_lhs" in generators
+    circuit = as_sparse(circuit, _Koe.order if has_pp else ORDER)
+    scheme = _scheme_of_generators(generators, circuit, gf)
+    if scheme is _Koe and mode == "reference":
+        raise NotImplementedError(_KOE_REFERENCE_TRANSCRIPT)
+    assert mode != "reference"
     order = gf.order
-    assert order == ORDER
-    if mode == "reference":             # host list code by construction
-        lists = _input_lists(xs, n_in)
-        gws = gamma_witnesses if gamma_witnesses is not None else [None] * len(lists)
-        return [protocol_8_excl_pivot_prover(generators, circuit, x, gf, gamma_witness=gw, transcript=mode)
-                for x, gw in zip(lists, gws)]
-    K, n_in, rows = _batch_inputs(xs, n_in)
+    K, n_in, rows = _batch_inputs(xs, n_in, circuit.field)
     if K == 0:
-        return []
+        return
     if n_in < circuit.n_x:
         raise ValueError(f"the circuit has {circuit.n_x} inputs, {n_in} given")
     if gamma_witnesses is not None:
@@ -941,27 +961,65 @@ def protocol_8_excl_pivot_prover_batch(generators, circuit, xs, gf, gamma_witnes
             raise ValueError(f"gamma_witnesses: {K} lists of {circuit.m} gate outputs expected")
     draws = [(prng.randrange(1, order), prng.randrange(1, order), prng.randrange(1, order)) for _ in range(K)]
     step = _chunk_size(circuit, n_in, K)
-    results = []
     for lo in range(0, K, step):
         hi = min(K, lo + step)
         part = rows[lo * n_in:hi * n_in] if isinstance(rows, ScalarVector) else rows[lo:hi]
-        results += _prove_chunk(generators, circuit, part, n_in, draws[lo:hi],
-                                gamma_witnesses[lo:hi] if gamma_witnesses is not None else None, gf, lo)
-    return results
+        yield _prove_chunk(generators, circuit, part, n_in, draws[lo:hi],
+                           gamma_witnesses[lo:hi] if gamma_witnesses is not None else None, gf, lo)
+
+
+def protocol_8_excl_pivot_prover_batch(generators, circuit, xs, gf, gamma_witnesses=None, transcript=None, n_in=None):
+    """[protocol_8_excl_pivot_prover(generators, circuit, x, gf, ...) for x in xs] for K inputs of ONE circuit, with the
+    random draws those K calls would make (r_a, r_b, gamma of witness 0, then witness 1, ..: all before the first launch)
+    and so the same proofs - but every stage once for all K: one launch per depth level, one batched extension, the K
+    commitments together, K queued sets of forms whose values are read back together.
+
+    The generators select the scheme and the field as in the single prover: Ed25519 generators commit by K queued
+    vector commitments read back together; a knowledge-of-exponent pp (a circuit and gf of the BN-256 order, the compact
+    transcript only) by ONE restriction_argument_prover_batch on the rows of Z - one staged matrix, one row-MSM in G1
+    and one on the twist.
+
+    xs: K input lists of one length; a (K, n_in, 32) uint8 array of little-endian residues; or a device vector of the
+    circuit's field (ScalarVector, BnScalarVector) of K n_in scalars with n_in=.  gamma_witnesses: K lists of gate
+    outputs, checked in one launch.  Each returned z is a slice of one device vector.  K is cut into chunks of at most
+    BATCH_BUDGET_BYTES of Z, row values and workspace."""
+    mode = _mode(transcript)
+    if mode == "reference":             # host list code by construction
+        if "pp_lhs" in generators:
+            raise NotImplementedError(_KOE_REFERENCE_TRANSCRIPT)
+        _scheme_of_generators(generators, as_sparse(circuit), gf)
+        lists = _input_lists(xs, n_in)
+        gws = gamma_witnesses if gamma_witnesses is not None else [None] * len(lists)
+        return [protocol_8_excl_pivot_prover(generators, circuit, x, gf, gamma_witness=gw, transcript=mode)
+                for x, gw in zip(lists, gws)]
+    return [r for results, _, _ in _prove_chunks(generators, circuit, xs, gf, gamma_witnesses, mode, n_in) for r in results]
 
 
 def circuit_sat_prover_batch(generators, circuit, xs, gf, pivot_choice="compressed", gamma_witnesses=None, transcript=None,
                              n_in=None):
     """[circuit_sat_prover(generators, circuit, x, gf, pivot_choice, ...) for x in xs]: Protocol 8 for all K witnesses
-    together (protocol_8_excl_pivot_prover_batch), then the compressed pivot per witness, in order.  The plain pivot and
-    the reference transcript are host list code: a loop over circuit_sat_prover."""
+    together (protocol_8_excl_pivot_prover_batch), then the pivot.  The compressed pivot runs per witness, in order.
+    The knowledge-of-exponent pivot (a pp, PivotChoice.koe) is ONE opening_linear_form_prover_batch per chunk of
+    witnesses on the commitments' P and pi and on the rows the commitment staged: one product, one split and one
+    row-MSM for the chunk, z and L on the device throughout.  The plain pivot and the reference
+    transcript are host list code: a loop over circuit_sat_prover."""
     choice = _choice(pivot_choice)
-    if choice == "koe":
-        raise NotImplementedError("PivotChoice.koe over a SparseCircuit: the knowledge-of-exponent pivot lives in "
-                                  "another field (BN-256); Protocol 8 is built over the Ed25519 scalar field")
-    if choice not in ("compressed", "pivot"):
-        raise NotImplementedError
+    _check_choice(choice, "pp_lhs" in generators)
     mode = _mode(transcript)
+    if choice == "koe":
+        if mode == "reference":
+            raise NotImplementedError(_KOE_REFERENCE_TRANSCRIPT)
+        proofs = []
+        for results, _, lhs in _prove_chunks(generators, circuit, xs, gf, gamma_witnesses, mode, n_in):
+            # L(z) = 0 is each opening's own coefficient N: nothing is evaluated here
+            opened = koe.opening_linear_form_prover_batch([L for _, _, L, _, _ in results], None,
+                                                          [gamma for _, _, _, _, gamma in results], generators,
+                                                          [zc["P"] for _, zc, _, _, _ in results],
+                                                          [zc["pi"] for _, zc, _, _, _ in results], lhs=lhs)
+            for (proof, _, _, _, _), (pivot_proof, _) in zip(results, opened):
+                proof["pivot_proof"] = pivot_proof
+                proofs.append(proof)
+        return proofs
     if choice == "pivot" or mode == "reference":
         lists = _input_lists(xs, n_in)
         gws = gamma_witnesses if gamma_witnesses is not None else [None] * len(lists)

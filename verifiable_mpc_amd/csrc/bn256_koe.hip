@@ -12,6 +12,10 @@
 //   k_koe_stage      the product's operands (gamma, x) and L reversed from a witness and a form in device memory, and
 //   k_koe_split      c[n] out of the product and zeroed in place: the opening of Protocol 8's L over BN-256 never
 //                    passes z or L through the host.
+//   k_koe_stage_batch  the same two for K openings of one length in one launch each: the operands as rows of matrices (the
+//   k_koe_split_batch  witness on the grid's y, one gamma per row from device memory), the K coefficients n taken out by
+//                      one lane per witness (vmpc_bn256_koe_stage_batch_dev, _split_batch_dev: the batch prover of
+//                      DESIGN.md section 32).  The single entries keep their own kernels.
 //
 // Product kernel: the output-stationary tile of csrc/fr_conv.h over one SEGMENT of the index i of a.  The triangle
 // (tiles near k = n meet the whole of a, tiles at the ends almost nothing) is balanced by the segments: a tile is cut
@@ -244,6 +248,67 @@ extern "C" int vmpc_bn256_koe_split_dev(vmpc_ctx *ctx, void *c, size_t n, void *
     VMPC_HIP_CHECK(hipSetDevice(ctx->device));
     vmpc_stage_scope s(ctx, "bn_koe_split");
     k_koe_split<<<1, 1, 0, ctx->stream>>>((uint32_t *)c, n, (uint32_t *)u_out);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+// ---- the same for K openings of one length ----------------------------------------------------------
+// grid (n + 1 lanes, witnesses): witness p reads row p of x and of L and gammas[p], and writes row p of lhs and of rhs (all
+// strides in scalars).  x NULL: no lhs; L NULL: no rhs.
+__global__ void __launch_bounds__(256)
+k_koe_stage_batch(const uint32_t *__restrict__ x, size_t x_stride, const uint32_t *__restrict__ gammas,
+                  const uint32_t *__restrict__ L, size_t L_stride, size_t n, uint32_t *__restrict__ lhs, size_t lhs_stride,
+                  uint32_t *__restrict__ rhs, size_t rhs_stride) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t p = blockIdx.y;
+    if (i < n) {
+        if (x) f256_st(lhs + 8 * p * lhs_stride, (long long)i + 1, f256_ld<frbn>(x + 8 * p * x_stride, (long long)i));
+        if (L) f256_st(rhs + 8 * p * rhs_stride, (long long)(n - 1 - i), f256_ld<frbn>(L + 8 * p * L_stride, (long long)i));
+    } else if (i == n && x) {
+        f256_st(lhs + 8 * p * lhs_stride, 0, f256_ld<frbn>(gammas, (long long)p));
+    }
+}
+
+// lane p: u[p] = c_p[n], then c_p[n] = 0
+__global__ void __launch_bounds__(256)
+k_koe_split_batch(uint32_t *__restrict__ c, size_t c_stride, size_t n, size_t n_wit, uint32_t *__restrict__ u) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_wit) return;
+    uint32_t *row = c + 8 * p * c_stride;
+    f256_st(u, (long long)p, f256_ld<frbn>(row, (long long)n));
+    f256_st(row, (long long)n, frbn_zero());
+}
+
+extern "C" int vmpc_bn256_koe_stage_batch_dev(vmpc_ctx *ctx, const void *x, size_t x_stride, const void *gammas,
+                                              const void *L, size_t L_stride, size_t n, size_t n_wit, void *lhs,
+                                              size_t lhs_stride, void *rhs, size_t rhs_stride) {
+    const size_t cap = (size_t)1 << 31;
+    if (n > VMPC_BN256_FR_POLY_MAX - 1 || n_wit > VMPC_BN256_QAP_MAX_WIT || x_stride > cap || L_stride > cap ||
+        lhs_stride > cap || rhs_stride > cap ||
+        (n_wit && (x_stride < n || L_stride < n || lhs_stride < n + 1 || rhs_stride < n)))
+        return VMPC_E_RANGE;
+    if (!ctx || (!x && !L) || (x && (!lhs || !gammas)) || (L && !rhs)) return VMPC_E_INVAL;
+    if (n_wit == 0) return VMPC_OK;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope s(ctx, "bn_koe_stage");
+    k_koe_stage_batch<<<dim3((unsigned)((n + 1 + 255) / 256), (unsigned)n_wit), 256, 0, ctx->stream>>>(
+        (const uint32_t *)x, x_stride, (const uint32_t *)gammas, (const uint32_t *)L, L_stride, n, (uint32_t *)lhs,
+        lhs_stride, (uint32_t *)rhs, rhs_stride);
+    VMPC_KERNEL_CHECK();
+    return VMPC_OK;
+}
+
+extern "C" int vmpc_bn256_koe_split_batch_dev(vmpc_ctx *ctx, void *c, size_t c_stride, size_t n, size_t n_wit,
+                                              void *u_out) {
+    if (n > VMPC_BN256_FR_POLY_MAX - 1 || n_wit > VMPC_BN256_QAP_MAX_WIT || c_stride > ((size_t)1 << 31) ||
+        (n_wit && c_stride < 2 * n))
+        return VMPC_E_RANGE;
+    if (!ctx || !c || !u_out || n == 0) return VMPC_E_INVAL;
+    if (n_wit == 0) return VMPC_OK;
+    VMPC_HIP_CHECK(hipSetDevice(ctx->device));
+    vmpc_stage_scope s(ctx, "bn_koe_split");
+    k_koe_split_batch<<<(unsigned)((n_wit + 255) / 256), 256, 0, ctx->stream>>>((uint32_t *)c, c_stride, n, n_wit,
+                                                                               (uint32_t *)u_out);
     VMPC_KERNEL_CHECK();
     return VMPC_OK;
 }

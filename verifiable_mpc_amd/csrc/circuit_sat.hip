@@ -52,7 +52,8 @@
 // (tables, lagrange) take it from the CALLER - a vmpc_bn256_fr_cs_*_scratch_bytes() query and a pointer - where the GF(l)
 // entries take it from the context arena and hand the taken pointers to the same body; the extension and the column sum
 // reserve inside cs_extend<F> / fr_colsum<F> for either field.  The share form (_fg) exists over both fields (the M-party
-// provers: DESIGN.md sections 18 and 30); the batch form stays GF(l) only.
+// provers: DESIGN.md sections 18 and 30), and so do the batch forms (vmpc_bn256_fr_cs_triples_batch_dev,
+// vmpc_bn256_fr_cs_extend_batch_dev: the batch prover of the knowledge-of-exponent variant).
 #include "common.h"
 #include "fr.h"
 #include "fr_bn.h"
@@ -159,12 +160,13 @@ extern "C" int vmpc_bn256_fr_cs_triples_dev(vmpc_ctx *ctx, const uint32_t *a_row
                                 n_x, gamma_offset, z, a_out, b_out, check, first_bad);
 }
 
-extern "C" int vmpc_fr_cs_triples_batch_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col,
-                                            const void *a_vals, const void *a_const, const uint32_t *b_row_ptr,
-                                            const uint32_t *b_col, const void *b_vals, const void *b_const,
-                                            const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset, void *z,
-                                            size_t z_stride, void *a_out, void *b_out, size_t ab_stride, size_t n_wit,
-                                            int check, uint32_t *first_bad) {
+// the batch entry of either field: the checks, then n_wit witnesses with the caller's strides
+template <class F>
+static int cs_triples_many(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_vals,
+                           const void *a_const, const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_vals,
+                           const void *b_const, const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset,
+                           void *z, size_t z_stride, void *a_out, void *b_out, size_t ab_stride, size_t n_wit, int check,
+                           uint32_t *first_bad) {
     if (n_gates > VMPC_FR_CS_MAX_M || n_x > ((size_t)1 << 30) || gamma_offset > ((size_t)1 << 30) ||
         n_wit > VMPC_FR_CS_MAX_WIT || z_stride > ((size_t)1 << 31) || ab_stride > ((size_t)1 << 31) ||
         (n_gates && n_wit && (z_stride < gamma_offset + (check == 2 ? 0 : n_gates) || ab_stride < n_gates)))
@@ -173,8 +175,28 @@ extern "C" int vmpc_fr_cs_triples_batch_dev(vmpc_ctx *ctx, const uint32_t *a_row
         check < 0 || check > 2)
         return VMPC_E_INVAL;
     if (n_gates == 0 || n_wit == 0) return VMPC_OK;
-    return cs_triples<fr>(ctx, a_row_ptr, a_col, a_vals, a_const, b_row_ptr, b_col, b_vals, b_const, gates, n_gates, n_x,
-                          gamma_offset, z, z_stride, a_out, b_out, ab_stride, n_wit, check, first_bad);
+    return cs_triples<F>(ctx, a_row_ptr, a_col, a_vals, a_const, b_row_ptr, b_col, b_vals, b_const, gates, n_gates, n_x,
+                         gamma_offset, z, z_stride, a_out, b_out, ab_stride, n_wit, check, first_bad);
+}
+
+extern "C" int vmpc_fr_cs_triples_batch_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col,
+                                            const void *a_vals, const void *a_const, const uint32_t *b_row_ptr,
+                                            const uint32_t *b_col, const void *b_vals, const void *b_const,
+                                            const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset, void *z,
+                                            size_t z_stride, void *a_out, void *b_out, size_t ab_stride, size_t n_wit,
+                                            int check, uint32_t *first_bad) {
+    return cs_triples_many<fr>(ctx, a_row_ptr, a_col, a_vals, a_const, b_row_ptr, b_col, b_vals, b_const, gates, n_gates,
+                               n_x, gamma_offset, z, z_stride, a_out, b_out, ab_stride, n_wit, check, first_bad);
+}
+
+extern "C" int vmpc_bn256_fr_cs_triples_batch_dev(vmpc_ctx *ctx, const uint32_t *a_row_ptr, const uint32_t *a_col,
+                                                  const void *a_vals, const void *a_const, const uint32_t *b_row_ptr,
+                                                  const uint32_t *b_col, const void *b_vals, const void *b_const,
+                                                  const uint32_t *gates, size_t n_gates, size_t n_x, size_t gamma_offset,
+                                                  void *z, size_t z_stride, void *a_out, void *b_out, size_t ab_stride,
+                                                  size_t n_wit, int check, uint32_t *first_bad) {
+    return cs_triples_many<frbn>(ctx, a_row_ptr, a_col, a_vals, a_const, b_row_ptr, b_col, b_vals, b_const, gates, n_gates,
+                                 n_x, gamma_offset, z, z_stride, a_out, b_out, ab_stride, n_wit, check, first_bad);
 }
 
 // ---- factorial tables ---------------------------------------------------------------------------------------------------
@@ -646,15 +668,37 @@ extern "C" size_t vmpc_fr_cs_extend_batch_bytes_ctx(const vmpc_ctx *ctx, size_t 
     return cs_extend_batch_plan(m, n_wit, ntt ? vmpc_ntt_arena_cap(ctx) : 0).total_b;
 }
 
-extern "C" int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m,
-                                           const void *fact, const void *ifact, void *z_tail, size_t z_stride,
-                                           size_t n_wit) {
+// the plan does not depend on the field (32-byte scalars, the same 18 primes): the GF(n) queries are the GF(l) ones
+extern "C" size_t vmpc_bn256_fr_cs_extend_batch_bytes(size_t m, size_t n_wit) {
+    return vmpc_fr_cs_extend_batch_bytes(m, n_wit);
+}
+
+extern "C" size_t vmpc_bn256_fr_cs_extend_batch_bytes_ctx(const vmpc_ctx *ctx, size_t m, size_t n_wit) {
+    return vmpc_fr_cs_extend_batch_bytes_ctx(ctx, m, n_wit);
+}
+
+// the batch entry of either field: the checks, then n_wit witnesses with the caller's strides
+template <class F>
+static int cs_extend_many(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m, const void *fact,
+                          const void *ifact, void *z_tail, size_t z_stride, size_t n_wit) {
     if (m > VMPC_FR_CS_MAX_M || n_wit > VMPC_FR_CS_MAX_WIT || ab_stride > ((size_t)1 << 31) ||
         z_stride > ((size_t)1 << 31) || (n_wit && (ab_stride < m + 1 || z_stride < 2 * m + 3)))
         return VMPC_E_RANGE;
     if (!ctx || !a || !b || !fact || !ifact || !z_tail) return VMPC_E_INVAL;
     if (n_wit == 0) return VMPC_OK;
-    return cs_extend<fr>(ctx, a, b, ab_stride, m, fact, ifact, z_tail, z_stride, nullptr, nullptr, n_wit);
+    return cs_extend<F>(ctx, a, b, ab_stride, m, fact, ifact, z_tail, z_stride, nullptr, nullptr, n_wit);
+}
+
+extern "C" int vmpc_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m,
+                                           const void *fact, const void *ifact, void *z_tail, size_t z_stride,
+                                           size_t n_wit) {
+    return cs_extend_many<fr>(ctx, a, b, ab_stride, m, fact, ifact, z_tail, z_stride, n_wit);
+}
+
+extern "C" int vmpc_bn256_fr_cs_extend_batch_dev(vmpc_ctx *ctx, const void *a, const void *b, size_t ab_stride, size_t m,
+                                                 const void *fact, const void *ifact, void *z_tail, size_t z_stride,
+                                                 size_t n_wit) {
+    return cs_extend_many<frbn>(ctx, a, b, ab_stride, m, fact, ifact, z_tail, z_stride, n_wit);
 }
 
 // ---- transposed sparse mat-vec -----------------------------------------------------------------------------------------

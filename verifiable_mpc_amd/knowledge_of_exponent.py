@@ -26,6 +26,11 @@ SparseCircuit of this order opens its L (circuit_sat_gpu.py, DESIGN.md section 2
 single calls: the proofs' 5 K pairings in one pairing_product launch, their sums R as rows of PPVector.msm_rows
 (vmpc_bn256_table_msm_rows_dev); DESIGN.md section 31.
 
+`restriction_argument_prover_batch` and `opening_linear_form_prover_batch` (not in the reference) are the prover's side
+of that: K commitments and K openings under one pp with the points and scalars of K single calls - one staged matrix,
+one batched product, one split launch and one msm_rows per sum, whatever K is (csrc/bn256_koe.hip
+vmpc_bn256_koe_stage_batch_dev / _split_batch_dev).
+
 `update_setup` is one party's pass over a pp - every point times that party's own g_exp z^(i+1) - and what the joint
 setup of mpc_koe.koe_trusted_setup is made of.
 
@@ -362,6 +367,213 @@ def opening_linear_form_prover(L, x, gamma, pp, P=None, pi=None):
         sample = constant if hasattr(constant, "value") else (coeffs[0] if n else 0)
     u = _like(sample, (u_linear + int(constant)) % ORDER)
     return proof, u
+
+
+# ---- K openings under one pp ---------------------------------------------------------------------
+# device bytes one chunk of opening_linear_form_prover_batch / restriction_argument_prover_batch may hold in its operand
+# matrices (lhs, L, rhs, c) and the product's arena: K is cut into chunks of that many (circuit_sat_gpu.BATCH_BUDGET_BYTES
+# is the same rule one layer up)
+PROVE_BATCH_BUDGET_BYTES = 1 << 30
+MAX_BATCH = 65535           # VMPC_BN256_QAP_MAX_WIT of include/vmpc.h
+
+
+class StagedRows:
+    """K rows lhs_p = (gamma_p, x_p[0..n-1]) of one device buffer, `stride` scalars apart: what the restriction argument
+    sums over pp_lhs and pp_rhs and the opening multiplies by the reversed form.  Made once (stage_lhs_batch) and
+    handed from the commitment to the opening."""
+
+    def __init__(self, buf, stride, n, K, ptr=None):
+        self.buf, self.ptr, self.stride, self.n, self.K = buf, buf.ptr if ptr is None else ptr, stride, n, K
+
+    def rows(self, lo, hi):
+        """rows lo..hi-1 as a StagedRows of the same buffer"""
+        assert 0 <= lo <= hi <= self.K
+        return StagedRows(self.buf, self.stride, self.n, hi - lo, self.ptr + 32 * self.stride * lo)
+
+
+def _input_rows(xs, K, stride, n):
+    """(xs, stride, n) of K rows: a device BnScalarVector (rows `stride` scalars apart, default len / K, the first n of
+    each - default all - being x_p) or K host lists of one length"""
+    if _on_device(xs):
+        if stride is None:
+            if len(xs) % K:
+                raise ValueError(f"xs holds {len(xs)} scalars, not a multiple of the {K} rows")
+            stride = len(xs) // K
+        n = stride if n is None else n
+        if n > stride or len(xs) < (K - 1) * stride + n:
+            raise ValueError(f"xs: {K} rows of {n} scalars, {stride} apart, do not fit {len(xs)} scalars")
+        return xs, stride, n
+    xs = [x.to_ints() if _on_device(x) else list(x) for x in xs]
+    if len(xs) != K or any(len(x) != len(xs[0]) for x in xs):
+        raise ValueError(f"xs: {K} vectors of one length expected")
+    return xs, len(xs[0]), len(xs[0])
+
+
+def stage_lhs_batch(xs, gammas, stride=None, n=None, ctx=None):
+    """StagedRows of K = len(gammas) rows (gamma_p, x_p).  xs on the device (a BnScalarVector of K rows, `stride` scalars
+    apart, n of each read): the gammas are one upload and the rows one launch (vmpc_bn256_koe_stage_batch_dev); K host
+    lists: the matrix is put together on the host and is one upload."""
+    ctx = ctx or get_context()
+    gammas = list(gammas)
+    K = len(gammas)
+    xs, stride, n = _input_rows(xs, K, stride, n)
+    if _on_device(xs):
+        buf = ctx.alloc(32 * (n + 1) * K)
+        dg = ctx.upload(scalars_to_array(gammas))
+        ctx.bn256_koe_stage_batch(xs.ptr, stride, dg.ptr, None, n, n, K, buf.ptr, n + 1, None, n)
+    else:
+        buf = ctx.upload(np.concatenate([scalars_to_array([g] + x) for g, x in zip(gammas, xs)]))
+    return StagedRows(buf, n + 1, n, K)
+
+
+def _points_of_rows(rows, group):
+    return [_CLS[group].from_bytes(r.tobytes()) for r in rows]
+
+
+def restriction_argument_prover_batch(xs, gammas, pp, stride=None, n=None, lhs=None, return_lhs=False):
+    """[restriction_argument_prover(range(n), x_p, gamma_p, pp) for p < K] -> [(P_p, pi_p)], the same points, for K
+    vectors of one length under one pp: ONE staged matrix lhs of K rows (gamma_p, x_p), one PPVector.msm_rows over
+    pp_lhs and one over pp_rhs (m = n + 1 each), two synchronisations whatever K is.
+
+    xs: a device BnScalarVector of K rows of n scalars, `stride` (default n) scalars apart, or K host lists (one upload).
+    lhs: the rows already staged (stage_lhs_batch), xs is then not read.  return_lhs: (pairs, lhs) instead, so that
+    opening_linear_form_prover_batch does not stage the rows again; the matrix is then ONE buffer of K (n + 1) scalars.
+    Otherwise K is cut into chunks of PROVE_BATCH_BUDGET_BYTES of lhs."""
+    ctx = get_context()
+    gammas = list(gammas)
+    K = len(gammas)
+    if K == 0:
+        return ([], None) if return_lhs else []
+    if lhs is None and not return_lhs:
+        xs, stride, n = _input_rows(xs, K, stride, n)
+        step = max(1, min(K, MAX_BATCH, PROVE_BATCH_BUDGET_BYTES // (32 * (n + 1))))
+        if step < K:
+            pairs = []
+            for lo in range(0, K, step):
+                hi = min(K, lo + step)
+                part = xs[lo * stride:(hi - 1) * stride + n] if _on_device(xs) else xs[lo:hi]
+                pairs += restriction_argument_prover_batch(part, gammas[lo:hi], pp, stride, n,
+                                                           lhs=stage_lhs_batch(part, gammas[lo:hi], stride, n, ctx))
+            return pairs
+    if lhs is None:
+        lhs = stage_lhs_batch(xs, gammas, stride, n, ctx)
+    assert lhs.K == K
+    m = lhs.n + 1
+    g1, g2 = _side(ctx, pp, "pp_lhs", m), _side(ctx, pp, "pp_rhs", m)
+    pairs = list(zip(_points_of_rows(g1.msm_rows(lhs, m, K, lhs.stride), 1),
+                     _points_of_rows(g2.msm_rows(lhs, m, K, lhs.stride), 2)))
+    return (pairs, lhs) if return_lhs else pairs
+
+
+def _product_arena_bytes(ctx, n, k):
+    """the arena bytes the batched product of k openings of length n reserves on ctx, by the route its mode selects"""
+    mode = ctx.get_poly_product()
+    if mode == _native.POLY_PRODUCT_NTT or (mode == _native.POLY_PRODUCT_AUTO and n >= _native.BN256_FR_NTT_MIN):
+        return _native.bn256_fr_poly_mul_ntt_batch_bytes(n + 1, n, 0, 2 * n, k)
+    return _native.bn256_fr_poly_mul_batch_bytes(n + 1, n, 0, 2 * n, k)
+
+
+def prove_batch_bytes(n, k, ctx=None):
+    """device bytes of k openings of length n inside opening_linear_form_prover_batch: lhs (n + 1), the gathered L (n),
+    rhs (n) and c (2n) scalars per opening, u, and the product's arena"""
+    return 32 * k * ((n + 1) + n + n + 2 * n + 1) + _product_arena_bytes(ctx or get_context(), n, k)
+
+
+def prove_chunk_size(n, K, ctx=None):
+    """the most openings (<= K) whose prove_batch_bytes stay within PROVE_BATCH_BUDGET_BYTES, at least one"""
+    ctx = ctx or get_context()
+    lo, hi = 1, min(K, MAX_BATCH)
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if prove_batch_bytes(n, mid, ctx) <= PROVE_BATCH_BUDGET_BYTES:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def opening_linear_form_prover_batch(Ls, xs, gammas, pp, Ps=None, pis=None, stride=None, n=None, lhs=None):
+    """[opening_linear_form_prover(L_p, x_p, gamma_p, pp, P_p, pi_p) for p < K] -> [(proof_p, u_p)] with the same points
+    and the same u (value and type), for K forms of one length n under one pp, every stage once per chunk of openings:
+
+        one vmpc_bn256_koe_stage_batch_dev     the rows (gamma_p, x_p) - unless `lhs` brings them, or the restriction
+                                               argument (Ps None) has just made them - and the rows L_p reversed
+        one ctx.bn256_fr_poly_mul_batch        c_p = lhs_p * rhs_p, b_stride = n, the whole window [0, 2n): schoolbook
+                                               or NTT by the context's poly_product mode, as in the single call
+        one vmpc_bn256_koe_split_batch_dev     u_p = c_p[n], c_p[n] = 0
+        one PPVector.msm_rows over pp_lhs      Q_p = -sum_i c_p[i] pp_lhs[i], m = 2n, negated on the host; an all-zero
+                                               row is the point at infinity, returned as the single call returns it
+        one download of the K scalars u
+
+    xs, stride, n, lhs: as in restriction_argument_prover_batch (host lists: the rows are one upload).  The forms'
+    coefficients may be device BnScalarVectors (gathered into one matrix by device copies, nothing passes through the
+    host) or lists (one upload).  K is cut into chunks of at most PROVE_BATCH_BUDGET_BYTES (prove_batch_bytes); the product's arena is
+    reserved by the entry itself."""
+    ctx = get_context()
+    Ls, gammas = list(Ls), list(gammas)
+    K = len(Ls)
+    if len(gammas) != K or (Ps is not None and (len(Ps) != K or pis is None or len(pis) != K)):
+        raise ValueError("opening_linear_form_prover_batch: Ls, gammas, Ps and pis differ in length")
+    if K == 0:
+        return []
+    if lhs is None:
+        xs, stride, n = _input_rows(xs, K, stride, n)
+    else:
+        assert lhs.K == K
+        n = lhs.n
+    n_lhs = len(pp["pp_lhs"])
+    assert 2 * n - 1 <= n_lhs, "Requirement does not hold: 2*len(x)-1 <= number of generators in first group."
+    for L in Ls:
+        assert len(L.coeffs) == n, "Length of inputs to be equal to coefficients of linear form."
+    assert n_lhs == 2 * n
+    side = _side(ctx, pp, "pp_lhs")
+    step = prove_chunk_size(n, K, ctx)
+    out = []
+    for lo in range(0, K, step):
+        hi = min(K, lo + step)
+        k = hi - lo
+        forms = Ls[lo:hi]
+        on_device = all(_on_device(L.coeffs) for L in forms)
+        if on_device:
+            d_L = ctx.alloc(32 * n * k)
+            for j, L in enumerate(forms):
+                ctx.copy(d_L.ptr + 32 * n * j, L.coeffs.ptr, 32 * n)
+            host_coeffs = None
+        else:
+            host_coeffs = [_form_parts(L)[0] for L in forms]
+            d_L = ctx.upload(np.concatenate([scalars_to_array(co[:n]) for co in host_coeffs]))
+        rhs, c_bar, d_u = ctx.alloc(32 * n * k), ctx.alloc(32 * 2 * n * k), ctx.alloc(32 * k)
+        if lhs is None and _on_device(xs):
+            # the one launch makes both operands
+            rows = StagedRows(ctx.alloc(32 * (n + 1) * k), n + 1, n, k)
+            dg = ctx.upload(scalars_to_array(gammas[lo:hi]))
+            ctx.bn256_koe_stage_batch(xs.ptr + 32 * stride * lo, stride, dg.ptr, d_L.ptr, n, n, k, rows.ptr, n + 1, rhs.ptr,
+                                      n)
+        else:
+            rows = lhs.rows(lo, hi) if lhs is not None else stage_lhs_batch(xs[lo:hi], gammas[lo:hi], ctx=ctx)
+            ctx.bn256_koe_stage_batch(None, n, None, d_L.ptr, n, n, k, None, n + 1, rhs.ptr, n)
+        if Ps is None:
+            pairs = restriction_argument_prover_batch(None, gammas[lo:hi], pp, lhs=rows)
+        else:
+            pairs = list(zip(Ps[lo:hi], pis[lo:hi]))
+        ctx.bn256_fr_poly_mul_batch(rows.ptr, rows.stride, n + 1, rhs.ptr, n, n, 0, 2 * n, c_bar.ptr, 2 * n, k)
+        ctx.bn256_koe_split_batch(c_bar.ptr, 2 * n, n, k, d_u.ptr)
+        Q_rows = side.msm_rows(c_bar, 2 * n, k, row_stride=2 * n)        # synchronises
+        us = ctx.download(d_u.ptr, 32 * k).reshape(k, 32)
+        for j, (L, (P, pi)) in enumerate(zip(forms, pairs)):
+            Q = BN256Point.from_bytes(Q_rows[j].tobytes())
+            if Q.coords is not None:
+                Q = BN256Point((Q.coords[0], -Q.coords[1]))
+            # u's type is the single call's: the constant's when that is a field element (or the coefficients live on
+            # the device), else that of the first coefficient
+            constant = getattr(L, "constant", 0)
+            if hasattr(constant, "value") or _on_device(L.coeffs):
+                sample = constant
+            else:
+                sample = host_coeffs[j][0] if n else 0
+            u = _like(sample, (int.from_bytes(us[j].tobytes(), "little") + int(constant)) % ORDER)
+            out.append(({"P": P, "pi": pi, "Q": Q}, u))
+    return out
 
 
 def opening_linear_form_verifier(L, pp, proof, u):
