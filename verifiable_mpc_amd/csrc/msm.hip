@@ -29,10 +29,7 @@
 #include "msm_sort.h"
 #include "ptio.h"
 
-// niels record stride in 32-bit words: 24 = packed 96 B, 32 = one 128-B line per gather
-#ifndef MSM_NIELS_STRIDE
-#define MSM_NIELS_STRIDE 24
-#endif
+// (a niels record is NIELS_WORDS = 32 words, one 128-B line per gather: ptio.h)
 #ifndef MSM_REDUCE_WAVES
 #define MSM_REDUCE_WAVES 2
 #endif
@@ -67,7 +64,8 @@ __device__ __forceinline__ ge_niels niels_ld(const uint32_t *niels, uint32_t e) 
 // whole window of its run in one burst of loads - before its first addition no accumulator or table entry is live,
 // so the burst has the registers - and parks it in its own column of the stage.  The stage is [entry][thread]: the
 // 64 lanes of a wave read 64 consecutive words, one per bank.  32 entries x 256 threads = 32 KB per workgroup, four
-// workgroups per CU in 128 of the 160 KB.
+// workgroups per CU in 128 of the 160 KB.  The 32-entry burst is nine 16-byte loads (msm_idx_fill16), the 8-entry
+// burst of short tasks and the refills are eight 4-byte loads (msm_idx_fill).
 #define MSM_IDX_WIN 32
 // the first n of N entries from src into the lane's column: one burst of loads off one address, then the LDS stores
 // (slots past the run get zeros that nobody reads)
@@ -78,6 +76,33 @@ __device__ __forceinline__ void msm_idx_fill(uint32_t *__restrict__ col, const u
     for (int k = 0; k < N; k++) v[k] = (uint32_t)k < n ? src[k] : 0u;
 #pragma unroll
     for (int k = 0; k < N; k++) col[k * MSM_BLOCK] = v[k];
+}
+
+// The same for a run of sorted[] that starts at position `first`, 16 bytes to a load: N dword loads off one address
+// are up to N requests for the same line, N / 4 + 1 vector loads ask for it a quarter as often.  The run's start is
+// aligned down to 16 bytes and the `lead` = first % 4 words in front of it are dropped on the way to the stage, by two
+// levels of selects on the bits of `lead` (the stores stay the lane's own N slots, at constant offsets).  A load is
+// issued only if it holds a word of the run, so it stays inside sorted[], whose base and size are multiples of 256
+// bytes (msm_layout); the words it brings from past the run's end land in slots nobody reads.
+template <int N>
+__device__ __forceinline__ void msm_idx_fill16(uint32_t *__restrict__ col, const uint32_t *__restrict__ sorted, uint32_t first,
+                                               uint32_t n) {
+    const uint32_t lead = first & 3u;
+    const uint4 *src = reinterpret_cast<const uint4 *>(sorted + (first - lead));
+    const uint32_t words = lead + n;        // of the aligned stretch, up to the run's end
+    uint32_t v[N + 4];
+#pragma unroll
+    for (int j = 0; j < N / 4 + 1; j++) {
+        const uint4 q = 4u * (uint32_t)j < words ? src[j] : make_uint4(0u, 0u, 0u, 0u);
+        v[4 * j] = q.x; v[4 * j + 1] = q.y; v[4 * j + 2] = q.z; v[4 * j + 3] = q.w;
+    }
+    // (as masks: written as `lead & 1 ? v[k + 1] : v[k]` the compiler indexes the array in scratch)
+    const uint32_t m1 = 0u - (lead & 1u), m2 = 0u - ((lead >> 1) & 1u);
+    uint32_t t[N + 2];
+#pragma unroll
+    for (int k = 0; k < N + 2; k++) t[k] = (v[k + 1] & m1) | (v[k] & ~m1);
+#pragma unroll
+    for (int k = 0; k < N; k++) col[k * MSM_BLOCK] = (t[k + 2] & m2) | (t[k] & ~m2);
 }
 
 __global__ void __launch_bounds__(MSM_BLOCK, MSM_BUCKET_WAVES)
@@ -97,7 +122,7 @@ k_msm_bucket(const uint32_t *__restrict__ niels, const uint32_t *__restrict__ so
     const uint32_t len = tk.y;
     // (tasks are numbered by length, so the lanes of a wave agree on the short burst almost always)
     if (len <= 8) msm_idx_fill<8>(col, run, len);
-    else msm_idx_fill<MSM_IDX_WIN>(col, run, len);
+    else msm_idx_fill16<MSM_IDX_WIN>(col, sorted, tk.x, len);
     // The next table entry is requested one addition ahead, but the compiler hoists its sign selection to right
     // behind the load, so in effect the gather latency is hidden by the 4 waves per SIMD, not by this
     // "prefetch".  A hand-scheduled version (inline-asm loads + manual s_waitcnt after the 7 multiplications,
